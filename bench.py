@@ -10,12 +10,21 @@ shard): 131 072 stereo 2048-sample blocks per GPU through the FULL mapping0_forw
 (config 2).
 
   python bench.py --gpus 1 --steps 10 --warmup 2
+  python bench.py --gpus 1 --steps 10 --warmup 2 --dump-outputs DIR
+  python bench.py --gpus 1 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the steps and prints the headline line (with its roofline,
+which takes no run of its own).  `--full` adds everything else: the parity sample of the timed
+batch against the CPU checker, the shader clock, the neighbouring stages, the other BASELINE
+configs, the host-fed figures and the CPU baseline (each of which a --no-* option still drops).
+`--dump-outputs DIR` writes what the last timed step computed, for a fixed seeded sample of the
+units, as DIR/<name>.npy (float32, or float64 for integer outputs).
+
 Multi-GPU: one process per GPU; rank 0 loads the setup blob and broadcasts its bytes over
 RCCL (the only collective: blocks are independent); every rank then analyses its
-own shard (weak scaling).  Rank 0 prints ONE JSON line.
+own shard (weak scaling).  Rank 0 prints ONE JSON line and writes rank 0's dump.
 """
 import argparse
 import json
@@ -223,11 +232,44 @@ def measured_traffic(workload, units, alg_bytes=None):
     return sum(per.values()), per, note
 
 
+DUMP_BUDGET = 48 << 20   # bytes of dumped arrays per run, below the 64 MB a comparison of two builds takes
+
+
+def as_dump(x):
+    """float32 / float64 as they are; 32- and 64-bit integers as float64 (exact), narrower ones as float32 (exact)."""
+    x = np.asarray(x)
+    if x.dtype in (np.float32, np.float64):
+        return x
+    return x.astype(np.float64 if x.dtype.kind in "iu" and x.dtype.itemsize >= 4 else np.float32)
+
+
+def sample_units(tensors, budget, seed):
+    """A fixed, seeded sample of the units (leading axis) of device tensors that share that axis, as many as fit `budget`
+    bytes once dumped (all of them when they fit).  Returns ({name: host array}, sorted unit indices)."""
+    n = next(iter(tensors.values())).shape[0]
+    row = sum(as_dump(v[:1].cpu().numpy()).nbytes for v in tensors.values())
+    k = min(n, max(1, budget // max(row, 1)))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(next(iter(tensors.values())).device)
+    return {name: v[sel].cpu().numpy() for name, v in tensors.items()}, idx
+
+
+def write_dump(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), as_dump(x))
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity sample, shader clock, neighbouring stages, the other BASELINE configs, "
+                         "host-fed figures and CPU baseline (the --no-* options below drop single parts of a --full run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (a fixed seeded sample of the units) as DIR/<name>.npy")
     ap.add_argument("--workload", choices=("c2", "c3", "c4", "c5"), default="c4")
     ap.add_argument("--blocks", type=int, default=None, help="stereo blocks per GPU (default 131072; c2/c3: 65536)")
     ap.add_argument("--setup", default=None, help="setup blob name (default 44k_stereo_q4; c5: 44k_stereo_q9)")
@@ -256,6 +298,10 @@ def parse(argv=None):
                     help="test aid: 'module:Class' of a runner that replaces the GPU runner (the CPU rehearsal of the rank logic "
                          "names a stub that does no analysis; the line then carries \"runner\" and is not a measurement)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:   # a plain run does only what the headline needs
+        a.no_cpu_baseline = a.no_neighbours = a.no_parity_sample = a.no_clock_probe = a.no_workloads = a.no_host_fed = True
     if a.setup is None:
         a.setup = "44k_stereo_q9" if a.workload == "c5" else "44k_stereo_q4"
     return a
@@ -517,6 +563,12 @@ class GpuRunner:
             bad += checker.compare_block(ref, {kk: v[k] for kk, v in got.items()}, nposts) != 0
         return len(idx), bad, chk.kind
 
+    def outputs(self, budget):
+        """What the last step handed back, for a seeded sample of the units: {name: host array}."""
+        got, idx = sample_units({"mdct": self.out} if self.a.workload == "c2" else self.outs, budget, 7 + self.rank)
+        got["sample_index"] = idx
+        return got
+
     def workload_text(self):
         nb = self.nb
         return {"c4": "C4 full mapping0_forward analysis (window+MDCT+FFT+noise/tone mask+floor1 fit+"
@@ -635,6 +687,21 @@ class StreamRunner:
             ref = chk.tap_block(pcm[W][j], int(L["lW"][W][i]), W, int(L["nW"][W][i]), int(L["blocktype"][W][i]), amp_in)
             bad += checker.compare_block(ref, {kk: v[j] for kk, v in got[W].items()}, self.an.posts[W]) != 0
         return len(pick), bad, chk.kind
+
+    def outputs(self, budget):
+        """What the last step handed back: each stream's ampmax state and block count, and per size class a seeded sample of
+        the planned blocks with their plan entries (window flags, block type, position) and analysis outputs."""
+        L = self.an.plan_lists(self.plan)
+        got = {"ampmax_state": self.amp.cpu().numpy(), "stream_start": L["stream_start"]}
+        for W, cls in ((0, "short_"), (1, "long_")):
+            nb = int(self.plan.nblocks[W])
+            if not nb:
+                continue
+            d, idx = sample_units({k: v[:nb] for k, v in self.outs[W].items()}, budget // 2, 7 + W + 2 * self.rank)
+            d.update({k: L[k][W][idx] for k in ("lW", "nW", "blocktype", "src")})
+            d["sample_index"] = idx
+            got.update({cls + k: v for k, v in d.items()})
+        return got
 
     def workload_text(self):
         return ("C5 mixed short/long-block streams: %d gated-noise stereo streams x %d samples per GPU, 44.1 kHz q=0.9 tables; per step: "
@@ -940,6 +1007,8 @@ def main(argv=None, make_runner=None):
     probe = ClockProbe(R, dev) if (make_runner is None and not a.no_clock_probe) else None
     elapsed, stage_ms = timed_run(a, R, dev, world, probe)
     clock = probe.result() if probe else None
+    if a.dump_outputs and rank == 0:
+        write_dump(a.dump_outputs, R.outputs(DUMP_BUDGET))
     parity = None if a.no_parity_sample else parity_of(a, R, dev, world, a.parity_blocks)
 
     rc = 0

@@ -5,6 +5,7 @@ import os
 import time
 
 import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -42,6 +43,15 @@ class StubRunner:
 
     def stage_bytes_total(self, stage):
         return self.bench.stage_bytes(stage, 2048) * self.units
+
+    def outputs(self, budget):
+        """Seeded host tensors in place of the analysis outputs: --dump-outputs' sampling and file writing."""
+        g = torch.Generator().manual_seed(5 + self.rank)
+        outs = {"mdct": torch.rand((self.units, 2, 1024), generator=g),
+                "posts": torch.randint(0, 1 << 20, (self.units, 2, 64), generator=g, dtype=torch.int32)}
+        got, idx = self.bench.sample_units(outs, budget, 7 + self.rank)
+        got["sample_index"] = idx
+        return got
 
     def workload_text(self):
         return "rank-logic rehearsal (no GPU work)"

@@ -210,7 +210,7 @@ import sys
 sys.path.insert(0, @ROOT@)
 import bench
 from tests.stub_runner import StubRunner
-rc = bench.main(["--gpus", "2", "--steps", "5", "--warmup", "1", "--backend", "gloo", "--blocks", "1000"], make_runner=StubRunner)
+rc = bench.main(["--gpus", "2", "--steps", "5", "--warmup", "1", "--backend", "gloo", "--blocks", "1000", "--full"], make_runner=StubRunner)
 sys.exit(rc)
 """
 
@@ -254,6 +254,34 @@ def test_bench_gpus_flag_launches_the_ranks_itself():
     assert r.returncode == 0, r.stdout + r.stderr
     line = _check_rehearsal_line(r.stdout)
     assert line["runner"] == "tests.stub_runner:StubRunner"     # a rehearsal says that it is one
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run times exactly --steps steps and prints the headline alone (the checks and the other figures are --full's);
+    --dump-outputs writes the last step's outputs as float32 / float64 .npy files, a fixed sample when they would pass the
+    budget, the same files on every run."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("d%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--blocks", "8000", "--runner", "tests.stub_runner:StubRunner", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stdout + r.stderr
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] >= 9.0
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "roofline"} <= set(line)
+        assert not {"parity_sample", "cpu_baseline", "workloads", "host_fed", "neighbours", "shader_clock"} & set(line)
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    assert set(dumps[0]) == {"mdct.npy", "posts.npy", "sample_index.npy"}
+    assert dumps[0]["mdct.npy"].dtype == np.float32 and dumps[0]["posts.npy"].dtype == np.float64
+    assert sum(x.nbytes for x in dumps[0].values()) <= 64 << 20
+    n = len(dumps[0]["sample_index.npy"])
+    assert 0 < n < 8000 and dumps[0]["mdct.npy"].shape == (n, 2, 1024)
+    for name, x in dumps[0].items():
+        assert np.array_equal(x, dumps[1][name]), name
 
 
 def test_bench_gpus_flag_must_agree_with_the_launcher():

@@ -1,4 +1,4 @@
-"""The drop-in as a deliverable (integration/Makefile): build/dropin/libvorbis.so.0.4.9 +
+"""The drop-in as a deliverable (integration/Makefile, built by build() under oracle/_ref/dropin): libvorbis.so.0.4.9 +
 libvorbisenc.so.2.0.12 with the reference's SONAMEs and export list, no test harness inside, and an application
 (integration/encode_loop.c: the call sequence of examples/encoder_example.c:140-236) that produces byte-identical
 packets on it and on the unmodified reference built beside it."""
@@ -8,10 +8,10 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "build", "dropin")
+OUT = os.path.join(ROOT, "oracle", "_ref", "dropin")
 LIB = os.path.join(OUT, "libvorbis.so.0.4.9")
 ENC = os.path.join(OUT, "libvorbisenc.so.2.0.12")
-needs_build = pytest.mark.skipif(not os.path.exists(LIB), reason="build/dropin not built (integration/Makefile needs the reference's sources)")
+needs_build = pytest.mark.skipif(not os.path.exists(LIB), reason="oracle/_ref/dropin not built (integration/Makefile needs the reference's sources)")
 
 
 def _names(path):

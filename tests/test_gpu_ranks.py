@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from oracle import ref
@@ -30,7 +31,7 @@ def _bench(*args):
 
 @pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (the per-rank parity sample needs it)")
 def test_two_ranks_of_the_real_runner_on_one_gpu():
-    common = ("--steps", "20", "--warmup", "3", "--blocks", "65536", "--no-cpu-baseline", "--no-neighbours", "--no-workloads")
+    common = ("--steps", "20", "--warmup", "3", "--blocks", "65536", "--full", "--no-cpu-baseline", "--no-neighbours", "--no-workloads")
     one = _bench("--gpus", "1", *common)
     two = _bench("--gpus", "2", "--backend", "gloo", "--share-gpu", *common)
     assert two["n_gpus"] == 2 and two["world"] == 2 and two["rccl_ranks_seen"] == 2 and two["backend"] == "gloo"
@@ -50,7 +51,7 @@ def test_two_ranks_default_line_carries_c5_host_fed_and_cpu_baseline():
     """The line a first multi-GPU run will print: with more than one rank the default run
     still yields C5, the host-fed figure and the CPU baseline (rank 0) -- rehearsed with two ranks on one GPU at reduced
     stream counts."""
-    two = _bench("--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "3", "--warmup", "1", "--streams", "48",
+    two = _bench("--gpus", "2", "--backend", "gloo", "--share-gpu", "--full", "--steps", "3", "--warmup", "1", "--streams", "48",
                  "--feed-streams", "16", "--feed-groups", "6", "--feed-lanes", "2", "--cpu-seconds", "2", "--no-neighbours")
     assert two["n_gpus"] == 2 and two["share_gpu"] is True
     c5 = two["workloads"]["c5"]
@@ -63,3 +64,22 @@ def test_two_ranks_default_line_carries_c5_host_fed_and_cpu_baseline():
     for d in (two, c5):
         r = d["roofline"]
         assert abs(r["alg_bytes_per_step"] / (d["ms_per_step"] * 1e-3) / 1e9 / r["peak"] - r["frac"]) < 0.01 * r["frac"]
+
+
+def test_plain_run_dumps_the_same_outputs_every_run(tmp_path):
+    """--dump-outputs on the real kernels: the timed path's outputs of its last step, float32 / float64 only, within 64 MB,
+    and the same arrays from a second run (the inputs are seeded); the mixed-size workload dumps both size classes."""
+    common = ("--gpus", "1", "--steps", "2", "--warmup", "1", "--blocks", "4096")
+    runs = []
+    for k in range(2):
+        line = _bench(*common, "--dump-outputs", str(tmp_path / ("c4_%d" % k)))
+        assert "parity_sample" not in line and line["steps"] == 2
+        runs.append({f.name: np.load(f) for f in sorted((tmp_path / ("c4_%d" % k)).iterdir())})
+    assert {"mdct.npy", "logmask.npy", "posts.npy", "iwork.npy", "ampmax_out.npy"} <= set(runs[0])
+    assert all(x.dtype in (np.float32, np.float64) for x in runs[0].values())
+    assert sum(x.nbytes for x in runs[0].values()) <= 64 << 20
+    for name, x in runs[0].items():
+        assert np.array_equal(x, runs[1][name], equal_nan=True), name
+    _bench("--gpus", "1", "--workload", "c5", "--streams", "32", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "c5"))
+    c5 = {f.name for f in (tmp_path / "c5").iterdir()}
+    assert {"ampmax_state.npy", "stream_start.npy", "short_mdct.npy", "long_mdct.npy", "long_blocktype.npy"} <= c5

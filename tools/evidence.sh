@@ -13,7 +13,7 @@ timeout 900 python tools/soak.py ${SOAK:-20000} $R/gpurun_out/soak.txt > /dev/nu
 tail -3 $R/gpurun_out/soak.txt > $E/soak_tail.txt
 bash tools/profile.sh > $E/profile.log 2>&1
 for w in c4 c5 c3 c2; do
-  timeout 900 python bench.py --workload $w > $E/bench_$w.json 2> $E/bench_$w.err
+  timeout 900 python bench.py --full --workload $w > $E/bench_$w.json 2> $E/bench_$w.err
 done
 timeout 900 bash tools/batcher_sweep.sh > $E/batcher.txt 2>&1
 timeout 300 bash tools/kt_block.sh > $E/block_path.txt 2>&1
@@ -38,7 +38,7 @@ python tools/prof_summary.py kt $R/gpurun_out/hf_prof/hf_results.db > $E/host_fe
 # the drop-in library driven by the C application (integration/encode_loop.c), against the unmodified reference beside it
 : > $E/encode_loop.txt
 for cfg in "1024 0.4 2646000" "4096 0.4 2646000" "65536 0.4 2646000" "1024 0.9 2646000" "65536 0.9 2646000"; do set -- $cfg
-  LD_LIBRARY_PATH=build/dropin/ref:build/dropin ./build/dropin/encode_loop $1 $2 $3 write /tmp/el.pkts 2>> $E/encode_loop.txt
-  LD_LIBRARY_PATH=build/dropin ./build/dropin/encode_loop $1 $2 $3 check /tmp/el.pkts 2>> $E/encode_loop.txt
+  LD_LIBRARY_PATH=oracle/_ref/dropin/ref:oracle/_ref/dropin ./oracle/_ref/dropin/encode_loop $1 $2 $3 write /tmp/el.pkts 2>> $E/encode_loop.txt
+  LD_LIBRARY_PATH=oracle/_ref/dropin ./oracle/_ref/dropin/encode_loop $1 $2 $3 check /tmp/el.pkts 2>> $E/encode_loop.txt
 done
 ls -la $E
