@@ -184,6 +184,25 @@ typedef struct vamd_book_tab {
   int32_t  pad;
 } vamd_book_tab;
 
+/* the bitrate manager as vorbis_bitrate_init() (lib/bitrate.c:28-56) leaves it in private_state.bms, and the
+ * vorbis_info / bitrate_manager_info fields vorbis_bitrate_addblock() (:73-227) reads: packed, not recomputed, so that
+ * no rint() of the setup is redone elsewhere.  `long` values as int64, doubles as doubles.  Present (header.off_bitrate
+ * != 0) exactly when header.managed is. */
+typedef struct vamd_bitrate_tab {
+  int64_t short_per_long;    /* bm->short_per_long = blocksizes[1] / blocksizes[0] */
+  int64_t avg_bitsper;       /* bm->avg_bitsper, bits per short block's half (0: no average target) */
+  int64_t min_bitsper;       /* bm->min_bitsper (0: no minimum) */
+  int64_t max_bitsper;       /* bm->max_bitsper (0: no maximum) */
+  int64_t minmax_reservoir;  /* bm->minmax_reservoir at the stream's start */
+  int64_t avg_reservoir;     /* bm->avg_reservoir at the stream's start */
+  int64_t reservoir_bits;    /* ci->bi.reservoir_bits */
+  int64_t rate;              /* vi->rate */
+  double  avgfloat;          /* bm->avgfloat at the stream's start (PACKETBLOBS / 2) */
+  double  reservoir_bias;    /* ci->bi.reservoir_bias */
+  double  slew_damp;         /* ci->bi.slew_damp */
+  int64_t pad;
+} vamd_bitrate_tab;
+
 typedef struct vamd_setup_header {
   uint64_t magic;
   uint32_t version;
@@ -194,7 +213,8 @@ typedef struct vamd_setup_header {
   int32_t  managed;                /* the host runs a bitrate manager: blocks want all 15 candidate packets */
   int32_t  modebits;               /* private_state.modebits: width of a packet's mode number */
   int32_t  modes;                  /* ci->modes (1: both size classes share mode 0) */
-  int32_t  pad;
+  uint32_t off_bitrate;            /* the bitrate manager's vamd_bitrate_tab, or 0: none (every VBR blob; a managed blob
+                                      packed before the section existed) */
   vamd_xform_tab      xform[2];
   vamd_psy_tab        psy[4];
   vamd_psy_global_tab psy_g;

@@ -393,6 +393,40 @@ int vamd_analyze_block_res(vamd_ctx *ctx, const float *const *pcm, int lW, int W
                            int32_t *iwork, int32_t *nonzero, float *ampmax_out, int32_t *res_class,
                            uint16_t *res_entries, int32_t *res_count);
 
+/* The bitrate manager of a whole stream (vorbis_bitrate_addblock, lib/bitrate.c:73-227) on the device.  It does not
+ * feed back into the analysis: per stream it is a serial walk over the blocks' fifteen candidate sizes, which picks one
+ * candidate per block and cuts it (oggpack_writetrunc) or pads it with zero bytes where the reference does.  Needs a
+ * setup blob with the manager's section (vamd_setup_header.off_bitrate, written by vamd_pack_setup for every managed
+ * encoder); on any other context the three calls below return VAMD_EIMPL.  Device pointers, asynchronous on the
+ * context's stream.
+ *
+ * vamd_bitrate_state: bitrate_manager_state's evolving part, per stream.  vamd_bitrate_init_states() sets `nstreams` of
+ * them to a stream's start (what vorbis_bitrate_init leaves); a walk reads and updates them, so a stream may be walked
+ * in pieces, in order. */
+typedef struct vamd_bitrate_state {
+  double  avgfloat;          /* bm->avgfloat */
+  int64_t minmax_reservoir;  /* bm->minmax_reservoir */
+  int64_t avg_reservoir;     /* bm->avg_reservoir */
+  int64_t pad;
+} vamd_bitrate_state;
+int vamd_bitrate_init_states(vamd_ctx *ctx, vamd_bitrate_state *states, long nstreams);
+/* order / stream_start / nstreams as vamd_analyze_streams_mixed (order[] bit 30 = W, bits 0..29 = the block's index in
+ * its size class); per size class W: packet_bits[W] [nb_W][15] the candidates' oggpack_bits() (vamd_managed_io), status[W]
+ * [nb_W][ch] (or NULL: every block has its packets); out choice[W] [nb_W] the chosen candidate (0..14) and final_bits[W]
+ * [nb_W] oggpack_bits() of the packet the manager hands out ((final_bits + 7) / 8 bytes: the first bytes of the chosen
+ * candidate, then zero bytes where it was padded).  A block with a non-zero status has no packet: the state is left as
+ * it is and final_bits = -1, choice = 0.  Either class's arrays may be NULL where it has no blocks. */
+int vamd_bitrate_walk(vamd_ctx *ctx, const int32_t *order, const int64_t *stream_start, long nstreams,
+                      const int32_t *const packet_bits[2], const uint8_t *const status[2], vamd_bitrate_state *states,
+                      int32_t *const choice[2], int32_t *const final_bits[2]);
+/* vamd_analyze_streams_mixed for a bitrate-managed setup: each block's fifteen candidate packets (m_short / m_long as
+ * vamd_analyze_batch_managed; posts / post_valid / iwork / nonzero required, packets and packet_bits for the walk above),
+ * the ampmax chains per stream through ampmax_states, the blocks read in place where io->pcm_src is given. */
+int vamd_analyze_streams_mixed_managed(vamd_ctx *ctx, const vamd_batch_desc *desc_short, const vamd_batch_io *io_short,
+                                       const vamd_managed_io *m_short, const vamd_batch_desc *desc_long,
+                                       const vamd_batch_io *io_long, const vamd_managed_io *m_long, const int32_t *order,
+                                       const int64_t *stream_start, long nstreams, long nblocks_total, float *ampmax_states);
+
 /* One block from host memory all the way to its packet(s): what mapping0_forward leaves in
  * vbi->packetblob[] (lib/mapping0.c:593-687).  managed == 0: one packet (candidate PACKETBLOBS/2, the
  * VBR case); managed != 0: all 15 candidates of a bitrate-managed block.  packets [1 or 15][packet_stride]
@@ -536,8 +570,13 @@ vamd_ctx *vamd_batcher_context(vamd_batcher *b);
  *     vamd_feed_release(f, slot)           the lane may be handed out again
  * Every stream of a group is complete; vamd_feed_wrote() takes streams of one length, vamd_feed_wrote_v() of any lengths.
  * Per stream the packets are byte for byte what the reference encoder emits for the same samples written 1024 frames
- * at a time and closed with vorbis_analysis_wrote(v, 0) -- first block to last (tests/test_feed.py).  VBR setups whose
- * packets the GPU assembles (vamd_packet_capacity() > 0).  Thread rules: one thread drives a feed (or several, each
+ * at a time and closed with vorbis_analysis_wrote(v, 0) -- first block to last (tests/test_feed.py).  Setups whose
+ * packets the GPU assembles (vamd_packet_capacity() > 0): VBR, and bitrate-managed (ABR / CBR / min-max) ones whose blob
+ * carries the manager's section -- then every block's fifteen candidates are made, the manager walks each stream
+ * (vamd_bitrate_walk) and the chosen packet, cut or padded, is what comes back (tests/test_feed_managed.py).  The
+ * candidates are made in slices of at most 2048 blocks of the group (about 0.5 MB of HBM per long stereo block in the
+ * slice), the ampmax chains and the managers carried from slice to slice.  A managed blob without the section (packed
+ * before it existed) is refused by vamd_feed_create (VAMD_EIMPL; vamd_feed_last_error(NULL) says why).  Thread rules: one thread drives a feed (or several, each
  * with its own slots); the lanes' threads are the library's. */
 typedef struct vamd_feed vamd_feed;
 #define VAMD_FEED_S16 0 /* int16_t, interleaved; sample = x / 32768.f */
@@ -563,13 +602,15 @@ typedef struct vamd_feed_result {
   const int32_t *bits;            /* [nblocks] oggpack_bits() of the packet: (bits + 7) / 8 bytes; -1: no packet, see info */
   const int64_t *granulepos;      /* [nblocks] ogg_packet.granulepos (vb->granulepos, lib/block.c:620) */
   const uint8_t *info;            /* [nblocks] bit 0: vb->W; bit 1: last packet of its stream (op.e_o_s); bits 2-3: VAMD_STATUS_*
-                                     of a block outside the input domain (no packet) */
+                                     of a block outside the input domain (no packet); bits 4-7: the candidate the bitrate
+                                     manager chose (0..14, info >> 4) on a managed setup, 0 on a VBR one */
   const uint8_t *bytes;           /* the packets, end to end */
   int64_t total_bytes;
   double upload_ms, device_ms, total_ms; /* of this group: the upload alone; upload to last kernel; wrote() to ready */
 } vamd_feed_result;
 int vamd_feed_packets(vamd_feed *f, int slot, vamd_feed_result *out);
 int vamd_feed_release(vamd_feed *f, int slot);
+/* the text of the feed's last failure; with f == NULL, of this thread's last vamd_feed_create() that failed */
 const char *vamd_feed_last_error(const vamd_feed *f);
 
 #ifdef __cplusplus

@@ -305,6 +305,28 @@ long vamd_pack_setup(vorbis_dsp_state *vd, void *dst, long cap) {
     }
   }
 
+  if (b->bms.managed) {
+    /* the bitrate manager's state as vorbis_bitrate_init left it (lib/bitrate.c:28-56) and what
+       vorbis_bitrate_addblock reads beside it (:73-227); VBR blobs carry no such section */
+    bitrate_manager_state *bm = &b->bms;
+    bitrate_manager_info *bi = &ci->bi;
+    vamd_bitrate_tab t;
+    memset(&t, 0, sizeof(t));
+    t.short_per_long = bm->short_per_long;
+    t.avg_bitsper = bm->avg_bitsper;
+    t.min_bitsper = bm->min_bitsper;
+    t.max_bitsper = bm->max_bitsper;
+    t.minmax_reservoir = bm->minmax_reservoir;
+    t.avg_reservoir = bm->avg_reservoir;
+    t.reservoir_bits = bi->reservoir_bits;
+    t.rate = vi->rate;
+    t.avgfloat = bm->avgfloat;
+    t.reservoir_bias = bi->reservoir_bias;
+    t.slew_damp = bi->slew_damp;
+    h.off_bitrate = place(&cur, (uint32_t)sizeof(t));
+    put(dst, h.off_bitrate, &t, (uint32_t)sizeof(t));
+  }
+
   cur = (cur + 15u) & ~15u;
   h.total_bytes = cur;
   if (dst) memcpy(dst, &h, sizeof(h));

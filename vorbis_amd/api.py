@@ -27,7 +27,8 @@ EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe",
                     "vamd_batcher_encode_block", "vamd_batcher_last_error", "vamd_batcher_stats", "vamd_batcher_context", "vamd_batcher_report",
                     "vamd_input_status", "vamd_calib_copy", "vamd_abi_version", "vamd_plan_streams_whole", "vamd_plan_streams_whole_v", "vamd_feed_wrote_v", "vamd_device_count", "vamd_batcher_create_multi",
                     "vamd_feed_create", "vamd_feed_destroy", "vamd_feed_lanes", "vamd_feed_device", "vamd_feed_buffer", "vamd_feed_wrote",
-                    "vamd_feed_packets", "vamd_feed_release", "vamd_feed_last_error"]
+                    "vamd_feed_packets", "vamd_feed_release", "vamd_feed_last_error",
+                    "vamd_analyze_streams_mixed_managed", "vamd_bitrate_init_states", "vamd_bitrate_walk"]
 PACKETBLOBS = 15
 
 _vp = C.c_void_p
@@ -151,6 +152,10 @@ def load_library():
     L.vamd_feed_release.argtypes = [_vp, C.c_int]
     L.vamd_feed_last_error.argtypes = [_vp]
     L.vamd_feed_last_error.restype = C.c_char_p
+    L.vamd_analyze_streams_mixed_managed.argtypes = [_vp, C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO), C.POINTER(_Desc),
+                                                     C.POINTER(_IO), C.POINTER(_MIO), _vp, _vp, C.c_long, C.c_long, _vp]
+    L.vamd_bitrate_init_states.argtypes = [_vp, _vp, C.c_long]
+    L.vamd_bitrate_walk.argtypes = [_vp, _vp, _vp, C.c_long, _vp * 2, _vp * 2, _vp, _vp * 2, _vp * 2]
     L.vamd_plan_fetch.argtypes = [_vp, C.POINTER(_Plan), _vp * 2, _vp * 2, _vp * 2, _vp * 2, _vp, _vp]
     L.vamd_packet_capacity.argtypes = [_vp, C.c_int]
     L.vamd_submaps.argtypes = [_vp, C.c_int]
@@ -661,6 +666,86 @@ class Analyzer:
                                                       plan.order, plan.stream_start, plan.nstreams, plan.nblocks[0] + plan.nblocks[1],
                                                       _vp(ampmax_states.data_ptr())))
 
+    # ---- bitrate-managed whole streams: fifteen candidates per planned block, the manager's walk ----
+    def analyze_plan_managed(self, plan, streams, ampmax_states):
+        """vamd_analyze_streams_mixed_managed over a plan, the blocks read in place from `streams` (the [nstreams, ch,
+        nsamples] tensor the plan was made from).  ampmax_states: cuda float32 [nstreams], updated in place.  Returns per
+        size class (index 0 short, 1 long) a dict with `m_packets` [nb,15,packet_capacity] uint8, `m_packet_bits` [nb,15],
+        `status` [nb,ch] and the candidates' `m_posts` / `m_post_valid` / `m_iwork` / `m_nonzero`."""
+        t = self.torch
+        self._need_tensor(streams, t.float32, "streams")
+        self._need(streams.dim() == 3 and streams.shape[1] == self.channels and streams.shape[0] == plan.nstreams and
+                   streams.shape[2] % 4 == 0, "streams must be the [%d, %d, nsamples] tensor the plan was made from" % (plan.nstreams, self.channels))
+        self._need_tensor(ampmax_states, t.float32, "ampmax_states", numel=plan.nstreams)
+        dev, ch = self._dev(), self.channels
+        descs, ios, mios, outs = [], [], [], []
+        for W in (0, 1):
+            nb, n2 = plan.nblocks[W], self.blocksizes[W] // 2
+            d = _Desc()
+            d.W, d.nblocks = W, nb
+            d.lW, d.nW, d.blocktype, d.ampmax_in = plan.lW[W], plan.nW[W], plan.blocktype[W], None
+            descs.append(d)
+            o = {}
+            io, m = _IO(), _MIO()
+            if nb:
+                o = {"status": t.zeros((nb, ch), dtype=t.uint8, device=dev),
+                     "m_posts": t.empty((nb, PACKETBLOBS, ch, POSTS_STRIDE), dtype=t.int32, device=dev),
+                     "m_post_valid": t.empty((nb, PACKETBLOBS, ch), dtype=t.int32, device=dev),
+                     "m_iwork": t.empty((nb, PACKETBLOBS, ch, n2), dtype=t.int32, device=dev),
+                     "m_nonzero": t.empty((nb, PACKETBLOBS, ch), dtype=t.int32, device=dev),
+                     "m_packets": t.zeros((nb, PACKETBLOBS, self.packet_capacity(W)), dtype=t.uint8, device=dev),
+                     "m_packet_bits": t.zeros((nb, PACKETBLOBS), dtype=t.int32, device=dev)}
+                io.pcm, io.status = _vp(streams.data_ptr()), _vp(o["status"].data_ptr())
+                io.pcm_src, io.pcm_channel_stride = plan.src[W], streams.shape[2]
+                for k in ("posts", "post_valid", "iwork", "nonzero", "packets", "packet_bits"):
+                    setattr(m, k, _vp(o["m_" + k].data_ptr()))
+                m.packet_stride = o["m_packets"].shape[-1]
+            ios.append(io)
+            mios.append(m)
+            outs.append(o)
+        self._bind_stream()
+        self._check(self.L.vamd_analyze_streams_mixed_managed(self.h, C.byref(descs[0]), C.byref(ios[0]), C.byref(mios[0]),
+                                                              C.byref(descs[1]), C.byref(ios[1]), C.byref(mios[1]), plan.order,
+                                                              plan.stream_start, plan.nstreams, plan.nblocks[0] + plan.nblocks[1],
+                                                              _vp(ampmax_states.data_ptr())))
+        return outs
+
+    def bitrate_init_states(self, nstreams):
+        """vamd_bitrate_init_states: cuda uint8 [nstreams, 32] (vamd_bitrate_state each) at a stream's start."""
+        t = self.torch
+        states = t.zeros((nstreams, 32), dtype=t.uint8, device=self._dev())
+        self._bind_stream()
+        self._check(self.L.vamd_bitrate_init_states(self.h, _vp(states.data_ptr()), nstreams))
+        return states
+
+    def bitrate_walk(self, order, stream_start, packet_bits, states, status=None):
+        """vamd_bitrate_walk.  order: cuda int32 [nb] (W << 30 | index), stream_start: cuda int64 [nstreams + 1],
+        packet_bits: per size class a cuda int32 [nb_W, 15] (or None where the class has no blocks), status: per class
+        cuda uint8 [nb_W, ch] or None, states: bitrate_init_states() (updated).  -> (choice, final_bits), per class cuda
+        int32 [nb_W] (None where the class has no blocks)."""
+        t = self.torch
+        self._need_tensor(order, t.int32, "order")
+        self._need_tensor(stream_start, t.int64, "stream_start")
+        self._need_tensor(states, t.uint8, "states", numel=(stream_start.numel() - 1) * 32)
+        choice, final = [None, None], [None, None]
+        pb, st, ch_p, fb_p = _vp * 2, _vp * 2, _vp * 2, _vp * 2
+        pb, st, ch_p, fb_p = pb(), st(), ch_p(), fb_p()
+        for W in (0, 1):
+            if packet_bits[W] is None:
+                continue
+            self._need_tensor(packet_bits[W], t.int32, "packet_bits[%d]" % W)
+            nb = packet_bits[W].shape[0]
+            choice[W] = t.full((nb,), -7, dtype=t.int32, device=self._dev())
+            final[W] = t.full((nb,), -7, dtype=t.int32, device=self._dev())
+            pb[W], ch_p[W], fb_p[W] = packet_bits[W].data_ptr(), choice[W].data_ptr(), final[W].data_ptr()
+            if status is not None and status[W] is not None:
+                self._need_tensor(status[W], t.uint8, "status[%d]" % W, numel=nb * self.channels)
+                st[W] = status[W].data_ptr()
+        self._bind_stream()
+        self._check(self.L.vamd_bitrate_walk(self.h, _vp(order.data_ptr()), _vp(stream_start.data_ptr()), stream_start.numel() - 1,
+                                             pb, st, _vp(states.data_ptr()), ch_p, fb_p))
+        return choice, final
+
     def analyze_block(self, pcm, lW=1, W=1, nW=1, blocktype=BLOCKTYPE_LONG, ampmax_in=-9999.0):
         """vamd_analyze_block: host numpy pcm[ch][n] in, host numpy results out (the per-block
         compatibility path that sits behind vorbis_analysis())."""
@@ -864,7 +949,8 @@ class Feed:
         r = self.L.vamd_feed_create(C.byref(h), _vp(blob.ctypes.data), blob.size, arr if devs else None, len(devs), lanes_per_device,
                                     max_streams, max_frames, fmt)
         if r:
-            raise VamdError(r, "vamd_feed_create failed (setup without GPU-assembled packets, bad arguments, or a HIP failure)")
+            why = self.L.vamd_feed_last_error(None).decode()
+            raise VamdError(r, "vamd_feed_create failed: " + (why or "setup without GPU-assembled packets, bad arguments, or a HIP failure"))
         self.h = h
         self.max_streams, self.max_frames, self.fmt = max_streams, max_frames, fmt
         self.dtype = np.int16 if fmt == FEED_S16 else np.float32
@@ -910,7 +996,8 @@ class Feed:
 
     def packets(self, slot, copy=True):
         """Waits for the group.  -> dict: nstreams, nblocks, stream_start, offset, bits, granulepos, info (numpy views over
-        the lane's pinned output arena, or copies), bytes, total_bytes, upload_ms, device_ms, total_ms."""
+        the lane's pinned output arena, or copies), choice (info >> 4: the bitrate manager's candidate, 0 on a VBR setup),
+        bytes, total_bytes, upload_ms, device_ms, total_ms."""
         r = _FeedResult()
         self._check(self.L.vamd_feed_packets(self.h, slot, C.byref(r)))
         nb, ns = int(r.nblocks), int(r.nstreams)
@@ -923,6 +1010,7 @@ class Feed:
         return {"nstreams": ns, "nblocks": nb, "stream_start": view(r.stream_start, C.c_int64, ns + 1),
                 "offset": view(r.offset, C.c_int64, nb), "bits": view(r.bits, C.c_int32, nb),
                 "granulepos": view(r.granulepos, C.c_int64, nb), "info": view(r.info, C.c_uint8, nb),
+                "choice": (view(r.info, C.c_uint8, nb) >> 4).astype(np.int32),
                 "bytes": view(r.bytes, C.c_uint8, int(r.total_bytes)), "total_bytes": int(r.total_bytes),
                 "upload_ms": r.upload_ms, "device_ms": r.device_ms, "total_ms": r.total_ms}
 

@@ -34,6 +34,8 @@ struct Bound {
   int res_off_ints[2];    // largest stages*slots + 1 over the mode's submaps (k_pack's offset arrays)
   float ampmax_att_per_sec;
   QLimitP qlimit[2];      // the input domain's integer edge per size class and channel (derive_quant_limit)
+  int has_bitrate;        // the blob carries the bitrate manager's section (header.off_bitrate != 0)
+  vamd_bitrate_tab bitrate;  // ... and this is it (zero without one)
 };
 
 // Checks the blob and produces `image` = blob + derived tables (what gets copied to HBM).
@@ -315,6 +317,23 @@ inline int build_image(const void *blob_v, size_t bytes, std::vector<unsigned ch
         }
   }
 
+  if (h.off_bitrate) {
+    // the bitrate manager's section (k_bitrate.h): only where the encoder has a manager, and with the values
+    // vorbis_bitrate_init can leave (lib/bitrate.c:33-54: reservoir_bits > 0, the floater inside the fifteen candidates)
+    vamd_bitrate_tab t;
+    if ((h.off_bitrate & 15u) || (uint64_t)h.off_bitrate + sizeof(t) > h.total_bytes || !h.managed) {
+      *err = "setup blob: bitrate manager section out of range, or on a setup without a manager";
+      return VAMD_EINVAL;
+    }
+    memcpy(&t, blob + h.off_bitrate, sizeof(t));
+    if (t.short_per_long < 1 || t.rate < 1 || t.reservoir_bits < 1 || !(t.slew_damp > 0.) || !(t.avgfloat >= 0.) ||
+        !(t.avgfloat <= VAMD_PACKETBLOBS - 1) || !(t.reservoir_bias >= 0.) || t.avg_bitsper < 0 || t.min_bitsper < 0 ||
+        t.max_bitsper < 0) {
+      *err = "setup blob: bitrate manager values out of range";
+      return VAMD_EINVAL;
+    }
+  }
+
   image->assign(blob, blob + h.total_bytes);
   derived->clear();
   derived_off->clear();
@@ -527,6 +546,9 @@ inline void bind_params(const std::vector<unsigned char> &image, const std::vect
   B->bs[0] = h.blocksizes[0];
   B->bs[1] = h.blocksizes[1];
   B->ampmax_att_per_sec = h.psy_g.ampmax_att_per_sec;
+  B->has_bitrate = h.off_bitrate != 0;
+  memset(&B->bitrate, 0, sizeof(B->bitrate));
+  if (h.off_bitrate) memcpy(&B->bitrate, image.data() + h.off_bitrate, sizeof(B->bitrate));
   for (int W = 0; W < 2; W++) {
     const vamd_xform_tab &x = h.xform[W];
     XformP &X = B->xf[W];

@@ -29,6 +29,7 @@
 #include <thread>
 #include <vector>
 #include "vorbis_amd.h"
+#include "vamd_knobs.h"
 
 namespace {
 
@@ -190,6 +191,100 @@ __global__ __launch_bounds__(64) void k_feed_sid(const int64_t *__restrict__ str
   for (int64_t k = stream_start[s] + threadIdx.x; k < stream_start[s + 1]; k += 64) sid[k] = (int32_t)s;
 }
 
+// ---- bitrate-managed setups: a slice of the group's blocks at a time (run_group_managed) ----
+// What the two kernels below need of a slice: its blocks in stream order (order[] rebased to the slice's own batches,
+// stream_start over the slice's pieces of streams), the walk's choice / final_bits, the candidates' rows and bit counts
+// -- and of the group: the plan's stream_start, src and the streams' lengths, for the records.
+struct FeedSlice {
+  const int32_t *order;          // [slice blocks] W << 30 | index in the slice's batch of class W
+  const int64_t *stream_start;   // [slice streams + 1] into order[]
+  const int64_t *g_start;        // the plan's stream_start (whole group)
+  const int64_t *src[2];         // the plan's src[W] (whole group)
+  const int32_t *choice[2], *fbits[2], *mbits[2];  // [slice batch] / [slice batch][15]
+  const uint8_t *status[2];
+  const uint8_t *packets[2];     // [slice batch][15][stride]
+  int64_t stride[2];
+  int64_t i0[2];                 // the slice's first block of class W in the plan's batches
+  int64_t k0;                    // ... and its first block in the plan's order[]
+  long s0;                       // the group stream of the slice's first stream
+  int bs[2];
+  int ch;
+  int64_t stream_stride, eof;
+  const long long *frames_of;
+  int head;
+};
+
+// a wave per slice stream: rel[k] = bytes (each handed-out packet rounded up to 4) of the slice stream's packets before k
+__global__ __launch_bounds__(64) void k_feed_sizes_managed(FeedSlice P, int64_t *__restrict__ rel, int64_t *__restrict__ stream_bytes) {
+  const long s = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int64_t k0 = P.stream_start[s], k1 = P.stream_start[s + 1];
+  int64_t run = 0;
+  for (int64_t base = k0; base < k1; base += 64) {
+    const int64_t k = base + lane;
+    int bytes = 0;
+    if (k < k1) {
+      const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
+      unsigned st = 0;
+      for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
+      bytes = st ? 0 : (((P.fbits[W][i] + 7) >> 3) + 3) & ~3;
+    }
+    int incl = bytes;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += up;
+    }
+    if (k < k1) rel[k] = run + incl - bytes;
+    run += __shfl(incl, 63, 64);
+  }
+  if (lane == 0) stream_bytes[s] = run;
+}
+
+// a wave per packet of the slice: the chosen candidate's first bytes, zero bytes behind them up to the handed-out size
+// (the manager's padding) and to the next multiple of 4, into the output arena at base + stream_off + rel; the record of
+// the packet at its place in the group (k0 + k)
+__global__ __launch_bounds__(256) void k_feed_copy_managed(FeedSlice P, long nblocks, int64_t base, const int64_t *__restrict__ rel,
+                                                           const int64_t *__restrict__ stream_off, const int32_t *__restrict__ sid,
+                                                           FeedOut O) {
+  const long k = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (k >= nblocks) return;
+  const int ls = sid[k];
+  const long s = P.s0 + ls;
+  const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
+  unsigned st = 0;
+  for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
+  const int choice = P.choice[W][i], fbits = P.fbits[W][i];
+  const int64_t fb = st ? 0 : ((int64_t)fbits + 7) >> 3;
+  int64_t own = st ? 0 : ((int64_t)P.mbits[W][(int64_t)i * VAMD_PACKETBLOBS + choice] + 7) >> 3;
+  if (own > P.stride[W]) own = P.stride[W];
+  const int64_t keep = own < fb ? own : fb, words = (fb + 3) >> 2;
+  const int64_t off = base + stream_off[ls] + rel[k];
+  if (off + 4 * words <= O.cap) {
+    const uint8_t *row = P.packets[W] + ((int64_t)i * VAMD_PACKETBLOBS + choice) * P.stride[W];
+    uint32_t *dst = (uint32_t *)(O.bytes + off);
+    for (int64_t w = lane; w < words; w += 64) {
+      uint32_t v = 0;
+      if (4 * w < keep) {
+        v = ((const uint32_t *)row)[w];
+        const int64_t live = keep - 4 * w;  // bytes of this word that are the candidate's
+        if (live < 4) v &= (1u << (8 * live)) - 1u;
+      }
+      dst[w] = v;
+    }
+  }
+  if (lane == 0) {
+    const int64_t g = P.k0 + k, gi = P.i0[W] + i;
+    const int64_t begin = P.src[W][gi] - (int64_t)s * P.stream_stride, center = begin + P.bs[W] / 2;
+    const bool last = g + 1 == P.g_start[s + 1];
+    O.offset[g] = off;
+    O.bits[g] = st ? -1 : fbits;
+    const int64_t eof = P.frames_of ? (int64_t)P.head + P.frames_of[s] : P.eof;
+    O.granulepos[g] = (center < eof ? center : eof) - P.bs[1] / 2;
+    O.info[g] = (uint8_t)(W | (last ? 2 : 0) | ((st & 3) << 2) | ((st ? 0 : choice) << 4));
+  }
+}
+
 struct Buf {
   void *p = nullptr;
   size_t bytes = 0;
@@ -206,6 +301,17 @@ struct Buf {
     if (p) (void)(host ? hipHostFree(p) : hipFree(p));
     p = nullptr, bytes = 0;
   }
+  // pinned host memory only: at least n bytes, the first `keep` kept
+  hipError_t grow_keeping(size_t n, size_t keep) {
+    if (bytes >= n) return hipSuccess;
+    void *q = nullptr;
+    const hipError_t e = hipHostMalloc(&q, n, hipHostMallocDefault);
+    if (e != hipSuccess) return e;
+    if (p && keep) memcpy(q, p, keep < bytes ? keep : bytes);
+    drop();
+    p = q, bytes = n;
+    return hipSuccess;
+  }
 };
 
 }  // namespace
@@ -221,6 +327,10 @@ struct FeedLane {
   Buf d_in, d_pcm, d_states, d_amp;            // HBM: the samples as they came; as floats, planar; detector states; ampmax chains
   Buf d_pk[2], d_bits[2], d_status[2];         // the analysis' packet rows per size class
   Buf d_rel, d_sid, d_sbytes, d_soff, d_len, h_len;  // (d_len / h_len: [frames_of | first_of] of a group of unequal streams)
+  // bitrate-managed setups (run_group_managed): a slice's fifteen candidates per block and what the analysis needs beside
+  // them, the walk's answers, the managers' states, the slices' rebased lists (h_slice pinned, d_slice its copy)
+  Buf d_mpk[2], d_mbits[2], d_mposts[2], d_mvalid[2], d_miwork[2], d_mnz[2], d_choice[2], d_fbits[2];
+  Buf d_bstate, d_slice, h_slice;
   std::thread worker;
   std::mutex *upload_turn = nullptr;  // its device's (vamd_feed::upload_turns)
   // the job (guarded by vamd_feed::m)
@@ -238,6 +348,8 @@ struct FeedLane {
 struct vamd_feed {
   std::vector<FeedLane> lanes;
   int ch = 0, bs[2] = {0, 0};
+  bool managed = false;  // the blob carries a bitrate manager (vamd_setup_header.off_bitrate): run_group_managed
+  long slice = 2048;     // blocks per slice of a managed group (VAMD_FEED_SLICE, a test knob)
   long pkcap[2] = {0, 0};
   long max_streams = 0, max_frames = 0;
   int format = VAMD_FEED_S16;
@@ -265,6 +377,180 @@ struct vamd_feed {
       return r__;                                                                   \
     }                                                                               \
   } while (0)
+
+// A bitrate-managed group, from its plan on: the blocks in slices of at most f->slice (in order[] order, so a slice holds
+// the end of one stream, whole streams, the start of another), each slice through
+//   vamd_analyze_streams_mixed_managed (fifteen candidate packets per block; the ampmax chains resume per stream) ->
+//   vamd_bitrate_walk (the managers resume per stream) -> the handed-out packets laid end to end behind the previous
+//   slice's, straight into the pinned arena
+// The workspace is bounded by the slice, not the group: a long stereo block's candidates alone take 15 x its integer
+// residue (120 KB) and 15 packet rows.  The host waits once per slice for the slice's byte count (to grow the arena
+// before anything is written into it: the candidates do not outlive their slice).
+static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, long ss, long cs, const long long *d_frames_of) {
+  const long ns = L.nstreams, frames = L.frames;
+  const int ch = f->ch, head = f->bs[1] / 2;
+  const long nb = (long)(plan.nblocks[0] + plan.nblocks[1]);
+  hipStream_t st = L.stream;
+  std::vector<int32_t> order((size_t)(nb ? nb : 1));
+  std::vector<int64_t> start((size_t)ns + 1);
+  FEED_CALL(vamd_plan_fetch(L.ctx, &plan, nullptr, nullptr, nullptr, nullptr, order.data(), start.data()));
+  // the slices: [k0, k1) of order[], their first stream, their classes' first blocks and counts, order[] rebased to the
+  // slice's batches and stream_start over the slice's pieces of streams -- all slices' lists in one upload
+  struct Slice {
+    long k0, k1, s0, s1;  // s1: one past the slice's last stream
+    int64_t i0[2], n[2];
+    size_t starts;        // where its stream_start lies in the uploaded lists (int64 units, behind the rebased order[])
+  };
+  std::vector<Slice> sl;
+  const long S = f->slice;
+  int64_t seen[2] = {0, 0}, most[2] = {0, 0};
+  size_t nstarts = 0;
+  long s = 0;
+  for (long k0 = 0; k0 < nb; k0 += S) {
+    Slice x;
+    x.k0 = k0, x.k1 = k0 + S < nb ? k0 + S : nb;
+    while (start[(size_t)s + 1] <= k0) s++;
+    x.s0 = s;
+    x.s1 = s;
+    while (x.s1 < ns && start[(size_t)x.s1] < x.k1) x.s1++;
+    x.i0[0] = seen[0], x.i0[1] = seen[1];
+    for (long k = x.k0; k < x.k1; k++) {
+      const int o = order[(size_t)k], W = (o >> 30) & 1, i = o & 0x3fffffff;
+      if (i != seen[W]) {  // (the plan numbers each class's blocks in stream order: vamd_plan_streams)
+        L.err = "stream plan: a size class's blocks are not numbered in stream order";
+        return VAMD_EFAULT;
+      }
+      seen[W]++;
+      order[(size_t)k] = (W << 30) | (int)(i - x.i0[W]);
+    }
+    for (int W = 0; W < 2; W++) {
+      x.n[W] = seen[W] - x.i0[W];
+      if (x.n[W] > most[W]) most[W] = x.n[W];
+    }
+    x.starts = nstarts;
+    nstarts += (size_t)(x.s1 - x.s0) + 1;
+    sl.push_back(x);
+  }
+  const size_t lists = al((size_t)(nb ? nb : 1) * 4, 8) + nstarts * 8;
+  FEED_TRY(L.h_slice.need(lists + 16));
+  FEED_TRY(L.d_slice.need(lists + 16));
+  int64_t *h_total = (int64_t *)L.h_slice.p;  // [0]: the slice's byte count on its way back
+  uint8_t *hl = (uint8_t *)L.h_slice.p + 16, *dl = (uint8_t *)L.d_slice.p + 16;
+  memcpy(hl, order.data(), (size_t)nb * 4);
+  int64_t *hs = (int64_t *)(hl + al((size_t)(nb ? nb : 1) * 4, 8));
+  for (const Slice &x : sl)
+    for (long j = x.s0; j <= x.s1; j++) {
+      const int64_t a = j == x.s0 ? x.k0 : (j == x.s1 ? x.k1 : start[(size_t)j]);
+      hs[x.starts + (size_t)(j - x.s0)] = (a < x.k0 ? x.k0 : (a > x.k1 ? x.k1 : a)) - x.k0;
+    }
+  FEED_TRY(hipMemcpyAsync(dl, hl, lists, hipMemcpyHostToDevice, st));
+  const int32_t *d_order = (const int32_t *)dl;
+  const int64_t *d_starts = (const int64_t *)(dl + al((size_t)(nb ? nb : 1) * 4, 8));
+  // the slice's buffers, sized for the largest slice of each class
+  const int K = VAMD_PACKETBLOBS;
+  for (int W = 0; W < 2; W++) {
+    const size_t m = (size_t)(most[W] ? most[W] : 1), n2 = (size_t)f->bs[W] / 2;
+    FEED_TRY(L.d_mpk[W].need(m * K * (size_t)f->pkcap[W]));
+    FEED_TRY(L.d_mbits[W].need(m * K * 4));
+    FEED_TRY(L.d_mposts[W].need(m * K * ch * VAMD_POSTS_STRIDE * 4));
+    FEED_TRY(L.d_mvalid[W].need(m * K * ch * 4));
+    FEED_TRY(L.d_miwork[W].need(m * K * ch * n2 * 4));
+    FEED_TRY(L.d_mnz[W].need(m * K * ch * 4));
+    FEED_TRY(L.d_status[W].need(m * (size_t)ch));
+    FEED_TRY(L.d_choice[W].need(m * 4));
+    FEED_TRY(L.d_fbits[W].need(m * 4));
+  }
+  const size_t most_slice = (size_t)(S < nb ? S : (nb ? nb : 1));
+  FEED_TRY(L.d_rel.need(most_slice * 8));
+  FEED_TRY(L.d_sid.need(most_slice * 4));
+  FEED_TRY(L.d_sbytes.need((size_t)ns * 8));
+  FEED_TRY(L.d_soff.need((size_t)(ns + 1) * 8));
+  FEED_TRY(L.d_bstate.need((size_t)ns * sizeof(vamd_bitrate_state)));
+  FEED_CALL(vamd_bitrate_init_states(L.ctx, (vamd_bitrate_state *)L.d_bstate.p, ns));
+  // records: [total | stream_start (ns + 1) | offset (nb) | granulepos (nb) | bits (nb) | info (nb)], as run_group's
+  const size_t o_start = 8, o_off = o_start + (size_t)(ns + 1) * 8, o_gp = o_off + (size_t)nb * 8, o_bits = o_gp + (size_t)nb * 8,
+               o_info = o_bits + (size_t)nb * 4, rec_bytes = al(o_info + (size_t)nb, 16);
+  FEED_TRY(L.h_rec.need(rec_bytes + rec_bytes / 4));
+  uint8_t *hrec = (uint8_t *)L.h_rec.p;
+  void *drec = nullptr;
+  FEED_TRY(hipHostGetDevicePointer(&drec, hrec, 0));
+  int64_t base = 0;  // bytes of the packets laid out so far
+  for (const Slice &x : sl) {
+    const long nss = x.s1 - x.s0, nbs = x.k1 - x.k0;
+    vamd_batch_desc desc[2];
+    vamd_batch_io io[2];
+    vamd_managed_io m[2];
+    for (int W = 0; W < 2; W++) {
+      memset(&desc[W], 0, sizeof(desc[W]));
+      memset(&io[W], 0, sizeof(io[W]));
+      memset(&m[W], 0, sizeof(m[W]));
+      desc[W].W = W;
+      desc[W].nblocks = (long)x.n[W];
+      if (!x.n[W]) continue;
+      desc[W].lW = plan.lW[W] + x.i0[W], desc[W].nW = plan.nW[W] + x.i0[W], desc[W].blocktype = plan.blocktype[W] + x.i0[W];
+      io[W].pcm = (const float *)L.d_pcm.p;
+      io[W].pcm_src = plan.src[W] + x.i0[W];
+      io[W].pcm_channel_stride = cs;
+      io[W].status = (uint8_t *)L.d_status[W].p;
+      m[W].posts = (int32_t *)L.d_mposts[W].p;
+      m[W].post_valid = (int32_t *)L.d_mvalid[W].p;
+      m[W].iwork = (int32_t *)L.d_miwork[W].p;
+      m[W].nonzero = (int32_t *)L.d_mnz[W].p;
+      m[W].packets = (uint8_t *)L.d_mpk[W].p;
+      m[W].packet_bits = (int32_t *)L.d_mbits[W].p;
+      m[W].packet_stride = f->pkcap[W];
+    }
+    const int32_t *o = d_order + x.k0;
+    const int64_t *ls = d_starts + x.starts;
+    FEED_CALL(vamd_analyze_streams_mixed_managed(L.ctx, &desc[0], &io[0], &m[0], &desc[1], &io[1], &m[1], o, ls, nss, nbs,
+                                                 (float *)L.d_amp.p + x.s0));
+    const int32_t *bits[2] = {(const int32_t *)L.d_mbits[0].p, (const int32_t *)L.d_mbits[1].p};
+    const uint8_t *stat[2] = {(const uint8_t *)L.d_status[0].p, (const uint8_t *)L.d_status[1].p};
+    int32_t *choice[2] = {(int32_t *)L.d_choice[0].p, (int32_t *)L.d_choice[1].p};
+    int32_t *fbits[2] = {(int32_t *)L.d_fbits[0].p, (int32_t *)L.d_fbits[1].p};
+    FEED_CALL(vamd_bitrate_walk(L.ctx, o, ls, nss, bits, stat, (vamd_bitrate_state *)L.d_bstate.p + x.s0, choice, fbits));
+    FeedSlice P;
+    P.order = o, P.stream_start = ls, P.g_start = plan.stream_start;
+    for (int W = 0; W < 2; W++) {
+      P.src[W] = plan.src[W], P.choice[W] = choice[W], P.fbits[W] = fbits[W], P.mbits[W] = bits[W], P.status[W] = stat[W];
+      P.packets[W] = (const uint8_t *)L.d_mpk[W].p, P.stride[W] = f->pkcap[W], P.i0[W] = x.i0[W], P.bs[W] = f->bs[W];
+    }
+    P.k0 = x.k0, P.s0 = x.s0, P.ch = ch, P.stream_stride = ss, P.eof = head + frames, P.frames_of = d_frames_of, P.head = head;
+    hipLaunchKernelGGL(k_feed_sid, dim3((unsigned)nss), dim3(64), 0, st, ls, (int32_t *)L.d_sid.p);
+    hipLaunchKernelGGL(k_feed_sizes_managed, dim3((unsigned)nss), dim3(64), 0, st, P, (int64_t *)L.d_rel.p, (int64_t *)L.d_sbytes.p);
+    hipLaunchKernelGGL(k_feed_scan, dim3(1), dim3(1024), 0, st, nss, (const int64_t *)L.d_sbytes.p, (int64_t *)L.d_soff.p);
+    FEED_TRY(hipGetLastError());
+    FEED_TRY(hipMemcpyAsync(h_total, (const int64_t *)L.d_soff.p + nss, 8, hipMemcpyDeviceToHost, st));
+    FEED_TRY(hipStreamSynchronize(st));
+    const int64_t need = base + *h_total;
+    if (need > (int64_t)L.h_out.bytes) FEED_TRY(L.h_out.grow_keeping((size_t)need + (size_t)need / 8, (size_t)base));
+    void *dbytes = nullptr;
+    FEED_TRY(hipHostGetDevicePointer(&dbytes, L.h_out.p, 0));
+    FeedOut O;
+    uint8_t *dr = (uint8_t *)drec;
+    O.total = (int64_t *)dr, O.stream_start = (int64_t *)(dr + o_start), O.offset = (int64_t *)(dr + o_off);
+    O.granulepos = (int64_t *)(dr + o_gp), O.bits = (int32_t *)(dr + o_bits), O.info = dr + o_info;
+    O.bytes = (uint8_t *)dbytes, O.cap = (int64_t)L.h_out.bytes;
+    hipLaunchKernelGGL(k_feed_copy_managed, dim3((unsigned)((nbs + 3) / 4)), dim3(256), 0, st, P, nbs, base, (const int64_t *)L.d_rel.p,
+                       (const int64_t *)L.d_soff.p, (const int32_t *)L.d_sid.p, O);
+    FEED_TRY(hipGetLastError());
+    base = need;
+  }
+  FEED_TRY(hipEventRecord(L.ev_end, st));
+  FEED_TRY(hipEventSynchronize(L.ev_end));
+  *(int64_t *)hrec = base;
+  memcpy(hrec + o_start, start.data(), (size_t)(ns + 1) * 8);
+  vamd_feed_result &R = L.result;
+  R.nstreams = ns, R.nblocks = nb;
+  R.stream_start = (const int64_t *)(hrec + o_start), R.offset = (const int64_t *)(hrec + o_off);
+  R.granulepos = (const int64_t *)(hrec + o_gp), R.bits = (const int32_t *)(hrec + o_bits), R.info = hrec + o_info;
+  R.bytes = (const uint8_t *)L.h_out.p, R.total_bytes = base;
+  float up = 0.f, dev = 0.f;
+  (void)hipEventElapsedTime(&up, L.ev0, L.ev_up);
+  (void)hipEventElapsedTime(&dev, L.ev0, L.ev_end);
+  L.result.upload_ms = up, L.result.device_ms = dev;
+  return VAMD_OK;
+}
 
 // one group through its lane (the lane's own thread; its device is current)
 static int run_group(vamd_feed *f, FeedLane &L) {
@@ -328,6 +614,7 @@ static int run_group(vamd_feed *f, FeedLane &L) {
     FEED_CALL(vamd_plan_streams_whole_v(L.ctx, (float *)L.d_pcm.p, ss, cs, ns, frames, L.frames_of.data(), (vamd_envelope_state *)L.d_states.p, &plan));
   else
     FEED_CALL(vamd_plan_streams_whole(L.ctx, (float *)L.d_pcm.p, ss, cs, ns, frames, (vamd_envelope_state *)L.d_states.p, &plan));
+  if (f->managed) return run_group_managed(f, L, plan, ss, cs, d_frames_of);
   const long nb = (long)(plan.nblocks[0] + plan.nblocks[1]);
   vamd_batch_desc desc[2];
   vamd_batch_io io[2];
@@ -445,7 +732,11 @@ static void feed_free(vamd_feed *f) {
     if (L.stream) (void)hipStreamSynchronize(L.stream);
     if (L.ctx) vamd_destroy(L.ctx);
     Buf *all[] = {&L.d_len, &L.h_len, &L.h_in, &L.h_out, &L.h_rec, &L.d_in, &L.d_pcm, &L.d_states, &L.d_amp, &L.d_pk[0], &L.d_pk[1], &L.d_bits[0],
-                  &L.d_bits[1], &L.d_status[0], &L.d_status[1], &L.d_rel, &L.d_sid, &L.d_sbytes, &L.d_soff};
+                  &L.d_bits[1], &L.d_status[0], &L.d_status[1], &L.d_rel, &L.d_sid, &L.d_sbytes, &L.d_soff, &L.d_bstate, &L.d_slice, &L.h_slice};
+    for (int W = 0; W < 2; W++) {
+      Buf *m[] = {&L.d_mpk[W], &L.d_mbits[W], &L.d_mposts[W], &L.d_mvalid[W], &L.d_miwork[W], &L.d_mnz[W], &L.d_choice[W], &L.d_fbits[W]};
+      for (Buf *b : m) b->drop();
+    }
     for (Buf *b : all) b->drop();
     if (L.ev0) (void)hipEventDestroy(L.ev0);
     if (L.ev_up) (void)hipEventDestroy(L.ev_up);
@@ -456,6 +747,9 @@ static void feed_free(vamd_feed *f) {
   f->lanes.clear();
 }
 
+// why this thread's last vamd_feed_create failed (vamd_feed_last_error(NULL))
+thread_local std::string feed_create_err;
+
 extern "C" {
 
 int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes, const int *devices, int ndevices,
@@ -465,6 +759,16 @@ int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes,
   if (!setup_blob || lanes_per_device < 1 || lanes_per_device > 8 || max_streams < 1 || max_frames < 1 || ndevices < 0 ||
       ndevices > 64 || (ndevices > 0 && !devices) || (format != VAMD_FEED_S16 && format != VAMD_FEED_F32))
     return VAMD_EINVAL;
+  feed_create_err.clear();
+  // a bitrate-managed setup is fed through its manager (run_group_managed), which needs the blob's manager section; a
+  // managed blob packed before the section existed would otherwise get the VBR candidate of every block
+  vamd_setup_header h;
+  memset(&h, 0, sizeof(h));
+  if (blob_bytes >= sizeof(h)) memcpy(&h, setup_blob, sizeof(h));
+  if (h.managed && !h.off_bitrate) {
+    feed_create_err = "bitrate-managed setup blob without the bitrate manager's section (packed before it existed): repack it with vamd_pack_setup";
+    return VAMD_EIMPL;
+  }
   int cur = 0;
   if (hipGetDevice(&cur) != hipSuccess) return VAMD_EFAULT;
   std::vector<int> devs;
@@ -472,6 +776,11 @@ int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes,
   for (int i = 0; i < ndevices; i++) devs.push_back(devices[i] >= 0 ? devices[i] : cur);
   vamd_feed *f = new vamd_feed;
   f->max_streams = max_streams, f->max_frames = max_frames, f->format = format;
+  f->managed = h.managed && h.off_bitrate;
+  {
+    const vamd::Knobs K = vamd::read_knobs();
+    f->slice = K.feed_slice > 0 ? K.feed_slice : 2048;
+  }
   f->lanes.resize(devs.size() * (size_t)lanes_per_device);
   for (size_t d = 0; d < devs.size(); d++) f->upload_turns.emplace_back(new std::mutex);
   int r = VAMD_OK;
@@ -480,7 +789,7 @@ int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes,
     FeedLane &L = f->lanes[l];
     L.device = devs[l % devs.size()];
     L.upload_turn = f->upload_turns[l % devs.size()].get();
-    L.h_in.host = L.h_out.host = L.h_rec.host = L.h_len.host = true;
+    L.h_in.host = L.h_out.host = L.h_rec.host = L.h_len.host = L.h_slice.host = true;
     r = vamd_create(&L.ctx, setup_blob, blob_bytes, L.device);
     if (r) break;
     hipError_t e = hipSetDevice(L.device);
@@ -510,6 +819,8 @@ int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes,
     }
   }
   if (r) {
+    feed_create_err = f->lanes.empty() || !f->lanes[0].ctx ? "vamd_create failed (setup blob refused, or a HIP failure)"
+                                                              : "the setup's packets are not assembled on the GPU, or a HIP failure";
     feed_free(f);
     delete f;
     return r;
@@ -615,6 +926,6 @@ int vamd_feed_release(vamd_feed *f, int slot) {
   return VAMD_OK;
 }
 
-const char *vamd_feed_last_error(const vamd_feed *f) { return f ? f->err.c_str() : "null feed"; }
+const char *vamd_feed_last_error(const vamd_feed *f) { return f ? f->err.c_str() : feed_create_err.c_str(); }
 
 }  // extern "C"

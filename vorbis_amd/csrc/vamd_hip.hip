@@ -35,6 +35,7 @@
 #include "k_pack.h"
 #include "k_blockout.h"
 #include "k_lpc.h"
+#include "k_bitrate.h"
 
 using namespace vamd;
 
@@ -1053,6 +1054,74 @@ int vamd_analyze_streams_mixed(vamd_ctx *c, const vamd_batch_desc *desc_short, c
   if (nstreams < 1 || !stream_start || !ampmax_states) return fail(c, VAMD_EINVAL, "stream_start / ampmax_states / nstreams");
   return run_streams_mixed(c, desc_short, io_short, desc_long, io_long, order, nblocks_total, nullptr, stream_start, nstreams,
                            ampmax_states);
+}
+
+int vamd_analyze_streams_mixed_managed(vamd_ctx *c, const vamd_batch_desc *desc_short, const vamd_batch_io *io_short,
+                                       const vamd_managed_io *m_short, const vamd_batch_desc *desc_long,
+                                       const vamd_batch_io *io_long, const vamd_managed_io *m_long, const int32_t *order,
+                                       const int64_t *stream_start, long nstreams, long nblocks_total, float *ampmax_states) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  if (!desc_short || !desc_long) return fail(c, VAMD_EINVAL, "null argument");
+  if (nstreams < 1 || !stream_start || !ampmax_states) return fail(c, VAMD_EINVAL, "stream_start / ampmax_states / nstreams");
+  const vamd_managed_io *m[2] = {m_short, m_long};
+  const vamd_batch_desc *d[2] = {desc_short, desc_long};
+  vamd_batch_io shared[2];
+  const vamd_batch_io *io[2] = {io_short, io_long};
+  for (int W = 0; W < 2; W++) {
+    memset(&shared[W], 0, sizeof(shared[W]));
+    if (!d[W]->nblocks) continue;
+    if (!io[W]) return fail(c, VAMD_EINVAL, "null io of a size class with blocks");
+    const vamd_managed_io *mm = m[W];
+    if (!mm || !mm->posts || !mm->post_valid || !mm->iwork || !mm->nonzero)
+      return fail(c, VAMD_EINVAL, "managed outputs posts / post_valid / iwork / nonzero are required");
+    if (mm->res_class || mm->res_entries || mm->res_count) {
+      if (!(mm->res_class && mm->res_entries && mm->res_count))
+        return fail(c, VAMD_EINVAL, "res_class / res_entries / res_count go together");
+      if (!c->B.res_cap[W])
+        return fail(c, VAMD_EIMPL, "this mode's residue back-end is not covered on the GPU (residue types 1 and 2 are)");
+    }
+    int r;
+    if ((mm->packets || mm->packet_bits) && (r = check_packets(c, W, VAMD_LEVEL_FULL, mm->packets, mm->packet_bits, mm->packet_stride)))
+      return r;
+    shared[W] = *io[W];  // per-candidate fields of the VBR io do not apply (vamd_analyze_batch_managed)
+    shared[W].packets = nullptr;
+    shared[W].packet_bits = nullptr;
+    shared[W].posts = shared[W].post_valid = shared[W].ilogmask = shared[W].iwork = shared[W].nonzero = nullptr;
+    shared[W].res_class = nullptr;
+    shared[W].res_entries = nullptr;
+    shared[W].res_count = nullptr;
+  }
+  return run_streams_mixed(c, desc_short, &shared[0], desc_long, &shared[1], order, nblocks_total, nullptr, stream_start, nstreams,
+                           ampmax_states, false, desc_short->nblocks ? m_short : nullptr, desc_long->nblocks ? m_long : nullptr);
+}
+
+int vamd_bitrate_init_states(vamd_ctx *c, vamd_bitrate_state *states, long nstreams) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  if (!c->B.has_bitrate) return fail(c, VAMD_EIMPL, "the setup blob carries no bitrate manager (a VBR setup, or one packed without the section)");
+  if (nstreams < 1 || !states) return fail(c, VAMD_EINVAL, "states / nstreams");
+  hipLaunchKernelGGL(k_bitrate_init, dim3((unsigned)((nstreams + 255) / 256)), dim3(256), 0, c->stream, c->B.bitrate, nstreams, states);
+  HIP_TRY(c, hipGetLastError());
+  return VAMD_OK;
+}
+
+int vamd_bitrate_walk(vamd_ctx *c, const int32_t *order, const int64_t *stream_start, long nstreams,
+                      const int32_t *const packet_bits[2], const uint8_t *const status[2], vamd_bitrate_state *states,
+                      int32_t *const choice[2], int32_t *const final_bits[2]) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  if (!c->B.has_bitrate) return fail(c, VAMD_EIMPL, "the setup blob carries no bitrate manager (a VBR setup, or one packed without the section)");
+  if (nstreams < 1 || !order || !stream_start || !states || !packet_bits || !choice || !final_bits)
+    return fail(c, VAMD_EINVAL, "order / stream_start / states / packet_bits / choice / final_bits / nstreams");
+  // (a size class without blocks may pass NULL arrays: order[] never names one of its blocks)
+  hipLaunchKernelGGL(k_bitrate_walk, dim3((unsigned)((nstreams + 63) / 64)), dim3(64), 0, c->stream, c->B.bitrate, c->B.bs[0] >> 1,
+                     c->B.bs[1] >> 1, c->B.channels, nstreams, (const long long *)stream_start, (const int *)order,
+                     (const int *)packet_bits[0], (const int *)packet_bits[1], status ? status[0] : nullptr,
+                     status ? status[1] : nullptr, states, (int *)choice[0], (int *)choice[1], (int *)final_bits[0],
+                     (int *)final_bits[1]);
+  HIP_TRY(c, hipGetLastError());
+  return VAMD_OK;
 }
 
 int vamd_analyze_block(vamd_ctx *c, const float *const *pcm, int lW, int W, int nW, int blocktype, float ampmax_in,

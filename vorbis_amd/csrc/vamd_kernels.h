@@ -394,6 +394,48 @@ __global__ __launch_bounds__(64) void k_ampmax_streams_mixed(int ch, long nstrea
   if (LANE == 0) states[sidx] = amp;
 }
 
+// the bitrate manager (k_bitrate.h): a lane per stream walks its blocks in order[] order with the stream's state in
+// registers; a block outside the input domain (status) has no packet and leaves the state alone
+__global__ __launch_bounds__(64) void k_bitrate_walk(vamd_bitrate_tab t, int samples0, int samples1, int ch, long nstreams,
+                                                     const long long *__restrict__ start, const int *__restrict__ order,
+                                                     const int *__restrict__ bits0, const int *__restrict__ bits1,
+                                                     const unsigned char *__restrict__ st0, const unsigned char *__restrict__ st1,
+                                                     vamd_bitrate_state *__restrict__ states, int *__restrict__ choice0,
+                                                     int *__restrict__ choice1, int *__restrict__ final0, int *__restrict__ final1) {
+  const long s = (long)blockIdx.x * 64 + threadIdx.x;
+  if (s >= nstreams) return;
+  vamd_bitrate_state bs = states[s];
+  for (long long k = start[s]; k < start[s + 1]; k++) {
+    const int o = order[k], W = (o >> 30) & 1;
+    const long i = o & 0x3fffffff;
+    const unsigned char *st = W ? st1 : st0;
+    unsigned bad = 0;
+    if (st)
+      for (int c = 0; c < ch; c++) bad |= st[i * ch + c];
+    int *ch_out = W ? choice1 : choice0, *fin_out = W ? final1 : final0;
+    if (bad) {
+      ch_out[i] = 0;
+      fin_out[i] = -1;
+      continue;
+    }
+    const int *bits = (W ? bits1 : bits0) + i * VAMD_PACKETBLOBS;
+    int32_t bytes[VAMD_PACKETBLOBS];
+#pragma unroll
+    for (int j = 0; j < VAMD_PACKETBLOBS; j++) bytes[j] = (bits[j] + 7) >> 3;
+    int64_t fbytes;
+    int fl;
+    const int c = bitrate_addblock(t, bs, bytes, W, W ? samples1 : samples0, &fbytes, &fl);
+    ch_out[i] = c;
+    fin_out[i] = (int)bitrate_final_bits(bits[c], fbytes < 0 ? 0 : fbytes);
+  }
+  states[s] = bs;
+}
+
+__global__ __launch_bounds__(256) void k_bitrate_init(vamd_bitrate_tab t, long nstreams, vamd_bitrate_state *__restrict__ states) {
+  const long s = (long)blockIdx.x * 256 + threadIdx.x;
+  if (s < nstreams) bitrate_state_init(t, states[s]);
+}
+
 // stage 3: _vp_tonemask, in three launches (k_tone.h).  nlp = octave lines padded to 32 (VAMD_LINES_PAD).
 template <int LP>
 __global__ __launch_bounds__(64) void k_tone_seed(PsyP P0, PsyP P1, DescP d, int ch, int nlp, int nrp,

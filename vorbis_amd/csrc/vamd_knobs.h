@@ -43,6 +43,7 @@ struct Knobs {
   int xf_variant = -1;           // VAMD_XF_VARIANT: transform kernel variant (-1: default)
   long fail_envelope_after = -1; // VAMD_FAIL_ENVELOPE_AFTER: vamd_envelope_search fails (VAMD_EFAULT) from its n-th call on
   long fail_encode_after = -1;   // VAMD_FAIL_ENCODE_AFTER: the same for vamd_encode_block / vamd_analyze_block*
+  long feed_slice = 2048;        // VAMD_FEED_SLICE: blocks per slice of a bitrate-managed vamd_feed group (small: many slices)
 };
 
 inline Knobs read_knobs() {
@@ -80,6 +81,7 @@ inline Knobs read_knobs() {
       k.xf_variant = (int)num("VAMD_XF_VARIANT", -1);
       k.fail_envelope_after = num("VAMD_FAIL_ENVELOPE_AFTER", -1);
       k.fail_encode_after = num("VAMD_FAIL_ENCODE_AFTER", -1);
+      k.feed_slice = num("VAMD_FEED_SLICE", k.feed_slice);
     }
     return k;
   }
@@ -94,11 +96,11 @@ inline void knobs_string(const Knobs &k, char *buf, size_t cap) {
              " VAMD_NO_OVERLAP=%d VAMD_COUPLE_BAND_LOG2=%s%d VAMD_XF_WAVES_CAP=%d VAMD_RES_TEAM_MAX=%ld VAMD_RES_IN_LDS=%d VAMD_PACK_PAIR_MAX=%ld VAMD_PACK_PER_PACKET=%d"
              " VAMD_FOLD_SEPARATE=%d VAMD_CHASE_WAVE_MAX=%ld VAMD_MASKS_SEPARATE=%d VAMD_NOISE_TEAMS=%d VAMD_NOISE_WAVES=%d VAMD_FLOOR_LDS_PAD=%ld"
              " VAMD_FLOOR_PAIR_MIN=%ld VAMD_FLOOR_PAIR_W=%d VAMD_STAGE_COPIES=%d VAMD_ENV_UNTILED=%d VAMD_XF_VARIANT=%d VAMD_FAIL_ENVELOPE_AFTER=%ld"
-             " VAMD_FAIL_ENCODE_AFTER=%ld",
+             " VAMD_FAIL_ENCODE_AFTER=%ld VAMD_FEED_SLICE=%ld",
              (int)k.no_overlap, k.couple_band_set ? "" : "unset:", k.couple_band_log2, k.xf_waves_cap, k.res_team_max, (int)k.res_in_lds,
              k.pack_pair_max, (int)k.pack_per_packet, (int)k.fold_separate, k.chase_wave_max, (int)k.masks_separate, k.noise_teams, k.noise_waves, k.floor_lds_pad,
              k.floor_pair_min, k.floor_pair_w, (int)k.stage_copies, (int)k.env_untiled, k.xf_variant, k.fail_envelope_after,
-             k.fail_encode_after);
+             k.fail_encode_after, k.feed_slice);
 }
 
 }  // namespace vamd
