@@ -577,7 +577,24 @@ vamd_ctx *vamd_batcher_context(vamd_batcher *b);
  * candidates are made in slices of at most 2048 blocks of the group (about 0.5 MB of HBM per long stereo block in the
  * slice), the ampmax chains and the managers carried from slice to slice.  A managed blob without the section (packed
  * before it existed) is refused by vamd_feed_create (VAMD_EIMPL; vamd_feed_last_error(NULL) says why).  Thread rules: one thread drives a feed (or several, each
- * with its own slots); the lanes' threads are the library's. */
+ * with its own slots); the lanes' threads are the library's.
+ * LENGTH CAP of a whole-stream feed: a group's plan holds every detector mark of a stream (one per 64 samples) in one
+ * workgroup's LDS, so a stream longer than about (LDS bytes - 16) * 64 - 3 * blocksizes[1] frames (160 KiB: ~10.5 M frames,
+ * 3 min 57 s at 44.1 kHz, 1 min 49 s at 96 kHz) fails when its group runs (VAMD_EINVAL, "streams too long for one plan").
+ * Longer streams, and sources that produce a stream while it plays, take a LIVE feed:
+ *     vamd_feed_create_live(..., write_frames)   the same lanes; each keeps max_streams CONTINUING streams
+ *     slot = vamd_feed_buffer(f, &pcm)           the next pieces of that lane's streams 0 .. nstreams-1, back to back
+ *     vamd_feed_wrote_live(f, slot, nstreams, frames, close)
+ *     vamd_feed_packets / vamd_feed_release      every packet whose block the samples so far determine
+ * Stream (slot, s) is the same stream on every write to lane `slot` until a piece closes it; its next piece starts a fresh
+ * one.  A stream's packets over all its groups are byte for byte what the reference's application loop emits when it gets
+ * the same samples write_frames at a time and is closed with vorbis_analysis_wrote(v, 0) -- for any cut into pieces,
+ * pieces of 0 or 1 frames included (tests/test_feed_live.py).  Between groups the device keeps per stream what the
+ * reference keeps: the detector state, the walk's W, lW, centerW, cursor and curmark, the detector flags of the steps still
+ * ahead of the walk, the ampmax chain, the bitrate manager, the granule position's origin and the samples from
+ * centerW - blocksizes[1]/2 on (at most about 1.5 long blocks + 448 samples) -- so neither stream
+ * length nor pinned memory grows with a stream.  A non-finite sample (VAMD_FEED_F32) ends its stream at the block that
+ * holds it: that packet and every later one of the stream has bits = -1 and VAMD_STATUS_NONFINITE until it is closed. */
 typedef struct vamd_feed vamd_feed;
 #define VAMD_FEED_S16 0 /* int16_t, interleaved; sample = x / 32768.f */
 #define VAMD_FEED_F32 1 /* float, interleaved, already scaled to +-1 */
@@ -595,6 +612,18 @@ int vamd_feed_wrote(vamd_feed *f, int slot, long nstreams, long frames);
 /* streams of unequal length: frames[s] (host array, each 1 .. max_frames, their sum <= max_streams * max_frames) frames of
  * stream s, the streams laid back to back in the arena (stream s starts at frame frames[0] + ... + frames[s-1]) */
 int vamd_feed_wrote_v(vamd_feed *f, int slot, long nstreams, const int64_t *frames);
+/* a live feed: max_frames is the longest PIECE; write_frames the reference's frames per vorbis_analysis_wrote() (1024 = the
+ * example), which decides when a stream's backward extrapolation runs (lib/block.c:524-528: at
+ * min(total, (blocksizes[1] / write_frames + 1) * write_frames) frames).  A write_frames whose extrapolation does not fit
+ * a workgroup's LDS is refused (VAMD_EIMPL, vamd_feed_last_error(NULL) says why).  vamd_feed_wrote / _wrote_v refuse a live
+ * feed and vamd_feed_wrote_live a whole-stream one (VAMD_EINVAL). */
+int vamd_feed_create_live(vamd_feed **out, const void *setup_blob, size_t blob_bytes, const int *devices, int ndevices,
+                          int lanes_per_device, long max_streams, long max_frames /* per piece */, int format,
+                          int write_frames);
+/* pieces of the lane's streams 0 .. nstreams-1 laid back to back in the arena as vamd_feed_wrote_v lays them; frames[s] in
+ * 0 .. max_frames; close (NULL: none): close[s] != 0 ends stream s after its piece (VAMD_EINVAL for a stream that never had
+ * a frame).  The lane's other open streams are left where they stand. */
+int vamd_feed_wrote_live(vamd_feed *f, int slot, long nstreams, const int64_t *frames, const uint8_t *close);
 typedef struct vamd_feed_result {
   int64_t nstreams, nblocks;      /* blocks == packets, all streams */
   const int64_t *stream_start;    /* [nstreams + 1]: stream s owns packets [stream_start[s], stream_start[s+1]), in stream order */

@@ -1,0 +1,141 @@
+"""The live feed's walk (k_blockout.h: plan_stream from a carried WalkState, walk_rebase) compiled with the host
+compiler, for the tests: the shipped header itself, built -ffp-contract=off as the library is.  With the host-compiled
+stream ends and detector of tests/emul it chains one stream's live sequence as vamd_live_plan does on the device."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+_SHIM = r"""
+#include <vector>
+#include "k_blockout.h"
+using namespace vamd;
+// one walk over flags[0, nsteps) (mark_at, as k_plan_live applies it), from state[5] = centerW, cursor, curmark, W, lW
+// (fresh: a new stream's); the state it ends in is written back.  Returns the number of blocks.
+extern "C" int live_walk(const unsigned char *flags, long nsteps, long nsamples, long eof, int bs0, int bs1, long long *state,
+                         int fresh, int maxblocks, int *kind, int *begin, long long *pending) {
+  BlockoutP B;
+  B.bs[0] = bs0, B.bs[1] = bs1;
+  blockout_set_step(B, 64);
+  B.nsamples = nsamples, B.nsteps = nsteps, B.eof = eof, B.maxblocks = maxblocks;
+  const long last = blockout_steps(B);
+  std::vector<unsigned char> marks((size_t)nsteps + 4, 0);
+  for (long p = 0; p < nsteps + 4; p++) marks[(size_t)p] = (unsigned char)mark_at(flags, last, p);
+  WalkState st = walk_fresh(B);
+  if (!fresh) st.centerW = state[0], st.cursor = state[1], st.curmark = state[2], st.W = (int)state[3], st.lW = (int)state[4];
+  std::vector<PlannedBlock> out((size_t)maxblocks);
+  int n0 = 0, n1 = 0;
+  long pc = 0;
+  const int n = plan_stream(B, marks.data(), out.data(), &n0, &n1, &pc, &st);
+  for (int k = 0; k < n; k++) kind[k] = out[(size_t)k].kind, begin[k] = out[(size_t)k].begin;
+  state[0] = st.centerW, state[1] = st.cursor, state[2] = st.curmark, state[3] = st.W, state[4] = st.lW;
+  *pending = pc;
+  return n;
+}
+extern "C" long live_rebase(int bs0, int bs1, long centerW) {
+  BlockoutP B;
+  B.bs[0] = bs0, B.bs[1] = bs1;
+  blockout_set_step(B, 64);
+  return walk_rebase(B, centerW);
+}
+"""
+
+
+def build(outdir):
+    src = os.path.join(outdir, "live_shim.cpp")
+    lib = os.path.join(outdir, "liblive.so")
+    with open(src, "w") as f:
+        f.write(_SHIM)
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unknown-pragmas",
+                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"), "-I" + os.path.join(ROOT, "tests", "emul"), src, "-o", lib])
+    return lib
+
+
+class LiveWalk:
+    def __init__(self, lib, bs):
+        self.L = C.CDLL(lib)
+        self.L.live_walk.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong)]
+        self.L.live_rebase.argtypes = [C.c_int, C.c_int, C.c_long]
+        self.L.live_rebase.restype = C.c_long
+        self.bs = bs
+
+    def walk(self, flags, nsamples, state, fresh, eof=0, maxblocks=8192):
+        flags = np.ascontiguousarray(flags, np.uint8)
+        kind = np.zeros(maxblocks, np.int32)
+        begin = np.zeros(maxblocks, np.int32)
+        pc = C.c_longlong(0)
+        n = self.L.live_walk(flags.ctypes.data, len(flags), nsamples, eof, self.bs[0], self.bs[1], state.ctypes.data, int(fresh),
+                             maxblocks, kind.ctypes.data, begin.ctypes.data, C.byref(pc))
+        return kind[:n], begin[:n], int(pc.value)
+
+    def rebase(self, centerW):
+        return int(self.L.live_rebase(self.bs[0], self.bs[1], centerW))
+
+
+def live_stream(em, lw, pcm, cuts, write_frames):
+    """One stream's live sequence on the host, pcm [ch][frames] in pieces `cuts` (the last one closes it): the stream ends
+    (tests/emul), the detector over each piece's new steps from its carried state, the resumed walk and the rebase.
+    -> its blocks as dicts: kind, begin (absolute), granulepos, eos, pcm [ch][n]."""
+    import vorbis_amd
+    ch = pcm.shape[0]
+    bs1, head, pad, step = lw.bs[1], lw.bs[1] // 2, 3 * lw.bs[1], 64
+    n_head = (bs1 // write_frames + 1) * write_frames
+    cap = head + pcm.shape[1] + pad + 4096
+    buf = np.zeros((ch, cap), np.float32)
+    have, total, steps, origin, headed = head, 0, 0, 0, False
+    flags = np.zeros(0, np.uint8)
+    env = vorbis_amd.EnvelopeState()
+    state = np.zeros(5, np.int64)
+    fresh = True
+    blocks = []
+    fp = C.POINTER(C.c_float)
+
+    def detect(first, n):
+        return em.envelope_search(np.ascontiguousarray(buf[:, first * step:first * step + (n - 1) * step + 128]), n, env) \
+            if n else np.zeros(0, np.uint8)
+
+    for i, n in enumerate(cuts):
+        close = i == len(cuts) - 1
+        buf[:, have:have + n] = pcm[:, total:total + n]
+        have += n
+        total += n
+        if not headed and (total >= n_head or close):
+            headed = True
+            for c in range(ch):
+                em.L.emul_lpc_head(buf[c].ctypes.data_as(fp), head, min(total, n_head))
+        if headed:
+            c1 = max(0, have // step - 4 - steps)
+            flags = np.concatenate([flags, detect(steps, c1)])
+            steps += c1
+        if close:
+            _, _, pending = lw.walk(flags, have, state.copy(), fresh)
+            for c in range(ch):
+                em.L.emul_lpc_tail(buf[c].ctypes.data_as(fp), have, pending - bs1 // 2, bs1, pad)
+            f2 = detect(steps, max(0, (have + pad) // step - 4 - steps))
+            kind, begin, _ = lw.walk(np.concatenate([flags, f2]), have + pad, state, fresh, eof=have)
+        else:
+            kind, begin, _ = lw.walk(flags, have, state, fresh)
+        fresh = False
+        for k, b in zip(kind, begin):
+            n = lw.bs[int(k) & 1]
+            centre = int(b) + n // 2
+            blocks.append({"kind": int(k), "begin": origin + int(b), "eos": 0, "pcm": buf[:, int(b):int(b) + n].copy(),
+                           "granulepos": (min(centre, have) if close else centre) - head + origin})
+        if close:
+            if blocks:
+                blocks[-1]["eos"] = 1
+            break
+        sh = lw.rebase(int(state[0]))
+        assert sh % step == 0 and state[1] >= sh, "the walk's cursor lies in front of the rebased buffer"
+        state[:3] -= sh
+        buf[:, :cap - sh] = buf[:, sh:].copy()
+        buf[:, cap - sh:] = 0
+        have -= sh
+        flags = flags[sh // step:]
+        steps -= sh // step
+        origin += sh
+    return blocks

@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe",
                     "vamd_batcher_encode_block", "vamd_batcher_last_error", "vamd_batcher_stats", "vamd_batcher_context", "vamd_batcher_report",
                     "vamd_input_status", "vamd_calib_copy", "vamd_abi_version", "vamd_plan_streams_whole", "vamd_plan_streams_whole_v", "vamd_feed_wrote_v", "vamd_device_count", "vamd_batcher_create_multi",
                     "vamd_feed_create", "vamd_feed_destroy", "vamd_feed_lanes", "vamd_feed_device", "vamd_feed_buffer", "vamd_feed_wrote",
-                    "vamd_feed_packets", "vamd_feed_release", "vamd_feed_last_error",
+                    "vamd_feed_packets", "vamd_feed_release", "vamd_feed_last_error", "vamd_feed_create_live", "vamd_feed_wrote_live",
                     "vamd_analyze_streams_mixed_managed", "vamd_bitrate_init_states", "vamd_bitrate_walk"]
 PACKETBLOBS = 15
 
@@ -142,6 +142,9 @@ def load_library():
     L.vamd_plan_streams_whole_v.argtypes = [_vp, _vp, C.c_long, C.c_long, C.c_long, C.c_long, _vp, _vp, C.POINTER(_Plan)]
     L.vamd_feed_wrote_v.argtypes = [_vp, C.c_int, C.c_long, _vp]
     L.vamd_feed_create.argtypes = [C.POINTER(_vp), _vp, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_long, C.c_long, C.c_int]
+    L.vamd_feed_create_live.argtypes = [C.POINTER(_vp), _vp, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_long, C.c_long, C.c_int,
+                                        C.c_int]
+    L.vamd_feed_wrote_live.argtypes = [_vp, C.c_int, C.c_long, _vp, _vp]
     L.vamd_feed_destroy.argtypes = [_vp]
     L.vamd_feed_destroy.restype = None
     L.vamd_feed_lanes.argtypes = [_vp]
@@ -938,16 +941,26 @@ FEED_S16, FEED_F32 = 0, 1
 class Feed:
     """vamd_feed: whole streams from HOST memory in (interleaved int16 / float32), finished packets back to host
     memory, over one or several GPUs (include/vorbis_amd.h, "the host-fed farm").  The call sequence is libvorbis'
-    own, for a group of streams: buffer() -> fill -> wrote() -> packets() -> release()."""
+    own, for a group of streams: buffer() -> fill -> wrote() -> packets() -> release().
 
-    def __init__(self, setup_blob, devices=None, lanes_per_device=2, max_streams=256, max_frames=131072, fmt=FEED_S16):
+    write_frames (an int): a LIVE feed (vamd_feed_create_live) -- every lane keeps max_streams continuing streams, fed in
+    pieces of at most max_frames frames: buffer() -> fill -> wrote_live() -> packets() -> release(); its packets are the
+    reference's when it gets the samples write_frames at a time."""
+
+    def __init__(self, setup_blob, devices=None, lanes_per_device=2, max_streams=256, max_frames=131072, fmt=FEED_S16,
+                 write_frames=None):
         self.L = load_library()
         blob = np.ascontiguousarray(setup_blob, dtype=np.uint8)
         devs = list(devices) if devices else []
         arr = (C.c_int * max(1, len(devs)))(*devs)
         h = _vp()
-        r = self.L.vamd_feed_create(C.byref(h), _vp(blob.ctypes.data), blob.size, arr if devs else None, len(devs), lanes_per_device,
-                                    max_streams, max_frames, fmt)
+        if write_frames is None:
+            r = self.L.vamd_feed_create(C.byref(h), _vp(blob.ctypes.data), blob.size, arr if devs else None, len(devs), lanes_per_device,
+                                        max_streams, max_frames, fmt)
+        else:
+            r = self.L.vamd_feed_create_live(C.byref(h), _vp(blob.ctypes.data), blob.size, arr if devs else None, len(devs),
+                                             lanes_per_device, max_streams, max_frames, fmt, int(write_frames))
+        self.write_frames = write_frames
         if r:
             why = self.L.vamd_feed_last_error(None).decode()
             raise VamdError(r, "vamd_feed_create failed: " + (why or "setup without GPU-assembled packets, bad arguments, or a HIP failure"))
@@ -994,6 +1007,17 @@ class Feed:
                 raise ValueError("frames must hold one length per stream")
             self._check(self.L.vamd_feed_wrote_v(self.h, slot, nstreams, _vp(fr.ctypes.data)))
 
+    def wrote_live(self, slot, frames, close=None):
+        """A live feed: frames[s] new frames of the lane's stream s (0 .. max_frames each, laid back to back in the arena);
+        close[s] true ends stream s after its piece."""
+        fr = np.ascontiguousarray(frames, dtype=np.int64).reshape(-1)
+        cl = None
+        if close is not None:
+            cl = np.ascontiguousarray(close, dtype=np.uint8).reshape(-1)
+            if cl.shape != fr.shape:
+                raise ValueError("close must hold one flag per stream")
+        self._check(self.L.vamd_feed_wrote_live(self.h, slot, fr.size, _vp(fr.ctypes.data), _vp(cl.ctypes.data) if cl is not None else None))
+
     def packets(self, slot, copy=True):
         """Waits for the group.  -> dict: nstreams, nblocks, stream_start, offset, bits, granulepos, info (numpy views over
         the lane's pinned output arena, or copies), choice (info >> 4: the bitrate manager's candidate, 0 on a VBR setup),
@@ -1016,6 +1040,44 @@ class Feed:
 
     def release(self, slot):
         self._check(self.L.vamd_feed_release(self.h, slot))
+
+    @staticmethod
+    def _rows(r, ns):
+        out = []
+        for s in range(ns):
+            row = []
+            for k in range(int(r["stream_start"][s]), int(r["stream_start"][s + 1])):
+                bits = int(r["bits"][k])
+                o = int(r["offset"][k])
+                data = bytes(r["bytes"][o:o + (bits + 7) // 8]) if bits >= 0 else None
+                row.append((data, int(r["granulepos"][k]), int(r["info"][k]) & 1, (int(r["info"][k]) >> 1) & 1))
+            out.append(row)
+        return out
+
+    def encode_live(self, pieces, close=None):
+        """One group of a live feed with ONE lane, synchronously: pieces = the next [frames_s, ch] samples of streams
+        0 .. len(pieces)-1 (the feed's sample type; 0 frames allowed); close[s] true ends stream s after its piece.
+        -> per stream the packets its blocks the samples so far determine, as (bytes, granulepos, W, e_o_s) tuples."""
+        if self.write_frames is None:
+            raise ValueError("encode_live needs a live feed (Feed(..., write_frames=...))")
+        if self.lanes != 1:
+            raise ValueError("encode_live drives a feed with one lane; with more, use buffer / wrote_live / packets / release")
+        parts = [np.ascontiguousarray(x, dtype=self.dtype) for x in pieces]
+        ch = max(x.shape[1] if x.ndim == 2 else 1 for x in parts)
+        parts = [x.reshape(-1, ch) for x in parts]
+        frames = np.array([x.shape[0] for x in parts], np.int64)
+        slot, buf = self.buffer(ch)
+        try:
+            flat = np.concatenate([x.reshape(-1) for x in parts]) if parts else np.zeros(0, self.dtype)
+            buf[:flat.size] = flat
+            self.wrote_live(slot, frames, close)
+            r = self.packets(slot)
+        finally:
+            try:
+                self.release(slot)
+            except VamdError:
+                pass
+        return self._rows(r, len(parts))
 
     def encode(self, pcm):
         """One group, synchronously: pcm [nstreams, frames, ch] of the feed's sample type (host), or a list of [frames_s, ch]

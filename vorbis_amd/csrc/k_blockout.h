@@ -68,17 +68,41 @@ VAMD_DEV long blockout_steps(const BlockoutP &B) {
   return last < 0 ? 0 : last;
 }
 
+// What the walk carries from one call to the next (v->W, v->lW, v->centerW, ve->cursor, ve->curmark), positions in the
+// stream buffer's coordinates.  A stream that is fed in pieces (the live feed) resumes from it.
+struct WalkState {
+  long centerW, cursor, curmark;
+  int W, lW;
+};
+// vorbis_analysis_init / _ve_envelope_init: lib/block.c:211-213, lib/envelope.c:41
+VAMD_HOSTDEV WalkState walk_fresh(const BlockoutP &B) {
+  WalkState s;
+  s.centerW = s.cursor = B.bs[1] / 2;
+  s.curmark = 0;
+  s.W = s.lW = 0;
+  return s;
+}
+// The live feed's rebase after a walk that stopped in front of the block centred at centerW: the reference's memmove
+// leaves its buffer starting at centerW - blocksizes[1]/2 (lib/block.c:657-690); one step more is kept, whose detector flag
+// still feeds the first kept mark (mark_at).  A multiple of the step: marks and detector steps keep their grid.
+VAMD_HOSTDEV long walk_rebase(const BlockoutP &B, long centerW) {
+  long sh = centerW - B.bs[1] / 2 - B.searchstep;
+  if (sh < 0) sh = 0;
+  return sh / B.searchstep * B.searchstep;
+}
+
 // The walk for one stream.  Returns the number of blocks planned (<= maxblocks) and counts per size class.
 //   marks  ve->mark[] of the steps [0, last) as bytes (mark_at applied by the caller's lanes; entries at and beyond
 //          `last` are 0: steps not taken yet)
 //   pending_center  (optional) centerW of the block the walk stopped in front of: where the reference's buffer would
 //          begin (centerW - blocksizes[1]/2) when vorbis_analysis_wrote(v, 0) pads the stream
+//   state  (optional, in/out) where the walk starts (null: a fresh stream) and, on return, where it stands
 VAMD_DEV int plan_stream(const BlockoutP &B, const unsigned char *marks, PlannedBlock *__restrict__ out,
-                         int *count_short, int *count_long, long *pending_center = nullptr) {
+                         int *count_short, int *count_long, long *pending_center = nullptr, WalkState *state = nullptr) {
   const long step = B.searchstep;
-  // vorbis_analysis_init / _ve_envelope_init: lib/block.c:211-213, lib/envelope.c:41
-  int W = 0, lW = 0;
-  long centerW = B.bs[1] / 2, cursor = B.bs[1] / 2, curmark = 0;
+  const WalkState s0 = state ? *state : walk_fresh(B);
+  int W = s0.W, lW = s0.lW;
+  long centerW = s0.centerW, cursor = s0.cursor, curmark = s0.curmark;
   // what _ve_envelope_search has marked: steps [0, last), last = pcm_current/searchstep - VE_WIN (:223-224)
   const long last = blockout_steps(B);
   const long current = last * step;
@@ -169,6 +193,10 @@ VAMD_DEV int plan_stream(const BlockoutP &B, const unsigned char *marks, Planned
   *count_short = n0;
   *count_long = n1;
   if (pending_center) *pending_center = centerW;  // (-1: the stream is over)
+  if (state) {
+    state->W = W, state->lW = lW;
+    state->centerW = centerW, state->cursor = cursor, state->curmark = curmark;
+  }
   return n;
 }
 

@@ -30,6 +30,7 @@
 #include <vector>
 #include "vorbis_amd.h"
 #include "vamd_knobs.h"
+#include "vamd_live.h"
 
 namespace {
 
@@ -83,6 +84,92 @@ __global__ void k_feed_ingest(const T *__restrict__ in, int ch, long nstreams, l
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < words; t += (long)gridDim.x * blockDim.x) ((uint32_t *)states)[t] = 0u;
 }
 
+// ---- the live feed (vamd_feed_create_live): continuing streams, their state on the device between groups ----
+// A live lane keeps every stream in one of two buffers [stream][channel][cs], swapped each group: a stream's samples from
+// where the reference's buffer begins (walk_rebase) on, then the group's piece, then zeroes (the end-of-stream padding's
+// room and the detector's reads).  Per stream and group, built by the lane's host mirror:
+struct LiveIn {
+  int64_t first, frames;  // the piece: its first frame in the arena, its frames
+  int64_t keep, shift;    // samples carried over from the other buffer, taken from sample `shift` of it on
+  int64_t origin;         // the stream's position (head room included) of buffer sample 0: granule positions go on from it
+  int64_t eof;            // a closing stream: its end in buffer coordinates; else LIVE_OPEN
+  int32_t fresh, close;   // the stream starts / ends in this group
+};
+#define LIVE_OPEN (1LL << 60)
+#define LIVE_NO_NAN (~0ull)
+
+// a fresh stream's states: the detector's (all zero), the ampmax chain's, the bitrate manager's (a copy of `tmpl`), no
+// non-finite sample yet.  A stream that goes on keeps all of them.
+__global__ void k_live_begin(long nstreams, const LiveIn *__restrict__ li, vamd_envelope_state *__restrict__ states,
+                             float *__restrict__ amp, vamd_bitrate_state *__restrict__ bst, const vamd_bitrate_state *__restrict__ tmpl,
+                             unsigned long long *__restrict__ nan) {
+  const long words = (long)(sizeof(vamd_envelope_state) / 4);
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < nstreams * words; t += (long)gridDim.x * blockDim.x) {
+    const long s = t / words;
+    if (!li[s].fresh) continue;
+    ((uint32_t *)states)[t] = 0u;
+    if (t - s * words == 0) {
+      amp[s] = VAMD_AMPMAX_FLOOR;
+      if (bst) bst[s] = *tmpl;
+      nan[s] = LIVE_NO_NAN;
+    }
+  }
+}
+
+// the group's buffer, a thread per four samples of every channel of a stream (one 16-byte store per channel): the kept
+// samples out of the other buffer (a fresh stream: the zeroed head room), the piece behind them (x / 32768.f for 16-bit
+// input, examples/encoder_example.c:197-202), zeroes up to `room` samples past the piece.  Float input: the first
+// non-finite sample of each stream is recorded (absolute position, nan[]).  A stream whose samples would not fit its
+// buffer is left alone and flagged in *status (the lane reports it; never written past the buffer).
+template <typename T>
+__global__ void k_live_ingest(const T *__restrict__ in, int ch, long nstreams, long quads, int room, const LiveIn *__restrict__ li,
+                              const float *__restrict__ old, float *__restrict__ pcm, long ss, long cs,
+                              unsigned long long *__restrict__ nan, int *__restrict__ status) {
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < nstreams * quads; t += (long)gridDim.x * blockDim.x) {
+    const long s = t / quads, p0 = (t - s * quads) << 2;
+    const LiveIn L = li[s];
+    const long data = L.keep + L.frames, end = data + room < cs ? data + room : cs;
+    if (data + room > cs || L.keep < 0 || L.shift < 0 || L.shift + L.keep > cs) {
+      if (p0 == 0) *(volatile int *)status = 1;  // (host memory, mapped: a plain store)
+      continue;
+    }
+    if (p0 >= end) continue;
+    for (int c = 0; c < ch; c++) {
+      float v[4];
+      bool bad = false;
+      long badp = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const long p = p0 + k;
+        float x = 0.f;
+        if (p < L.keep) {
+          if (!L.fresh) x = old[s * ss + (long)c * cs + L.shift + p];
+        } else if (p < data) {
+          const T y = in[(L.first + p - L.keep) * ch + c];
+          if (sizeof(T) == 2) x = (float)(int)y / 32768.f;
+          else {
+            x = (float)y;
+            if (!bad && (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) bad = true, badp = p;
+          }
+        }
+        v[k] = x;
+      }
+      ((float4 *)(pcm + s * ss + (long)c * cs))[p0 >> 2] = make_float4(v[0], v[1], v[2], v[3]);
+      if (bad) atomicMin(nan + s, (unsigned long long)(L.origin + badp));
+    }
+  }
+}
+
+// what a live group adds to a packet's record: its granule position goes on from the stream's origin, e_o_s only where the
+// stream closes, and from the block that holds a stream's first non-finite sample on no packet (VAMD_STATUS_NONFINITE)
+struct FeedLive {
+  const LiveIn *in;
+  const unsigned long long *nan;
+};
+__device__ __forceinline__ unsigned live_status(const FeedLive &V, long s, int64_t begin, int bs) {
+  return V.in && (unsigned long long)(V.in[s].origin + begin + bs) > V.nan[s] ? VAMD_STATUS_NONFINITE : 0u;
+}
+
 struct FeedPlan {  // what the packing kernels need of a vamd_stream_plan and of the analysis' outputs
   const int32_t *order;
   const int64_t *stream_start;
@@ -96,6 +183,7 @@ struct FeedPlan {  // what the packing kernels need of a vamd_stream_plan and of
   int64_t stream_stride, eof;  // eof: first sample past the stream's real ones, in its buffer's coordinates
   const long long *frames_of;  // streams of unequal length: eof = head + frames_of[s]
   int head;
+  FeedLive live;               // a live group's streams (in == null: whole streams)
 };
 
 // a wave per stream: rel[k] = bytes (each packet rounded up to 4) of the stream's packets before packet k
@@ -111,6 +199,7 @@ __global__ __launch_bounds__(64) void k_feed_sizes(FeedPlan P, long nstreams, in
       const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
       unsigned st = 0;
       for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
+      st |= live_status(P.live, s, P.src[W][i] - s * P.stream_stride, P.bs[W]);
       bytes = st ? 0 : (((P.bits[W][i] + 7) >> 3) + 3) & ~3;
     }
     int incl = bytes;  // inclusive scan over the wave
@@ -166,6 +255,7 @@ __global__ __launch_bounds__(256) void k_feed_copy(FeedPlan P, long nstreams, lo
   const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
   unsigned st = 0;
   for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
+  st |= live_status(P.live, s, P.src[W][i] - (int64_t)s * P.stream_stride, P.bs[W]);
   const int bits = P.bits[W][i], words = st ? 0 : (((bits + 7) >> 3) + 3) >> 2;
   const int64_t off = stream_off[s] + rel[k];
   const bool fits = off + 4 * (int64_t)words <= O.cap;
@@ -176,11 +266,11 @@ __global__ __launch_bounds__(256) void k_feed_copy(FeedPlan P, long nstreams, lo
   }
   if (lane == 0) {
     const int64_t begin = P.src[W][i] - (int64_t)s * P.stream_stride, center = begin + P.bs[W] / 2;
-    const bool last = k + 1 == P.stream_start[s + 1];
+    const bool last = k + 1 == P.stream_start[s + 1] && (!P.live.in || P.live.in[s].close);
     O.offset[k] = off;
     O.bits[k] = st ? -1 : bits;
-    const int64_t eof = P.frames_of ? (int64_t)P.head + P.frames_of[s] : P.eof;
-    O.granulepos[k] = (center < eof ? center : eof) - P.bs[1] / 2;
+    const int64_t eof = P.live.in ? P.live.in[s].eof : (P.frames_of ? (int64_t)P.head + P.frames_of[s] : P.eof);
+    O.granulepos[k] = (center < eof ? center : eof) - P.bs[1] / 2 + (P.live.in ? P.live.in[s].origin : 0);
     O.info[k] = (uint8_t)(W | (last ? 2 : 0) | ((st & 3) << 2));
   }
 }
@@ -212,6 +302,7 @@ struct FeedSlice {
   int64_t stream_stride, eof;
   const long long *frames_of;
   int head;
+  FeedLive live;
 };
 
 // a wave per slice stream: rel[k] = bytes (each handed-out packet rounded up to 4) of the slice stream's packets before k
@@ -227,6 +318,8 @@ __global__ __launch_bounds__(64) void k_feed_sizes_managed(FeedSlice P, int64_t 
       const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
       unsigned st = 0;
       for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
+      const long gs = P.s0 + s;
+      st |= live_status(P.live, gs, P.src[W][P.i0[W] + i] - gs * P.stream_stride, P.bs[W]);
       bytes = st ? 0 : (((P.fbits[W][i] + 7) >> 3) + 3) & ~3;
     }
     int incl = bytes;
@@ -254,6 +347,7 @@ __global__ __launch_bounds__(256) void k_feed_copy_managed(FeedSlice P, long nbl
   const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
   unsigned st = 0;
   for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
+  st |= live_status(P.live, s, P.src[W][P.i0[W] + i] - s * P.stream_stride, P.bs[W]);
   const int choice = P.choice[W][i], fbits = P.fbits[W][i];
   const int64_t fb = st ? 0 : ((int64_t)fbits + 7) >> 3;
   int64_t own = st ? 0 : ((int64_t)P.mbits[W][(int64_t)i * VAMD_PACKETBLOBS + choice] + 7) >> 3;
@@ -276,11 +370,11 @@ __global__ __launch_bounds__(256) void k_feed_copy_managed(FeedSlice P, long nbl
   if (lane == 0) {
     const int64_t g = P.k0 + k, gi = P.i0[W] + i;
     const int64_t begin = P.src[W][gi] - (int64_t)s * P.stream_stride, center = begin + P.bs[W] / 2;
-    const bool last = g + 1 == P.g_start[s + 1];
+    const bool last = g + 1 == P.g_start[s + 1] && (!P.live.in || P.live.in[s].close);
     O.offset[g] = off;
     O.bits[g] = st ? -1 : fbits;
-    const int64_t eof = P.frames_of ? (int64_t)P.head + P.frames_of[s] : P.eof;
-    O.granulepos[g] = (center < eof ? center : eof) - P.bs[1] / 2;
+    const int64_t eof = P.live.in ? P.live.in[s].eof : (P.frames_of ? (int64_t)P.head + P.frames_of[s] : P.eof);
+    O.granulepos[g] = (center < eof ? center : eof) - P.bs[1] / 2 + (P.live.in ? P.live.in[s].origin : 0);
     O.info[g] = (uint8_t)(W | (last ? 2 : 0) | ((st & 3) << 2) | ((st ? 0 : choice) << 4));
   }
 }
@@ -331,6 +425,20 @@ struct FeedLane {
   // them, the walk's answers, the managers' states, the slices' rebased lists (h_slice pinned, d_slice its copy)
   Buf d_mpk[2], d_mbits[2], d_mposts[2], d_mvalid[2], d_miwork[2], d_mnz[2], d_choice[2], d_fbits[2];
   Buf d_bstate, d_slice, h_slice;
+  // a live feed (run_group_live): the two stream buffers, the walks' states, the carried detector flags, the first
+  // non-finite sample per stream, the manager's fresh state; the group's LiveIn (pinned, its copy) and the host mirror
+  Buf d_buf[2], d_walk, d_rows, d_nan, d_btmpl, d_live, h_live, h_lstatus;
+  int cur = 0;                    // the buffer that holds the streams now
+  bool btmpl_ready = false;
+  struct LiveStream {             // the host's mirror of one stream of the lane
+    bool open = false, headed = false;
+    int64_t origin = 0;           // the stream's position (head room included) of buffer sample 0
+    int64_t have = 0, total = 0;  // samples in the buffer; frames received
+    int64_t steps = 0;            // detector steps taken (buffer coordinates)
+    int64_t shift = 0;            // where the next buffer begins (the last walk's rebase)
+  };
+  std::vector<LiveStream> live;
+  std::vector<uint8_t> close_of;  // the job's closes (live)
   std::thread worker;
   std::mutex *upload_turn = nullptr;  // its device's (vamd_feed::upload_turns)
   // the job (guarded by vamd_feed::m)
@@ -353,6 +461,8 @@ struct vamd_feed {
   long pkcap[2] = {0, 0};
   long max_streams = 0, max_frames = 0;
   int format = VAMD_FEED_S16;
+  int write_frames = 0;             // > 0: a live feed (vamd_feed_create_live), the reference's frames per write
+  long live_cs = 0, row_stride = 0, retain = 0;  // its buffers' samples per channel, flag rows, the retention bound
   std::mutex m;
   std::vector<std::unique_ptr<std::mutex>> upload_turns;  // one per device
   std::condition_variable cv_work, cv_done;
@@ -386,8 +496,10 @@ struct vamd_feed {
 // The workspace is bounded by the slice, not the group: a long stereo block's candidates alone take 15 x its integer
 // residue (120 KB) and 15 packet rows.  The host waits once per slice for the slice's byte count (to grow the arena
 // before anything is written into it: the candidates do not outlive their slice).
-static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, long ss, long cs, const long long *d_frames_of) {
-  const long ns = L.nstreams, frames = L.frames;
+// (live: `live` set, ns streams planned of which the caller's first ns_out are reported; the managers carried across groups)
+static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, const float *pcm, long ns, long ss, long cs,
+                             const long long *d_frames_of, FeedLive live, long ns_out) {
+  const long frames = L.frames;
   const int ch = f->ch, head = f->bs[1] / 2;
   const long nb = (long)(plan.nblocks[0] + plan.nblocks[1]);
   hipStream_t st = L.stream;
@@ -465,8 +577,10 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
   FEED_TRY(L.d_sid.need(most_slice * 4));
   FEED_TRY(L.d_sbytes.need((size_t)ns * 8));
   FEED_TRY(L.d_soff.need((size_t)(ns + 1) * 8));
-  FEED_TRY(L.d_bstate.need((size_t)ns * sizeof(vamd_bitrate_state)));
-  FEED_CALL(vamd_bitrate_init_states(L.ctx, (vamd_bitrate_state *)L.d_bstate.p, ns));
+  if (!live.in) {  // (a live lane's managers live across groups: k_live_begin starts the fresh ones)
+    FEED_TRY(L.d_bstate.need((size_t)ns * sizeof(vamd_bitrate_state)));
+    FEED_CALL(vamd_bitrate_init_states(L.ctx, (vamd_bitrate_state *)L.d_bstate.p, ns));
+  }
   // records: [total | stream_start (ns + 1) | offset (nb) | granulepos (nb) | bits (nb) | info (nb)], as run_group's
   const size_t o_start = 8, o_off = o_start + (size_t)(ns + 1) * 8, o_gp = o_off + (size_t)nb * 8, o_bits = o_gp + (size_t)nb * 8,
                o_info = o_bits + (size_t)nb * 4, rec_bytes = al(o_info + (size_t)nb, 16);
@@ -488,7 +602,7 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
       desc[W].nblocks = (long)x.n[W];
       if (!x.n[W]) continue;
       desc[W].lW = plan.lW[W] + x.i0[W], desc[W].nW = plan.nW[W] + x.i0[W], desc[W].blocktype = plan.blocktype[W] + x.i0[W];
-      io[W].pcm = (const float *)L.d_pcm.p;
+      io[W].pcm = pcm;
       io[W].pcm_src = plan.src[W] + x.i0[W];
       io[W].pcm_channel_stride = cs;
       io[W].status = (uint8_t *)L.d_status[W].p;
@@ -516,6 +630,7 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
       P.packets[W] = (const uint8_t *)L.d_mpk[W].p, P.stride[W] = f->pkcap[W], P.i0[W] = x.i0[W], P.bs[W] = f->bs[W];
     }
     P.k0 = x.k0, P.s0 = x.s0, P.ch = ch, P.stream_stride = ss, P.eof = head + frames, P.frames_of = d_frames_of, P.head = head;
+    P.live = live;
     hipLaunchKernelGGL(k_feed_sid, dim3((unsigned)nss), dim3(64), 0, st, ls, (int32_t *)L.d_sid.p);
     hipLaunchKernelGGL(k_feed_sizes_managed, dim3((unsigned)nss), dim3(64), 0, st, P, (int64_t *)L.d_rel.p, (int64_t *)L.d_sbytes.p);
     hipLaunchKernelGGL(k_feed_scan, dim3(1), dim3(1024), 0, st, nss, (const int64_t *)L.d_sbytes.p, (int64_t *)L.d_soff.p);
@@ -541,7 +656,7 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
   *(int64_t *)hrec = base;
   memcpy(hrec + o_start, start.data(), (size_t)(ns + 1) * 8);
   vamd_feed_result &R = L.result;
-  R.nstreams = ns, R.nblocks = nb;
+  R.nstreams = ns_out, R.nblocks = nb;
   R.stream_start = (const int64_t *)(hrec + o_start), R.offset = (const int64_t *)(hrec + o_off);
   R.granulepos = (const int64_t *)(hrec + o_gp), R.bits = (const int32_t *)(hrec + o_bits), R.info = hrec + o_info;
   R.bytes = (const uint8_t *)L.h_out.p, R.total_bytes = base;
@@ -551,6 +666,9 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
   L.result.upload_ms = up, L.result.device_ms = dev;
   return VAMD_OK;
 }
+
+static int finish_group(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, const float *pcm, long ns, long ss, long cs,
+                        const long long *d_frames_of, FeedLive live, long ns_out);
 
 // one group through its lane (the lane's own thread; its device is current)
 static int run_group(vamd_feed *f, FeedLane &L) {
@@ -614,7 +732,18 @@ static int run_group(vamd_feed *f, FeedLane &L) {
     FEED_CALL(vamd_plan_streams_whole_v(L.ctx, (float *)L.d_pcm.p, ss, cs, ns, frames, L.frames_of.data(), (vamd_envelope_state *)L.d_states.p, &plan));
   else
     FEED_CALL(vamd_plan_streams_whole(L.ctx, (float *)L.d_pcm.p, ss, cs, ns, frames, (vamd_envelope_state *)L.d_states.p, &plan));
-  if (f->managed) return run_group_managed(f, L, plan, ss, cs, d_frames_of);
+  FeedLive none;
+  none.in = nullptr, none.nan = nullptr;
+  return finish_group(f, L, plan, (const float *)L.d_pcm.p, ns, ss, cs, d_frames_of, none, ns);
+}
+
+// a group from its plan on (whole or live): the analysis, the packets end to end into the pinned arena
+static int finish_group(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, const float *pcm, long ns, long ss, long cs,
+                        const long long *d_frames_of, FeedLive live, long ns_out) {
+  const long frames = L.frames;
+  const int ch = f->ch, head = f->bs[1] / 2;
+  hipStream_t st = L.stream;
+  if (f->managed) return run_group_managed(f, L, plan, pcm, ns, ss, cs, d_frames_of, live, ns_out);
   const long nb = (long)(plan.nblocks[0] + plan.nblocks[1]);
   vamd_batch_desc desc[2];
   vamd_batch_io io[2];
@@ -629,7 +758,7 @@ static int run_group(vamd_feed *f, FeedLane &L) {
     desc[W].nblocks = (long)n;
     desc[W].lW = plan.lW[W], desc[W].nW = plan.nW[W], desc[W].blocktype = plan.blocktype[W];
     if (!n) continue;
-    io[W].pcm = (const float *)L.d_pcm.p;
+    io[W].pcm = pcm;
     io[W].pcm_src = plan.src[W];
     io[W].pcm_channel_stride = cs;
     io[W].packets = (uint8_t *)L.d_pk[W].p;
@@ -656,6 +785,7 @@ static int run_group(vamd_feed *f, FeedLane &L) {
     P.packets[W] = (const uint8_t *)L.d_pk[W].p, P.stride[W] = f->pkcap[W], P.bs[W] = f->bs[W];
   }
   P.ch = ch, P.stream_stride = ss, P.eof = head + frames, P.frames_of = d_frames_of, P.head = head;
+  P.live = live;
   for (int attempt = 0;; attempt++) {
     uint8_t *hrec = (uint8_t *)L.h_rec.p;
     void *drec = nullptr, *dbytes = nullptr;
@@ -678,7 +808,7 @@ static int run_group(vamd_feed *f, FeedLane &L) {
     const int64_t total = *(const int64_t *)hrec;
     if (total <= (int64_t)L.h_out.bytes) {
       vamd_feed_result &R = L.result;
-      R.nstreams = ns, R.nblocks = nb;
+      R.nstreams = ns_out, R.nblocks = nb;
       R.stream_start = (const int64_t *)(hrec + o_start), R.offset = (const int64_t *)(hrec + o_off);
       R.granulepos = (const int64_t *)(hrec + o_gp), R.bits = (const int32_t *)(hrec + o_bits), R.info = hrec + o_info;
       R.bytes = (const uint8_t *)L.h_out.p, R.total_bytes = total;
@@ -697,6 +827,143 @@ static int run_group(vamd_feed *f, FeedLane &L) {
   return VAMD_OK;
 }
 
+// one group of a live lane: the pieces of its streams 0 .. L.nstreams-1 (and 0-frame pieces of its other open streams, which
+// then emit nothing: their walks stop where they stood).  Upload -> k_live_begin (fresh streams' states) -> k_live_ingest
+// (kept samples + piece into the other buffer) -> vamd_live_plan (stream ends where due, detector over the new steps,
+// resumed walk, rebase; its wait brings the block counts and every stream's next rebase home) -> analysis and packets as
+// a whole group's.  The host mirror of each stream says what the device holds of it.
+static int run_group_live(vamd_feed *f, FeedLane &L) {
+  const long nsc = L.nstreams;
+  const int ch = f->ch, bs1 = f->bs[1], head = bs1 / 2, pad = 3 * bs1, step = 64;
+  long ns = nsc;
+  for (long i = nsc; i < f->max_streams; i++)
+    if (L.live[(size_t)i].open) ns = i + 1;
+  const long cs = f->live_cs, ss = cs * ch;
+  const size_t sample = L.format == VAMD_FEED_S16 ? 2 : 4;
+  const long n_head = ((long)bs1 / f->write_frames + 1) * f->write_frames;  // lib/block.c:525-526
+  hipStream_t st = L.stream;
+  FEED_TRY(L.d_live.need((size_t)ns * sizeof(LiveIn)));
+  FEED_TRY(L.h_live.need((size_t)ns * (sizeof(LiveIn) + sizeof(vamd_live_geo) + 8)));
+  LiveIn *hin = (LiveIn *)L.h_live.p;
+  vamd_live_geo *geo = (vamd_live_geo *)(hin + ns);
+  long long *shift = (long long *)(geo + ns);
+  int64_t first = 0, quads = 0;
+  for (long i = 0; i < ns; i++) {
+    const int64_t n = i < nsc ? L.frames_of[(size_t)i] : 0;
+    const bool cl = i < nsc && L.close_of[(size_t)i];
+    FeedLane::LiveStream &m = L.live[(size_t)i];
+    LiveIn &in = hin[i];
+    vamd_live_geo &g = geo[i];
+    memset(&in, 0, sizeof(in));
+    memset(&g, 0, sizeof(g));
+    in.first = first, in.frames = n;
+    first += n;
+    in.fresh = !m.open;
+    if (!m.open && !n) {  // (a stream starts with its first frame: until then it is not there, and nothing of it is planned)
+      in.eof = LIVE_OPEN;
+      g.fresh = 1;
+      continue;
+    }
+    if (!m.open) {
+      m = FeedLane::LiveStream();
+      m.open = true, m.have = head;
+      in.keep = head;
+    } else {  // the rebase the last walk asked for
+      in.shift = m.shift, in.keep = m.have - m.shift;
+      m.origin += m.shift, m.steps -= m.shift / step, m.have = in.keep, m.shift = 0;
+    }
+    in.origin = m.origin;
+    m.have += n, m.total += n;
+    if (!m.headed && (m.total >= n_head || cl)) {  // the backward extrapolation: lib/block.c:524-528, or the close (:480-481)
+      m.headed = true;
+      g.n_head = (int)(m.total < n_head ? m.total : n_head);
+    }
+    g.have = m.have, g.kept = m.steps;
+    if (m.headed) {
+      const int64_t last = m.have / step - 4;  // lib/envelope.c:223-224
+      g.c1 = last > m.steps ? last - m.steps : 0;
+    }
+    if (cl) {
+      const int64_t s1 = m.steps + g.c1, sa = (m.have + pad) / step - 4;
+      g.c2 = sa > s1 ? sa - s1 : 0;
+    }
+    g.fresh = in.fresh, g.close = cl;
+    in.close = cl, in.eof = cl ? m.have : LIVE_OPEN;
+    m.steps += g.c1;
+    if (in.keep + n + pad + 256 > cs) {
+      L.err = "live feed: a stream's kept samples and piece exceed its buffer (the retention bound does not hold)";
+      return VAMD_EFAULT;
+    }
+    const int64_t q = (in.keep + n + pad + 256 + 3) / 4;
+    if (q > quads) quads = q;
+  }
+  const size_t in_bytes = (size_t)first * ch * sample;
+  FEED_TRY(L.d_in.need(in_bytes ? in_bytes : 16));
+  {
+    std::lock_guard<std::mutex> turn(*L.upload_turn);  // (run_group: one upload at a time per device)
+    FEED_TRY(hipEventRecord(L.ev0, st));
+    if (in_bytes) FEED_TRY(hipMemcpyAsync(L.d_in.p, L.h_in.p, in_bytes, hipMemcpyHostToDevice, st));
+    FEED_TRY(hipMemcpyAsync(L.d_live.p, hin, (size_t)ns * sizeof(LiveIn), hipMemcpyHostToDevice, st));
+    FEED_TRY(hipEventRecord(L.ev_up, st));
+    FEED_TRY(hipEventSynchronize(L.ev_up));
+  }
+  const LiveIn *d_live = (const LiveIn *)L.d_live.p;
+  vamd_bitrate_state *bst = f->managed ? (vamd_bitrate_state *)L.d_bstate.p : nullptr;
+  if (f->managed && !L.btmpl_ready) {
+    FEED_CALL(vamd_bitrate_init_states(L.ctx, (vamd_bitrate_state *)L.d_btmpl.p, 1));
+    L.btmpl_ready = true;
+  }
+  {
+    const long words = ns * (long)(sizeof(vamd_envelope_state) / 4);
+    hipLaunchKernelGGL(k_live_begin, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, ns, d_live, (vamd_envelope_state *)L.d_states.p,
+                       (float *)L.d_amp.p, bst, (const vamd_bitrate_state *)L.d_btmpl.p, (unsigned long long *)L.d_nan.p);
+    *(volatile int *)L.h_lstatus.p = 0;
+    void *d_lstatus = nullptr;
+    FEED_TRY(hipHostGetDevicePointer(&d_lstatus, L.h_lstatus.p, 0));
+    long blocks = (ns * quads + 255) / 256;
+    if (blocks > 256L * 32) blocks = 256L * 32;
+    if (blocks < 1) blocks = 1;
+    const float *old = (const float *)L.d_buf[L.cur].p;
+    float *pcm = (float *)L.d_buf[1 - L.cur].p;
+    if (L.format == VAMD_FEED_S16)
+      hipLaunchKernelGGL(k_live_ingest<int16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const int16_t *)L.d_in.p, ch, ns, (long)quads, pad + 256,
+                         d_live, old, pcm, ss, cs, (unsigned long long *)L.d_nan.p, (int *)d_lstatus);
+    else
+      hipLaunchKernelGGL(k_live_ingest<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float *)L.d_in.p, ch, ns, (long)quads, pad + 256,
+                         d_live, old, pcm, ss, cs, (unsigned long long *)L.d_nan.p, (int *)d_lstatus);
+    FEED_TRY(hipGetLastError());
+  }
+  L.cur = 1 - L.cur;
+  float *pcm = (float *)L.d_buf[L.cur].p;
+  vamd_stream_plan plan;
+  FEED_CALL(vamd_live_plan(L.ctx, pcm, ss, cs, ns, geo, (int)n_head, L.d_walk.p, (unsigned char *)L.d_rows.p, f->row_stride,
+                           (vamd_envelope_state *)L.d_states.p, shift, &plan));
+  if (*(volatile int *)L.h_lstatus.p) {  // (written by the ingest, mapped; the plan's wait is behind it)
+    L.err = "live feed: the ingest found a stream whose samples exceed its buffer";
+    return VAMD_EFAULT;
+  }
+  for (long i = 0; i < ns; i++) {
+    FeedLane::LiveStream &m = L.live[(size_t)i];
+    if (hin[i].close) {
+      m = FeedLane::LiveStream();  // (its next piece starts a fresh stream)
+      continue;
+    }
+    m.shift = shift[i];
+    if (m.shift < 0 || m.shift > m.have || m.have - m.shift > f->retain) {
+      L.err = "live feed: a stream would keep more samples than the retention bound allows";
+      return VAMD_EFAULT;
+    }
+  }
+  FeedLive live;
+  live.in = d_live, live.nan = (const unsigned long long *)L.d_nan.p;
+  const int r = finish_group(f, L, plan, pcm, ns, ss, cs, nullptr, live, nsc);
+  if (!r && L.result.stream_start && L.result.stream_start[nsc] != L.result.nblocks) {
+    L.err = "live feed: a stream outside the group emitted blocks";
+    return VAMD_EFAULT;
+  }
+  return r;
+}
+
 static void feed_lane_main(vamd_feed *f, FeedLane *lane) {
   FeedLane &L = *lane;
   (void)hipSetDevice(L.device);
@@ -705,7 +972,9 @@ static void feed_lane_main(vamd_feed *f, FeedLane *lane) {
     f->cv_work.wait(g, [&] { return f->stop || L.state == LANE_QUEUED; });
     if (f->stop) return;
     g.unlock();
-    const int r = run_group(f, L);
+    const int r = f->write_frames ? run_group_live(f, L) : run_group(f, L);
+    if (r && f->write_frames)  // (what the device holds of the lane's streams is unknown: they start afresh)
+      for (FeedLane::LiveStream &m : L.live) m = FeedLane::LiveStream();
     const double t = now_s();
     g.lock();
     L.status = r;
@@ -732,7 +1001,8 @@ static void feed_free(vamd_feed *f) {
     if (L.stream) (void)hipStreamSynchronize(L.stream);
     if (L.ctx) vamd_destroy(L.ctx);
     Buf *all[] = {&L.d_len, &L.h_len, &L.h_in, &L.h_out, &L.h_rec, &L.d_in, &L.d_pcm, &L.d_states, &L.d_amp, &L.d_pk[0], &L.d_pk[1], &L.d_bits[0],
-                  &L.d_bits[1], &L.d_status[0], &L.d_status[1], &L.d_rel, &L.d_sid, &L.d_sbytes, &L.d_soff, &L.d_bstate, &L.d_slice, &L.h_slice};
+                  &L.d_bits[1], &L.d_status[0], &L.d_status[1], &L.d_rel, &L.d_sid, &L.d_sbytes, &L.d_soff, &L.d_bstate, &L.d_slice, &L.h_slice,
+                  &L.d_buf[0], &L.d_buf[1], &L.d_walk, &L.d_rows, &L.d_nan, &L.d_btmpl, &L.d_live, &L.h_live, &L.h_lstatus};
     for (int W = 0; W < 2; W++) {
       Buf *m[] = {&L.d_mpk[W], &L.d_mbits[W], &L.d_mposts[W], &L.d_mvalid[W], &L.d_miwork[W], &L.d_mnz[W], &L.d_choice[W], &L.d_fbits[W]};
       for (Buf *b : m) b->drop();
@@ -750,14 +1020,12 @@ static void feed_free(vamd_feed *f) {
 // why this thread's last vamd_feed_create failed (vamd_feed_last_error(NULL))
 thread_local std::string feed_create_err;
 
-extern "C" {
-
-int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes, const int *devices, int ndevices,
-                     int lanes_per_device, long max_streams, long max_frames, int format) {
+static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes, const int *devices, int ndevices,
+                       int lanes_per_device, long max_streams, long max_frames, int format, int write_frames) {
   if (!out) return VAMD_EINVAL;
   *out = nullptr;
   if (!setup_blob || lanes_per_device < 1 || lanes_per_device > 8 || max_streams < 1 || max_frames < 1 || ndevices < 0 ||
-      ndevices > 64 || (ndevices > 0 && !devices) || (format != VAMD_FEED_S16 && format != VAMD_FEED_F32))
+      ndevices > 64 || (ndevices > 0 && !devices) || (format != VAMD_FEED_S16 && format != VAMD_FEED_F32) || write_frames < 0)
     return VAMD_EINVAL;
   feed_create_err.clear();
   // a bitrate-managed setup is fed through its manager (run_group_managed), which needs the blob's manager section; a
@@ -775,7 +1043,7 @@ int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes,
   if (ndevices == 0) devs.push_back(cur);
   for (int i = 0; i < ndevices; i++) devs.push_back(devices[i] >= 0 ? devices[i] : cur);
   vamd_feed *f = new vamd_feed;
-  f->max_streams = max_streams, f->max_frames = max_frames, f->format = format;
+  f->max_streams = max_streams, f->max_frames = max_frames, f->format = format, f->write_frames = write_frames;
   f->managed = h.managed && h.off_bitrate;
   {
     const vamd::Knobs K = vamd::read_knobs();
@@ -789,7 +1057,7 @@ int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes,
     FeedLane &L = f->lanes[l];
     L.device = devs[l % devs.size()];
     L.upload_turn = f->upload_turns[l % devs.size()].get();
-    L.h_in.host = L.h_out.host = L.h_rec.host = L.h_len.host = L.h_slice.host = true;
+    L.h_in.host = L.h_out.host = L.h_rec.host = L.h_len.host = L.h_slice.host = L.h_live.host = L.h_lstatus.host = true;
     r = vamd_create(&L.ctx, setup_blob, blob_bytes, L.device);
     if (r) break;
     hipError_t e = hipSetDevice(L.device);
@@ -802,6 +1070,29 @@ int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes,
       f->ch = vamd_channels(L.ctx);
       for (int W = 0; W < 2; W++) f->bs[W] = vamd_blocksize(L.ctx, W), f->pkcap[W] = vamd_packet_capacity(L.ctx, W);
       if (f->pkcap[0] <= 0 || f->pkcap[1] <= 0) r = VAMD_EIMPL;  // packets of this mode are not assembled on the GPU
+      if (!r && write_frames) {
+        const char *why = vamd_live_check(L.ctx, write_frames, max_frames);
+        if (why) {
+          feed_create_err = why;
+          r = VAMD_EIMPL;
+        }
+        f->retain = vamd_live_retain(L.ctx, write_frames);
+        f->live_cs = (long)al((size_t)(2 * f->retain + max_frames + 3 * f->bs[1] + 512), 64);
+        f->row_stride = f->live_cs / 64 + 16;
+      }
+    }
+    if (e == hipSuccess && !r && write_frames) {  // a live lane's device state, for every stream it may carry
+      const size_t ns = (size_t)max_streams;
+      for (int b = 0; b < 2 && e == hipSuccess; b++) e = L.d_buf[b].need(ns * f->ch * (size_t)f->live_cs * 4);
+      if (e == hipSuccess) e = L.d_walk.need(ns * VAMD_LIVE_WALK_BYTES);
+      if (e == hipSuccess) e = L.d_rows.need(ns * (size_t)f->row_stride);
+      if (e == hipSuccess) e = L.d_nan.need(ns * 8);
+      if (e == hipSuccess) e = L.d_states.need(ns * sizeof(vamd_envelope_state));
+      if (e == hipSuccess) e = L.d_amp.need(ns * 4);
+      if (e == hipSuccess) e = L.d_bstate.need(ns * sizeof(vamd_bitrate_state));
+      if (e == hipSuccess) e = L.d_btmpl.need(sizeof(vamd_bitrate_state));
+      if (e == hipSuccess) e = L.h_lstatus.need(64);
+      L.live.resize(ns);
     }
     // the arenas: the group's samples; packets: half the samples' size AS 16-BIT to start with (a q 0.4 stream is a
     // tenth of that, q 1.0 on noise a third; run_group grows the arena when a group needs more)
@@ -819,14 +1110,31 @@ int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes,
     }
   }
   if (r) {
-    feed_create_err = f->lanes.empty() || !f->lanes[0].ctx ? "vamd_create failed (setup blob refused, or a HIP failure)"
-                                                              : "the setup's packets are not assembled on the GPU, or a HIP failure";
+    if (feed_create_err.empty())
+      feed_create_err = f->lanes.empty() || !f->lanes[0].ctx ? "vamd_create failed (setup blob refused, or a HIP failure)"
+                                                                : "the setup's packets are not assembled on the GPU, or a HIP failure";
     feed_free(f);
     delete f;
     return r;
   }
   *out = f;
   return VAMD_OK;
+}
+
+extern "C" {
+
+int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes, const int *devices, int ndevices,
+                     int lanes_per_device, long max_streams, long max_frames, int format) {
+  return feed_create(out, setup_blob, blob_bytes, devices, ndevices, lanes_per_device, max_streams, max_frames, format, 0);
+}
+
+int vamd_feed_create_live(vamd_feed **out, const void *setup_blob, size_t blob_bytes, const int *devices, int ndevices,
+                          int lanes_per_device, long max_streams, long max_frames, int format, int write_frames) {
+  if (write_frames < 1) {
+    if (out) *out = nullptr;
+    return VAMD_EINVAL;
+  }
+  return feed_create(out, setup_blob, blob_bytes, devices, ndevices, lanes_per_device, max_streams, max_frames, format, write_frames);
 }
 
 void vamd_feed_destroy(vamd_feed *f) {
@@ -866,7 +1174,7 @@ int vamd_feed_buffer(vamd_feed *f, void **pcm) {
 }
 
 int vamd_feed_wrote(vamd_feed *f, int slot, long nstreams, long frames) {
-  if (!f || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  if (!f || slot < 0 || slot >= (int)f->lanes.size() || f->write_frames) return VAMD_EINVAL;
   if (nstreams < 1 || nstreams > f->max_streams || frames < 1 || frames > f->max_frames) return VAMD_EINVAL;
   std::lock_guard<std::mutex> g(f->m);
   FeedLane &L = f->lanes[(size_t)slot];
@@ -882,7 +1190,7 @@ int vamd_feed_wrote(vamd_feed *f, int slot, long nstreams, long frames) {
 }
 
 int vamd_feed_wrote_v(vamd_feed *f, int slot, long nstreams, const int64_t *frames) {
-  if (!f || !frames || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  if (!f || !frames || slot < 0 || slot >= (int)f->lanes.size() || f->write_frames) return VAMD_EINVAL;
   if (nstreams < 1 || nstreams > f->max_streams) return VAMD_EINVAL;
   long longest = 0;
   long long total = 0;
@@ -897,6 +1205,29 @@ int vamd_feed_wrote_v(vamd_feed *f, int slot, long nstreams, const int64_t *fram
   if (L.state != LANE_FILLING) return VAMD_EINVAL;
   L.nstreams = nstreams, L.frames = longest, L.format = f->format;
   L.frames_of.assign(frames, frames + nstreams);
+  L.status = 0;
+  memset(&L.result, 0, sizeof(L.result));
+  L.t_wrote = now_s();
+  L.state = LANE_QUEUED;
+  f->cv_work.notify_all();
+  return VAMD_OK;
+}
+
+int vamd_feed_wrote_live(vamd_feed *f, int slot, long nstreams, const int64_t *frames, const uint8_t *close) {
+  if (!f || !frames || slot < 0 || slot >= (int)f->lanes.size() || !f->write_frames) return VAMD_EINVAL;
+  if (nstreams < 1 || nstreams > f->max_streams) return VAMD_EINVAL;
+  std::lock_guard<std::mutex> g(f->m);
+  FeedLane &L = f->lanes[(size_t)slot];
+  if (L.state != LANE_FILLING) return VAMD_EINVAL;
+  for (long i = 0; i < nstreams; i++) {
+    if (frames[i] < 0 || frames[i] > f->max_frames) return VAMD_EINVAL;
+    if (close && close[i] && !frames[i] && !L.live[(size_t)i].open) return VAMD_EINVAL;  // (closing a stream that never had a frame)
+  }
+  L.nstreams = nstreams, L.frames = f->max_frames, L.format = f->format;
+  L.frames_of.assign(frames, frames + nstreams);
+  L.close_of.assign((size_t)nstreams, 0);
+  if (close)
+    for (long i = 0; i < nstreams; i++) L.close_of[(size_t)i] = close[i] != 0;
   L.status = 0;
   memset(&L.result, 0, sizeof(L.result));
   L.t_wrote = now_s();

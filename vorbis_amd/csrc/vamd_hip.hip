@@ -24,6 +24,7 @@
 #include "vorbis_amd.h"
 #include "vamd_bind.h"
 #include "vamd_knobs.h"
+#include "vamd_live.h"
 #include "k_transform.h"
 #include "k_noise.h"
 #include "k_tone.h"
@@ -1593,6 +1594,9 @@ int vamd_envelope_search(vamd_ctx *c, const float *const *pcm, long nsteps, vamd
   return VAMD_OK;
 }
 
+static int plan_emit(vamd_ctx *c, const BlockoutP &B, long nstreams, long stream_stride, void *v_blocks, void *v_counts, void *v_base,
+                     vamd_stream_plan *plan, void *extra_host = nullptr, const void *extra_dev = nullptr, size_t extra_bytes = 0);
+
 // whole != 0: the streams are complete (vamd_plan_streams_whole) -- `nsamples` counts the space in front of the first
 // sample and the real samples; the buffers have room for the end-of-stream padding behind them
 // frames_of (host, whole streams only): the streams' own lengths, each <= nsamples - blocksizes[1]/2
@@ -1715,8 +1719,19 @@ static int plan_streams(vamd_ctx *c, float *pcm, long stream_stride, long channe
   hipLaunchKernelGGL(k_plan_streams, dim3((unsigned)nstreams), dim3(64), plan_lds, s, B, nstreams, flags1, steps1, steps1, flags2, steps2,
                      (PlannedBlock *)v_blocks, (int *)v_counts, (long long *)nullptr, geo, 1);
   HIP_TRY(c, hipGetLastError());
+  return plan_emit(c, B, nstreams, stream_stride, v_blocks, v_counts, v_base, plan);
+}
+
+// The walk's blocks of every stream -> the plan's per-class arrays and order[]: the block counts come home (the plan's one
+// wait; `extra_bytes` more of the device's `extra_dev` beside them, into `extra_host`), the bases go up, k_plan_emit lays
+// the blocks out.  (The tail of plan_streams, shared with vamd_live_plan.)
+static int plan_emit(vamd_ctx *c, const BlockoutP &B, long nstreams, long stream_stride, void *v_blocks, void *v_counts, void *v_base,
+                     vamd_stream_plan *plan, void *extra_host, const void *extra_dev, size_t extra_bytes) {
+  hipStream_t s = c->stream;
+  int r;
   std::vector<int> counts((size_t)nstreams * 2);
   HIP_TRY(c, hipMemcpyAsync(counts.data(), v_counts, counts.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (extra_bytes) HIP_TRY(c, hipMemcpyAsync(extra_host, extra_dev, extra_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   for (long i = 0; i < nstreams; i++)
     if (counts[2 * i] < 0 || counts[2 * i + 1] < 0 || (long)counts[2 * i] + counts[2 * i + 1] > B.maxblocks)
@@ -1791,6 +1806,140 @@ int vamd_plan_streams_whole_v(vamd_ctx *c, float *pcm, long stream_stride, long 
                               const int64_t *nframes, vamd_envelope_state *states, vamd_stream_plan *plan) {
   if (c && (max_frames < 0 || !nframes)) return fail(c, VAMD_EINVAL, "negative frame count / null lengths");
   return plan_streams(c, pcm, stream_stride, channel_stride, nstreams, c ? c->B.bs[1] / 2 + max_frames : 0, states, plan, 1, nframes);
+}
+
+// ---- the live feed's plan (vamd_live.h; vamd_feed.hip is its caller) ----
+static long live_n_head(const vamd_ctx *c, int write_frames) { return ((long)c->B.bs[1] / write_frames + 1) * write_frames; }  // lib/block.c:525-526
+
+long vamd_live_retain(const vamd_ctx *c, int write_frames) {
+  const long bs0 = c->B.bs[0], bs1 = c->B.bs[1], step = c->B.env.searchstep;
+  long run = 3 * bs1 / 4 + bs0 / 4 + (VAMD_VE_WIN + 3) * step;  // (a): out of detector steps
+  if (run < bs1) run = bs1;                                    // (b): the next window does not fit
+  const long walk = run + bs1 / 2 + 2 * step, head = bs1 / 2 + live_n_head(c, write_frames);
+  return walk > head ? walk : head;
+}
+
+static size_t live_lpc_lds(const vamd_ctx *c, int write_frames) {
+  const long bs1 = c->B.bs[1], head = bs1 / 2, pad = 3 * bs1, n = live_n_head(c, write_frames) + head;
+  return 80 * 8 + VAMD_LPC_MAX_ORDER * 4 + (size_t)(n > bs1 + pad ? n : bs1 + pad) * 4;
+}
+
+// (the walk's LDS: a mark and a flag byte per step of the largest buffer)
+static size_t live_plan_lds(long steps) { return (size_t)(((steps + 4 + 15) & ~15L) + ((steps + 15) & ~15L)); }
+
+const char *vamd_live_check(const vamd_ctx *c, int write_frames, long max_frames) {
+  if (!c || write_frames < 1) return "bad context / write cadence";
+  if (live_lpc_lds(c, write_frames) > c->lds_per_block)
+    return "write_frames too large: the backward extrapolation over its first n_head frames does not fit a workgroup's LDS";
+  const long cap = 2 * vamd_live_retain(c, write_frames) + max_frames + 3 * c->B.bs[1] + 256;
+  if (live_plan_lds(cap / c->B.env.searchstep) > c->lds_per_block) return "max_frames too large for one piece: its detector marks must fit a workgroup's LDS";
+  return nullptr;
+}
+
+int vamd_live_plan(vamd_ctx *c, float *pcm, long ss, long cs, long nstreams, const vamd_live_geo *lg, int n_head,
+                   void *walk, unsigned char *rows, long row_stride, vamd_envelope_state *states, long long *shift,
+                   vamd_stream_plan *plan) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  if (!plan || !lg || !pcm || !walk || !rows || !states || !shift || nstreams < 1) return fail(c, VAMD_EINVAL, "live plan: null argument");
+  memset(plan, 0, sizeof(*plan));
+  plan->nstreams = nstreams;
+  static_assert(sizeof(WalkState) == VAMD_LIVE_WALK_BYTES, "vamd_live.h: VAMD_LIVE_WALK_BYTES");
+  const EnvP &E = c->B.env;
+  const int ch = c->B.channels, head = c->B.bs[1] / 2, pad = 3 * c->B.bs[1];
+  const long step = E.searchstep;
+  BlockoutP B;
+  B.bs[0] = c->B.bs[0];
+  B.bs[1] = c->B.bs[1];
+  blockout_set_step(B, E.searchstep);
+  B.nsamples = cs;
+  B.eof = 0;
+  B.nsteps = 0;
+  B.maxblocks = (int)(cs / (B.bs[0] / 2)) + 2;
+  // per stream: k_plan_live's geometry, the two extrapolations' (eof < 0: not in this group), the detector passes' step
+  // counts and first samples; one upload out of the context's pinned buffer.  (shift[]: written by the walk, fetched.)
+  const size_t o_ph = (size_t)nstreams * sizeof(LiveGeo), o_pt = o_ph + (size_t)nstreams * sizeof(PlanGeo),
+               o_c1 = o_pt + (size_t)nstreams * sizeof(PlanGeo), o_c2 = o_c1 + (size_t)nstreams * 4,
+               o_f1 = (o_c2 + (size_t)nstreams * 4 + 7) & ~(size_t)7, o_f2 = o_f1 + (size_t)nstreams * 8, o_sh = o_f2 + (size_t)nstreams * 8,
+               total = o_sh + (size_t)nstreams * 8;
+  if (c->h_geo_bytes < total) {
+    if (c->h_geo) HIP_TRY(c, hipHostFree(c->h_geo));
+    c->h_geo = nullptr, c->h_geo_bytes = 0;
+    HIP_TRY(c, hipHostMalloc(&c->h_geo, total + total / 2, hipHostMallocDefault));
+    c->h_geo_bytes = total + total / 2;
+  }
+  void *v_geo;
+  int r;
+  if ((r = ws_get(c, 0, vamd_ctx::WS_PLAN_GEO, total, &v_geo))) return r;
+  unsigned char *hg = (unsigned char *)c->h_geo, *dg = (unsigned char *)v_geo;
+  LiveGeo *g = (LiveGeo *)hg;
+  PlanGeo *gh = (PlanGeo *)(hg + o_ph), *gt = (PlanGeo *)(hg + o_pt);
+  int *c1 = (int *)(hg + o_c1), *c2 = (int *)(hg + o_c2);
+  long long *f1 = (long long *)(hg + o_f1), *f2 = (long long *)(hg + o_f2);
+  long n1 = 0, n2 = 0, steps_max = 0;
+  bool heads = false, closes = false;
+  for (long i = 0; i < nstreams; i++) {
+    const vamd_live_geo &x = lg[i];
+    const long steps = (long)(x.kept + x.c1 + (x.close ? x.c2 : 0));
+    if (x.have < 0 || x.have + pad + 128 > cs || x.kept < 0 || x.c1 < 0 || x.c2 < 0 || steps * step > cs)
+      return fail(c, VAMD_EINVAL, "live plan: a stream's geometry outside its buffer");
+    g[i].have = x.have, g[i].kept = (int)x.kept, g[i].c1 = (int)x.c1, g[i].c2 = (int)x.c2, g[i].fresh = x.fresh, g[i].close = x.close;
+    gh[i].nsamples = gt[i].nsamples = x.have + pad;
+    gh[i].eof = x.n_head > 0 ? head + x.n_head : -1;
+    gt[i].eof = x.close ? x.have : -1;
+    gh[i].nsteps = gt[i].nsteps = gh[i].split = gt[i].split = 0;
+    // a stream with no steps in a pass reads from its buffer's start (the launch takes the longest stream's steps for all)
+    c1[i] = (int)x.c1, f1[i] = x.c1 ? x.kept * step : 0;
+    c2[i] = x.close ? (int)x.c2 : 0, f2[i] = c2[i] ? (x.kept + x.c1) * step : 0;
+    if (c1[i] > n1) n1 = c1[i];
+    if (c2[i] > n2) n2 = c2[i];
+    if (steps > steps_max) steps_max = steps;
+    heads |= x.n_head > 0;
+    closes |= x.close != 0;
+    if (x.kept + x.c1 > row_stride) return fail(c, VAMD_EINVAL, "live plan: a stream's flags do not fit its row");
+  }
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemcpyAsync(dg, hg, o_sh, hipMemcpyHostToDevice, s));
+  const LiveGeo *d_g = (const LiveGeo *)dg;
+  const PlanGeo *d_gh = (const PlanGeo *)(dg + o_ph), *d_gt = (const PlanGeo *)(dg + o_pt);
+  const int *d_c1 = (const int *)(dg + o_c1), *d_c2 = (const int *)(dg + o_c2);
+  const long long *d_f1 = (const long long *)(dg + o_f1), *d_f2 = (const long long *)(dg + o_f2);
+  long long *d_sh = (long long *)(dg + o_sh);
+  void *v_flags, *v_blocks, *v_counts, *v_base, *v_pending;
+  if ((r = ws_get(c, 0, vamd_ctx::WS_PLAN_FLAGS, (size_t)nstreams * (n1 + n2 + 1), &v_flags))) return r;
+  if ((r = ws_get(c, 0, vamd_ctx::WS_PLAN_BLOCKS, (size_t)nstreams * B.maxblocks * sizeof(PlannedBlock), &v_blocks))) return r;
+  if ((r = ws_get(c, 0, vamd_ctx::WS_PLAN_COUNTS, (size_t)nstreams * 2 * sizeof(int), &v_counts))) return r;
+  if ((r = ws_get(c, 0, vamd_ctx::WS_PLAN_BASE, (size_t)(3 * nstreams + 1) * sizeof(long long), &v_base))) return r;
+  if ((r = ws_get(c, 0, vamd_ctx::WS_PLAN_PENDING, (size_t)nstreams * sizeof(long long), &v_pending))) return r;
+  unsigned char *flags1 = (unsigned char *)v_flags, *flags2 = flags1 + (size_t)nstreams * n1;
+  const size_t plan_lds = live_plan_lds(steps_max), lpc_lds = (size_t)(80 * 8 + VAMD_LPC_MAX_ORDER * 4) +
+                                                                 (size_t)(n_head + head > c->B.bs[1] + pad ? n_head + head : c->B.bs[1] + pad) * 4;
+  if (plan_lds > c->lds_per_block) return fail(c, VAMD_EINVAL, "live plan: a piece too long for one plan (its marks must fit a workgroup's LDS)");
+  if (lpc_lds > c->lds_per_block) return fail(c, VAMD_EIMPL, "live plan: write cadence too large for the stream-start extrapolation");
+  HIP_TRY(c, hipFuncSetAttribute((const void *)k_plan_live, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block));
+  HIP_TRY(c, hipFuncSetAttribute((const void *)k_lpc_head, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block));
+  HIP_TRY(c, hipFuncSetAttribute((const void *)k_lpc_tail, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block));
+  // the stream starts that are due: lib/block.c:417-458 over the first n_head frames
+  if (heads && n_head > 32)
+    hipLaunchKernelGGL(k_lpc_head, dim3((unsigned)(nstreams * ch)), dim3(64), lpc_lds, s, ch, nstreams, pcm, ss, cs, head, n_head, d_gh);
+  // the detector over every stream's new steps, from its carried state
+  if (n1 && (r = envelope_search_batch(c, pcm, ss, cs, nstreams, n1, states, flags1, c->d_bad + 1, d_c1, d_f1))) return r;
+  WalkState *d_walk = (WalkState *)walk;
+  if (closes) {
+    // the closing streams' ends as vamd_plan_streams_whole makes them: where the walk stands when the data runs out, the
+    // forward extrapolation from there (lib/block.c:474-512), the detector over the padding
+    hipLaunchKernelGGL(k_plan_live, dim3((unsigned)nstreams), dim3(64), plan_lds, s, B, nstreams, steps_max, d_g, rows, row_stride,
+                       flags1, n1, flags2, n2, pad, d_walk, (PlannedBlock *)nullptr, (int *)nullptr, (long long *)v_pending, (long long *)nullptr);
+    hipLaunchKernelGGL(k_lpc_tail, dim3((unsigned)(nstreams * ch)), dim3(64), lpc_lds, s, ch, nstreams, pcm, ss, cs, 0L, c->B.bs[1], pad,
+                       (const long long *)v_pending, d_gt);
+    HIP_TRY(c, hipGetLastError());
+    if (n2 && (r = envelope_search_batch(c, pcm, ss, cs, nstreams, n2, states, flags2, c->d_bad + 1, d_c2, d_f2))) return r;
+  }
+  HIP_TRY(c, hipMemsetAsync(v_counts, 0, (size_t)nstreams * 2 * sizeof(int), s));
+  hipLaunchKernelGGL(k_plan_live, dim3((unsigned)nstreams), dim3(64), plan_lds, s, B, nstreams, steps_max, d_g, rows, row_stride,
+                     flags1, n1, flags2, n2, pad, d_walk, (PlannedBlock *)v_blocks, (int *)v_counts, (long long *)nullptr, d_sh);
+  HIP_TRY(c, hipGetLastError());
+  return plan_emit(c, B, nstreams, ss, v_blocks, v_counts, v_base, plan, shift, d_sh, (size_t)nstreams * 8);
 }
 
 int vamd_gather_blocks(vamd_ctx *c, const vamd_stream_plan *plan, int W, const float *pcm, long channel_stride,

@@ -1480,6 +1480,71 @@ __global__ __launch_bounds__(64) void k_plan_streams(BlockoutP B, long nstreams,
   }
 }
 
+// The live feed's walk (vamd_live_plan): a stream fed in pieces resumes from its WalkState, over the flags of the steps it
+// keeps (rows[s][0, kept), carried from its earlier groups) followed by this group's first detector pass (f1, c1 steps) and,
+// for a stream that closes, its second pass over the padding (f2, c2 steps).  Positions are in the group's buffer
+// coordinates.  pending != null: the dry run of a closing group (nothing emitted, nothing carried).  Otherwise the blocks
+// are emitted and a stream that goes on is rebased (walk_rebase): its state and its row of kept flags move down by
+// shift[s] samples, where the next group's buffer begins.
+struct LiveGeo {
+  long long have;     // samples in the buffer: the kept ones and this group's piece (the head room at a stream's start included)
+  int kept, c1, c2;   // detector steps, see above
+  int fresh, close;   // the stream starts / ends in this group
+};
+__global__ __launch_bounds__(64) void k_plan_live(BlockoutP B, long nstreams, long lds_steps, const LiveGeo *__restrict__ geo,
+                                                  unsigned char *__restrict__ rows, long row_stride, const unsigned char *__restrict__ f1,
+                                                  long n1, const unsigned char *__restrict__ f2, long n2, int pad, WalkState *__restrict__ walk,
+                                                  PlannedBlock *__restrict__ blocks, int *__restrict__ counts,
+                                                  long long *__restrict__ pending, long long *__restrict__ shift) {
+  unsigned char *marks = (unsigned char *)vamd_smem;  // [lds_steps + 4]
+  unsigned char *fl = marks + ((lds_steps + 4 + 15) & ~15L);  // [lds_steps]: the raw flags
+  const long s = blockIdx.x;
+  const LiveGeo g = geo[s];
+  const bool emit = pending == nullptr, eof = emit && g.close;
+  B.nsamples = eof ? g.have + pad : g.have;
+  B.eof = eof ? g.have : 0;
+  B.nsteps = (long)g.kept + g.c1 + (eof ? g.c2 : 0);
+  if (B.nsteps > lds_steps) B.nsteps = lds_steps;  // (the host sized lds_steps for every stream: never taken)
+  const long last = blockout_steps(B);
+  unsigned char *row = rows + s * row_stride;
+  for (long p = threadIdx.x; p < B.nsteps; p += 64)
+    fl[p] = p < g.kept ? row[p] : (p < (long)g.kept + g.c1 ? f1[s * n1 + p - g.kept] : f2[s * n2 + p - g.kept - g.c1]);
+  __syncthreads();
+  for (long p = threadIdx.x; p < lds_steps + 4; p += 64) {
+    int m = 0;  // mark_at()
+    if (p < last) {
+      if (p >= 1) m |= fl[p - 1] & 1;
+      m |= fl[p] & 3;
+      if (p + 1 < last) m |= fl[p + 1] & 2;
+    }
+    marks[p] = (unsigned char)(m != 0);
+  }
+  __syncthreads();
+  WalkState st = g.fresh ? walk_fresh(B) : walk[s];
+  int n0 = 0, nl = 0;
+  long pc = 0;
+  plan_stream(B, marks, emit ? blocks + s * B.maxblocks : nullptr, &n0, &nl, &pc, &st);
+  if (!emit) {
+    if (threadIdx.x == 0) pending[s] = pc;
+    return;
+  }
+  if (threadIdx.x == 0) {
+    counts[2 * s] = n0;
+    counts[2 * s + 1] = nl;
+  }
+  if (g.close) {  // (the stream's next piece starts a fresh one)
+    if (threadIdx.x == 0) shift[s] = 0;
+    return;
+  }
+  const long sh = walk_rebase(B, st.centerW), k = blockout_div_step(B, sh);
+  for (long p = threadIdx.x; p + k < B.nsteps; p += 64) row[p] = fl[p + k];
+  if (threadIdx.x == 0) {
+    st.centerW -= sh, st.cursor -= sh, st.curmark -= sh;
+    walk[s] = st;
+    shift[s] = sh;
+  }
+}
+
 // ---- the two ends of a stream (k_lpc.h): what vorbis_analysis_wrote() extrapolates on the host in the reference ----
 // a wave per (stream, channel).  x = the channel's buffer: x[0, head) the (zero) space in front of the first sample,
 // x[head, head + n) the first n real samples.  lib/block.c:417-458.
@@ -1510,6 +1575,7 @@ __global__ __launch_bounds__(64) void k_lpc_tail(int ch, long nstreams, float *_
                                                  const long long *__restrict__ pending, const PlanGeo *__restrict__ geo) {
   const long sc = blockIdx.x, s = sc / ch;
   if (geo) eof = (long)geo[s].eof;
+  if (eof < 0) return;  // (a live group's stream that does not close here)
   const int c = (int)(sc - s * ch);
   float *x = pcm + s * stream_stride + (long)c * channel_stride;
   double *aut = (double *)vamd_smem;                      // [2 * 32 + 1], padded to 80
