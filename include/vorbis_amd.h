@@ -553,7 +553,7 @@ vamd_ctx *vamd_batcher_context(vamd_batcher *b);
 /* ---- the host-fed farm (ABI 9): whole streams in from HOST memory, finished packets back to host memory, over one
  * or several GPUs (SURVEY.md 8d "report separately H2D/D2H-inclusive", 8e).  Everything above assumes samples that are
  * already in HBM, or one block per call; an encoder farm holds decoded audio in host memory -- 16-bit interleaved, as
- * examples/encoder_example.c:179-202 reads it -- and wants Ogg payloads back.  A vamd_feed owns LANES (per device: a
+ * examples/encoder_example.c:179-202 reads it -- and wants Ogg payloads back ("the Ogg feed", below).  A vamd_feed owns LANES (per device: a
  * context, a HIP stream, a library thread, pinned input and output arenas, the streams' HBM buffers); a GROUP of streams
  * travels through one lane:
  *     upload (one copy command out of the pinned arena) -> 16-bit to float on the device (x / 32768.f, exactly
@@ -641,6 +641,47 @@ int vamd_feed_packets(vamd_feed *f, int slot, vamd_feed_result *out);
 int vamd_feed_release(vamd_feed *f, int slot);
 /* the text of the feed's last failure; with f == NULL, of this thread's last vamd_feed_create() that failed */
 const char *vamd_feed_last_error(const vamd_feed *f);
+
+/* ---- the Ogg feed: complete Ogg Vorbis I files beside the packets (whole-stream feeds; still ABI 9: additions only).
+ *     vamd_feed_ogg_headers(f, id, comment, setup)   once, before the first vamd_feed_buffer: the feed is an Ogg feed
+ *     slot = vamd_feed_buffer(f, &pcm) ... [vamd_feed_ogg_serials(f, slot, ...)] ... vamd_feed_wrote / _wrote_v
+ *     vamd_feed_ogg(f, slot, &files)                 waits as vamd_feed_packets does; one byte range per stream
+ *     vamd_feed_packets(f, slot, &out)               unchanged, and still there
+ * The three header packets are what vorbis_analysis_headerout() gives for the encoder setup the blob was packed from (the
+ * setup header is libvorbis' codebook packing: the host's, once per setup); they are validated -- packet types 1 / 3 / 5
+ * + "vorbis", a 30-byte identification header whose channels, rate and block sizes are the context's -- else VAMD_EINVAL,
+ * the reason in vamd_feed_last_error.  A live feed answers VAMD_EIMPL: a page may span two groups, so the open page's
+ * packets would have to stay on the device between them (not built yet).  One comment packet serves every stream.
+ * Framing (doc/framing.html, doc/a1-encapsulation-ogg.tex) happens on the device behind the group's last packet: the
+ * copy kernels keep a mirror of the packet arena in HBM, k_ogg_plan walks every stream's packet sizes into pages,
+ * k_ogg_pages writes each page -- header, lacing, body, CRC -- straight into a second pinned arena; no further host wait.
+ * THE PAGING POLICY is fixed, so a stream's file is a function of its packets and serial number alone:
+ *   - a packet of n bytes is n / 255 lacing values of 255 and one of n % 255;
+ *   - page 0 holds the identification header alone (flags 0x02, granule position 0, sequence number 0; 58 bytes);
+ *   - the comment and setup headers start on page 1, granule position 0; the page on which the setup header ends is closed;
+ *   - the first audio packet starts a fresh page; segments are taken in order; before a segment is taken the page is
+ *     closed if it holds 255 segments, wherever that falls; at a packet boundary it is closed once its body holds more
+ *     than 4096 bytes and at least four packets have been completed on it; the end of the stream closes the last page;
+ *   - flags: 0x01 where the page's first segment continues a packet, 0x04 on the page with the stream's last segment;
+ *     sequence numbers count from 0; a page's granule position is that of the last packet completed on it, -1 if none
+ *     (so the last page's is the stream's frame count, which trims the decoder's output); the CRC is framing.html's.
+ * Byte equality with libogg's own page cuts is not claimed.  A stream in which any block has no packet (bits = -1) gets
+ * NO file -- a hole would decode out of lap: its range is empty, status[s] carries that block's VAMD_STATUS_*; the other
+ * streams of the group are untouched.  Serial numbers: stream s of a group gets the feed's running counter (0, 1, 2, ...
+ * over all groups in vamd_feed_wrote order) unless vamd_feed_ogg_serials, between vamd_feed_buffer and vamd_feed_wrote*,
+ * names the first n streams' itself.  Pinned memory: the file arena is sized from the packet arena (about 7 % more). */
+typedef struct vamd_feed_ogg_result {
+  int64_t nstreams;
+  const int64_t *stream_offset;   /* [nstreams + 1]: stream s's file is bytes[stream_offset[s] .. stream_offset[s + 1]) */
+  const int32_t *npages;          /* [nstreams] */
+  const uint8_t *status;          /* [nstreams] 0, or the VAMD_STATUS_* of the block that cost the stream its file */
+  const uint8_t *bytes;           /* the files, end to end (the lane's pinned file arena; valid until vamd_feed_release) */
+  int64_t total_bytes;
+} vamd_feed_ogg_result;
+int vamd_feed_ogg_headers(vamd_feed *f, const void *id, long id_bytes, const void *comment, long comment_bytes,
+                          const void *setup, long setup_bytes);
+int vamd_feed_ogg_serials(vamd_feed *f, int slot, const uint32_t *serials, long n);
+int vamd_feed_ogg(vamd_feed *f, int slot, vamd_feed_ogg_result *out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,231 @@
+"""CPU suite: the Ogg feed's paging walk, CRC and host mux (vorbis_amd/csrc/k_ogg.h compiled with the host compiler,
+tests/ogg_host.py) against a bit-serial CRC and a demuxer written from doc/framing.html alone -- and, with the reference
+build, against the reference's own header packets, packets and decoder."""
+import tempfile
+
+import numpy as np
+import pytest
+
+from tests import ogg_host as oh
+
+
+@pytest.fixture(scope="module")
+def host():
+    return oh.HostOgg(oh.build(tempfile.mkdtemp(prefix="ogg")))
+
+
+def test_chunked_crc_equals_the_bit_serial_one(host):
+    """The shipped CRC in its chunk-and-combine form (a chunk per lane, a log-step tree of multiplies by x^(8 k) mod P)
+    with the kernel's constants and with others: every length 0 .. 600, lengths around every multiple of the chunk size
+    up to a full page (27 + 255 + 255 * 255 = 65 307 bytes), 200 random lengths."""
+    rng = np.random.default_rng(1)
+    full = 27 + 255 + 255 * 255
+    data = rng.integers(0, 256, full + 8, dtype=np.uint8).tobytes()
+    serial = {}
+
+    def want(n):
+        if n not in serial:
+            serial[n] = oh.crc_bitserial(data[:n])
+        return serial[n]
+    for n in range(601):
+        assert host.crc_shipped(data[:n]) == want(n), n
+        for chunk, lanes in ((1, 64), (16, 64), (7, 8), (3, 2), (5, 1), (64, 32)):
+            assert host.crc_chunked(data[:n], chunk, lanes) == want(n), (n, chunk, lanes)
+    # around every multiple of the kernel's chunk for a full page, and of its smallest chunk
+    chunk = (full + 63) // 64
+    lengths = set()
+    for c in (chunk, 16 * 64):
+        for m in range(c, full + 1, c):
+            lengths.update((m - 1, m, m + 1))
+    lengths.update((full - 1, full))
+    lengths.update(int(v) for v in rng.integers(0, full + 1, 200))
+    lengths = sorted(n for n in lengths if n <= full)
+    # the bit-serial routine is slow in Python: its value at n continues from the one before (same definition, one pass)
+    r, at, table = 0, 0, {}
+    for n in lengths:
+        for b in data[at:n]:
+            r ^= b << 24
+            for _ in range(8):
+                r = ((r << 1) ^ 0x04c11db7) & 0xffffffff if r & 0x80000000 else (r << 1) & 0xffffffff
+        at = n
+        table[n] = r
+    assert table[lengths[3]] == oh.crc_bitserial(data[:lengths[3]])
+    for n in lengths:
+        assert host.crc_shipped(data[:n]) == table[n], n
+        assert host.crc_chunked(data[:n], chunk, 64) == table[n], n
+        assert host.crc_chunked(data[:n], 1, 16) == table[n], n
+
+
+SIZE_LISTS = {
+    "empty_packets": [0, 0, 0],
+    "one": [1],
+    "254": [254],
+    "255": [255],
+    "256": [256],
+    "510": [510],
+    "65025": [65025],
+    "70000": [70000],
+    "70000_then_small": [70000, 10, 20, 5000, 30, 40, 50],
+    "300_one_byte": [1] * 300,
+    "254_one_byte_then_300": [1] * 254 + [300],
+    "fill_rule": [1500, 1500, 1500, 1500, 1500, 10, 10, 10, 10, 5000, 10],
+    "three_big": [3000, 3000, 3000],
+    "mixed": [0, 255, 1, 510, 0, 4097, 2, 2, 2, 2, 2, 765, 0],
+}
+
+
+@pytest.mark.parametrize("name", list(SIZE_LISTS))
+def test_walk_on_synthetic_sizes(host, name):
+    """The walk and the host mux on size lists no real encoder gives -- empty packets, packets that are multiples of 255,
+    packets longer than a page, pages cut by the 255-segment rule inside a packet.  The page with granule position -1 and
+    header runs of more than 255 segments cannot occur through the GPU path with real packets (no Vorbis packet of these
+    setups reaches 65 025 bytes, and their comment + setup headers take under 30 segments), so this test is their only
+    cover."""
+    sizes = SIZE_LISTS[name]
+    rng = np.random.default_rng(len(sizes))
+    packets = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in sizes]
+    granules = [1000 * (i + 1) for i in range(len(sizes))]
+    f = host.mux(None, packets, granules, 0xfeedface)
+    pages, got = oh.demux(f)
+    assert got == packets
+    assert [len(p) for p in got] == sizes
+    oh.check_policy(pages, 0)
+    planned, file_bytes = host.plan(sizes, granules)
+    assert file_bytes == len(f) and len(planned) == len(pages)
+    done = 0
+    for want, p in zip(planned, pages):
+        assert (want["nseg"], want["body"], want["flags"], want["granule"], want["seq"], want["file_off"], want["done"]) == \
+               (p["nseg"], p["body"], p["flags"], p["granule"], p["seq"], p["offset"], p["done"])
+        assert p["serial"] == 0xfeedface
+        done += p["done"]
+        assert p["granule"] == (granules[done - 1] if p["done"] else -1)
+        assert bool(p["flags"] & 1) == (want["byte0"] > 0)
+    assert done == len(sizes)
+    if name.startswith("70000"):
+        # its first 255 segments fill a page and complete nothing
+        assert (pages[0]["nseg"], pages[0]["done"], pages[0]["granule"], pages[0]["flags"]) == (255, 0, -1, 0)
+        assert pages[1]["flags"] & 1
+    if name == "254_one_byte_then_300":
+        # segment 255 is the 300-byte packet's first: the page is cut inside it
+        assert (pages[0]["nseg"], pages[0]["body"], pages[0]["done"]) == (255, 254 + 255, 254)
+        assert (pages[1]["flags"], pages[1]["nseg"], pages[1]["body"]) == (1 | 4, 1, 45)
+    if name == "300_one_byte":
+        assert [p["nseg"] for p in pages] == [255, 45]
+    if name == "fill_rule":
+        # closed at the first packet boundary past 4096 bytes once four packets are complete: after the fourth packet here
+        assert (pages[0]["done"], pages[0]["body"]) == (4, 6000)
+    if name == "three_big":
+        assert len(pages) == 1  # more than 4096 bytes, but never four packets
+
+
+def test_walks_agree_on_random_lists(host):
+    """The two shipped forms of the walk -- 64 packets at a time with a page per step (k_ogg_plan's), and a packet at a time
+    -- give the same pages on lists long enough to cross many chunks, and the spec demuxer reads the mux's file back."""
+    rng = np.random.default_rng(9)
+    for trial in range(40):
+        n = int(rng.integers(1, 500))
+        top = int(rng.choice([3, 300, 2000, 20000, 70000]))
+        sizes = [int(v) for v in rng.integers(0, top + 1, n)]
+        if trial % 5 == 0:
+            sizes = [int(v) for v in rng.choice([0, 1, 254, 255, 256, 509, 510, 511, 65025], n)]
+        granules = list(range(10, 10 + n))
+        a, fa = host.plan(sizes, granules)
+        b, fb = host.plan(sizes, granules, serial=True)
+        assert fa == fb and a == b, trial
+        if trial % 4 == 0 and sum(sizes) < 3_000_000:
+            packets = [rng.integers(0, 256, v, dtype=np.uint8).tobytes() for v in sizes]
+            pages, got = oh.demux(host.mux(None, packets, granules, trial))
+            assert got == packets
+            oh.check_policy(pages, 0)
+            assert [(p["nseg"], p["body"], p["granule"], p["flags"]) for p in pages] == [(q["nseg"], q["body"], q["granule"], q["flags"]) for q in a]
+
+
+def test_header_runs(host):
+    """Page 0 is the identification header alone; comment and setup share the pages from 1 on, also beyond 255 segments;
+    the first audio packet starts a fresh page."""
+    rng = np.random.default_rng(3)
+    for hb in ([30, 89, 4140], [30, 40, 70000], [30, 255 * 100, 255 * 200]):
+        headers = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in hb]
+        packets = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (100, 200, 300)]
+        f = host.mux(headers, packets, [64, 1088, 2000], 7)
+        pages, got = oh.demux(f)
+        assert got == headers + packets
+        assert (pages[0]["flags"], pages[0]["granule"], pages[0]["seq"], pages[0]["bytes"], pages[0]["done"]) == (2, 0, 0, 58, 1)
+        nh = next(i for i, p in enumerate(pages) if sum(q["done"] for q in pages[:i + 1]) == 3) + 1
+        for p in pages[1:nh]:
+            assert p["granule"] == (0 if p["done"] else -1) and not p["flags"] & 6
+        assert all(p["nseg"] == 255 for p in pages[1:nh - 1])
+        oh.check_policy(pages, nh)
+        assert (pages[nh]["flags"] & 1) == 0 and pages[-1]["granule"] == 2000
+        assert nh <= host.slots(hb, 0, 0)
+
+
+def test_bounds_hold(host):
+    """What the feed sizes its page table and its file arena by, before any size is known."""
+    rng = np.random.default_rng(5)
+    hb = [30, 89, 4140]
+    for trial in range(60):
+        cap = int(rng.choice([300, 4096, 16384, 70000]))
+        n = int(rng.integers(1, 400))
+        kind = trial % 4
+        sizes = [rng.integers(0, cap + 1, n), np.full(n, cap), rng.integers(0, 3, n), rng.choice([254, 255, 256, 1020, cap], n)][kind]
+        sizes = [int(v) for v in sizes]
+        planned, file_bytes = host.plan(sizes, list(range(n)), hb)
+        assert len(planned) <= host.slots(hb, n, cap), (trial, len(planned))
+        rounded = sum((v + 3) // 4 * 4 for v in sizes)
+        assert file_bytes <= host.file_bound(sum(sizes), n, 1, hb)
+        assert file_bytes <= host.file_bound(rounded + 1000, n, 1, hb)
+
+
+KINDS = ["noise", "gated", "sine", "clicks", "silence"]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_reference_packets_through_the_host_mux(host, kind):
+    """The reference's own header packets and packets of a 44.1 kHz stereo q 0.4 stream, muxed by the shipped host code:
+    the spec demuxer returns them unchanged, page 0 is 58 bytes, the reference decoder returns exactly the stream's
+    frame count, the last page carries 0x04 and its granule position is the frame count."""
+    from oracle import ref
+    if not ref.available():
+        pytest.skip("needs the reference build")
+    rng = np.random.default_rng(11)
+    frames = 30000
+    pcm = oh.s16_streams(rng, 2, frames, [kind])[0]
+    headers = oh.reference_headers(2, 44100, 0.4)
+    assert [len(h) for h in headers][0] == 30
+    recs = ref.RefEncoder(2, 44100, 0.4).encode_stream(oh.planar(pcm))
+    packets, granules = [r["packet"] for r in recs], [r["granulepos"] for r in recs]
+    f = host.mux(headers, packets, granules, 0x1234)
+    pages, got = oh.demux(f)
+    assert got == headers + packets
+    assert pages[0]["bytes"] == 58 and pages[0]["flags"] == 2 and pages[1]["done"] == 2
+    oh.check_policy(pages, 2)
+    assert all(p["serial"] == 0x1234 for p in pages)
+    assert pages[-1]["flags"] & 4 and pages[-1]["granule"] == frames
+    dec = oh.reference_decode(got, oh.page_granules(pages, len(packets)))
+    assert dec.shape == (2, frames)
+    if kind == "sine":
+        # it is the stream that went in, in place, not merely as long: a lossy coder keeps a -4 dB tone, far above any
+        # masking threshold, with its error at least 20 dB below it -- a correlation of 1 / sqrt(1 + 0.01) > 0.99
+        x = oh.planar(pcm)
+        assert np.corrcoef(dec[0, 2000:20000], x[0, 2000:20000])[0, 1] > 0.99
+
+
+def test_reference_headers_and_short_streams(host):
+    from oracle import ref
+    if not ref.available():
+        pytest.skip("needs the reference build")
+    import numpy as np
+    a = oh.reference_headers(2, 44100, 0.4)
+    b, _, _ = ref.matrix_case(2, 44100, 0.4, np.zeros(4096, np.float32))
+    assert a[0] == b[0] and a[2] == b[2] and a[0][:7] == b"\x01vorbis" and a[1][:7] == b"\x03vorbis" and a[2][:7] == b"\x05vorbis"
+    m = oh.reference_headers(2, 44100, managed=(-1, 128000, -1))
+    assert m[0] != a[0] and m[2] == a[2]
+    rng = np.random.default_rng(2)
+    for frames in (1, 3000):
+        pcm = oh.s16_streams(rng, 2, frames, ["noise"])[0]
+        recs = ref.RefEncoder(2, 44100, 0.4).encode_stream(oh.planar(pcm))
+        packets, granules = [r["packet"] for r in recs], [r["granulepos"] for r in recs]
+        pages, got = oh.demux(host.mux(a, packets, granules, 1))
+        assert got == a + packets and pages[-1]["granule"] == frames
+        assert oh.reference_decode(got, oh.page_granules(pages, len(packets))).shape == (2, frames)

@@ -2,14 +2,16 @@
 them (-Rpass-analysis=kernel-resource-usage), one line per kernel whose demangled name matches the pattern.
 
     python tools/kernel_resources.py ['k_noise|k_floor']
+    python tools/kernel_resources.py k_ogg --unit=vamd_feed
 """
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pat = re.compile(sys.argv[1] if len(sys.argv) > 1 else ".")
-extra = sys.argv[2:]   # further compiler flags, e.g. -DVAMD_NOISE_NO_PREFETCH
+extra = [x for x in sys.argv[2:] if not x.startswith("--unit=")]   # further compiler flags, e.g. -DVAMD_NOISE_NO_PREFETCH
+unit = ([x[7:] for x in sys.argv[2:] if x.startswith("--unit=")] or ["vamd_hip"])[0]   # --unit=vamd_feed: the feed's kernels (k_ogg.h)
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"),
-       "-Rpass-analysis=kernel-resource-usage"] + extra + ["-c", os.path.join(ROOT, "vorbis_amd", "csrc", "vamd_hip.hip"), "-o", "/tmp/vamd_res.o"]
+       "-Rpass-analysis=kernel-resource-usage"] + extra + ["-c", os.path.join(ROOT, "vorbis_amd", "csrc", unit + ".hip"), "-o", "/tmp/vamd_res.o"]
 err = subprocess.run(cmd, capture_output=True, text=True, stdin=subprocess.DEVNULL, timeout=900).stderr
 cur, rows = None, []
 for line in err.splitlines():

@@ -28,7 +28,8 @@ EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe",
                     "vamd_input_status", "vamd_calib_copy", "vamd_abi_version", "vamd_plan_streams_whole", "vamd_plan_streams_whole_v", "vamd_feed_wrote_v", "vamd_device_count", "vamd_batcher_create_multi",
                     "vamd_feed_create", "vamd_feed_destroy", "vamd_feed_lanes", "vamd_feed_device", "vamd_feed_buffer", "vamd_feed_wrote",
                     "vamd_feed_packets", "vamd_feed_release", "vamd_feed_last_error", "vamd_feed_create_live", "vamd_feed_wrote_live",
-                    "vamd_analyze_streams_mixed_managed", "vamd_bitrate_init_states", "vamd_bitrate_walk"]
+                    "vamd_analyze_streams_mixed_managed", "vamd_bitrate_init_states", "vamd_bitrate_walk",
+                    "vamd_feed_ogg_headers", "vamd_feed_ogg_serials", "vamd_feed_ogg"]
 PACKETBLOBS = 15
 
 _vp = C.c_void_p
@@ -43,6 +44,11 @@ class _FeedResult(C.Structure):  # vamd_feed_result
     _fields_ = [("nstreams", C.c_int64), ("nblocks", C.c_int64), ("stream_start", _vp), ("offset", _vp), ("bits", _vp),
                 ("granulepos", _vp), ("info", _vp), ("bytes", _vp), ("total_bytes", C.c_int64), ("upload_ms", C.c_double),
                 ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class _FeedOggResult(C.Structure):  # vamd_feed_ogg_result
+    _fields_ = [("nstreams", C.c_int64), ("stream_offset", _vp), ("npages", _vp), ("status", _vp), ("bytes", _vp),
+                ("total_bytes", C.c_int64)]
 
 
 class _Desc(C.Structure):
@@ -153,6 +159,9 @@ def load_library():
     L.vamd_feed_wrote.argtypes = [_vp, C.c_int, C.c_long, C.c_long]
     L.vamd_feed_packets.argtypes = [_vp, C.c_int, C.POINTER(_FeedResult)]
     L.vamd_feed_release.argtypes = [_vp, C.c_int]
+    L.vamd_feed_ogg_headers.argtypes = [_vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long]
+    L.vamd_feed_ogg_serials.argtypes = [_vp, C.c_int, _vp, C.c_long]
+    L.vamd_feed_ogg.argtypes = [_vp, C.c_int, C.POINTER(_FeedOggResult)]
     L.vamd_feed_last_error.argtypes = [_vp]
     L.vamd_feed_last_error.restype = C.c_char_p
     L.vamd_analyze_streams_mixed_managed.argtypes = [_vp, C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO), C.POINTER(_Desc),
@@ -945,10 +954,14 @@ class Feed:
 
     write_frames (an int): a LIVE feed (vamd_feed_create_live) -- every lane keeps max_streams continuing streams, fed in
     pieces of at most max_frames frames: buffer() -> fill -> wrote_live() -> packets() -> release(); its packets are the
-    reference's when it gets the samples write_frames at a time."""
+    reference's when it gets the samples write_frames at a time.
+
+    ogg_headers = (identification, comment, setup), the packets vorbis_analysis_headerout() gives for the blob's encoder
+    setup: an OGG feed (vamd_feed_ogg_headers) -- besides packets(), ogg() returns one complete Ogg Vorbis I file per
+    stream, framed on the device: buffer() -> fill -> [ogg_serials()] -> wrote() -> ogg() / packets() -> release()."""
 
     def __init__(self, setup_blob, devices=None, lanes_per_device=2, max_streams=256, max_frames=131072, fmt=FEED_S16,
-                 write_frames=None):
+                 write_frames=None, ogg_headers=None):
         self.L = load_library()
         blob = np.ascontiguousarray(setup_blob, dtype=np.uint8)
         devs = list(devices) if devices else []
@@ -968,6 +981,66 @@ class Feed:
         self.max_streams, self.max_frames, self.fmt = max_streams, max_frames, fmt
         self.dtype = np.int16 if fmt == FEED_S16 else np.float32
         self.lanes = self.L.vamd_feed_lanes(self.h)
+        if ogg_headers is not None:
+            try:
+                self.ogg_headers(*ogg_headers)
+            except Exception:
+                self.close()
+                raise
+
+    def ogg_headers(self, ident, comment, setup):
+        """Makes the feed an Ogg feed; before the first buffer()."""
+        pk = [bytes(p) for p in (ident, comment, setup)]
+        self._check(self.L.vamd_feed_ogg_headers(self.h, pk[0], len(pk[0]), pk[1], len(pk[1]), pk[2], len(pk[2])))
+
+    def ogg_serials(self, slot, serials):
+        """The stream serial numbers of the group being filled in `slot` (between buffer() and wrote())."""
+        a = np.ascontiguousarray(serials, dtype=np.uint32).reshape(-1)
+        self._check(self.L.vamd_feed_ogg_serials(self.h, slot, _vp(a.ctypes.data), a.size))
+
+    def ogg(self, slot, copy=True):
+        """Waits for the group.  -> dict: nstreams, stream_offset [nstreams + 1], npages, status [nstreams], bytes (a view
+        over the lane's pinned file arena, or a copy), total_bytes: stream s's file is bytes[stream_offset[s]:stream_offset[s + 1]]
+        (empty, with status[s] = the VAMD_STATUS_* bits, where a block of the stream has no packet)."""
+        r = _FeedOggResult()
+        self._check(self.L.vamd_feed_ogg(self.h, slot, C.byref(r)))
+        ns = int(r.nstreams)
+
+        def view(p, ct, n):
+            if n == 0:
+                return np.zeros(0, np.dtype(ct))
+            a = np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,))
+            return a.copy() if copy else a
+        return {"nstreams": ns, "stream_offset": view(r.stream_offset, C.c_int64, ns + 1), "npages": view(r.npages, C.c_int32, ns),
+                "status": view(r.status, C.c_uint8, ns), "bytes": view(r.bytes, C.c_uint8, int(r.total_bytes)),
+                "total_bytes": int(r.total_bytes)}
+
+    def encode_ogg(self, pcm, serials=None):
+        """One group of an Ogg feed, synchronously: pcm as encode() takes it.  -> list[bytes], one complete Ogg Vorbis file
+        per stream (b"" for a stream without one: see ogg())."""
+        if isinstance(pcm, (list, tuple)):
+            parts = [np.ascontiguousarray(x, dtype=self.dtype) for x in pcm]
+            ns, ch = len(parts), parts[0].shape[1]
+            frames = np.array([x.shape[0] for x in parts], np.int64)
+            flat = np.concatenate([x.reshape(-1) for x in parts])
+        else:
+            pcm = np.ascontiguousarray(pcm, dtype=self.dtype)
+            ns, frames, ch = pcm.shape
+            flat = pcm.reshape(-1)
+        slot, buf = self.buffer(ch)
+        try:
+            buf[:flat.size] = flat
+            if serials is not None:
+                self.ogg_serials(slot, serials)
+            self.wrote(slot, ns, frames)
+            r = self.ogg(slot, copy=False)
+            off = r["stream_offset"]
+            return [bytes(r["bytes"][int(off[s]):int(off[s + 1])]) for s in range(ns)]
+        finally:
+            try:
+                self.release(slot)
+            except VamdError:
+                pass
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,0 +1,577 @@
+// k_ogg.h -- Ogg pages around the feed's packets (doc/framing.html: page layout, lacing, CRC; doc/a1-encapsulation-ogg.tex:
+// how Vorbis I sits in Ogg).  Three parts:
+//   * the CRC: table-driven per byte, and the algebra that lets a page be summed in chunks -- the register after a message
+//     M (initial value 0, no final XOR, MSb first) is M(x) x^32 mod P, so crc(A || B) = crc(A) x^(8 |B|) + crc(B): every
+//     lane sums a contiguous chunk, and a log-step tree joins neighbours with one multiply mod P each;
+//   * the paging walk: from a stream's packet sizes to its pages (the policy is fixed, include/vorbis_amd.h "the Ogg
+//     feed"), in two forms that the CPU suite holds together: a packet at a time (the header runs), and 64 packets at a
+//     time with a page per step (the audio run: prefix sums of the sizes, every packet asked at once where the page ends);
+//   * the kernels: k_ogg_plan (a wave per stream runs the walk, sizes scanned into LDS 64 at a time) and k_ogg_pages (a
+//     wave per page: header, lacing table, body gathered from the packets, CRC, written with aligned dword stores).
+// The CRC functions and the walk are ONE body: the library compiles them for gfx950, the CPU suite compiles this very
+// file with the host compiler (tests/ogg_host.py) together with the host-only mux at the end, which lays the same
+// pages out byte by byte -- the second implementation of the policy that the GPU's files are held against.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#if defined(__HIPCC__)
+#define VAMD_OGG_FN __host__ __device__ inline
+#else
+#define VAMD_OGG_FN inline
+#endif
+
+namespace vamd {
+
+enum {
+  OGG_HEADER = 27,       // bytes of a page header in front of its lacing table
+  OGG_MAX_SEGS = 255,    // segments a page holds at most
+  OGG_FILL = 4096,       // a page is closed at a packet boundary once its body holds MORE than this ...
+  OGG_MIN_PACKETS = 4,   // ... and at least this many packets have been completed on it
+  OGG_CRC_LANES = 64,    // k_ogg_pages: chunks a page is summed in
+  OGG_CRC_MIN_CHUNK = 16 // ... none shorter than this (a short page leaves its first lanes empty)
+};
+#define VAMD_OGG_POLY 0x04c11db7u
+
+// ---- CRC (framing.html: polynomial 0x04c11db7, direct, initial value and final XOR 0, MSb first) ----
+VAMD_OGG_FN uint32_t ogg_crc_entry(uint32_t byte) {  // entry `byte` of the 256-entry table
+  uint32_t r = byte << 24;
+  for (int i = 0; i < 8; i++) r = (r & 0x80000000u) ? (r << 1) ^ VAMD_OGG_POLY : r << 1;
+  return r;
+}
+VAMD_OGG_FN uint32_t ogg_crc_byte(const uint32_t *table, uint32_t crc, uint32_t byte) {
+  return (crc << 8) ^ table[((crc >> 24) ^ byte) & 0xffu];
+}
+// a * b mod P (bit i of a word is the coefficient of x^i): Horner over b's bits, 32 shift-and-xor steps
+VAMD_OGG_FN uint32_t ogg_crc_mul(uint32_t a, uint32_t b) {
+  uint32_t r = 0;
+  for (int i = 31; i >= 0; i--) {
+    r = (r & 0x80000000u) ? (r << 1) ^ VAMD_OGG_POLY : r << 1;
+    if ((b >> i) & 1u) r ^= a;
+  }
+  return r;
+}
+// x^(8 n) mod P: what n more bytes multiply a CRC register by
+VAMD_OGG_FN uint32_t ogg_crc_xpow8(int64_t n) {
+  uint32_t r = 1u, base = 0x100u;
+  while (n > 0) {
+    if (n & 1) r = ogg_crc_mul(r, base);
+    base = ogg_crc_mul(base, base);
+    n >>= 1;
+  }
+  return r;
+}
+// The chunks of an n-byte page over `lanes` lanes: all of length c, laid from the page's END backwards, so that what lies
+// behind any lane's chunk is a whole number of chunks (the short one is the first, in front of which nothing is summed;
+// lanes before it are empty and hold a CRC of 0).  Lane l sums bytes [lo, hi).
+VAMD_OGG_FN int64_t ogg_crc_chunk(int64_t n, int lanes, int min_chunk) {
+  int64_t c = (n + lanes - 1) / lanes;
+  if (c < min_chunk) c = min_chunk;
+  return c < 1 ? 1 : c;
+}
+VAMD_OGG_FN void ogg_crc_range(int64_t n, int lanes, int64_t c, int lane, int64_t *lo, int64_t *hi) {
+  const int64_t h = n - (int64_t)(lanes - 1 - lane) * c, l = h - c;
+  *hi = h < 0 ? 0 : h;
+  *lo = l < 0 ? 0 : l;
+}
+// one step of the tree: `mine` sums a run of chunks, `right` the equally long run behind it, m = x^(8 * that run's bytes)
+VAMD_OGG_FN uint32_t ogg_crc_join(uint32_t mine, uint32_t right, uint32_t m) { return ogg_crc_mul(mine, m) ^ right; }
+
+// ---- lacing ----
+// A packet of n bytes is n / 255 segments of 255 and one of n % 255 (a multiple of 255 ends in a 0).
+VAMD_OGG_FN int32_t ogg_segments(int32_t bytes) { return bytes / 255 + 1; }
+VAMD_OGG_FN int32_t ogg_lace_value(int32_t bytes, int32_t q) { return q < bytes / 255 ? 255 : bytes % 255; }  // segment q of the packet
+// bytes of the `take` segments of a packet from byte `start` (a multiple of 255) on
+VAMD_OGG_FN int32_t ogg_piece_len(int32_t bytes, int32_t start, int32_t take) {
+  return start / 255 + take == ogg_segments(bytes) ? bytes - start : take * 255;
+}
+
+// ---- the paging walk ----
+// A stream's file is three RUNS of packets, each starting on a fresh page: the identification header alone (page 0, 58
+// bytes with a 30-byte header), the comment and setup headers, the audio packets.  Within a run the walk takes segments
+// in order; before taking one it closes the page if the page holds 255 segments, wherever that falls; before a packet's
+// first segment it closes the page if its body holds more than OGG_FILL bytes and OGG_MIN_PACKETS packets have been
+// completed on it; the end of a run closes its page.  A page's granule position is that of the last packet completed
+// on it, -1 where none is.
+// Whole streams start at granule position 0, so a1-encapsulation-ogg's rule for a stream that does not (the second audio
+// packet flushes its page, so that the decoder learns the offset at once) never applies here; a live form that resumes a
+// stream inside a file would have to add it where the audio run begins.
+struct OggPage {
+  int64_t file_off;  // where the page starts in its stream's file
+  int64_t granule;
+  int32_t run;       // 0: identification header; 1: comment + setup; 2: audio; -1: an unused slot of the page table
+  int32_t first;     // the packet (of its run's list: headers 0..2, or the stream's audio packets) its first segment belongs to
+  int32_t byte0;     // bytes of that packet on earlier pages (a multiple of 255; > 0: the page carries the continued flag)
+  int32_t npackets;  // packets with a segment on the page
+  int32_t nseg, body;
+  int32_t seq, flags;
+  int32_t stream, done;  // done: packets completed on the page
+};
+
+struct OggWalk {
+  OggPage pg;       // the page being filled
+  int64_t file_off; // where it starts
+  int32_t seq, npages;
+};
+
+VAMD_OGG_FN void ogg_page_reset(OggWalk &w, int run) {
+  w.pg.file_off = 0, w.pg.granule = -1;
+  w.pg.run = run, w.pg.first = 0, w.pg.byte0 = 0, w.pg.npackets = 0, w.pg.nseg = 0, w.pg.body = 0, w.pg.seq = 0, w.pg.flags = 0;
+  w.pg.done = 0;
+}
+VAMD_OGG_FN void ogg_walk_init(OggWalk &w, int stream) {
+  w.file_off = 0, w.seq = 0, w.npages = 0;
+  w.pg.stream = stream;
+  ogg_page_reset(w, 0);
+}
+// the page is complete: into out[] (when it fits; npages counts on regardless), the next one begins empty
+VAMD_OGG_FN void ogg_page_close(OggWalk &w, OggPage *out, int64_t cap, int extra_flags) {
+  w.pg.file_off = w.file_off, w.pg.seq = w.seq, w.pg.flags |= extra_flags;
+  if (w.npages < cap) out[w.npages] = w.pg;
+  w.npages++, w.seq++;
+  w.file_off += OGG_HEADER + w.pg.nseg + w.pg.body;
+  ogg_page_reset(w, w.pg.run);
+}
+VAMD_OGG_FN void ogg_run_begin(OggWalk &w, int run, int bos) {
+  ogg_page_reset(w, run);
+  w.pg.flags = bos ? 0x02 : 0;
+}
+// packet k of the run: `bytes` long, granule position `granule`
+VAMD_OGG_FN void ogg_walk_packet(OggWalk &w, OggPage *out, int64_t cap, int32_t k, int32_t bytes, int64_t granule) {
+  const int32_t segs = ogg_segments(bytes);
+  int32_t taken = 0;
+  if (w.pg.nseg > 0 && w.pg.body > OGG_FILL && w.pg.done >= OGG_MIN_PACKETS) ogg_page_close(w, out, cap, 0);
+  for (;;) {
+    if (w.pg.nseg == OGG_MAX_SEGS) ogg_page_close(w, out, cap, 0);
+    if (w.pg.npackets == 0) {
+      w.pg.first = k, w.pg.byte0 = taken * 255;
+      if (taken) w.pg.flags |= 0x01;
+    }
+    const int32_t room = OGG_MAX_SEGS - w.pg.nseg, take = segs - taken < room ? segs - taken : room;
+    w.pg.body += ogg_piece_len(bytes, taken * 255, take);
+    w.pg.nseg += take, w.pg.npackets++;
+    taken += take;
+    if (taken == segs) {
+      w.pg.done++, w.pg.granule = granule;
+      return;
+    }
+  }
+}
+// The same walk, up to 64 packets of a run at a time, a PAGE per step instead of a packet: with the chunk's sizes summed up
+// in front of every packet (Bx[j], Sx[j]: bytes and segments of packets 0 .. j-1; n + 1 entries), what the page would hold
+// if packets c .. j-1 joined it whole is a difference of two sums, so whether the walk stops in front of or inside packet j
+// can be asked of every j at once -- a lane each on the device, the first lane that says yes found with one ballot
+// (k_ogg_plan); the host asks them in turn (ogg_plan_stream).  c is the chunk's next packet, `taken` its segments already
+// on earlier pages.
+VAMD_OGG_FN void ogg_ahead(const OggPage &pg, const int32_t *Bx, const int32_t *Sx, int c, int taken, int j, int32_t *nseg, int32_t *body,
+                           int32_t *done) {
+  *nseg = pg.nseg + (Sx[j] - Sx[c]) - (j > c ? taken : 0);
+  *body = pg.body + (Bx[j] - Bx[c]) - (j > c ? taken * 255 : 0);
+  *done = pg.done + (j - c);
+}
+// 0: packet j joins the page whole; 1: the page is closed in front of it (4096 bytes and four packets); 2: it does not fit
+// whole (the page is closed at 255 segments, inside the packet or in front of it)
+VAMD_OGG_FN int ogg_stop_at(const OggPage &pg, const int32_t *Bx, const int32_t *Sx, const int32_t *bytes, int c, int taken, int j) {
+  int32_t nseg, body, done;
+  ogg_ahead(pg, Bx, Sx, c, taken, j, &nseg, &body, &done);
+  if ((j > c || taken == 0) && nseg > 0 && body > OGG_FILL && done >= OGG_MIN_PACKETS) return 1;
+  return nseg + ogg_segments(bytes[j]) - (j == c ? taken : 0) > OGG_MAX_SEGS ? 2 : 0;
+}
+// packets c .. j-1 join the page whole; then, by `why` (ogg_stop_at of packet j; 0 with j = n: the chunk is used up), the
+// page is closed in front of packet j or filled up with its next segments and closed.  kbase: the chunk's first packet.
+VAMD_OGG_FN void ogg_walk_join(OggWalk &w, OggPage *out, int64_t cap, int32_t kbase, const int32_t *Bx, const int32_t *Sx,
+                               const int64_t *granule, int *c, int *taken, int j, int why) {
+  if (j > *c) {
+    int32_t nseg, body, done;
+    ogg_ahead(w.pg, Bx, Sx, *c, *taken, j, &nseg, &body, &done);
+    if (w.pg.npackets == 0) {
+      w.pg.first = kbase + *c, w.pg.byte0 = *taken * 255;
+      if (*taken) w.pg.flags |= 0x01;
+    }
+    w.pg.npackets += j - *c;
+    w.pg.nseg = nseg, w.pg.body = body, w.pg.done = done, w.pg.granule = granule[j - 1];
+    *c = j, *taken = 0;
+  }
+  if (why == 2) {
+    const int32_t room = OGG_MAX_SEGS - w.pg.nseg;
+    if (room > 0) {  // (fewer than the packet still has: none of them is its last, all are 255 long)
+      if (w.pg.npackets == 0) {
+        w.pg.first = kbase + *c, w.pg.byte0 = *taken * 255;
+        if (*taken) w.pg.flags |= 0x01;
+      }
+      w.pg.npackets++, w.pg.nseg = OGG_MAX_SEGS, w.pg.body += room * 255;
+      *taken += room;
+    }
+  }
+  if (why) ogg_page_close(w, out, cap, 0);
+}
+
+VAMD_OGG_FN void ogg_run_end(OggWalk &w, OggPage *out, int64_t cap, int eos) {
+  if (w.pg.nseg > 0) ogg_page_close(w, out, cap, eos ? 0x04 : 0);
+}
+// the two header runs of a stream (header_bytes: identification, comment, setup)
+VAMD_OGG_FN void ogg_walk_headers(OggWalk &w, OggPage *out, int64_t cap, const int32_t *header_bytes) {
+  ogg_run_begin(w, 0, 1);
+  ogg_walk_packet(w, out, cap, 0, header_bytes[0], 0);
+  ogg_run_end(w, out, cap, 0);
+  ogg_run_begin(w, 1, 0);
+  ogg_walk_packet(w, out, cap, 1, header_bytes[1], 0);
+  ogg_walk_packet(w, out, cap, 2, header_bytes[2], 0);
+  ogg_run_end(w, out, cap, 0);
+}
+// the first 27 bytes of a page, checksum field zero
+VAMD_OGG_FN void ogg_page_header(const OggPage &pg, uint32_t serial, uint8_t *h) {
+  h[0] = 'O', h[1] = 'g', h[2] = 'g', h[3] = 'S', h[4] = 0, h[5] = (uint8_t)pg.flags;
+  for (int i = 0; i < 8; i++) h[6 + i] = (uint8_t)((uint64_t)pg.granule >> (8 * i));
+  for (int i = 0; i < 4; i++) h[14 + i] = (uint8_t)(serial >> (8 * i));
+  for (int i = 0; i < 4; i++) h[18 + i] = (uint8_t)((uint32_t)pg.seq >> (8 * i));
+  h[22] = h[23] = h[24] = h[25] = 0;
+  h[26] = (uint8_t)pg.nseg;
+}
+
+// Page slots a stream needs at most, so that the page table can be laid out before any size is known: `header_slots`
+// for the two header runs (1 + one page per 255 segments of comment + setup, rounded up), and per audio packet
+// ogg_slots_per_packet(cap) slots, cap the longest packet the setup can make -- every audio page but the run's last either
+// completes four packets or holds 255 segments, and a stream of n packets of at most cap bytes has at most
+// n (1 + cap / 255) segments: n / 4 + n (1 + cap / 255) / 255 pages, and the run's last (among the header slots' + 2).
+VAMD_OGG_FN int64_t ogg_slots_per_packet(int64_t packet_cap) { return 2 + (1 + packet_cap / 255) / 255; }
+VAMD_OGG_FN int64_t ogg_header_slots(const int32_t *header_bytes) {
+  return 1 + (ogg_segments(header_bytes[1]) + ogg_segments(header_bytes[2]) + 254) / 255 + 2;
+}
+// ... and the bytes the files of a group take at most, from its packets' bytes (each rounded up to 4 or not), their number
+// and the streams': every page but a run's last holds more than OGG_FILL body bytes or 255 segments.
+VAMD_OGG_FN int64_t ogg_file_bound(int64_t packet_bytes, int64_t npackets, int64_t nstreams, const int32_t *header_bytes) {
+  const int64_t pages = packet_bytes / (OGG_FILL + 1) + (npackets + packet_bytes / 255) / 255 + nstreams * (2 + ogg_header_slots(header_bytes));
+  return packet_bytes + nstreams * ((int64_t)header_bytes[0] + header_bytes[1] + header_bytes[2]) + pages * (OGG_HEADER + OGG_MAX_SEGS);
+}
+
+#if defined(__HIPCC__)
+// ---- the kernels ----
+// What the pager reads: the device mirror of the group's packets (bytes at the offsets of the output arena, each packet at
+// a multiple of 4, and their records), the three header packets, the streams' serial numbers.
+struct OggIn {
+  const int64_t *stream_start;  // [nstreams + 1] into the packets
+  const int64_t *off, *gp;      // [packets] where a packet's bytes lie in `bytes`; its granule position
+  const int32_t *bits;          // [packets] -1: no packet
+  const uint8_t *info;          // [packets] (vamd_feed_result.info)
+  const uint8_t *bytes;
+  int64_t cap;                  // bytes of the mirror that hold packets (8 more are readable behind them)
+  const int64_t *packet_total;  // null, or the bytes the group's packets take: beyond cap, nothing was mirrored
+  const uint8_t *hdr;           // the header packets, each at a multiple of 4
+  int32_t hdr_off[3], hdr_bytes[3];
+  const uint32_t *serial;       // [nstreams]
+  int64_t header_slots, slots_per_packet;
+};
+__device__ __forceinline__ int64_t ogg_slot_base(const OggIn &I, long s) { return s * I.header_slots + I.slots_per_packet * I.stream_start[s]; }
+
+// a wave per stream: its pages into its slots of the page table, the unused slots marked; file_bytes, npages, status.
+// 64 packets at a time: one coalesced load of their sizes and granule positions, a wave-wide scan of bytes and segments
+// into LDS, then a step per PAGE (ogg_stop_at in every lane, one ballot, ogg_walk_join) -- the walk is serial in pages
+// only, and never touches memory.  A stream in which a block has no packet gets no page at all.
+__global__ __launch_bounds__(64) void k_ogg_plan(OggIn I, long nstreams, OggPage *__restrict__ pages, int64_t *__restrict__ file_bytes,
+                                                 int32_t *__restrict__ npages, uint8_t *__restrict__ status) {
+  __shared__ int32_t sz[64], Bx[65], Sx[65];
+  __shared__ int64_t gr[64];
+  const long s = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int64_t k0 = I.stream_start[s], k1 = I.stream_start[s + 1];
+  const int64_t cap = I.header_slots + I.slots_per_packet * (k1 - k0);
+  OggPage *out = pages + ogg_slot_base(I, s);
+  unsigned st = 0;
+  for (int64_t base = k0; base < k1 && !st; base += 64) {
+    const int64_t k = base + lane;
+    unsigned mine = 0;
+    if (k < k1 && I.bits[k] < 0) mine = ((I.info[k] >> 2) & 3u) ? ((I.info[k] >> 2) & 3u) : 3u;
+    const unsigned long long m = __ballot(mine != 0);
+    if (m) st = (unsigned)__shfl((int)mine, __ffsll((long long)m) - 1, 64);
+  }
+  const bool none = st || (I.packet_total && *I.packet_total > I.cap);
+  // every lane keeps the walk's state (it is the same in all of them); lane 0 alone writes pages
+  const int64_t wcap = lane == 0 ? cap : 0;
+  OggWalk w;
+  ogg_walk_init(w, (int)s);
+  if (!none) {
+    ogg_walk_headers(w, out, wcap, I.hdr_bytes);
+    ogg_run_begin(w, 2, 0);
+    for (int64_t base = k0; base < k1; base += 64) {
+      const int64_t k = base + lane;
+      const int n = k1 - base < 64 ? (int)(k1 - base) : 64;
+      const int32_t bytes = k < k1 ? (I.bits[k] + 7) >> 3 : 0, segs = k < k1 ? ogg_segments(bytes) : 0;
+      int ib = bytes, is = segs;  // inclusive scans over the wave
+      for (int d = 1; d < 64; d <<= 1) {
+        const int ub = __shfl_up(ib, d, 64), us = __shfl_up(is, d, 64);
+        if (lane >= d) ib += ub, is += us;
+      }
+      __syncthreads();
+      sz[lane] = bytes, gr[lane] = k < k1 ? I.gp[k] : 0;
+      Bx[lane + 1] = ib, Sx[lane + 1] = is;
+      if (lane == 0) Bx[0] = 0, Sx[0] = 0;
+      __syncthreads();
+      int c = 0, taken = 0;
+      while (c < n) {
+        const int why = lane >= c && lane < n ? ogg_stop_at(w.pg, Bx, Sx, sz, c, taken, lane) : 0;
+        const unsigned long long m = __ballot(why != 0);
+        const int j = m ? __ffsll((long long)m) - 1 : n;
+        ogg_walk_join(w, out, wcap, (int32_t)(base - k0), Bx, Sx, gr, &c, &taken, j, m ? __shfl(why, j, 64) : 0);
+      }
+    }
+    ogg_run_end(w, out, wcap, 1);
+  }
+  int np = __shfl(w.npages, 0, 64);
+  if (np > cap) np = 0, st |= 0x80u;  // (the slot bound did not hold: no file rather than a cut one)
+  for (int64_t i = np + lane; i < cap; i += 64) out[i].run = -1;
+  if (lane == 0) {
+    file_bytes[s] = (none || (st & 0x80u)) ? 0 : w.file_off;
+    npages[s] = (none || (st & 0x80u)) ? 0 : np;
+    status[s] = (uint8_t)st;
+  }
+}
+
+// where the pages go: the pinned arena and the group's record beside it (host memory, mapped)
+struct OggOut {
+  int64_t *total, *stream_offset;  // [1], [nstreams + 1]
+  int32_t *npages;                 // [nstreams]
+  uint8_t *status;                 // [nstreams]
+  uint8_t *bytes;
+  int64_t cap;
+};
+
+// A wave per page slot.  The page is a virtual byte string V: header (27 bytes), lacing table, then the pieces of the
+// packets on it, each piece a run of bytes of the mirror.  LDS holds header + lacing, the pieces' places in V and in the
+// mirror, and the CRC table.
+//   CRC: lane l sums its chunk of V byte by byte (ogg_crc_range), the tree joins the 64 sums in six steps.
+//   Stores: the arena is host memory across the link, so only whole aligned dwords are written, consecutive lanes to
+//   consecutive dwords.  A page starts wherever the one before ends; the dword that holds a page's last bytes belongs to
+//   that page's wave, which fills it up with the bytes that follow -- always the next page's capture pattern "OggS" (or
+//   nothing anyone reads, behind the arena's last page).  So no byte is written twice and no dword in parts.  A dword
+//   inside one piece is two aligned words of the mirror joined by v_alignbyte; one that straddles pieces (packets of a
+//   few bytes), the header or the page's end is put together byte by byte.
+__global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const OggPage *__restrict__ pages,
+                                                  const int64_t *__restrict__ stream_off, const int32_t *__restrict__ npages,
+                                                  const uint8_t *__restrict__ status, OggOut O) {
+  __shared__ uint32_t table[256];
+  __shared__ __attribute__((aligned(8))) uint8_t head[OGG_HEADER + OGG_MAX_SEGS + 6];
+  __shared__ int32_t pdst[OGG_MAX_SEGS + 1];
+  __shared__ const uint8_t *psrc[OGG_MAX_SEGS];
+  const int lane = threadIdx.x;
+  {  // the group's record (the first (nstreams + 1 + 63) / 64 blocks; there are at least nstreams slots)
+    const long t = (long)blockIdx.x * 64 + lane;
+    if (t <= nstreams) O.stream_offset[t] = stream_off[t];
+    if (t < nstreams) O.npages[t] = npages[t], O.status[t] = status[t];
+    if (t == 0) *O.total = stream_off[nstreams];
+  }
+  const OggPage pg = pages[blockIdx.x];
+  if (pg.run < 0 || pg.nseg < 1 || pg.nseg > OGG_MAX_SEGS || pg.npackets < 1 || pg.npackets > pg.nseg) return;
+  const long s = pg.stream;
+  for (int e = lane; e < 256; e += 64) table[e] = ogg_crc_entry((uint32_t)e);
+  // the pieces and the lacing table
+  const int64_t kbase = I.stream_start[s] + pg.first;
+  int carry_s = 0, carry_b = 0;
+  bool bad = false;
+  for (int j0 = 0; j0 < pg.npackets; j0 += 64) {
+    const int j = j0 + lane;
+    const bool valid = j < pg.npackets;
+    int32_t bytes = 0;
+    const uint8_t *src = I.bytes;
+    if (valid) {
+      if (pg.run == 2) {
+        const int64_t k = kbase + j, o = I.off[k];
+        bytes = (I.bits[k] + 7) >> 3;
+        if (bytes < 0 || o < 0 || o + bytes > I.cap) bad = true, bytes = 0;
+        else src = I.bytes + o;
+      } else {
+        const int h = pg.first + j;
+        if (h > 2) bad = true;
+        else bytes = I.hdr_bytes[h], src = I.hdr + I.hdr_off[h];
+      }
+    }
+    const int32_t start = j == 0 ? pg.byte0 : 0;
+    const int32_t left = valid && start <= bytes ? ogg_segments(bytes) - start / 255 : 0;
+    int incl = left;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += up;
+    }
+    const int before = carry_s + incl - left;
+    int32_t take = pg.nseg - before < left ? pg.nseg - before : left;
+    if (take < 0) take = 0;
+    const int32_t len = valid && take > 0 ? ogg_piece_len(bytes, start, take) : 0;
+    int incb = len;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incb, d, 64);
+      if (lane >= d) incb += up;
+    }
+    if (valid) {
+      pdst[j] = carry_b + incb - len;
+      psrc[j] = src + start;
+      for (int q = 0; q < take; q++) head[OGG_HEADER + before + q] = (uint8_t)ogg_lace_value(bytes, start / 255 + q);
+    }
+    carry_s += __shfl(incl, 63, 64);
+    carry_b += __shfl(incb, 63, 64);
+  }
+  if (carry_b != pg.body || carry_s < pg.nseg) bad = true;  // (the mirror and the page table disagree: nothing is written)
+  if (__ballot(bad)) return;
+  if (lane == 0) {
+    pdst[pg.npackets] = pg.body;
+    ogg_page_header(pg, I.serial[s], head);
+  }
+  __syncthreads();
+  const int hlen = OGG_HEADER + pg.nseg, len = hlen + pg.body;
+  auto piece_of = [&](int b) {  // the piece that holds body byte b: the last one that starts at or before it
+    int lo = 0, hi = pg.npackets;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (pdst[mid] <= b) lo = mid;
+      else hi = mid;
+    }
+    return lo;
+  };
+  // CRC
+  {
+    const int64_t c = ogg_crc_chunk(len, OGG_CRC_LANES, OGG_CRC_MIN_CHUNK);
+    int64_t lo, hi;
+    ogg_crc_range(len, OGG_CRC_LANES, c, lane, &lo, &hi);
+    uint32_t crc = 0;
+    int v = (int)lo;
+    for (; v < hi && v < hlen; v++) crc = ogg_crc_byte(table, crc, head[v]);
+    if (v < hi) {
+      int i = piece_of(v - hlen);
+      for (; v < hi; v++) {
+        const int b = v - hlen;
+        while (b >= pdst[i + 1]) i++;
+        crc = ogg_crc_byte(table, crc, psrc[i][b - pdst[i]]);
+      }
+    }
+    uint32_t m = ogg_crc_xpow8(c);
+    for (int d = 1; d < OGG_CRC_LANES; d <<= 1) {
+      const uint32_t right = (uint32_t)__shfl_down((int)crc, d, 64);
+      crc = ogg_crc_join(crc, right, m);
+      m = ogg_crc_mul(m, m);
+    }
+    __syncthreads();
+    if (lane == 0)
+      for (int i = 0; i < 4; i++) head[22 + i] = (uint8_t)(crc >> (8 * i));
+    __syncthreads();
+  }
+  // stores
+  const int64_t g0 = stream_off[s] + pg.file_off, g1 = g0 + len;
+  const int64_t a0 = (g0 + 3) & ~(int64_t)3, a1 = (g1 + 3) & ~(int64_t)3;
+  if (a1 > O.cap) return;
+  for (int64_t a = a0 + 4 * lane; a < a1; a += 256) {
+    const int v = (int)(a - g0);
+    uint32_t word = 0;
+    bool whole = false;
+    if (v >= hlen && v + 4 <= len) {
+      const int b = v - hlen, i = piece_of(b);
+      if (b + 4 <= pdst[i + 1]) {
+        const uint8_t *p = psrc[i] + (b - pdst[i]);
+        const uint32_t *wp = (const uint32_t *)((uintptr_t)p & ~(uintptr_t)3);
+        const unsigned sh = (unsigned)((uintptr_t)p & 3);
+        const uint32_t w0 = wp[0], w1 = sh ? wp[1] : 0u;
+        word = __builtin_amdgcn_alignbyte(w1, w0, sh);
+        whole = true;
+      }
+    }
+    if (!whole) {
+      for (int t = 0; t < 4; t++) {
+        const int u = v + t;
+        uint32_t x;
+        if (u < hlen) x = head[u];
+        else if (u >= len) x = (uint32_t)"OggS"[(u - len) & 3];
+        else {
+          const int b = u - hlen, i = piece_of(b);
+          x = psrc[i][b - pdst[i]];
+        }
+        word |= x << (8 * t);
+      }
+    }
+    *(uint32_t *)(O.bytes + a) = word;
+  }
+}
+#endif  // __HIPCC__
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- host only: the chunked CRC as k_ogg_pages computes it, and the mux (the CPU suite; the GPU's files are held
+// against the mux byte for byte) ----
+inline uint32_t ogg_crc_chunked(const uint8_t *data, int64_t n, int min_chunk, int lanes) {
+  uint32_t table[256], part[64], next[64];
+  for (int e = 0; e < 256; e++) table[e] = ogg_crc_entry((uint32_t)e);
+  if (lanes > 64) lanes = 64;
+  const int64_t c = ogg_crc_chunk(n, lanes, min_chunk);
+  for (int l = 0; l < lanes; l++) {
+    int64_t lo, hi;
+    ogg_crc_range(n, lanes, c, l, &lo, &hi);
+    uint32_t crc = 0;
+    for (int64_t v = lo; v < hi; v++) crc = ogg_crc_byte(table, crc, data[v]);
+    part[l] = crc;
+  }
+  uint32_t m = ogg_crc_xpow8(c);
+  for (int d = 1; d < lanes; d <<= 1) {
+    for (int l = 0; l < lanes; l++) next[l] = ogg_crc_join(part[l], l + d < lanes ? part[l + d] : part[l], m);
+    memcpy(part, next, sizeof(part));
+    m = ogg_crc_mul(m, m);
+  }
+  return part[0];
+}
+
+// a stream's pages from its packet sizes: pages[] (up to cap of them) <- the walk; returns their number, *file_bytes the file's
+inline int64_t ogg_plan_stream(const int32_t *header_bytes, int64_t npackets, const int32_t *bytes, const int64_t *granule,
+                               OggPage *pages, int64_t cap, int64_t *file_bytes) {
+  OggWalk w;
+  ogg_walk_init(w, 0);
+  if (header_bytes) ogg_walk_headers(w, pages, cap, header_bytes);
+  ogg_run_begin(w, 2, 0);
+  for (int64_t base = 0; base < npackets; base += 64) {  // as k_ogg_plan takes them: 64 packets at a time, a page per step
+    const int n = npackets - base < 64 ? (int)(npackets - base) : 64;
+    int32_t Bx[65], Sx[65];
+    Bx[0] = Sx[0] = 0;
+    for (int j = 0; j < n; j++) Bx[j + 1] = Bx[j] + bytes[base + j], Sx[j + 1] = Sx[j] + ogg_segments(bytes[base + j]);
+    int c = 0, taken = 0;
+    while (c < n) {
+      int j = c, why = 0;
+      for (; j < n; j++)
+        if ((why = ogg_stop_at(w.pg, Bx, Sx, bytes + base, c, taken, j)) != 0) break;
+      ogg_walk_join(w, pages, cap, (int32_t)base, Bx, Sx, granule + base, &c, &taken, j, why);
+    }
+  }
+  ogg_run_end(w, pages, cap, 1);
+  if (file_bytes) *file_bytes = w.file_off;
+  return w.npages;
+}
+
+// one page of a planned stream laid out at `dst` (header, lacing, body, checksum): list[] / bytes[] the packets of its run
+inline void ogg_write_page(const OggPage &pg, uint32_t serial, const uint8_t *const *list, const int32_t *bytes, uint8_t *dst) {
+  ogg_page_header(pg, serial, dst);
+  uint8_t *lace = dst + OGG_HEADER, *body = lace + pg.nseg;
+  int segs = 0;
+  for (int j = 0; j < pg.npackets; j++) {
+    const int32_t n = bytes[pg.first + j], start = j == 0 ? pg.byte0 : 0, left = ogg_segments(n) - start / 255;
+    const int32_t take = left < pg.nseg - segs ? left : pg.nseg - segs, len = ogg_piece_len(n, start, take);
+    for (int q = 0; q < take; q++) lace[segs + q] = (uint8_t)ogg_lace_value(n, start / 255 + q);
+    if (len) memcpy(body, list[pg.first + j] + start, (size_t)len);
+    segs += take, body += len;
+  }
+  const int64_t total = OGG_HEADER + pg.nseg + pg.body;
+  const uint32_t crc = ogg_crc_chunked(dst, total, OGG_CRC_MIN_CHUNK, OGG_CRC_LANES);
+  for (int i = 0; i < 4; i++) dst[22 + i] = (uint8_t)(crc >> (8 * i));
+}
+
+// a whole file: headers[3] (null: audio pages only, a bare run for the CPU suite), the audio packets.  Returns the file's
+// bytes; writes them when they fit `cap`.
+inline int64_t ogg_mux(const uint8_t *const *headers, const int32_t *header_bytes, int64_t npackets, const uint8_t *const *packets,
+                       const int32_t *bytes, const int64_t *granule, uint32_t serial, uint8_t *out, int64_t cap, OggPage *pages,
+                       int64_t page_cap, int64_t *npages) {
+  int64_t total = 0;
+  const int64_t np = ogg_plan_stream(headers ? header_bytes : nullptr, npackets, bytes, granule, pages, page_cap, &total);
+  if (npages) *npages = np;
+  if (np > page_cap || total > cap) return total;
+  for (int64_t p = 0; p < np; p++) {
+    const OggPage &pg = pages[p];
+    if (pg.run == 2) ogg_write_page(pg, serial, packets, bytes, out + pg.file_off);
+    else ogg_write_page(pg, serial, headers, header_bytes, out + pg.file_off);
+  }
+  return total;
+}
+#endif
+
+}  // namespace vamd

@@ -31,6 +31,7 @@
 #include "vorbis_amd.h"
 #include "vamd_knobs.h"
 #include "vamd_live.h"
+#include "k_ogg.h"
 
 namespace {
 
@@ -242,6 +243,10 @@ struct FeedOut {
   int32_t *bits;
   uint8_t *info, *bytes;
   int64_t cap;  // bytes the arena holds
+  // an Ogg feed (m_bytes set): the device mirror of the arena and of the records, which the pager reads (k_ogg.h)
+  uint8_t *m_bytes, *m_info;
+  int64_t *m_off, *m_gp;
+  int32_t *m_bits;
 };
 __global__ __launch_bounds__(256) void k_feed_copy(FeedPlan P, long nstreams, long nblocks, const int64_t *__restrict__ rel,
                                                    const int64_t *__restrict__ stream_off, const int32_t *__restrict__ sid,
@@ -262,7 +267,12 @@ __global__ __launch_bounds__(256) void k_feed_copy(FeedPlan P, long nstreams, lo
   if (fits) {
     const uint32_t *src = (const uint32_t *)(P.packets[W] + (int64_t)i * P.stride[W]);
     uint32_t *dst = (uint32_t *)(O.bytes + off);
-    for (int w = lane; w < words; w += 64) dst[w] = src[w];
+    uint32_t *mir = O.m_bytes ? (uint32_t *)(O.m_bytes + off) : nullptr;
+    for (int w = lane; w < words; w += 64) {
+      const uint32_t v = src[w];
+      dst[w] = v;
+      if (mir) mir[w] = v;
+    }
   }
   if (lane == 0) {
     const int64_t begin = P.src[W][i] - (int64_t)s * P.stream_stride, center = begin + P.bs[W] / 2;
@@ -270,8 +280,11 @@ __global__ __launch_bounds__(256) void k_feed_copy(FeedPlan P, long nstreams, lo
     O.offset[k] = off;
     O.bits[k] = st ? -1 : bits;
     const int64_t eof = P.live.in ? P.live.in[s].eof : (P.frames_of ? (int64_t)P.head + P.frames_of[s] : P.eof);
-    O.granulepos[k] = (center < eof ? center : eof) - P.bs[1] / 2 + (P.live.in ? P.live.in[s].origin : 0);
-    O.info[k] = (uint8_t)(W | (last ? 2 : 0) | ((st & 3) << 2));
+    const int64_t gp = (center < eof ? center : eof) - P.bs[1] / 2 + (P.live.in ? P.live.in[s].origin : 0);
+    const uint8_t info = (uint8_t)(W | (last ? 2 : 0) | ((st & 3) << 2));
+    O.granulepos[k] = gp;
+    O.info[k] = info;
+    if (O.m_bytes) O.m_off[k] = off, O.m_bits[k] = st ? -1 : bits, O.m_gp[k] = gp, O.m_info[k] = info;
   }
 }
 
@@ -357,6 +370,7 @@ __global__ __launch_bounds__(256) void k_feed_copy_managed(FeedSlice P, long nbl
   if (off + 4 * words <= O.cap) {
     const uint8_t *row = P.packets[W] + ((int64_t)i * VAMD_PACKETBLOBS + choice) * P.stride[W];
     uint32_t *dst = (uint32_t *)(O.bytes + off);
+    uint32_t *mir = O.m_bytes ? (uint32_t *)(O.m_bytes + off) : nullptr;
     for (int64_t w = lane; w < words; w += 64) {
       uint32_t v = 0;
       if (4 * w < keep) {
@@ -365,6 +379,7 @@ __global__ __launch_bounds__(256) void k_feed_copy_managed(FeedSlice P, long nbl
         if (live < 4) v &= (1u << (8 * live)) - 1u;
       }
       dst[w] = v;
+      if (mir) mir[w] = v;
     }
   }
   if (lane == 0) {
@@ -374,8 +389,11 @@ __global__ __launch_bounds__(256) void k_feed_copy_managed(FeedSlice P, long nbl
     O.offset[g] = off;
     O.bits[g] = st ? -1 : fbits;
     const int64_t eof = P.live.in ? P.live.in[s].eof : (P.frames_of ? (int64_t)P.head + P.frames_of[s] : P.eof);
-    O.granulepos[g] = (center < eof ? center : eof) - P.bs[1] / 2 + (P.live.in ? P.live.in[s].origin : 0);
-    O.info[g] = (uint8_t)(W | (last ? 2 : 0) | ((st & 3) << 2) | ((st ? 0 : choice) << 4));
+    const int64_t gp = (center < eof ? center : eof) - P.bs[1] / 2 + (P.live.in ? P.live.in[s].origin : 0);
+    const uint8_t info = (uint8_t)(W | (last ? 2 : 0) | ((st & 3) << 2) | ((st ? 0 : choice) << 4));
+    O.granulepos[g] = gp;
+    O.info[g] = info;
+    if (O.m_bytes) O.m_off[g] = off, O.m_bits[g] = st ? -1 : fbits, O.m_gp[g] = gp, O.m_info[g] = info;
   }
 }
 
@@ -438,6 +456,13 @@ struct FeedLane {
     int64_t shift = 0;            // where the next buffer begins (the last walk's rebase)
   };
   std::vector<LiveStream> live;
+  // an Ogg feed (vamd_feed_ogg_headers): the device mirror of the packet arena and of the records, the header packets, the
+  // group's serial numbers, the page table and the streams' file sizes; the files (pinned) and their record (pinned)
+  Buf d_mirror, d_moff, d_mgp, d_mrbits, d_minfo, d_hdr, d_serial, h_serial, d_pages, d_fbytes, d_foff, d_npages, d_ostatus;
+  Buf h_ogg, h_orec;
+  int32_t hdr_off[3] = {0, 0, 0};
+  std::vector<uint32_t> serials, user_serials;  // the job's; what vamd_feed_ogg_serials set for it
+  vamd_feed_ogg_result ogg_result;
   std::vector<uint8_t> close_of;  // the job's closes (live)
   std::thread worker;
   std::mutex *upload_turn = nullptr;  // its device's (vamd_feed::upload_turns)
@@ -463,6 +488,10 @@ struct vamd_feed {
   int format = VAMD_FEED_S16;
   int write_frames = 0;             // > 0: a live feed (vamd_feed_create_live), the reference's frames per write
   long live_cs = 0, row_stride = 0, retain = 0;  // its buffers' samples per channel, flag rows, the retention bound
+  bool ogg = false;                 // an Ogg feed (vamd_feed_ogg_headers): files beside the packets
+  std::vector<uint8_t> ogg_hdr[3];  // its identification, comment and setup packets
+  uint32_t next_serial = 0;         // the running serial number (a group's streams take the next nstreams)
+  long rate = 0;
   std::mutex m;
   std::vector<std::unique_ptr<std::mutex>> upload_turns;  // one per device
   std::condition_variable cv_work, cv_done;
@@ -487,6 +516,125 @@ struct vamd_feed {
       return r__;                                                                   \
     }                                                                               \
   } while (0)
+
+#define FEED_OWN(expr)           \
+  do {                           \
+    const int r__ = (expr);      \
+    if (r__) return r__;         \
+  } while (0)
+
+// ---- an Ogg feed: the mirror the copy kernels fill, the pager behind the last packet (k_ogg.h) ----
+// The mirror's buffers for a group of nb packets, as large as the packet arena (+ 16: the pager reads whole words), the
+// first `keep` bytes kept when it has to grow in mid-group (a managed group's earlier slices); O's mirror pointers set, or
+// null on a feed without Ogg headers.
+static int feed_mirror(vamd_feed *f, FeedLane &L, FeedOut &O, long nb, size_t keep) {
+  O.m_bytes = O.m_info = nullptr, O.m_off = O.m_gp = nullptr, O.m_bits = nullptr;
+  if (!f->ogg) return VAMD_OK;
+  const size_t want = L.h_out.bytes + 16, n = (size_t)(nb ? nb : 1);
+  if (L.d_mirror.bytes < want) {
+    if (keep && L.d_mirror.p) {
+      void *q = nullptr;
+      FEED_TRY(hipMalloc(&q, want));
+      FEED_TRY(hipMemcpyAsync(q, L.d_mirror.p, keep < L.d_mirror.bytes ? keep : L.d_mirror.bytes, hipMemcpyDeviceToDevice, L.stream));
+      FEED_TRY(hipStreamSynchronize(L.stream));
+      L.d_mirror.drop();
+      L.d_mirror.p = q, L.d_mirror.bytes = want;
+    } else {
+      FEED_TRY(hipStreamSynchronize(L.stream));  // (nothing in flight reads the old one when it goes)
+      FEED_TRY(L.d_mirror.need(want));
+    }
+  }
+  FEED_TRY(L.d_moff.need(n * 8));
+  FEED_TRY(L.d_mgp.need(n * 8));
+  FEED_TRY(L.d_mrbits.need(n * 4));
+  FEED_TRY(L.d_minfo.need(n));
+  O.m_bytes = (uint8_t *)L.d_mirror.p, O.m_info = (uint8_t *)L.d_minfo.p;
+  O.m_off = (int64_t *)L.d_moff.p, O.m_gp = (int64_t *)L.d_mgp.p, O.m_bits = (int32_t *)L.d_mrbits.p;
+  return VAMD_OK;
+}
+
+// the group's record of its files, in pinned memory: [total | stream_offset (ns + 1) | npages (ns) | status (ns)]
+static size_t orec_npages(long ns) { return 8 + (size_t)(ns + 1) * 8; }
+static size_t orec_status(long ns) { return orec_npages(ns) + (size_t)ns * 4; }
+
+// The pager, queued behind the group's last copy kernel: k_ogg_plan (a wave per stream) -> k_feed_scan (the files end to
+// end) -> k_ogg_pages (a wave per page slot; the pages cross the link inside it).  Nothing here waits: the page table is
+// sized by ogg_slots_per_packet, the arena by ogg_file_bound of the PACKET arena's size -- packets that fit theirs make
+// files that fit this one.  d_packet_total (VBR): the packets' bytes on the device; beyond the arena nothing was mirrored
+// and nothing is paged (finish_group lays the group out again).
+static int run_pager(vamd_feed *f, FeedLane &L, const int64_t *d_stream_start, long ns, long nb, const int64_t *d_packet_total) {
+  hipStream_t st = L.stream;
+  int32_t hb[3];
+  for (int i = 0; i < 3; i++) hb[i] = (int32_t)f->ogg_hdr[i].size();
+  if (!L.d_hdr.p) {  // the header packets, each at a multiple of 4: once per lane
+    size_t at = 0;
+    for (int i = 0; i < 3; i++) L.hdr_off[i] = (int32_t)at, at += al((size_t)hb[i], 4);
+    std::vector<uint8_t> img(at + 16, 0);
+    for (int i = 0; i < 3; i++) memcpy(img.data() + L.hdr_off[i], f->ogg_hdr[i].data(), (size_t)hb[i]);
+    FEED_TRY(L.d_hdr.need(img.size()));
+    FEED_TRY(hipMemcpy(L.d_hdr.p, img.data(), img.size(), hipMemcpyHostToDevice));
+  }
+  if ((long)L.serials.size() != ns || !L.d_mirror.p) {
+    L.err = "Ogg feed: the group has no serial numbers or no mirror";
+    return VAMD_EFAULT;
+  }
+  FEED_TRY(L.h_serial.need((size_t)ns * 4));
+  FEED_TRY(L.d_serial.need((size_t)ns * 4));
+  memcpy(L.h_serial.p, L.serials.data(), (size_t)ns * 4);
+  FEED_TRY(hipMemcpyAsync(L.d_serial.p, L.h_serial.p, (size_t)ns * 4, hipMemcpyHostToDevice, st));
+  const int64_t hs = vamd::ogg_header_slots(hb), sp = vamd::ogg_slots_per_packet(f->pkcap[0] > f->pkcap[1] ? f->pkcap[0] : f->pkcap[1]);
+  const int64_t nslots = ns * hs + sp * nb;
+  FEED_TRY(L.d_pages.need((size_t)nslots * sizeof(vamd::OggPage)));
+  FEED_TRY(L.d_fbytes.need((size_t)ns * 8));
+  FEED_TRY(L.d_foff.need((size_t)(ns + 1) * 8));
+  FEED_TRY(L.d_npages.need((size_t)ns * 4));
+  FEED_TRY(L.d_ostatus.need((size_t)ns));
+  FEED_TRY(L.h_orec.need(al(orec_status(ns) + (size_t)ns, 16)));
+  FEED_TRY(L.h_ogg.need(al((size_t)vamd::ogg_file_bound((int64_t)L.h_out.bytes, nb, ns, hb) + 16, 4096)));
+  void *drec = nullptr, *dbytes = nullptr;
+  FEED_TRY(hipHostGetDevicePointer(&drec, L.h_orec.p, 0));
+  FEED_TRY(hipHostGetDevicePointer(&dbytes, L.h_ogg.p, 0));
+  vamd::OggIn I;
+  I.stream_start = d_stream_start;
+  I.off = (const int64_t *)L.d_moff.p, I.gp = (const int64_t *)L.d_mgp.p, I.bits = (const int32_t *)L.d_mrbits.p;
+  I.info = (const uint8_t *)L.d_minfo.p, I.bytes = (const uint8_t *)L.d_mirror.p, I.cap = (int64_t)L.h_out.bytes;
+  I.packet_total = d_packet_total;
+  I.hdr = (const uint8_t *)L.d_hdr.p;
+  for (int i = 0; i < 3; i++) I.hdr_off[i] = L.hdr_off[i], I.hdr_bytes[i] = hb[i];
+  I.serial = (const uint32_t *)L.d_serial.p;
+  I.header_slots = hs, I.slots_per_packet = sp;
+  vamd::OggOut O;
+  uint8_t *dr = (uint8_t *)drec;
+  O.total = (int64_t *)dr, O.stream_offset = (int64_t *)(dr + 8), O.npages = (int32_t *)(dr + orec_npages(ns)), O.status = dr + orec_status(ns);
+  O.bytes = (uint8_t *)dbytes, O.cap = (int64_t)L.h_ogg.bytes;
+  hipLaunchKernelGGL(vamd::k_ogg_plan, dim3((unsigned)ns), dim3(64), 0, st, I, ns, (vamd::OggPage *)L.d_pages.p, (int64_t *)L.d_fbytes.p,
+                     (int32_t *)L.d_npages.p, (uint8_t *)L.d_ostatus.p);
+  hipLaunchKernelGGL(k_feed_scan, dim3(1), dim3(1024), 0, st, ns, (const int64_t *)L.d_fbytes.p, (int64_t *)L.d_foff.p);
+  hipLaunchKernelGGL(vamd::k_ogg_pages, dim3((unsigned)nslots), dim3(64), 0, st, I, ns, (const vamd::OggPage *)L.d_pages.p,
+                     (const int64_t *)L.d_foff.p, (const int32_t *)L.d_npages.p, (const uint8_t *)L.d_ostatus.p, O);
+  FEED_TRY(hipGetLastError());
+  return VAMD_OK;
+}
+
+// ... and after the group's wait: what vamd_feed_ogg hands out
+static int pager_result(vamd_feed *f, FeedLane &L, long ns) {
+  (void)f;
+  const uint8_t *hr = (const uint8_t *)L.h_orec.p;
+  vamd_feed_ogg_result &R = L.ogg_result;
+  R.nstreams = ns;
+  R.stream_offset = (const int64_t *)(hr + 8), R.npages = (const int32_t *)(hr + orec_npages(ns)), R.status = hr + orec_status(ns);
+  R.bytes = (const uint8_t *)L.h_ogg.p, R.total_bytes = *(const int64_t *)hr;
+  for (long s = 0; s < ns; s++)
+    if (R.status[s] & 0x80) {
+      L.err = "Ogg feed: a stream needed more pages than its slots of the page table";
+      return VAMD_EFAULT;
+    }
+  if (R.total_bytes + 4 > (int64_t)L.h_ogg.bytes) {
+    L.err = "Ogg feed: the files exceed the bound their arena was sized by";
+    return VAMD_EFAULT;
+  }
+  return VAMD_OK;
+}
 
 // A bitrate-managed group, from its plan on: the blocks in slices of at most f->slice (in order[] order, so a slice holds
 // the end of one stream, whole streams, the start of another), each slice through
@@ -646,13 +794,16 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
     O.total = (int64_t *)dr, O.stream_start = (int64_t *)(dr + o_start), O.offset = (int64_t *)(dr + o_off);
     O.granulepos = (int64_t *)(dr + o_gp), O.bits = (int32_t *)(dr + o_bits), O.info = dr + o_info;
     O.bytes = (uint8_t *)dbytes, O.cap = (int64_t)L.h_out.bytes;
+    FEED_OWN(feed_mirror(f, L, O, nb, (size_t)base));
     hipLaunchKernelGGL(k_feed_copy_managed, dim3((unsigned)((nbs + 3) / 4)), dim3(256), 0, st, P, nbs, base, (const int64_t *)L.d_rel.p,
                        (const int64_t *)L.d_soff.p, (const int32_t *)L.d_sid.p, O);
     FEED_TRY(hipGetLastError());
     base = need;
   }
+  if (f->ogg) FEED_OWN(run_pager(f, L, plan.stream_start, ns, nb, nullptr));
   FEED_TRY(hipEventRecord(L.ev_end, st));
   FEED_TRY(hipEventSynchronize(L.ev_end));
+  if (f->ogg) FEED_OWN(pager_result(f, L, ns));
   *(int64_t *)hrec = base;
   memcpy(hrec + o_start, start.data(), (size_t)(ns + 1) * 8);
   vamd_feed_result &R = L.result;
@@ -796,6 +947,7 @@ static int finish_group(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan,
     O.total = (int64_t *)dr, O.stream_start = (int64_t *)(dr + o_start), O.offset = (int64_t *)(dr + o_off);
     O.granulepos = (int64_t *)(dr + o_gp), O.bits = (int32_t *)(dr + o_bits), O.info = dr + o_info;
     O.bytes = (uint8_t *)dbytes, O.cap = (int64_t)L.h_out.bytes;
+    FEED_OWN(feed_mirror(f, L, O, nb, 0));
     hipLaunchKernelGGL(k_feed_sid, dim3((unsigned)ns), dim3(64), 0, st, plan.stream_start, (int32_t *)L.d_sid.p);
     hipLaunchKernelGGL(k_feed_sizes, dim3((unsigned)ns), dim3(64), 0, st, P, ns, (int64_t *)L.d_rel.p, (int64_t *)L.d_sbytes.p);
     hipLaunchKernelGGL(k_feed_scan, dim3(1), dim3(1024), 0, st, ns, (const int64_t *)L.d_sbytes.p, (int64_t *)L.d_soff.p);
@@ -803,10 +955,12 @@ static int finish_group(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan,
     hipLaunchKernelGGL(k_feed_copy, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, P, ns, nb, (const int64_t *)L.d_rel.p,
                        (const int64_t *)L.d_soff.p, (const int32_t *)L.d_sid.p, O);
     FEED_TRY(hipGetLastError());
+    if (f->ogg) FEED_OWN(run_pager(f, L, plan.stream_start, ns, nb, (const int64_t *)L.d_soff.p + ns));
     FEED_TRY(hipEventRecord(L.ev_end, st));
     FEED_TRY(hipEventSynchronize(L.ev_end));
     const int64_t total = *(const int64_t *)hrec;
     if (total <= (int64_t)L.h_out.bytes) {
+      if (f->ogg) FEED_OWN(pager_result(f, L, ns));
       vamd_feed_result &R = L.result;
       R.nstreams = ns_out, R.nblocks = nb;
       R.stream_start = (const int64_t *)(hrec + o_start), R.offset = (const int64_t *)(hrec + o_off);
@@ -1002,7 +1156,9 @@ static void feed_free(vamd_feed *f) {
     if (L.ctx) vamd_destroy(L.ctx);
     Buf *all[] = {&L.d_len, &L.h_len, &L.h_in, &L.h_out, &L.h_rec, &L.d_in, &L.d_pcm, &L.d_states, &L.d_amp, &L.d_pk[0], &L.d_pk[1], &L.d_bits[0],
                   &L.d_bits[1], &L.d_status[0], &L.d_status[1], &L.d_rel, &L.d_sid, &L.d_sbytes, &L.d_soff, &L.d_bstate, &L.d_slice, &L.h_slice,
-                  &L.d_buf[0], &L.d_buf[1], &L.d_walk, &L.d_rows, &L.d_nan, &L.d_btmpl, &L.d_live, &L.h_live, &L.h_lstatus};
+                  &L.d_buf[0], &L.d_buf[1], &L.d_walk, &L.d_rows, &L.d_nan, &L.d_btmpl, &L.d_live, &L.h_live, &L.h_lstatus,
+                  &L.d_mirror, &L.d_moff, &L.d_mgp, &L.d_mrbits, &L.d_minfo, &L.d_hdr, &L.d_serial, &L.h_serial, &L.d_pages, &L.d_fbytes,
+                  &L.d_foff, &L.d_npages, &L.d_ostatus, &L.h_ogg, &L.h_orec};
     for (int W = 0; W < 2; W++) {
       Buf *m[] = {&L.d_mpk[W], &L.d_mbits[W], &L.d_mposts[W], &L.d_mvalid[W], &L.d_miwork[W], &L.d_mnz[W], &L.d_choice[W], &L.d_fbits[W]};
       for (Buf *b : m) b->drop();
@@ -1045,6 +1201,7 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
   vamd_feed *f = new vamd_feed;
   f->max_streams = max_streams, f->max_frames = max_frames, f->format = format, f->write_frames = write_frames;
   f->managed = h.managed && h.off_bitrate;
+  f->rate = h.rate;
   {
     const vamd::Knobs K = vamd::read_knobs();
     f->slice = K.feed_slice > 0 ? K.feed_slice : 2048;
@@ -1058,6 +1215,7 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
     L.device = devs[l % devs.size()];
     L.upload_turn = f->upload_turns[l % devs.size()].get();
     L.h_in.host = L.h_out.host = L.h_rec.host = L.h_len.host = L.h_slice.host = L.h_live.host = L.h_lstatus.host = true;
+    L.h_ogg.host = L.h_orec.host = L.h_serial.host = true;
     r = vamd_create(&L.ctx, setup_blob, blob_bytes, L.device);
     if (r) break;
     hipError_t e = hipSetDevice(L.device);
@@ -1121,7 +1279,88 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
   return VAMD_OK;
 }
 
+// an Ogg feed's group (f->m held): its serial numbers -- the next nstreams of the feed's running counter, then what
+// vamd_feed_ogg_serials set for the slot in their place
+static void ogg_job(vamd_feed *f, FeedLane &L, long nstreams) {
+  memset(&L.ogg_result, 0, sizeof(L.ogg_result));
+  if (!f->ogg) return;
+  L.serials.resize((size_t)nstreams);
+  for (long s = 0; s < nstreams; s++) L.serials[(size_t)s] = f->next_serial++;
+  for (size_t s = 0; s < L.user_serials.size() && s < (size_t)nstreams; s++) L.serials[s] = L.user_serials[s];
+  L.user_serials.clear();
+}
+
+static uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
 extern "C" {
+
+int vamd_feed_ogg_headers(vamd_feed *f, const void *id, long id_bytes, const void *comment, long comment_bytes, const void *setup,
+                          long setup_bytes) {
+  if (!f) return VAMD_EINVAL;
+  std::lock_guard<std::mutex> g(f->m);
+  if (f->write_frames) {
+    f->err = "Ogg files of a live feed are not implemented (a page may span two groups)";
+    return VAMD_EIMPL;
+  }
+  if (f->turn) {
+    f->err = "vamd_feed_ogg_headers comes before the first vamd_feed_buffer";
+    return VAMD_EINVAL;
+  }
+  const uint8_t *pk[3] = {(const uint8_t *)id, (const uint8_t *)comment, (const uint8_t *)setup};
+  const long n[3] = {id_bytes, comment_bytes, setup_bytes};
+  for (int i = 0; i < 3; i++)
+    if (!pk[i] || n[i] < 7 || n[i] > (1L << 24) || pk[i][0] != 1 + 2 * i || memcmp(pk[i] + 1, "vorbis", 6)) {
+      f->err = std::string("Ogg headers: packet ") + std::to_string(i) + " is not a Vorbis header of type " + std::to_string(1 + 2 * i);
+      return VAMD_EINVAL;
+    }
+  if (id_bytes != 30) {
+    f->err = "Ogg headers: the identification header is not 30 bytes";
+    return VAMD_EINVAL;
+  }
+  const uint8_t *h = pk[0];
+  const long hch = h[11], hrate = (long)le32(h + 12);
+  const int b0 = 1 << (h[28] & 15), b1 = 1 << (h[28] >> 4);
+  if (le32(h + 7) != 0 || !(h[29] & 1)) {
+    f->err = "Ogg headers: the identification header's version or framing bit is wrong";
+    return VAMD_EINVAL;
+  }
+  if (hch != f->ch || hrate != f->rate || b0 != f->bs[0] || b1 != f->bs[1]) {
+    f->err = "Ogg headers: identification header (" + std::to_string(hch) + " ch, " + std::to_string(hrate) + " Hz, blocks " + std::to_string(b0) +
+             "/" + std::to_string(b1) + ") is not the setup's (" + std::to_string(f->ch) + " ch, " + std::to_string(f->rate) + " Hz, blocks " +
+             std::to_string(f->bs[0]) + "/" + std::to_string(f->bs[1]) + ")";
+    return VAMD_EINVAL;
+  }
+  for (int i = 0; i < 3; i++) f->ogg_hdr[i].assign(pk[i], pk[i] + n[i]);
+  f->ogg = true;
+  return VAMD_OK;
+}
+
+int vamd_feed_ogg_serials(vamd_feed *f, int slot, const uint32_t *serials, long n) {
+  if (!f || !serials || n < 0 || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  std::lock_guard<std::mutex> g(f->m);
+  FeedLane &L = f->lanes[(size_t)slot];
+  if (!f->ogg || L.state != LANE_FILLING || n > f->max_streams) {
+    f->err = "vamd_feed_ogg_serials: an Ogg feed's slot between vamd_feed_buffer and vamd_feed_wrote, at most max_streams numbers";
+    return VAMD_EINVAL;
+  }
+  L.user_serials.assign(serials, serials + n);
+  return VAMD_OK;
+}
+
+int vamd_feed_ogg(vamd_feed *f, int slot, vamd_feed_ogg_result *out) {
+  if (!f || !out || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  std::unique_lock<std::mutex> g(f->m);
+  if (!f->ogg) {
+    f->err = "vamd_feed_ogg: the feed has no Ogg headers (vamd_feed_ogg_headers)";
+    return VAMD_EINVAL;
+  }
+  FeedLane &L = f->lanes[(size_t)slot];
+  if (L.state != LANE_QUEUED && L.state != LANE_DONE) return VAMD_EINVAL;
+  f->cv_done.wait(g, [&] { return f->stop || L.state == LANE_DONE; });
+  if (L.state != LANE_DONE) return VAMD_EFAULT;
+  *out = L.ogg_result;
+  return L.status;
+}
 
 int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes, const int *devices, int ndevices,
                      int lanes_per_device, long max_streams, long max_frames, int format) {
@@ -1183,6 +1422,7 @@ int vamd_feed_wrote(vamd_feed *f, int slot, long nstreams, long frames) {
   L.frames_of.clear();
   L.status = 0;
   memset(&L.result, 0, sizeof(L.result));
+  ogg_job(f, L, nstreams);
   L.t_wrote = now_s();
   L.state = LANE_QUEUED;
   f->cv_work.notify_all();
@@ -1207,6 +1447,7 @@ int vamd_feed_wrote_v(vamd_feed *f, int slot, long nstreams, const int64_t *fram
   L.frames_of.assign(frames, frames + nstreams);
   L.status = 0;
   memset(&L.result, 0, sizeof(L.result));
+  ogg_job(f, L, nstreams);
   L.t_wrote = now_s();
   L.state = LANE_QUEUED;
   f->cv_work.notify_all();
@@ -1252,6 +1493,7 @@ int vamd_feed_release(vamd_feed *f, int slot) {
   std::lock_guard<std::mutex> g(f->m);
   FeedLane &L = f->lanes[(size_t)slot];
   if (L.state != LANE_DONE && L.state != LANE_FILLING) return VAMD_EINVAL;
+  L.user_serials.clear();
   L.state = LANE_FREE;
   f->cv_done.notify_all();
   return VAMD_OK;
