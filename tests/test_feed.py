@@ -58,6 +58,27 @@ def compare(setup, pcm, got):
     return bad
 
 
+def small_arena(monkeypatch, arena):
+    """arena (a string, or None): VAMD_FEED_OUT_BYTES (a test knob) -- every lane's packet arena starts that small, so a
+    group whose packets take more has to grow it (the VBR retry, the growth between a managed group's slices, the Ogg
+    mirror's)."""
+    if arena:
+        monkeypatch.setenv("VAMD_TEST_KNOBS", "1")
+        monkeypatch.setenv("VAMD_FEED_OUT_BYTES", arena)
+
+
+def spy_totals(feed):
+    """-> a list that receives total_bytes of every group feed.packets() returns from now on"""
+    totals, packets = [], feed.packets
+
+    def spy(slot, copy=True):
+        r = packets(slot, copy)
+        totals.append(r["total_bytes"])
+        return r
+    feed.packets = spy
+    return totals
+
+
 @pytest.mark.parametrize("setup", ["44k_stereo_q4", "44k_stereo_q9", "44k_mono_q5"])
 def test_whole_streams_from_host_s16_match_the_reference(setup):
     import vorbis_amd
@@ -135,22 +156,28 @@ def test_groups_in_flight(as_float):
         assert not bad, "group %d\n" % gi + "\n".join(bad)
 
 
-@pytest.mark.parametrize("setup", ["44k_stereo_q4", "44k_stereo_q9"])
-def test_streams_of_unequal_length_in_one_group(setup):
+@pytest.mark.parametrize("setup,arena", [pytest.param("44k_stereo_q4", None, id="44k_stereo_q4"), pytest.param("44k_stereo_q9", None, id="44k_stereo_q9"),
+                                         pytest.param("44k_stereo_q4", "4096", id="44k_stereo_q4-arena4096"),
+                                         pytest.param("44k_stereo_q9", "4096", id="44k_stereo_q9-arena4096")])
+def test_streams_of_unequal_length_in_one_group(setup, arena, monkeypatch):
     """vamd_feed_wrote_v: eleven streams from 1 to 40 000 frames back to back in one group -- every stream gets its own LPC
-    ends, its own share of the detector's steps and its own walk, and emits what the reference emits for it alone."""
+    ends, its own share of the detector's steps and its own walk, and emits what the reference emits for it alone.
+    arena: each lane's packet arena starts at 4096 bytes, so both groups are laid out twice (the arena grown in between)."""
     import vorbis_amd
     from oracle import ref
     if not ref.available():
         pytest.skip("needs the reference build")
+    small_arena(monkeypatch, arena)
     rng = np.random.default_rng(31)
     lengths = [40000, 1, 33, 2049, 17000, 3072, 39999, 700, 25000, 4097, 12345]
     kinds = ["gated", "noise", "sine", "clicks", "noise", "gated", "sine", "gated", "clicks", "noise", "gated"]
     parts = [s16_streams(rng, 2, n, [k])[0] for n, k in zip(lengths, kinds)]
     feed = vorbis_amd.Feed(vorbis_amd.default_setup_blob(setup), lanes_per_device=2, max_streams=16, max_frames=40000)
+    totals = spy_totals(feed)
     got = feed.encode(parts)
     again = feed.encode(parts[::-1])[::-1]          # (the same streams in another order, on the other lane)
     feed.close()
+    assert len(totals) == 2 and (not arena or min(totals) > 4096), totals
     bad = []
     for s, (pcm, g) in enumerate(zip(parts, got)):
         bad += compare(setup, pcm[None], [g])

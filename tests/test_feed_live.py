@@ -7,7 +7,7 @@ import pytest
 
 from tests import bitrate_host as bh
 from tests import checker
-from tests.test_feed import s16_streams
+from tests.test_feed import s16_streams, small_arena, spy_totals
 
 pytestmark = pytest.mark.gpu
 
@@ -147,19 +147,27 @@ def test_cadence_over_the_lds_bound_is_refused():
 
 
 @pytest.mark.parametrize("slice_", [None, "5"])
-@pytest.mark.parametrize("name,ch,rates,kind", [bh.CONFIGS[0], bh.CONFIGS[2], bh.CONFIGS[3]], ids=["abr", "cbr", "minmax"])
-def test_managed_in_pieces(name, ch, rates, kind, slice_, monkeypatch):
+@pytest.mark.parametrize("name,ch,rates,kind,lengths,arena",
+                         [bh.CONFIGS[0] + ([26000, 9000, 2000], None), bh.CONFIGS[2] + ([26000, 9000, 2000], None),
+                          bh.CONFIGS[3] + ([26000, 9000, 2000], None), bh.CONFIGS[0] + ([90000, 60000, 2000], "4096")],
+                         ids=["abr", "cbr", "minmax", "abr-arena4096"])
+def test_managed_in_pieces(name, ch, rates, kind, lengths, arena, slice_, monkeypatch):
+    """arena: the lane's packet arena starts at 4096 bytes (VAMD_FEED_OUT_BYTES) and the streams are long enough for a
+    group's packets to outgrow it (between its slices, where it has several)."""
     import vorbis_amd
     ref = _ref()
     if slice_:
         monkeypatch.setenv("VAMD_TEST_KNOBS", "1")
         monkeypatch.setenv("VAMD_FEED_SLICE", slice_)
+    small_arena(monkeypatch, arena)
     rng = np.random.default_rng(3)
     streams = [np.clip(np.round(bh.signal(kind, ch, n, 40 + i).T * 32768.0), -32768, 32767).astype(np.int16)
-               for i, n in enumerate([26000, 9000, 2000])]
-    feed = vorbis_amd.Feed(bh.managed_blob(ch, rates), lanes_per_device=1, max_streams=4, max_frames=26000, write_frames=1024)
+               for i, n in enumerate(lengths)]
+    feed = vorbis_amd.Feed(bh.managed_blob(ch, rates), lanes_per_device=1, max_streams=4, max_frames=max(lengths), write_frames=1024)
+    totals = spy_totals(feed)
     got = run_live(feed, streams, [random_cuts(rng, len(x)) for x in streams])
     feed.close()
+    assert not arena or max(totals) > 4096, totals
     bad = []
     for s, x in enumerate(streams):
         bad += diff(reference(ref.RefEncoder(ch, 44100, managed=rates), x), got[s], s)

@@ -112,9 +112,12 @@ def _tmp():
     return tempfile.mkdtemp(prefix="walk")
 
 
-def test_slices_change_nothing(monkeypatch):
+@pytest.mark.parametrize("arena", [None, "4096"])
+def test_slices_change_nothing(arena, monkeypatch):
     """VAMD_FEED_SLICE (a test knob) forced down to 7 blocks: a group of two streams then runs in many slices, at least
-    three of them inside one stream, with the ampmax chains and the managers carried across -- same bytes as one slice."""
+    three of them inside one stream, with the ampmax chains and the managers carried across -- same bytes as one slice.
+    arena: the packet arena starts at 4096 bytes (VAMD_FEED_OUT_BYTES), so it grows between slices, the earlier slices'
+    packets kept."""
     import vorbis_amd
     ref = _ref()
     rates = (160000, 96000, 64000)
@@ -136,7 +139,10 @@ def test_slices_change_nothing(monkeypatch):
     one = run()
     monkeypatch.setenv("VAMD_TEST_KNOBS", "1")
     monkeypatch.setenv("VAMD_FEED_SLICE", "7")
+    if arena:
+        monkeypatch.setenv("VAMD_FEED_OUT_BYTES", arena)
     many = run()
+    assert not arena or many["total_bytes"] > 4096
     first = int(one["stream_start"][1])
     assert first >= 3 * 7, "the first stream must span at least three slices"
     for k in ("stream_start", "offset", "bits", "granulepos", "info"):

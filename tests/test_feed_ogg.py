@@ -12,7 +12,7 @@ import pytest
 from tests import bitrate_host as bh
 from tests import checker
 from tests import ogg_host as oh
-from tests.test_feed import s16_streams
+from tests.test_feed import s16_streams, small_arena, spy_totals
 
 pytestmark = pytest.mark.gpu
 
@@ -87,22 +87,28 @@ def check_group(host, ref, setup, headers, parts, files, rows, o, serials):
     return out
 
 
-@pytest.mark.parametrize("setup", ["44k_stereo_q4", "44k_stereo_q9", "44k_mono_q5"])
-def test_files_of_whole_streams(host, setup):
+@pytest.mark.parametrize("setup,arena", [pytest.param(s, None, id=s) for s in ("44k_stereo_q4", "44k_stereo_q9", "44k_mono_q5")] +
+                         [pytest.param(s, "4096", id=s + "-arena4096") for s in ("44k_stereo_q4", "44k_stereo_q9", "44k_mono_q5")])
+def test_files_of_whole_streams(host, setup, arena, monkeypatch):
+    """arena: each lane's packet arena starts at 4096 bytes (VAMD_FEED_OUT_BYTES), so the group is laid out and paged a
+    second time, the arena and its mirror grown in between."""
     import vorbis_amd
     ref = _ref()
+    small_arena(monkeypatch, arena)
     ch, rate, q = checker.SETUPS[setup]
     headers = oh.reference_headers(ch, rate, q)
     rng = np.random.default_rng(2026)
     frames = 30000
     pcm = s16_streams(rng, ch, frames, ["noise", "gated", "sine", "clicks", "silence", "gated"])
     feed = vorbis_amd.Feed(vorbis_amd.default_setup_blob(setup), lanes_per_device=2, max_streams=8, max_frames=frames, ogg_headers=headers)
+    totals = spy_totals(feed)
     try:
         files, rows, o = run_group(feed, list(pcm))
         again = feed.encode_ogg(pcm, serials=range(6))     # (the other lane; encode_ogg's own path)
     finally:
         feed.close()
     assert again == files
+    assert len(totals) == 1 and (not arena or totals[0] > 4096), totals
     check_group(host, ref, setup, headers, list(pcm), files, rows, o, list(range(6)))
 
 
@@ -192,9 +198,11 @@ def test_a_continued_page(host):
     assert got[1][2]["nseg"] == 255 and got[1][3]["flags"] & 1
 
 
-def test_managed_and_its_slices(host, monkeypatch):
+@pytest.mark.parametrize("arena", [None, "4096"])
+def test_managed_and_its_slices(host, arena, monkeypatch):
     """An ABR setup; once with the default slice and once with slices of 7 blocks, so that pages straddle slices: the
-    same files."""
+    same files.  arena: in the sliced run the packet arena starts at 4096 bytes (VAMD_FEED_OUT_BYTES), so it and its
+    mirror grow between slices, the earlier slices' packets kept."""
     import vorbis_amd
     ref = _ref()
     rates = (-1, 128000, -1)
@@ -207,14 +215,19 @@ def test_managed_and_its_slices(host, monkeypatch):
 
     def run():
         feed = vorbis_amd.Feed(blob, lanes_per_device=1, max_streams=4, max_frames=66150, ogg_headers=headers)
+        totals.append(spy_totals(feed))
         try:
             return run_group(feed, parts, [7, 8, 9])
         finally:
             feed.close()
+    totals = []
     files, rows, o = run()
     monkeypatch.setenv("VAMD_TEST_KNOBS", "1")
     monkeypatch.setenv("VAMD_FEED_SLICE", "7")
+    if arena:
+        monkeypatch.setenv("VAMD_FEED_OUT_BYTES", arena)
     files7, rows7, o7 = run()
+    assert not arena or totals[1][0] > 4096, totals
     assert files7 == files and rows7 == rows
     assert len(rows[0]) >= 3 * 7, "the first stream must span several slices"
     for s, x in enumerate(parts):

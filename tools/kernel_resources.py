@@ -29,7 +29,7 @@ if not rows:  # the compile failed (c++filt without arguments would wait on stdi
 names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True, stdin=subprocess.DEVNULL).stdout.splitlines()
 print("%-44s %5s %5s %7s %7s %7s %4s" % ("kernel", "VGPR", "SGPR", "vspill", "sspill", "scratch", "occ"))
 for r, nm in zip(rows, names):
-    nm = re.sub(r"\(.*$", "", nm).replace("void ", "")
+    nm = re.sub(r"\(.*$", "", nm.replace("(anonymous namespace)::", "")).replace("void ", "")
     if pat.search(nm):
         print("%-44s %5s %5s %7s %7s %7s %4s" % (nm, r.get("VGPRs"), r.get("TotalSGPRs"), r.get("VGPRs Spill"), r.get("SGPRs Spill"),
                                                  r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]")))

@@ -24,6 +24,7 @@
 #include <chrono>
 #include <memory>
 #include <condition_variable>
+#include <deque>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -31,400 +32,54 @@
 #include "vorbis_amd.h"
 #include "vamd_knobs.h"
 #include "vamd_live.h"
+#include "k_feed.h"
 #include "k_ogg.h"
+
+using namespace vamd;  // (the feed's kernels and their structs: k_feed.h, k_ogg.h)
 
 namespace {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 size_t al(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// ---- kernels ------------------------------------------------------------------------------------------------
-
-// in [s][frame][c] (int16 or float) -> pcm[s * ss + c * cs + head + frame]; the room in front (head samples) and behind
-// (pad samples) zeroed, as the reference's calloc'ed / not yet written buffer is.  A thread takes four frames of every
-// channel: one 8 ch-byte (16-bit) or 16 ch-byte read, one 16-byte store per channel.
-// frames_of / first_of (optional): streams of unequal length laid back to back -- stream s has frames_of[s] <= frames frames
-// starting at frame first_of[s] of the arena; the rest of its buffer (laid out for `frames`) is zeroed.
-template <typename T>
-__global__ void k_feed_ingest(const T *__restrict__ in, int ch, long nstreams, long frames, int head, int pad,
-                              float *__restrict__ pcm, long ss, long cs, float *__restrict__ amp,
-                              vamd_envelope_state *__restrict__ states, const long long *__restrict__ frames_of,
-                              const long long *__restrict__ first_of) {
-  const long quads = (frames + 3) >> 2, hq = head >> 2, pq = pad >> 2, per = hq + quads + pq, total = nstreams * per;
-  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const long s = t / per, q = t - s * per;
-    float *row = pcm + s * ss;
-    const long mine = frames_of ? (long)frames_of[s] : frames, first = first_of ? (long)first_of[s] : s * frames;
-    if (q < hq) {
-      for (int c = 0; c < ch; c++) ((float4 *)(row + (long)c * cs))[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (q == 0) amp[s] = VAMD_AMPMAX_FLOOR;
-    } else if (q < hq + quads) {
-      const long f0 = (q - hq) << 2;
-      const T *src = in + (first + f0) * ch;
-      const int live = mine - f0 < 4 ? (mine > f0 ? (int)(mine - f0) : 0) : 4;
-      for (int c = 0; c < ch; c++) {
-        float v[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          float x = 0.f;
-          if (k < live) {
-            if (sizeof(T) == 2) x = (float)(int)src[k * ch + c] / 32768.f;  // examples/encoder_example.c:197-202
-            else x = (float)src[k * ch + c];
-          }
-          v[k] = x;
-        }
-        ((float4 *)(row + (long)c * cs + head))[q - hq] = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    } else {
-      const long f0 = (quads << 2) + ((q - hq - quads) << 2);
-      for (int c = 0; c < ch; c++) ((float4 *)(row + (long)c * cs + head + f0))[0] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  // a fresh detector state per stream (all-zero == a stream's start, include/vorbis_amd.h)
-  const long words = nstreams * (long)(sizeof(vamd_envelope_state) / 4);
-  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < words; t += (long)gridDim.x * blockDim.x) ((uint32_t *)states)[t] = 0u;
-}
-
-// ---- the live feed (vamd_feed_create_live): continuing streams, their state on the device between groups ----
-// A live lane keeps every stream in one of two buffers [stream][channel][cs], swapped each group: a stream's samples from
-// where the reference's buffer begins (walk_rebase) on, then the group's piece, then zeroes (the end-of-stream padding's
-// room and the detector's reads).  Per stream and group, built by the lane's host mirror:
-struct LiveIn {
-  int64_t first, frames;  // the piece: its first frame in the arena, its frames
-  int64_t keep, shift;    // samples carried over from the other buffer, taken from sample `shift` of it on
-  int64_t origin;         // the stream's position (head room included) of buffer sample 0: granule positions go on from it
-  int64_t eof;            // a closing stream: its end in buffer coordinates; else LIVE_OPEN
-  int32_t fresh, close;   // the stream starts / ends in this group
-};
-#define LIVE_OPEN (1LL << 60)
-#define LIVE_NO_NAN (~0ull)
-
-// a fresh stream's states: the detector's (all zero), the ampmax chain's, the bitrate manager's (a copy of `tmpl`), no
-// non-finite sample yet.  A stream that goes on keeps all of them.
-__global__ void k_live_begin(long nstreams, const LiveIn *__restrict__ li, vamd_envelope_state *__restrict__ states,
-                             float *__restrict__ amp, vamd_bitrate_state *__restrict__ bst, const vamd_bitrate_state *__restrict__ tmpl,
-                             unsigned long long *__restrict__ nan) {
-  const long words = (long)(sizeof(vamd_envelope_state) / 4);
-  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < nstreams * words; t += (long)gridDim.x * blockDim.x) {
-    const long s = t / words;
-    if (!li[s].fresh) continue;
-    ((uint32_t *)states)[t] = 0u;
-    if (t - s * words == 0) {
-      amp[s] = VAMD_AMPMAX_FLOOR;
-      if (bst) bst[s] = *tmpl;
-      nan[s] = LIVE_NO_NAN;
-    }
-  }
-}
-
-// the group's buffer, a thread per four samples of every channel of a stream (one 16-byte store per channel): the kept
-// samples out of the other buffer (a fresh stream: the zeroed head room), the piece behind them (x / 32768.f for 16-bit
-// input, examples/encoder_example.c:197-202), zeroes up to `room` samples past the piece.  Float input: the first
-// non-finite sample of each stream is recorded (absolute position, nan[]).  A stream whose samples would not fit its
-// buffer is left alone and flagged in *status (the lane reports it; never written past the buffer).
-template <typename T>
-__global__ void k_live_ingest(const T *__restrict__ in, int ch, long nstreams, long quads, int room, const LiveIn *__restrict__ li,
-                              const float *__restrict__ old, float *__restrict__ pcm, long ss, long cs,
-                              unsigned long long *__restrict__ nan, int *__restrict__ status) {
-  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < nstreams * quads; t += (long)gridDim.x * blockDim.x) {
-    const long s = t / quads, p0 = (t - s * quads) << 2;
-    const LiveIn L = li[s];
-    const long data = L.keep + L.frames, end = data + room < cs ? data + room : cs;
-    if (data + room > cs || L.keep < 0 || L.shift < 0 || L.shift + L.keep > cs) {
-      if (p0 == 0) *(volatile int *)status = 1;  // (host memory, mapped: a plain store)
-      continue;
-    }
-    if (p0 >= end) continue;
-    for (int c = 0; c < ch; c++) {
-      float v[4];
-      bool bad = false;
-      long badp = 0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const long p = p0 + k;
-        float x = 0.f;
-        if (p < L.keep) {
-          if (!L.fresh) x = old[s * ss + (long)c * cs + L.shift + p];
-        } else if (p < data) {
-          const T y = in[(L.first + p - L.keep) * ch + c];
-          if (sizeof(T) == 2) x = (float)(int)y / 32768.f;
-          else {
-            x = (float)y;
-            if (!bad && (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) bad = true, badp = p;
-          }
-        }
-        v[k] = x;
-      }
-      ((float4 *)(pcm + s * ss + (long)c * cs))[p0 >> 2] = make_float4(v[0], v[1], v[2], v[3]);
-      if (bad) atomicMin(nan + s, (unsigned long long)(L.origin + badp));
-    }
-  }
-}
-
-// what a live group adds to a packet's record: its granule position goes on from the stream's origin, e_o_s only where the
-// stream closes, and from the block that holds a stream's first non-finite sample on no packet (VAMD_STATUS_NONFINITE)
-struct FeedLive {
-  const LiveIn *in;
-  const unsigned long long *nan;
-};
-__device__ __forceinline__ unsigned live_status(const FeedLive &V, long s, int64_t begin, int bs) {
-  return V.in && (unsigned long long)(V.in[s].origin + begin + bs) > V.nan[s] ? VAMD_STATUS_NONFINITE : 0u;
-}
-
-struct FeedPlan {  // what the packing kernels need of a vamd_stream_plan and of the analysis' outputs
-  const int32_t *order;
-  const int64_t *stream_start;
-  const int64_t *src[2];
-  const int32_t *bits[2];
-  const uint8_t *status[2];
-  const uint8_t *packets[2];
-  int64_t stride[2];
-  int bs[2];
-  int ch;
-  int64_t stream_stride, eof;  // eof: first sample past the stream's real ones, in its buffer's coordinates
-  const long long *frames_of;  // streams of unequal length: eof = head + frames_of[s]
-  int head;
-  FeedLive live;               // a live group's streams (in == null: whole streams)
-};
-
-// a wave per stream: rel[k] = bytes (each packet rounded up to 4) of the stream's packets before packet k
-__global__ __launch_bounds__(64) void k_feed_sizes(FeedPlan P, long nstreams, int64_t *__restrict__ rel, int64_t *__restrict__ stream_bytes) {
-  const long s = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int64_t k0 = P.stream_start[s], k1 = P.stream_start[s + 1];
-  int64_t run = 0;
-  for (int64_t base = k0; base < k1; base += 64) {
-    const int64_t k = base + lane;
-    int bytes = 0;
-    if (k < k1) {
-      const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
-      unsigned st = 0;
-      for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
-      st |= live_status(P.live, s, P.src[W][i] - s * P.stream_stride, P.bs[W]);
-      bytes = st ? 0 : (((P.bits[W][i] + 7) >> 3) + 3) & ~3;
-    }
-    int incl = bytes;  // inclusive scan over the wave
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    if (k < k1) rel[k] = run + incl - bytes;
-    run += __shfl(incl, 63, 64);
-  }
-  if (lane == 0) stream_bytes[s] = run;
-}
-
-// one workgroup: stream_off[s] = bytes of all streams before s; stream_off[nstreams] = the total
-__global__ __launch_bounds__(1024) void k_feed_scan(long nstreams, const int64_t *__restrict__ stream_bytes, int64_t *__restrict__ stream_off) {
-  __shared__ int64_t part[1024];
-  const int t = threadIdx.x;
-  const long per = (nstreams + 1023) / 1024, lo = (long)t * per, hi = lo + per < nstreams ? lo + per : nstreams;
-  int64_t sum = 0;
-  for (long s = lo; s < hi; s++) sum += stream_bytes[s];
-  part[t] = sum;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const int64_t v = t >= d ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int64_t run = part[t] - sum;
-  for (long s = lo; s < hi; s++) {
-    stream_off[s] = run;
-    run += stream_bytes[s];
-  }
-  if (t == 1023) stream_off[nstreams] = part[1023];
-}
-
-// a wave per packet: its words into the output arena (host memory, mapped), its record beside them
-struct FeedOut {
-  int64_t *stream_start, *offset, *granulepos, *total;
-  int32_t *bits;
-  uint8_t *info, *bytes;
-  int64_t cap;  // bytes the arena holds
-  // an Ogg feed (m_bytes set): the device mirror of the arena and of the records, which the pager reads (k_ogg.h)
-  uint8_t *m_bytes, *m_info;
-  int64_t *m_off, *m_gp;
-  int32_t *m_bits;
-};
-__global__ __launch_bounds__(256) void k_feed_copy(FeedPlan P, long nstreams, long nblocks, const int64_t *__restrict__ rel,
-                                                   const int64_t *__restrict__ stream_off, const int32_t *__restrict__ sid,
-                                                   FeedOut O) {
-  const long k = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (k == 0 && lane == 0) *O.total = stream_off[nstreams];
-  if (k <= nstreams && lane == 1) O.stream_start[k] = P.stream_start[k];  // (nstreams + 1 <= nblocks + 1 entries; see the launch)
-  if (k >= nblocks) return;
-  const int s = sid[k];
-  const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
-  unsigned st = 0;
-  for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
-  st |= live_status(P.live, s, P.src[W][i] - (int64_t)s * P.stream_stride, P.bs[W]);
-  const int bits = P.bits[W][i], words = st ? 0 : (((bits + 7) >> 3) + 3) >> 2;
-  const int64_t off = stream_off[s] + rel[k];
-  const bool fits = off + 4 * (int64_t)words <= O.cap;
-  if (fits) {
-    const uint32_t *src = (const uint32_t *)(P.packets[W] + (int64_t)i * P.stride[W]);
-    uint32_t *dst = (uint32_t *)(O.bytes + off);
-    uint32_t *mir = O.m_bytes ? (uint32_t *)(O.m_bytes + off) : nullptr;
-    for (int w = lane; w < words; w += 64) {
-      const uint32_t v = src[w];
-      dst[w] = v;
-      if (mir) mir[w] = v;
-    }
-  }
-  if (lane == 0) {
-    const int64_t begin = P.src[W][i] - (int64_t)s * P.stream_stride, center = begin + P.bs[W] / 2;
-    const bool last = k + 1 == P.stream_start[s + 1] && (!P.live.in || P.live.in[s].close);
-    O.offset[k] = off;
-    O.bits[k] = st ? -1 : bits;
-    const int64_t eof = P.live.in ? P.live.in[s].eof : (P.frames_of ? (int64_t)P.head + P.frames_of[s] : P.eof);
-    const int64_t gp = (center < eof ? center : eof) - P.bs[1] / 2 + (P.live.in ? P.live.in[s].origin : 0);
-    const uint8_t info = (uint8_t)(W | (last ? 2 : 0) | ((st & 3) << 2));
-    O.granulepos[k] = gp;
-    O.info[k] = info;
-    if (O.m_bytes) O.m_off[k] = off, O.m_bits[k] = st ? -1 : bits, O.m_gp[k] = gp, O.m_info[k] = info;
-  }
-}
-
-// sid[k] = the stream packet k belongs to (a wave per stream)
-__global__ __launch_bounds__(64) void k_feed_sid(const int64_t *__restrict__ stream_start, int32_t *__restrict__ sid) {
-  const long s = blockIdx.x;
-  for (int64_t k = stream_start[s] + threadIdx.x; k < stream_start[s + 1]; k += 64) sid[k] = (int32_t)s;
-}
-
-// ---- bitrate-managed setups: a slice of the group's blocks at a time (run_group_managed) ----
-// What the two kernels below need of a slice: its blocks in stream order (order[] rebased to the slice's own batches,
-// stream_start over the slice's pieces of streams), the walk's choice / final_bits, the candidates' rows and bit counts
-// -- and of the group: the plan's stream_start, src and the streams' lengths, for the records.
-struct FeedSlice {
-  const int32_t *order;          // [slice blocks] W << 30 | index in the slice's batch of class W
-  const int64_t *stream_start;   // [slice streams + 1] into order[]
-  const int64_t *g_start;        // the plan's stream_start (whole group)
-  const int64_t *src[2];         // the plan's src[W] (whole group)
-  const int32_t *choice[2], *fbits[2], *mbits[2];  // [slice batch] / [slice batch][15]
-  const uint8_t *status[2];
-  const uint8_t *packets[2];     // [slice batch][15][stride]
-  int64_t stride[2];
-  int64_t i0[2];                 // the slice's first block of class W in the plan's batches
-  int64_t k0;                    // ... and its first block in the plan's order[]
-  long s0;                       // the group stream of the slice's first stream
-  int bs[2];
-  int ch;
-  int64_t stream_stride, eof;
-  const long long *frames_of;
-  int head;
-  FeedLive live;
-};
-
-// a wave per slice stream: rel[k] = bytes (each handed-out packet rounded up to 4) of the slice stream's packets before k
-__global__ __launch_bounds__(64) void k_feed_sizes_managed(FeedSlice P, int64_t *__restrict__ rel, int64_t *__restrict__ stream_bytes) {
-  const long s = blockIdx.x;
-  const int lane = threadIdx.x;
-  const int64_t k0 = P.stream_start[s], k1 = P.stream_start[s + 1];
-  int64_t run = 0;
-  for (int64_t base = k0; base < k1; base += 64) {
-    const int64_t k = base + lane;
-    int bytes = 0;
-    if (k < k1) {
-      const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
-      unsigned st = 0;
-      for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
-      const long gs = P.s0 + s;
-      st |= live_status(P.live, gs, P.src[W][P.i0[W] + i] - gs * P.stream_stride, P.bs[W]);
-      bytes = st ? 0 : (((P.fbits[W][i] + 7) >> 3) + 3) & ~3;
-    }
-    int incl = bytes;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    if (k < k1) rel[k] = run + incl - bytes;
-    run += __shfl(incl, 63, 64);
-  }
-  if (lane == 0) stream_bytes[s] = run;
-}
-
-// a wave per packet of the slice: the chosen candidate's first bytes, zero bytes behind them up to the handed-out size
-// (the manager's padding) and to the next multiple of 4, into the output arena at base + stream_off + rel; the record of
-// the packet at its place in the group (k0 + k)
-__global__ __launch_bounds__(256) void k_feed_copy_managed(FeedSlice P, long nblocks, int64_t base, const int64_t *__restrict__ rel,
-                                                           const int64_t *__restrict__ stream_off, const int32_t *__restrict__ sid,
-                                                           FeedOut O) {
-  const long k = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (k >= nblocks) return;
-  const int ls = sid[k];
-  const long s = P.s0 + ls;
-  const int o = P.order[k], W = (o >> 30) & 1, i = o & 0x3fffffff;
-  unsigned st = 0;
-  for (int c = 0; c < P.ch; c++) st |= P.status[W][(int64_t)i * P.ch + c];
-  st |= live_status(P.live, s, P.src[W][P.i0[W] + i] - s * P.stream_stride, P.bs[W]);
-  const int choice = P.choice[W][i], fbits = P.fbits[W][i];
-  const int64_t fb = st ? 0 : ((int64_t)fbits + 7) >> 3;
-  int64_t own = st ? 0 : ((int64_t)P.mbits[W][(int64_t)i * VAMD_PACKETBLOBS + choice] + 7) >> 3;
-  if (own > P.stride[W]) own = P.stride[W];
-  const int64_t keep = own < fb ? own : fb, words = (fb + 3) >> 2;
-  const int64_t off = base + stream_off[ls] + rel[k];
-  if (off + 4 * words <= O.cap) {
-    const uint8_t *row = P.packets[W] + ((int64_t)i * VAMD_PACKETBLOBS + choice) * P.stride[W];
-    uint32_t *dst = (uint32_t *)(O.bytes + off);
-    uint32_t *mir = O.m_bytes ? (uint32_t *)(O.m_bytes + off) : nullptr;
-    for (int64_t w = lane; w < words; w += 64) {
-      uint32_t v = 0;
-      if (4 * w < keep) {
-        v = ((const uint32_t *)row)[w];
-        const int64_t live = keep - 4 * w;  // bytes of this word that are the candidate's
-        if (live < 4) v &= (1u << (8 * live)) - 1u;
-      }
-      dst[w] = v;
-      if (mir) mir[w] = v;
-    }
-  }
-  if (lane == 0) {
-    const int64_t g = P.k0 + k, gi = P.i0[W] + i;
-    const int64_t begin = P.src[W][gi] - (int64_t)s * P.stream_stride, center = begin + P.bs[W] / 2;
-    const bool last = g + 1 == P.g_start[s + 1] && (!P.live.in || P.live.in[s].close);
-    O.offset[g] = off;
-    O.bits[g] = st ? -1 : fbits;
-    const int64_t eof = P.live.in ? P.live.in[s].eof : (P.frames_of ? (int64_t)P.head + P.frames_of[s] : P.eof);
-    const int64_t gp = (center < eof ? center : eof) - P.bs[1] / 2 + (P.live.in ? P.live.in[s].origin : 0);
-    const uint8_t info = (uint8_t)(W | (last ? 2 : 0) | ((st & 3) << 2) | ((st ? 0 : choice) << 4));
-    O.granulepos[g] = gp;
-    O.info[g] = info;
-    if (O.m_bytes) O.m_off[g] = off, O.m_bits[g] = st ? -1 : fbits, O.m_gp[g] = gp, O.m_info[g] = info;
-  }
-}
-
-struct Buf {
+// A buffer that says where it lives -- HBM, or pinned host memory (what the copy engine reads and what the kernels write
+// across the link) -- and frees itself: a lane's buffers go with the lane (~FeedLane), each exactly once.
+template <bool pinned>
+struct BufIn {
   void *p = nullptr;
   size_t bytes = 0;
-  bool host = false;
+  BufIn() = default;
+  BufIn(const BufIn &) = delete;
+  BufIn &operator=(const BufIn &) = delete;
+  ~BufIn() { drop(); }
+  static hipError_t take(void **q, size_t n) { return pinned ? hipHostMalloc(q, n, hipHostMallocDefault) : hipMalloc(q, n); }
+  void drop() {
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr, bytes = 0;
+  }
+  void adopt(void *q, size_t n) { drop(), p = q, bytes = n; }
+  // at least n bytes; what it held is gone when it has to grow
   hipError_t need(size_t n) {
     if (bytes >= n) return hipSuccess;
-    if (p) (void)(host ? hipHostFree(p) : hipFree(p));
-    p = nullptr, bytes = 0;
-    const hipError_t e = host ? hipHostMalloc(&p, n, hipHostMallocDefault) : hipMalloc(&p, n);
+    drop();
+    const hipError_t e = take(&p, n);
     if (e == hipSuccess) bytes = n;
     return e;
   }
-  void drop() {
-    if (p) (void)(host ? hipHostFree(p) : hipFree(p));
-    p = nullptr, bytes = 0;
-  }
   // pinned host memory only: at least n bytes, the first `keep` kept
   hipError_t grow_keeping(size_t n, size_t keep) {
+    static_assert(pinned, "the host copies what is kept");
     if (bytes >= n) return hipSuccess;
     void *q = nullptr;
-    const hipError_t e = hipHostMalloc(&q, n, hipHostMallocDefault);
+    const hipError_t e = take(&q, n);
     if (e != hipSuccess) return e;
     if (p && keep) memcpy(q, p, keep < bytes ? keep : bytes);
-    drop();
-    p = q, bytes = n;
+    adopt(q, n);
     return hipSuccess;
   }
 };
+using Buf = BufIn<false>;     // HBM
+using Pinned = BufIn<true>;   // pinned host memory
 
 }  // namespace
 
@@ -435,17 +90,21 @@ struct FeedLane {
   vamd_ctx *ctx = nullptr;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev_up = nullptr, ev_end = nullptr;
-  Buf h_in, h_out, h_rec;                      // pinned: the group's samples; its packets; their records
+  Pinned h_in, h_out, h_rec;                   // the group's samples; its packets; their records
   Buf d_in, d_pcm, d_states, d_amp;            // HBM: the samples as they came; as floats, planar; detector states; ampmax chains
   Buf d_pk[2], d_bits[2], d_status[2];         // the analysis' packet rows per size class
-  Buf d_rel, d_sid, d_sbytes, d_soff, d_len, h_len;  // (d_len / h_len: [frames_of | first_of] of a group of unequal streams)
+  Buf d_rel, d_sid, d_sbytes, d_soff, d_len;   // (d_len: [frames_of | first_of] of a group of unequal streams: h_len's copy)
+  Pinned h_len;
   // bitrate-managed setups (run_group_managed): a slice's fifteen candidates per block and what the analysis needs beside
-  // them, the walk's answers, the managers' states, the slices' rebased lists (h_slice pinned, d_slice its copy)
+  // them, the walk's answers, the managers' states, the slices' rebased lists (d_slice: h_slice's copy)
   Buf d_mpk[2], d_mbits[2], d_mposts[2], d_mvalid[2], d_miwork[2], d_mnz[2], d_choice[2], d_fbits[2];
-  Buf d_bstate, d_slice, h_slice;
+  Buf d_bstate, d_slice;
+  Pinned h_slice;
   // a live feed (run_group_live): the two stream buffers, the walks' states, the carried detector flags, the first
-  // non-finite sample per stream, the manager's fresh state; the group's LiveIn (pinned, its copy) and the host mirror
-  Buf d_buf[2], d_walk, d_rows, d_nan, d_btmpl, d_live, h_live, h_lstatus;
+  // non-finite sample per stream, the manager's fresh state; the group's LiveIn (d_live: h_live's copy), the ingest's
+  // complaint (h_lstatus) and the host mirror
+  Buf d_buf[2], d_walk, d_rows, d_nan, d_btmpl, d_live;
+  Pinned h_live, h_lstatus;
   int cur = 0;                    // the buffer that holds the streams now
   bool btmpl_ready = false;
   struct LiveStream {             // the host's mirror of one stream of the lane
@@ -457,9 +116,9 @@ struct FeedLane {
   };
   std::vector<LiveStream> live;
   // an Ogg feed (vamd_feed_ogg_headers): the device mirror of the packet arena and of the records, the header packets, the
-  // group's serial numbers, the page table and the streams' file sizes; the files (pinned) and their record (pinned)
-  Buf d_mirror, d_moff, d_mgp, d_mrbits, d_minfo, d_hdr, d_serial, h_serial, d_pages, d_fbytes, d_foff, d_npages, d_ostatus;
-  Buf h_ogg, h_orec;
+  // group's serial numbers, the page table and the streams' file sizes; the files and their record
+  Buf d_mirror, d_moff, d_mgp, d_mrbits, d_minfo, d_hdr, d_serial, d_pages, d_fbytes, d_foff, d_npages, d_ostatus;
+  Pinned h_serial, h_ogg, h_orec;
   int32_t hdr_off[3] = {0, 0, 0};
   std::vector<uint32_t> serials, user_serials;  // the job's; what vamd_feed_ogg_serials set for it
   vamd_feed_ogg_result ogg_result;
@@ -476,13 +135,25 @@ struct FeedLane {
   vamd_feed_result result;
   double t_wrote = 0.;
   long served = 0;  // groups this lane has carried (the free lane that has waited longest goes out first)
+  // The lane's end (feed_free has joined its worker): its device current, nothing of its stream in flight, the context
+  // before the buffers it was given -- which, members, free themselves behind this body, the device still current.
+  ~FeedLane() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (ctx) vamd_destroy(ctx);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev_up) (void)hipEventDestroy(ev_up);
+    if (ev_end) (void)hipEventDestroy(ev_end);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 struct vamd_feed {
-  std::vector<FeedLane> lanes;
+  std::deque<FeedLane> lanes;  // (a deque: a lane is made in place and never moved -- its worker holds its address)
   int ch = 0, bs[2] = {0, 0};
   bool managed = false;  // the blob carries a bitrate manager (vamd_setup_header.off_bitrate): run_group_managed
   long slice = 2048;     // blocks per slice of a managed group (VAMD_FEED_SLICE, a test knob)
+  long out_bytes = 0;    // > 0: a lane's packet arena to start with (VAMD_FEED_OUT_BYTES, a test knob: the arena then has to grow)
   long pkcap[2] = {0, 0};
   long max_streams = 0, max_frames = 0;
   int format = VAMD_FEED_S16;
@@ -537,8 +208,7 @@ static int feed_mirror(vamd_feed *f, FeedLane &L, FeedOut &O, long nb, size_t ke
       FEED_TRY(hipMalloc(&q, want));
       FEED_TRY(hipMemcpyAsync(q, L.d_mirror.p, keep < L.d_mirror.bytes ? keep : L.d_mirror.bytes, hipMemcpyDeviceToDevice, L.stream));
       FEED_TRY(hipStreamSynchronize(L.stream));
-      L.d_mirror.drop();
-      L.d_mirror.p = q, L.d_mirror.bytes = want;
+      L.d_mirror.adopt(q, want);
     } else {
       FEED_TRY(hipStreamSynchronize(L.stream));  // (nothing in flight reads the old one when it goes)
       FEED_TRY(L.d_mirror.need(want));
@@ -636,35 +306,87 @@ static int pager_result(vamd_feed *f, FeedLane &L, long ns) {
   return VAMD_OK;
 }
 
-// A bitrate-managed group, from its plan on: the blocks in slices of at most f->slice (in order[] order, so a slice holds
-// the end of one stream, whole streams, the start of another), each slice through
-//   vamd_analyze_streams_mixed_managed (fifteen candidate packets per block; the ampmax chains resume per stream) ->
-//   vamd_bitrate_walk (the managers resume per stream) -> the handed-out packets laid end to end behind the previous
-//   slice's, straight into the pinned arena
-// The workspace is bounded by the slice, not the group: a long stereo block's candidates alone take 15 x its integer
-// residue (120 KB) and 15 packet rows.  The host waits once per slice for the slice's byte count (to grow the arena
-// before anything is written into it: the candidates do not outlive their slice).
-// (live: `live` set, ns streams planned of which the caller's first ns_out are reported; the managers carried across groups)
-static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, const float *pcm, long ns, long ss, long cs,
-                             const long long *d_frames_of, FeedLive live, long ns_out) {
-  const long frames = L.frames;
-  const int ch = f->ch, head = f->bs[1] / 2;
-  const long nb = (long)(plan.nblocks[0] + plan.nblocks[1]);
-  hipStream_t st = L.stream;
-  std::vector<int32_t> order((size_t)(nb ? nb : 1));
-  std::vector<int64_t> start((size_t)ns + 1);
-  FEED_CALL(vamd_plan_fetch(L.ctx, &plan, nullptr, nullptr, nullptr, nullptr, order.data(), start.data()));
-  // the slices: [k0, k1) of order[], their first stream, their classes' first blocks and counts, order[] rebased to the
-  // slice's batches and stream_start over the slice's pieces of streams -- all slices' lists in one upload
-  struct Slice {
-    long k0, k1, s0, s1;  // s1: one past the slice's last stream
-    int64_t i0[2], n[2];
-    size_t starts;        // where its stream_start lies in the uploaded lists (int64 units, behind the rebased order[])
-  };
+// ---- what the two group paths share: the group's record, a size class's batch, the run the hand-over kernels take ----
+// The group's record in pinned memory, which the copy kernels write and vamd_feed_packets hands out:
+// [total | stream_start (ns + 1) | offset (nb) | granulepos (nb) | bits (nb) | info (nb)]
+struct RecLayout {
+  size_t start, offset, granulepos, bits, info, bytes;
+  RecLayout(long ns, long nb) {
+    start = 8, offset = start + (size_t)(ns + 1) * 8, granulepos = offset + (size_t)nb * 8, bits = granulepos + (size_t)nb * 8;
+    info = bits + (size_t)nb * 4, bytes = al(info + (size_t)nb, 16);
+  }
+};
+
+// where a copy kernel writes: the record and the packet arena as the device sees them, and the Ogg mirror (feed_mirror;
+// the first `keep` bytes of the mirror are a managed group's earlier slices)
+static int feed_out(vamd_feed *f, FeedLane &L, const RecLayout &R, long nb, size_t keep, FeedOut &O) {
+  void *drec = nullptr, *dbytes = nullptr;
+  FEED_TRY(hipHostGetDevicePointer(&drec, L.h_rec.p, 0));
+  FEED_TRY(hipHostGetDevicePointer(&dbytes, L.h_out.p, 0));
+  uint8_t *dr = (uint8_t *)drec;
+  O.total = (int64_t *)dr, O.stream_start = (int64_t *)(dr + R.start), O.offset = (int64_t *)(dr + R.offset);
+  O.granulepos = (int64_t *)(dr + R.granulepos), O.bits = (int32_t *)(dr + R.bits), O.info = dr + R.info;
+  O.bytes = (uint8_t *)dbytes, O.cap = (int64_t)L.h_out.bytes;
+  return feed_mirror(f, L, O, nb, keep);
+}
+
+// ... and behind the group's wait: what vamd_feed_packets hands out, and the two timings
+static void feed_result(FeedLane &L, const RecLayout &R, long ns_out, long nb, int64_t total) {
+  const uint8_t *hrec = (const uint8_t *)L.h_rec.p;
+  vamd_feed_result &out = L.result;
+  out.nstreams = ns_out, out.nblocks = nb;
+  out.stream_start = (const int64_t *)(hrec + R.start), out.offset = (const int64_t *)(hrec + R.offset);
+  out.granulepos = (const int64_t *)(hrec + R.granulepos), out.bits = (const int32_t *)(hrec + R.bits), out.info = hrec + R.info;
+  out.bytes = (const uint8_t *)L.h_out.p, out.total_bytes = total;
+  float up = 0.f, dev = 0.f;
+  (void)hipEventElapsedTime(&up, L.ev0, L.ev_up);
+  (void)hipEventElapsedTime(&dev, L.ev0, L.ev_end);
+  out.upload_ms = up, out.device_ms = dev;
+}
+
+// the analysis' batch of size class W: blocks [i0, i0 + n) of the plan's, read where they lie in pcm
+static void batch_of(const vamd_stream_plan &plan, int W, int64_t i0, int64_t n, const float *pcm, long cs, Buf &status,
+                     vamd_batch_desc &desc, vamd_batch_io &io) {
+  memset(&desc, 0, sizeof(desc));
+  memset(&io, 0, sizeof(io));
+  desc.W = W;
+  desc.nblocks = (long)n;
+  desc.lW = plan.lW[W] + i0, desc.nW = plan.nW[W] + i0, desc.blocktype = plan.blocktype[W] + i0;
+  if (!n) return;
+  io.pcm = pcm;
+  io.pcm_src = plan.src[W] + i0;
+  io.pcm_channel_stride = cs;
+  io.status = (uint8_t *)status.p;
+}
+
+// the group's part of a FeedSlice (k_feed.h); the run's own lists, rows and place in the group are its caller's
+static FeedSlice feed_slice_of(vamd_feed *f, const FeedLane &L, const vamd_stream_plan &plan, long ss, const long long *d_frames_of,
+                               FeedLive live) {
+  FeedSlice P;
+  memset(&P, 0, sizeof(P));
+  const int head = f->bs[1] / 2;
+  P.g_start = plan.stream_start;
+  for (int W = 0; W < 2; W++) P.src[W] = plan.src[W], P.status[W] = (const uint8_t *)L.d_status[W].p, P.stride[W] = f->pkcap[W], P.bs[W] = f->bs[W];
+  P.ch = f->ch, P.stream_stride = ss, P.eof = head + L.frames, P.frames_of = d_frames_of, P.head = head;
+  P.live = live;
+  return P;
+}
+
+// ---- a bitrate-managed group ----
+struct Slice {
+  long k0, k1, s0, s1;  // [k0, k1) of order[]; its first stream, and one past its last
+  int64_t i0[2], n[2];  // its classes' first blocks in the plan's batches, and their counts
+  size_t starts;        // where its stream_start lies in `starts` (one list behind the other)
+};
+
+// The slices of a group of nb = order.size() blocks in ns streams (start[]), at most S blocks each, in order[] order -- so a
+// slice holds the end of one stream, whole streams, the start of another.  order[] is rebased in place to each slice's own
+// batches; starts receives every slice's stream_start over its pieces of streams, relative to its first block.  Host
+// arithmetic only.  *why set: the plan is not what the slices rely on.
+static std::vector<Slice> plan_slices(std::vector<int32_t> &order, const std::vector<int64_t> &start, long ns, long nb, long S,
+                                      std::vector<int64_t> &starts, const char **why) {
   std::vector<Slice> sl;
-  const long S = f->slice;
-  int64_t seen[2] = {0, 0}, most[2] = {0, 0};
-  size_t nstarts = 0;
+  int64_t seen[2] = {0, 0};
   long s = 0;
   for (long k0 = 0; k0 < nb; k0 += S) {
     Slice x;
@@ -677,39 +399,62 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
     for (long k = x.k0; k < x.k1; k++) {
       const int o = order[(size_t)k], W = (o >> 30) & 1, i = o & 0x3fffffff;
       if (i != seen[W]) {  // (the plan numbers each class's blocks in stream order: vamd_plan_streams)
-        L.err = "stream plan: a size class's blocks are not numbered in stream order";
-        return VAMD_EFAULT;
+        *why = "stream plan: a size class's blocks are not numbered in stream order";
+        return sl;
       }
       seen[W]++;
       order[(size_t)k] = (W << 30) | (int)(i - x.i0[W]);
     }
-    for (int W = 0; W < 2; W++) {
-      x.n[W] = seen[W] - x.i0[W];
-      if (x.n[W] > most[W]) most[W] = x.n[W];
-    }
-    x.starts = nstarts;
-    nstarts += (size_t)(x.s1 - x.s0) + 1;
-    sl.push_back(x);
-  }
-  const size_t lists = al((size_t)(nb ? nb : 1) * 4, 8) + nstarts * 8;
-  FEED_TRY(L.h_slice.need(lists + 16));
-  FEED_TRY(L.d_slice.need(lists + 16));
-  int64_t *h_total = (int64_t *)L.h_slice.p;  // [0]: the slice's byte count on its way back
-  uint8_t *hl = (uint8_t *)L.h_slice.p + 16, *dl = (uint8_t *)L.d_slice.p + 16;
-  memcpy(hl, order.data(), (size_t)nb * 4);
-  int64_t *hs = (int64_t *)(hl + al((size_t)(nb ? nb : 1) * 4, 8));
-  for (const Slice &x : sl)
+    for (int W = 0; W < 2; W++) x.n[W] = seen[W] - x.i0[W];
+    x.starts = starts.size();
     for (long j = x.s0; j <= x.s1; j++) {
       const int64_t a = j == x.s0 ? x.k0 : (j == x.s1 ? x.k1 : start[(size_t)j]);
-      hs[x.starts + (size_t)(j - x.s0)] = (a < x.k0 ? x.k0 : (a > x.k1 ? x.k1 : a)) - x.k0;
+      starts.push_back((a < x.k0 ? x.k0 : (a > x.k1 ? x.k1 : a)) - x.k0);
     }
+    sl.push_back(x);
+  }
+  return sl;
+}
+
+// A bitrate-managed group, from its plan on: the blocks in slices of at most f->slice (plan_slices), each slice through
+//   vamd_analyze_streams_mixed_managed (fifteen candidate packets per block; the ampmax chains resume per stream) ->
+//   vamd_bitrate_walk (the managers resume per stream) -> the handed-out packets laid end to end behind the previous
+//   slice's, straight into the pinned arena
+// The workspace is bounded by the slice, not the group: a long stereo block's candidates alone take 15 x its integer
+// residue (120 KB) and 15 packet rows.  The host waits once per slice for the slice's byte count (to grow the arena
+// before anything is written into it: the candidates do not outlive their slice).
+// (live: `live` set, ns streams planned of which the caller's first ns_out are reported; the managers carried across groups)
+static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, const float *pcm, long ns, long ss, long cs,
+                             const long long *d_frames_of, FeedLive live, long ns_out) {
+  const int ch = f->ch;
+  const long nb = (long)(plan.nblocks[0] + plan.nblocks[1]);
+  hipStream_t st = L.stream;
+  std::vector<int32_t> order((size_t)(nb ? nb : 1));
+  std::vector<int64_t> start((size_t)ns + 1), starts;
+  FEED_CALL(vamd_plan_fetch(L.ctx, &plan, nullptr, nullptr, nullptr, nullptr, order.data(), start.data()));
+  const char *why = nullptr;
+  const std::vector<Slice> sl = plan_slices(order, start, ns, nb, f->slice, starts, &why);
+  if (why) {
+    L.err = why;
+    return VAMD_EFAULT;
+  }
+  // all slices' lists in one upload: [the slice's byte count on its way back (16) | order[] rebased | the stream_starts]
+  const size_t order_bytes = al((size_t)(nb ? nb : 1) * 4, 8), lists = order_bytes + starts.size() * 8;
+  FEED_TRY(L.h_slice.need(lists + 16));
+  FEED_TRY(L.d_slice.need(lists + 16));
+  int64_t *h_total = (int64_t *)L.h_slice.p;
+  uint8_t *hl = (uint8_t *)L.h_slice.p + 16, *dl = (uint8_t *)L.d_slice.p + 16;
+  memcpy(hl, order.data(), (size_t)nb * 4);
+  memcpy(hl + order_bytes, starts.data(), starts.size() * 8);
   FEED_TRY(hipMemcpyAsync(dl, hl, lists, hipMemcpyHostToDevice, st));
   const int32_t *d_order = (const int32_t *)dl;
-  const int64_t *d_starts = (const int64_t *)(dl + al((size_t)(nb ? nb : 1) * 4, 8));
+  const int64_t *d_starts = (const int64_t *)(dl + order_bytes);
   // the slice's buffers, sized for the largest slice of each class
   const int K = VAMD_PACKETBLOBS;
   for (int W = 0; W < 2; W++) {
-    const size_t m = (size_t)(most[W] ? most[W] : 1), n2 = (size_t)f->bs[W] / 2;
+    int64_t most = 1;
+    for (const Slice &x : sl) most = x.n[W] > most ? x.n[W] : most;
+    const size_t m = (size_t)most, n2 = (size_t)f->bs[W] / 2;
     FEED_TRY(L.d_mpk[W].need(m * K * (size_t)f->pkcap[W]));
     FEED_TRY(L.d_mbits[W].need(m * K * 4));
     FEED_TRY(L.d_mposts[W].need(m * K * ch * VAMD_POSTS_STRIDE * 4));
@@ -720,7 +465,7 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
     FEED_TRY(L.d_choice[W].need(m * 4));
     FEED_TRY(L.d_fbits[W].need(m * 4));
   }
-  const size_t most_slice = (size_t)(S < nb ? S : (nb ? nb : 1));
+  const size_t most_slice = (size_t)(f->slice < nb ? f->slice : (nb ? nb : 1));
   FEED_TRY(L.d_rel.need(most_slice * 8));
   FEED_TRY(L.d_sid.need(most_slice * 4));
   FEED_TRY(L.d_sbytes.need((size_t)ns * 8));
@@ -729,31 +474,26 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
     FEED_TRY(L.d_bstate.need((size_t)ns * sizeof(vamd_bitrate_state)));
     FEED_CALL(vamd_bitrate_init_states(L.ctx, (vamd_bitrate_state *)L.d_bstate.p, ns));
   }
-  // records: [total | stream_start (ns + 1) | offset (nb) | granulepos (nb) | bits (nb) | info (nb)], as run_group's
-  const size_t o_start = 8, o_off = o_start + (size_t)(ns + 1) * 8, o_gp = o_off + (size_t)nb * 8, o_bits = o_gp + (size_t)nb * 8,
-               o_info = o_bits + (size_t)nb * 4, rec_bytes = al(o_info + (size_t)nb, 16);
-  FEED_TRY(L.h_rec.need(rec_bytes + rec_bytes / 4));
-  uint8_t *hrec = (uint8_t *)L.h_rec.p;
-  void *drec = nullptr;
-  FEED_TRY(hipHostGetDevicePointer(&drec, hrec, 0));
+  const RecLayout R(ns, nb);
+  FEED_TRY(L.h_rec.need(R.bytes + R.bytes / 4));
+  FeedSlice P = feed_slice_of(f, L, plan, ss, d_frames_of, live);
+  for (int W = 0; W < 2; W++) {
+    P.choice[W] = (const int32_t *)L.d_choice[W].p, P.fbits[W] = (const int32_t *)L.d_fbits[W].p, P.mbits[W] = (const int32_t *)L.d_mbits[W].p;
+    P.packets[W] = (const uint8_t *)L.d_mpk[W].p;
+  }
   int64_t base = 0;  // bytes of the packets laid out so far
   for (const Slice &x : sl) {
     const long nss = x.s1 - x.s0, nbs = x.k1 - x.k0;
+    P.order = d_order + x.k0, P.stream_start = d_starts + x.starts;
+    P.i0[0] = x.i0[0], P.i0[1] = x.i0[1], P.k0 = x.k0, P.s0 = x.s0;
+    // analyse: the slice's fifteen candidates per block
     vamd_batch_desc desc[2];
     vamd_batch_io io[2];
     vamd_managed_io m[2];
     for (int W = 0; W < 2; W++) {
-      memset(&desc[W], 0, sizeof(desc[W]));
-      memset(&io[W], 0, sizeof(io[W]));
+      batch_of(plan, W, x.i0[W], x.n[W], pcm, cs, L.d_status[W], desc[W], io[W]);
       memset(&m[W], 0, sizeof(m[W]));
-      desc[W].W = W;
-      desc[W].nblocks = (long)x.n[W];
       if (!x.n[W]) continue;
-      desc[W].lW = plan.lW[W] + x.i0[W], desc[W].nW = plan.nW[W] + x.i0[W], desc[W].blocktype = plan.blocktype[W] + x.i0[W];
-      io[W].pcm = pcm;
-      io[W].pcm_src = plan.src[W] + x.i0[W];
-      io[W].pcm_channel_stride = cs;
-      io[W].status = (uint8_t *)L.d_status[W].p;
       m[W].posts = (int32_t *)L.d_mposts[W].p;
       m[W].post_valid = (int32_t *)L.d_mvalid[W].p;
       m[W].iwork = (int32_t *)L.d_miwork[W].p;
@@ -762,39 +502,24 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
       m[W].packet_bits = (int32_t *)L.d_mbits[W].p;
       m[W].packet_stride = f->pkcap[W];
     }
-    const int32_t *o = d_order + x.k0;
-    const int64_t *ls = d_starts + x.starts;
-    FEED_CALL(vamd_analyze_streams_mixed_managed(L.ctx, &desc[0], &io[0], &m[0], &desc[1], &io[1], &m[1], o, ls, nss, nbs,
+    FEED_CALL(vamd_analyze_streams_mixed_managed(L.ctx, &desc[0], &io[0], &m[0], &desc[1], &io[1], &m[1], P.order, P.stream_start, nss, nbs,
                                                  (float *)L.d_amp.p + x.s0));
-    const int32_t *bits[2] = {(const int32_t *)L.d_mbits[0].p, (const int32_t *)L.d_mbits[1].p};
-    const uint8_t *stat[2] = {(const uint8_t *)L.d_status[0].p, (const uint8_t *)L.d_status[1].p};
+    // walk: the managers' choice and the size they hand out
     int32_t *choice[2] = {(int32_t *)L.d_choice[0].p, (int32_t *)L.d_choice[1].p};
     int32_t *fbits[2] = {(int32_t *)L.d_fbits[0].p, (int32_t *)L.d_fbits[1].p};
-    FEED_CALL(vamd_bitrate_walk(L.ctx, o, ls, nss, bits, stat, (vamd_bitrate_state *)L.d_bstate.p + x.s0, choice, fbits));
-    FeedSlice P;
-    P.order = o, P.stream_start = ls, P.g_start = plan.stream_start;
-    for (int W = 0; W < 2; W++) {
-      P.src[W] = plan.src[W], P.choice[W] = choice[W], P.fbits[W] = fbits[W], P.mbits[W] = bits[W], P.status[W] = stat[W];
-      P.packets[W] = (const uint8_t *)L.d_mpk[W].p, P.stride[W] = f->pkcap[W], P.i0[W] = x.i0[W], P.bs[W] = f->bs[W];
-    }
-    P.k0 = x.k0, P.s0 = x.s0, P.ch = ch, P.stream_stride = ss, P.eof = head + frames, P.frames_of = d_frames_of, P.head = head;
-    P.live = live;
-    hipLaunchKernelGGL(k_feed_sid, dim3((unsigned)nss), dim3(64), 0, st, ls, (int32_t *)L.d_sid.p);
-    hipLaunchKernelGGL(k_feed_sizes_managed, dim3((unsigned)nss), dim3(64), 0, st, P, (int64_t *)L.d_rel.p, (int64_t *)L.d_sbytes.p);
+    FEED_CALL(vamd_bitrate_walk(L.ctx, P.order, P.stream_start, nss, P.mbits, P.status, (vamd_bitrate_state *)L.d_bstate.p + x.s0, choice, fbits));
+    // sizes, and the wait for their sum
+    hipLaunchKernelGGL(k_feed_sid, dim3((unsigned)nss), dim3(64), 0, st, P.stream_start, (int32_t *)L.d_sid.p);
+    hipLaunchKernelGGL(k_feed_sizes, dim3((unsigned)nss), dim3(64), 0, st, P, (int64_t *)L.d_rel.p, (int64_t *)L.d_sbytes.p);
     hipLaunchKernelGGL(k_feed_scan, dim3(1), dim3(1024), 0, st, nss, (const int64_t *)L.d_sbytes.p, (int64_t *)L.d_soff.p);
     FEED_TRY(hipGetLastError());
     FEED_TRY(hipMemcpyAsync(h_total, (const int64_t *)L.d_soff.p + nss, 8, hipMemcpyDeviceToHost, st));
     FEED_TRY(hipStreamSynchronize(st));
+    // grow the arena (and the mirror) where the slice needs it, the earlier slices' packets kept; copy
     const int64_t need = base + *h_total;
     if (need > (int64_t)L.h_out.bytes) FEED_TRY(L.h_out.grow_keeping((size_t)need + (size_t)need / 8, (size_t)base));
-    void *dbytes = nullptr;
-    FEED_TRY(hipHostGetDevicePointer(&dbytes, L.h_out.p, 0));
     FeedOut O;
-    uint8_t *dr = (uint8_t *)drec;
-    O.total = (int64_t *)dr, O.stream_start = (int64_t *)(dr + o_start), O.offset = (int64_t *)(dr + o_off);
-    O.granulepos = (int64_t *)(dr + o_gp), O.bits = (int32_t *)(dr + o_bits), O.info = dr + o_info;
-    O.bytes = (uint8_t *)dbytes, O.cap = (int64_t)L.h_out.bytes;
-    FEED_OWN(feed_mirror(f, L, O, nb, (size_t)base));
+    FEED_OWN(feed_out(f, L, R, nb, (size_t)base, O));
     hipLaunchKernelGGL(k_feed_copy_managed, dim3((unsigned)((nbs + 3) / 4)), dim3(256), 0, st, P, nbs, base, (const int64_t *)L.d_rel.p,
                        (const int64_t *)L.d_soff.p, (const int32_t *)L.d_sid.p, O);
     FEED_TRY(hipGetLastError());
@@ -804,22 +529,99 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
   FEED_TRY(hipEventRecord(L.ev_end, st));
   FEED_TRY(hipEventSynchronize(L.ev_end));
   if (f->ogg) FEED_OWN(pager_result(f, L, ns));
+  uint8_t *hrec = (uint8_t *)L.h_rec.p;  // (the total and stream_start, which a VBR group's copy kernel writes, from here)
   *(int64_t *)hrec = base;
-  memcpy(hrec + o_start, start.data(), (size_t)(ns + 1) * 8);
-  vamd_feed_result &R = L.result;
-  R.nstreams = ns_out, R.nblocks = nb;
-  R.stream_start = (const int64_t *)(hrec + o_start), R.offset = (const int64_t *)(hrec + o_off);
-  R.granulepos = (const int64_t *)(hrec + o_gp), R.bits = (const int32_t *)(hrec + o_bits), R.info = hrec + o_info;
-  R.bytes = (const uint8_t *)L.h_out.p, R.total_bytes = base;
-  float up = 0.f, dev = 0.f;
-  (void)hipEventElapsedTime(&up, L.ev0, L.ev_up);
-  (void)hipEventElapsedTime(&dev, L.ev0, L.ev_end);
-  L.result.upload_ms = up, L.result.device_ms = dev;
+  memcpy(hrec + R.start, start.data(), (size_t)(ns + 1) * 8);
+  feed_result(L, R, ns_out, nb, base);
   return VAMD_OK;
 }
 
+// a group from its plan on (whole or live): the analysis, the packets end to end into the pinned arena
 static int finish_group(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, const float *pcm, long ns, long ss, long cs,
-                        const long long *d_frames_of, FeedLive live, long ns_out);
+                        const long long *d_frames_of, FeedLive live, long ns_out) {
+  hipStream_t st = L.stream;
+  if (f->managed) return run_group_managed(f, L, plan, pcm, ns, ss, cs, d_frames_of, live, ns_out);
+  const long nb = (long)(plan.nblocks[0] + plan.nblocks[1]);
+  vamd_batch_desc desc[2];
+  vamd_batch_io io[2];
+  for (int W = 0; W < 2; W++) {
+    const size_t n = (size_t)plan.nblocks[W];
+    FEED_TRY(L.d_pk[W].need((n ? n : 1) * (size_t)f->pkcap[W]));
+    FEED_TRY(L.d_bits[W].need((n ? n : 1) * 4));
+    FEED_TRY(L.d_status[W].need((n ? n : 1) * (size_t)f->ch));
+    batch_of(plan, W, 0, plan.nblocks[W], pcm, cs, L.d_status[W], desc[W], io[W]);
+    if (!n) continue;
+    io[W].packets = (uint8_t *)L.d_pk[W].p;
+    io[W].packet_bits = (int32_t *)L.d_bits[W].p;
+    io[W].packet_stride = f->pkcap[W];
+  }
+  if (nb)
+    FEED_CALL(vamd_analyze_streams_mixed(L.ctx, &desc[0], &io[0], &desc[1], &io[1], plan.order, plan.stream_start, ns, nb,
+                                         (float *)L.d_amp.p));
+  // the packets end to end, into the pinned arena
+  FEED_TRY(L.d_rel.need((size_t)(nb ? nb : 1) * 8));
+  FEED_TRY(L.d_sid.need((size_t)(nb ? nb : 1) * 4));
+  FEED_TRY(L.d_sbytes.need((size_t)ns * 8));
+  FEED_TRY(L.d_soff.need((size_t)(ns + 1) * 8));
+  const RecLayout R(ns, nb);
+  FEED_TRY(L.h_rec.need(R.bytes + R.bytes / 4));
+  FeedSlice P = feed_slice_of(f, L, plan, ss, d_frames_of, live);  // (the whole group as one run: k_feed.h)
+  P.order = plan.order, P.stream_start = plan.stream_start;
+  for (int W = 0; W < 2; W++) P.fbits[W] = (const int32_t *)L.d_bits[W].p, P.packets[W] = (const uint8_t *)L.d_pk[W].p;
+  for (int attempt = 0;; attempt++) {
+    FeedOut O;
+    FEED_OWN(feed_out(f, L, R, nb, 0, O));
+    hipLaunchKernelGGL(k_feed_sid, dim3((unsigned)ns), dim3(64), 0, st, plan.stream_start, (int32_t *)L.d_sid.p);
+    hipLaunchKernelGGL(k_feed_sizes, dim3((unsigned)ns), dim3(64), 0, st, P, (int64_t *)L.d_rel.p, (int64_t *)L.d_sbytes.p);
+    hipLaunchKernelGGL(k_feed_scan, dim3(1), dim3(1024), 0, st, ns, (const int64_t *)L.d_sbytes.p, (int64_t *)L.d_soff.p);
+    const long waves = (nb > ns + 1 ? nb : ns + 1);
+    hipLaunchKernelGGL(k_feed_copy, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, P, ns, nb, (const int64_t *)L.d_rel.p,
+                       (const int64_t *)L.d_soff.p, (const int32_t *)L.d_sid.p, O);
+    FEED_TRY(hipGetLastError());
+    if (f->ogg) FEED_OWN(run_pager(f, L, plan.stream_start, ns, nb, (const int64_t *)L.d_soff.p + ns));
+    FEED_TRY(hipEventRecord(L.ev_end, st));
+    FEED_TRY(hipEventSynchronize(L.ev_end));
+    const int64_t total = *(const int64_t *)L.h_rec.p;
+    if (total <= (int64_t)L.h_out.bytes) {
+      if (f->ogg) FEED_OWN(pager_result(f, L, ns));
+      feed_result(L, R, ns_out, nb, total);
+      return VAMD_OK;
+    }
+    if (attempt) {
+      L.err = "packet arena still too small after growing it";
+      return VAMD_EFAULT;
+    }
+    FEED_TRY(L.h_out.need((size_t)total + (size_t)total / 8));  // the packets are still in HBM: lay them out again
+  }
+}
+
+// The group's samples up: in_bytes of the pinned input arena into d_in, and a small list beside them (side_bytes from
+// side_src, pinned, to side_dst; 0: none), between the events the upload time is read from; returns when they are up.
+// ONE upload at a time per device.  The link is a single resource: lanes that upload side by side each get a share
+// of it and all finish late together -- and then all compute together while the link idles (measured: three lanes
+// in lockstep, 2.3 ms of every 13 without a single kernel on the chip).  Taking turns, a lane has the whole link,
+// starts its kernels the moment its samples are up, and the next lane's upload runs beside them: the lanes stagger
+// themselves.
+static int upload(FeedLane &L, size_t in_bytes, void *side_dst = nullptr, const void *side_src = nullptr, size_t side_bytes = 0) {
+  std::lock_guard<std::mutex> turn(*L.upload_turn);
+  FEED_TRY(hipEventRecord(L.ev0, L.stream));
+  if (in_bytes) FEED_TRY(hipMemcpyAsync(L.d_in.p, L.h_in.p, in_bytes, hipMemcpyHostToDevice, L.stream));
+  if (side_bytes) FEED_TRY(hipMemcpyAsync(side_dst, side_src, side_bytes, hipMemcpyHostToDevice, L.stream));
+  FEED_TRY(hipEventRecord(L.ev_up, L.stream));
+  FEED_TRY(hipEventSynchronize(L.ev_up));
+  return VAMD_OK;
+}
+
+// an ingest kernel over the group's samples as their type has it (k16: 16-bit, k32: float; d_in in front of args): `items`
+// threads' worth of work in workgroups of 256, at most 8192 of them (the kernels stride)
+template <typename K16, typename K32, typename... A>
+static void launch_ingest(const FeedLane &L, K16 *k16, K32 *k32, long items, A... args) {
+  long blocks = (items + 255) / 256;
+  if (blocks > 256L * 32) blocks = 256L * 32;
+  if (blocks < 1) blocks = 1;
+  if (L.format == VAMD_FEED_S16) hipLaunchKernelGGL(k16, dim3((unsigned)blocks), dim3(256), 0, L.stream, (const int16_t *)L.d_in.p, args...);
+  else hipLaunchKernelGGL(k32, dim3((unsigned)blocks), dim3(256), 0, L.stream, (const float *)L.d_in.p, args...);
+}
 
 // one group through its lane (the lane's own thread; its device is current)
 static int run_group(vamd_feed *f, FeedLane &L) {
@@ -853,31 +655,10 @@ static int run_group(vamd_feed *f, FeedLane &L) {
     d_frames_of = (const long long *)L.d_len.p;
     d_first_of = d_frames_of + ns;
   }
-  {
-    // ONE upload at a time per device.  The link is a single resource: lanes that upload side by side each get a share
-    // of it and all finish late together -- and then all compute together while the link idles (measured: three lanes
-    // in lockstep, 2.3 ms of every 13 without a single kernel on the chip).  Taking turns, a lane has the whole link,
-    // starts its kernels the moment its samples are up, and the next lane's upload runs beside them: the lanes stagger
-    // themselves.
-    std::lock_guard<std::mutex> turn(*L.upload_turn);
-    FEED_TRY(hipEventRecord(L.ev0, st));
-    if (in_bytes) FEED_TRY(hipMemcpyAsync(L.d_in.p, L.h_in.p, in_bytes, hipMemcpyHostToDevice, st));
-    FEED_TRY(hipEventRecord(L.ev_up, st));
-    FEED_TRY(hipEventSynchronize(L.ev_up));
-  }
-  {
-    const long total = ns * ((long)(head >> 2) + ((frames + 3) >> 2) + (pad >> 2));
-    long blocks = (total + 255) / 256;
-    if (blocks > 256L * 32) blocks = 256L * 32;
-    if (blocks < 1) blocks = 1;
-    if (L.format == VAMD_FEED_S16)
-      hipLaunchKernelGGL(k_feed_ingest<int16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const int16_t *)L.d_in.p, ch, ns, frames, head, pad,
-                         (float *)L.d_pcm.p, ss, cs, (float *)L.d_amp.p, (vamd_envelope_state *)L.d_states.p, d_frames_of, d_first_of);
-    else
-      hipLaunchKernelGGL(k_feed_ingest<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float *)L.d_in.p, ch, ns, frames, head, pad,
-                         (float *)L.d_pcm.p, ss, cs, (float *)L.d_amp.p, (vamd_envelope_state *)L.d_states.p, d_frames_of, d_first_of);
-    FEED_TRY(hipGetLastError());
-  }
+  FEED_OWN(upload(L, in_bytes));
+  launch_ingest(L, k_feed_ingest<int16_t>, k_feed_ingest<float>, ns * ((long)(head >> 2) + ((frames + 3) >> 2) + (pad >> 2)), ch, ns, frames,
+                head, pad, (float *)L.d_pcm.p, ss, cs, (float *)L.d_amp.p, (vamd_envelope_state *)L.d_states.p, d_frames_of, d_first_of);
+  FEED_TRY(hipGetLastError());
   vamd_stream_plan plan;
   if (uneven)
     FEED_CALL(vamd_plan_streams_whole_v(L.ctx, (float *)L.d_pcm.p, ss, cs, ns, frames, L.frames_of.data(), (vamd_envelope_state *)L.d_states.p, &plan));
@@ -886,99 +667,6 @@ static int run_group(vamd_feed *f, FeedLane &L) {
   FeedLive none;
   none.in = nullptr, none.nan = nullptr;
   return finish_group(f, L, plan, (const float *)L.d_pcm.p, ns, ss, cs, d_frames_of, none, ns);
-}
-
-// a group from its plan on (whole or live): the analysis, the packets end to end into the pinned arena
-static int finish_group(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, const float *pcm, long ns, long ss, long cs,
-                        const long long *d_frames_of, FeedLive live, long ns_out) {
-  const long frames = L.frames;
-  const int ch = f->ch, head = f->bs[1] / 2;
-  hipStream_t st = L.stream;
-  if (f->managed) return run_group_managed(f, L, plan, pcm, ns, ss, cs, d_frames_of, live, ns_out);
-  const long nb = (long)(plan.nblocks[0] + plan.nblocks[1]);
-  vamd_batch_desc desc[2];
-  vamd_batch_io io[2];
-  for (int W = 0; W < 2; W++) {
-    const size_t n = (size_t)plan.nblocks[W];
-    FEED_TRY(L.d_pk[W].need((n ? n : 1) * (size_t)f->pkcap[W]));
-    FEED_TRY(L.d_bits[W].need((n ? n : 1) * 4));
-    FEED_TRY(L.d_status[W].need((n ? n : 1) * (size_t)ch));
-    memset(&desc[W], 0, sizeof(desc[W]));
-    memset(&io[W], 0, sizeof(io[W]));
-    desc[W].W = W;
-    desc[W].nblocks = (long)n;
-    desc[W].lW = plan.lW[W], desc[W].nW = plan.nW[W], desc[W].blocktype = plan.blocktype[W];
-    if (!n) continue;
-    io[W].pcm = pcm;
-    io[W].pcm_src = plan.src[W];
-    io[W].pcm_channel_stride = cs;
-    io[W].packets = (uint8_t *)L.d_pk[W].p;
-    io[W].packet_bits = (int32_t *)L.d_bits[W].p;
-    io[W].packet_stride = f->pkcap[W];
-    io[W].status = (uint8_t *)L.d_status[W].p;
-  }
-  if (nb)
-    FEED_CALL(vamd_analyze_streams_mixed(L.ctx, &desc[0], &io[0], &desc[1], &io[1], plan.order, plan.stream_start, ns, nb,
-                                         (float *)L.d_amp.p));
-  // the packets end to end, into the pinned arena
-  FEED_TRY(L.d_rel.need((size_t)(nb ? nb : 1) * 8));
-  FEED_TRY(L.d_sid.need((size_t)(nb ? nb : 1) * 4));
-  FEED_TRY(L.d_sbytes.need((size_t)ns * 8));
-  FEED_TRY(L.d_soff.need((size_t)(ns + 1) * 8));
-  // records: [total | stream_start (ns + 1) | offset (nb) | granulepos (nb) | bits (nb) | info (nb)]
-  const size_t o_start = 8, o_off = o_start + (size_t)(ns + 1) * 8, o_gp = o_off + (size_t)nb * 8, o_bits = o_gp + (size_t)nb * 8,
-               o_info = o_bits + (size_t)nb * 4, rec_bytes = al(o_info + (size_t)nb, 16);
-  FEED_TRY(L.h_rec.need(rec_bytes + rec_bytes / 4));
-  FeedPlan P;
-  P.order = plan.order, P.stream_start = plan.stream_start;
-  for (int W = 0; W < 2; W++) {
-    P.src[W] = plan.src[W], P.bits[W] = (const int32_t *)L.d_bits[W].p, P.status[W] = (const uint8_t *)L.d_status[W].p;
-    P.packets[W] = (const uint8_t *)L.d_pk[W].p, P.stride[W] = f->pkcap[W], P.bs[W] = f->bs[W];
-  }
-  P.ch = ch, P.stream_stride = ss, P.eof = head + frames, P.frames_of = d_frames_of, P.head = head;
-  P.live = live;
-  for (int attempt = 0;; attempt++) {
-    uint8_t *hrec = (uint8_t *)L.h_rec.p;
-    void *drec = nullptr, *dbytes = nullptr;
-    FEED_TRY(hipHostGetDevicePointer(&drec, hrec, 0));
-    FEED_TRY(hipHostGetDevicePointer(&dbytes, L.h_out.p, 0));
-    FeedOut O;
-    uint8_t *dr = (uint8_t *)drec;
-    O.total = (int64_t *)dr, O.stream_start = (int64_t *)(dr + o_start), O.offset = (int64_t *)(dr + o_off);
-    O.granulepos = (int64_t *)(dr + o_gp), O.bits = (int32_t *)(dr + o_bits), O.info = dr + o_info;
-    O.bytes = (uint8_t *)dbytes, O.cap = (int64_t)L.h_out.bytes;
-    FEED_OWN(feed_mirror(f, L, O, nb, 0));
-    hipLaunchKernelGGL(k_feed_sid, dim3((unsigned)ns), dim3(64), 0, st, plan.stream_start, (int32_t *)L.d_sid.p);
-    hipLaunchKernelGGL(k_feed_sizes, dim3((unsigned)ns), dim3(64), 0, st, P, ns, (int64_t *)L.d_rel.p, (int64_t *)L.d_sbytes.p);
-    hipLaunchKernelGGL(k_feed_scan, dim3(1), dim3(1024), 0, st, ns, (const int64_t *)L.d_sbytes.p, (int64_t *)L.d_soff.p);
-    const long waves = (nb > ns + 1 ? nb : ns + 1);
-    hipLaunchKernelGGL(k_feed_copy, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, P, ns, nb, (const int64_t *)L.d_rel.p,
-                       (const int64_t *)L.d_soff.p, (const int32_t *)L.d_sid.p, O);
-    FEED_TRY(hipGetLastError());
-    if (f->ogg) FEED_OWN(run_pager(f, L, plan.stream_start, ns, nb, (const int64_t *)L.d_soff.p + ns));
-    FEED_TRY(hipEventRecord(L.ev_end, st));
-    FEED_TRY(hipEventSynchronize(L.ev_end));
-    const int64_t total = *(const int64_t *)hrec;
-    if (total <= (int64_t)L.h_out.bytes) {
-      if (f->ogg) FEED_OWN(pager_result(f, L, ns));
-      vamd_feed_result &R = L.result;
-      R.nstreams = ns_out, R.nblocks = nb;
-      R.stream_start = (const int64_t *)(hrec + o_start), R.offset = (const int64_t *)(hrec + o_off);
-      R.granulepos = (const int64_t *)(hrec + o_gp), R.bits = (const int32_t *)(hrec + o_bits), R.info = hrec + o_info;
-      R.bytes = (const uint8_t *)L.h_out.p, R.total_bytes = total;
-      break;
-    }
-    if (attempt) {
-      L.err = "packet arena still too small after growing it";
-      return VAMD_EFAULT;
-    }
-    FEED_TRY(L.h_out.need((size_t)total + (size_t)total / 8));  // the packets are still in HBM: lay them out again
-  }
-  float up = 0.f, dev = 0.f;
-  (void)hipEventElapsedTime(&up, L.ev0, L.ev_up);
-  (void)hipEventElapsedTime(&dev, L.ev0, L.ev_end);
-  L.result.upload_ms = up, L.result.device_ms = dev;
-  return VAMD_OK;
 }
 
 // one group of a live lane: the pieces of its streams 0 .. L.nstreams-1 (and 0-frame pieces of its other open streams, which
@@ -1053,14 +741,7 @@ static int run_group_live(vamd_feed *f, FeedLane &L) {
   }
   const size_t in_bytes = (size_t)first * ch * sample;
   FEED_TRY(L.d_in.need(in_bytes ? in_bytes : 16));
-  {
-    std::lock_guard<std::mutex> turn(*L.upload_turn);  // (run_group: one upload at a time per device)
-    FEED_TRY(hipEventRecord(L.ev0, st));
-    if (in_bytes) FEED_TRY(hipMemcpyAsync(L.d_in.p, L.h_in.p, in_bytes, hipMemcpyHostToDevice, st));
-    FEED_TRY(hipMemcpyAsync(L.d_live.p, hin, (size_t)ns * sizeof(LiveIn), hipMemcpyHostToDevice, st));
-    FEED_TRY(hipEventRecord(L.ev_up, st));
-    FEED_TRY(hipEventSynchronize(L.ev_up));
-  }
+  FEED_OWN(upload(L, in_bytes, L.d_live.p, hin, (size_t)ns * sizeof(LiveIn)));
   const LiveIn *d_live = (const LiveIn *)L.d_live.p;
   vamd_bitrate_state *bst = f->managed ? (vamd_bitrate_state *)L.d_bstate.p : nullptr;
   if (f->managed && !L.btmpl_ready) {
@@ -1074,17 +755,8 @@ static int run_group_live(vamd_feed *f, FeedLane &L) {
     *(volatile int *)L.h_lstatus.p = 0;
     void *d_lstatus = nullptr;
     FEED_TRY(hipHostGetDevicePointer(&d_lstatus, L.h_lstatus.p, 0));
-    long blocks = (ns * quads + 255) / 256;
-    if (blocks > 256L * 32) blocks = 256L * 32;
-    if (blocks < 1) blocks = 1;
-    const float *old = (const float *)L.d_buf[L.cur].p;
-    float *pcm = (float *)L.d_buf[1 - L.cur].p;
-    if (L.format == VAMD_FEED_S16)
-      hipLaunchKernelGGL(k_live_ingest<int16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const int16_t *)L.d_in.p, ch, ns, (long)quads, pad + 256,
-                         d_live, old, pcm, ss, cs, (unsigned long long *)L.d_nan.p, (int *)d_lstatus);
-    else
-      hipLaunchKernelGGL(k_live_ingest<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float *)L.d_in.p, ch, ns, (long)quads, pad + 256,
-                         d_live, old, pcm, ss, cs, (unsigned long long *)L.d_nan.p, (int *)d_lstatus);
+    launch_ingest(L, k_live_ingest<int16_t>, k_live_ingest<float>, ns * (long)quads, ch, ns, (long)quads, pad + 256, d_live,
+                  (const float *)L.d_buf[L.cur].p, (float *)L.d_buf[1 - L.cur].p, ss, cs, (unsigned long long *)L.d_nan.p, (int *)d_lstatus);
     FEED_TRY(hipGetLastError());
   }
   L.cur = 1 - L.cur;
@@ -1150,27 +822,8 @@ static void feed_free(vamd_feed *f) {
     if (L.worker.joinable()) L.worker.join();
   int cur = 0;
   (void)hipGetDevice(&cur);
-  for (FeedLane &L : f->lanes) {
-    (void)hipSetDevice(L.device);
-    if (L.stream) (void)hipStreamSynchronize(L.stream);
-    if (L.ctx) vamd_destroy(L.ctx);
-    Buf *all[] = {&L.d_len, &L.h_len, &L.h_in, &L.h_out, &L.h_rec, &L.d_in, &L.d_pcm, &L.d_states, &L.d_amp, &L.d_pk[0], &L.d_pk[1], &L.d_bits[0],
-                  &L.d_bits[1], &L.d_status[0], &L.d_status[1], &L.d_rel, &L.d_sid, &L.d_sbytes, &L.d_soff, &L.d_bstate, &L.d_slice, &L.h_slice,
-                  &L.d_buf[0], &L.d_buf[1], &L.d_walk, &L.d_rows, &L.d_nan, &L.d_btmpl, &L.d_live, &L.h_live, &L.h_lstatus,
-                  &L.d_mirror, &L.d_moff, &L.d_mgp, &L.d_mrbits, &L.d_minfo, &L.d_hdr, &L.d_serial, &L.h_serial, &L.d_pages, &L.d_fbytes,
-                  &L.d_foff, &L.d_npages, &L.d_ostatus, &L.h_ogg, &L.h_orec};
-    for (int W = 0; W < 2; W++) {
-      Buf *m[] = {&L.d_mpk[W], &L.d_mbits[W], &L.d_mposts[W], &L.d_mvalid[W], &L.d_miwork[W], &L.d_mnz[W], &L.d_choice[W], &L.d_fbits[W]};
-      for (Buf *b : m) b->drop();
-    }
-    for (Buf *b : all) b->drop();
-    if (L.ev0) (void)hipEventDestroy(L.ev0);
-    if (L.ev_up) (void)hipEventDestroy(L.ev_up);
-    if (L.ev_end) (void)hipEventDestroy(L.ev_end);
-    if (L.stream) (void)hipStreamDestroy(L.stream);
-  }
+  f->lanes.clear();  // (~FeedLane, each on its own device)
   (void)hipSetDevice(cur);
-  f->lanes.clear();
 }
 
 // why this thread's last vamd_feed_create failed (vamd_feed_last_error(NULL))
@@ -1205,8 +858,9 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
   {
     const vamd::Knobs K = vamd::read_knobs();
     f->slice = K.feed_slice > 0 ? K.feed_slice : 2048;
+    f->out_bytes = K.feed_out_bytes > 0 ? K.feed_out_bytes : 0;
   }
-  f->lanes.resize(devs.size() * (size_t)lanes_per_device);
+  for (size_t l = 0; l < devs.size() * (size_t)lanes_per_device; l++) f->lanes.emplace_back();
   for (size_t d = 0; d < devs.size(); d++) f->upload_turns.emplace_back(new std::mutex);
   int r = VAMD_OK;
   // lane l runs on device l % ndevices: consecutive groups go to different devices first, to a device's next lane after
@@ -1214,8 +868,6 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
     FeedLane &L = f->lanes[l];
     L.device = devs[l % devs.size()];
     L.upload_turn = f->upload_turns[l % devs.size()].get();
-    L.h_in.host = L.h_out.host = L.h_rec.host = L.h_len.host = L.h_slice.host = L.h_live.host = L.h_lstatus.host = true;
-    L.h_ogg.host = L.h_orec.host = L.h_serial.host = true;
     r = vamd_create(&L.ctx, setup_blob, blob_bytes, L.device);
     if (r) break;
     hipError_t e = hipSetDevice(L.device);
@@ -1256,7 +908,8 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
     // tenth of that, q 1.0 on noise a third; run_group grows the arena when a group needs more)
     const size_t in_cap = (size_t)max_streams * max_frames * f->ch * (format == VAMD_FEED_S16 ? 2 : 4);
     if (e == hipSuccess && !r) e = L.h_in.need(in_cap);
-    if (e == hipSuccess && !r) e = L.h_out.need(al((size_t)max_streams * max_frames * f->ch + (size_t)max_streams * 65536, 4096));
+    const size_t out_cap = f->out_bytes ? (size_t)f->out_bytes : (size_t)max_streams * max_frames * f->ch + (size_t)max_streams * 65536;
+    if (e == hipSuccess && !r) e = L.h_out.need(al(out_cap, 4096));
     if (e != hipSuccess) r = VAMD_EFAULT;
   }
   (void)hipSetDevice(cur);
@@ -1288,6 +941,36 @@ static void ogg_job(vamd_feed *f, FeedLane &L, long nstreams) {
   for (long s = 0; s < nstreams; s++) L.serials[(size_t)s] = f->next_serial++;
   for (size_t s = 0; s < L.user_serials.size() && s < (size_t)nstreams; s++) L.serials[s] = L.user_serials[s];
   L.user_serials.clear();
+}
+
+// the tail of vamd_feed_wrote / _wrote_v / _wrote_live (f->m held; the lane's frames_of / close_of are set): the group
+// goes to its lane's thread
+static int queue_group(vamd_feed *f, FeedLane &L, long nstreams, long frames) {
+  L.nstreams = nstreams, L.frames = frames, L.format = f->format;
+  L.status = 0;
+  memset(&L.result, 0, sizeof(L.result));
+  ogg_job(f, L, nstreams);
+  L.t_wrote = now_s();
+  L.state = LANE_QUEUED;
+  f->cv_work.notify_all();
+  return VAMD_OK;
+}
+
+// vamd_feed_packets / vamd_feed_ogg: waits for the slot's group, then hands out what its lane holds for the caller
+template <typename R>
+static int await_group(vamd_feed *f, int slot, R FeedLane::*result, R *out, bool ogg) {
+  if (!f || !out || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  std::unique_lock<std::mutex> g(f->m);
+  if (ogg && !f->ogg) {
+    f->err = "vamd_feed_ogg: the feed has no Ogg headers (vamd_feed_ogg_headers)";
+    return VAMD_EINVAL;
+  }
+  FeedLane &L = f->lanes[(size_t)slot];
+  if (L.state != LANE_QUEUED && L.state != LANE_DONE) return VAMD_EINVAL;
+  f->cv_done.wait(g, [&] { return f->stop || L.state == LANE_DONE; });
+  if (L.state != LANE_DONE) return VAMD_EFAULT;
+  *out = L.*result;
+  return L.status;
 }
 
 static uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
@@ -1347,20 +1030,7 @@ int vamd_feed_ogg_serials(vamd_feed *f, int slot, const uint32_t *serials, long 
   return VAMD_OK;
 }
 
-int vamd_feed_ogg(vamd_feed *f, int slot, vamd_feed_ogg_result *out) {
-  if (!f || !out || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
-  std::unique_lock<std::mutex> g(f->m);
-  if (!f->ogg) {
-    f->err = "vamd_feed_ogg: the feed has no Ogg headers (vamd_feed_ogg_headers)";
-    return VAMD_EINVAL;
-  }
-  FeedLane &L = f->lanes[(size_t)slot];
-  if (L.state != LANE_QUEUED && L.state != LANE_DONE) return VAMD_EINVAL;
-  f->cv_done.wait(g, [&] { return f->stop || L.state == LANE_DONE; });
-  if (L.state != LANE_DONE) return VAMD_EFAULT;
-  *out = L.ogg_result;
-  return L.status;
-}
+int vamd_feed_ogg(vamd_feed *f, int slot, vamd_feed_ogg_result *out) { return await_group(f, slot, &FeedLane::ogg_result, out, true); }
 
 int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes, const int *devices, int ndevices,
                      int lanes_per_device, long max_streams, long max_frames, int format) {
@@ -1418,15 +1088,8 @@ int vamd_feed_wrote(vamd_feed *f, int slot, long nstreams, long frames) {
   std::lock_guard<std::mutex> g(f->m);
   FeedLane &L = f->lanes[(size_t)slot];
   if (L.state != LANE_FILLING) return VAMD_EINVAL;
-  L.nstreams = nstreams, L.frames = frames, L.format = f->format;
   L.frames_of.clear();
-  L.status = 0;
-  memset(&L.result, 0, sizeof(L.result));
-  ogg_job(f, L, nstreams);
-  L.t_wrote = now_s();
-  L.state = LANE_QUEUED;
-  f->cv_work.notify_all();
-  return VAMD_OK;
+  return queue_group(f, L, nstreams, frames);
 }
 
 int vamd_feed_wrote_v(vamd_feed *f, int slot, long nstreams, const int64_t *frames) {
@@ -1443,15 +1106,8 @@ int vamd_feed_wrote_v(vamd_feed *f, int slot, long nstreams, const int64_t *fram
   std::lock_guard<std::mutex> g(f->m);
   FeedLane &L = f->lanes[(size_t)slot];
   if (L.state != LANE_FILLING) return VAMD_EINVAL;
-  L.nstreams = nstreams, L.frames = longest, L.format = f->format;
   L.frames_of.assign(frames, frames + nstreams);
-  L.status = 0;
-  memset(&L.result, 0, sizeof(L.result));
-  ogg_job(f, L, nstreams);
-  L.t_wrote = now_s();
-  L.state = LANE_QUEUED;
-  f->cv_work.notify_all();
-  return VAMD_OK;
+  return queue_group(f, L, nstreams, longest);
 }
 
 int vamd_feed_wrote_live(vamd_feed *f, int slot, long nstreams, const int64_t *frames, const uint8_t *close) {
@@ -1464,29 +1120,14 @@ int vamd_feed_wrote_live(vamd_feed *f, int slot, long nstreams, const int64_t *f
     if (frames[i] < 0 || frames[i] > f->max_frames) return VAMD_EINVAL;
     if (close && close[i] && !frames[i] && !L.live[(size_t)i].open) return VAMD_EINVAL;  // (closing a stream that never had a frame)
   }
-  L.nstreams = nstreams, L.frames = f->max_frames, L.format = f->format;
   L.frames_of.assign(frames, frames + nstreams);
   L.close_of.assign((size_t)nstreams, 0);
   if (close)
     for (long i = 0; i < nstreams; i++) L.close_of[(size_t)i] = close[i] != 0;
-  L.status = 0;
-  memset(&L.result, 0, sizeof(L.result));
-  L.t_wrote = now_s();
-  L.state = LANE_QUEUED;
-  f->cv_work.notify_all();
-  return VAMD_OK;
+  return queue_group(f, L, nstreams, f->max_frames);  // (no Ogg files of a live feed: vamd_feed_ogg_headers)
 }
 
-int vamd_feed_packets(vamd_feed *f, int slot, vamd_feed_result *out) {
-  if (!f || !out || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
-  std::unique_lock<std::mutex> g(f->m);
-  FeedLane &L = f->lanes[(size_t)slot];
-  if (L.state != LANE_QUEUED && L.state != LANE_DONE) return VAMD_EINVAL;
-  f->cv_done.wait(g, [&] { return f->stop || L.state == LANE_DONE; });
-  if (L.state != LANE_DONE) return VAMD_EFAULT;
-  *out = L.result;
-  return L.status;
-}
+int vamd_feed_packets(vamd_feed *f, int slot, vamd_feed_result *out) { return await_group(f, slot, &FeedLane::result, out, false); }
 
 int vamd_feed_release(vamd_feed *f, int slot) {
   if (!f || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
