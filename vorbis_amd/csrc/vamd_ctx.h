@@ -1,7 +1,8 @@
 // vamd_ctx.h -- the context behind a vamd_ctx handle: the parameter structs bound to the HBM image, streams and events,
 // the workspace, staging, the profiling hooks, the environment knobs -- and the small helpers every entry point uses
-// (fail / HIP_TRY, DeviceGuard, ws_get).  Part of the library's single translation unit: included by vamd_hip.hip, once,
-// after vamd_kernels.h.
+// (fail / HIP_TRY, DeviceGuard, ws_get, pinned_get, Arena).  Part of the library's single translation unit: included by
+// vamd_hip.hip, once, after vamd_kernels.h and before the three parts of the host side (vamd_batch.h, vamd_block.h,
+// vamd_plan.h).
 #pragma once
 // ---------------------------------------------------------------------------
 // context
@@ -10,6 +11,7 @@ struct DevBuf {
   void *p = nullptr;
   size_t bytes = 0;
 };
+struct HostBuf : DevBuf {};  // pinned host memory, grown on demand (pinned_get)
 
 struct vamd_ctx {
   int device = 0;
@@ -39,12 +41,9 @@ struct vamd_ctx {
          WS_PLAN_FLAGS, WS_PLAN_BLOCKS, WS_PLAN_COUNTS, WS_PLAN_BASE, WS_PLAN_DESC, WS_PLAN_ORDER, WS_STATUS, WS_WRAPPED, WS_RES_BOOKS, WS_PLAN_PENDING, WS_PLAN_GEO, WS_COUNT };
   DevBuf ws[2][WS_COUNT];  // per size class (a mixed stream keeps both batches in flight)
   // pinned staging for the per-block host API
-  void *h_stage = nullptr;
-  size_t h_stage_bytes = 0;
-  void *h_plan = nullptr;  // pinned: a stream plan's per-stream bases on their way up (vamd_plan_streams)
-  size_t h_plan_bytes = 0;
-  void *h_geo = nullptr;   // pinned: per-stream geometry of whole streams of unequal length (vamd_plan_streams_whole_v)
-  size_t h_geo_bytes = 0;
+  HostBuf h_stage;
+  HostBuf h_plan;  // a stream plan's per-stream bases on their way up (vamd_plan_streams)
+  HostBuf h_geo;   // per-stream geometry of whole streams of unequal length (vamd_plan_streams_whole_v), of a live group
   // optional per-stage timing (vamd_profile): one event before each stage + one after the last
   unsigned long long *d_dbg = nullptr;  // 80 phase-stopwatch slots when armed
   bool profile = false;
@@ -133,3 +132,28 @@ static int ws_get(vamd_ctx *c, int W, int which, size_t bytes, void **out) {
   *out = b.p;
   return VAMD_OK;
 }
+
+// a pinned buffer of the context's of at least `bytes`; `slack`: half as much again when it has to grow (buffers whose
+// size follows the call -- the look-ahead's arena, the plans' geometry -- would otherwise be reallocated at every new maximum)
+static int pinned_get(vamd_ctx *c, HostBuf &b, size_t bytes, bool slack) {
+  if (b.bytes < bytes) {
+    if (b.p) HIP_TRY(c, hipHostFree(b.p));
+    b.p = nullptr;
+    b.bytes = 0;
+    const size_t want = slack ? bytes + bytes / 2 : bytes;
+    HIP_TRY(c, hipHostMalloc(&b.p, want, hipHostMallocDefault));
+    b.bytes = want;
+  }
+  return VAMD_OK;
+}
+
+// the layout of a host-pointer call's arena (pinned and device side alike): every part begins on a 16-byte boundary --
+// the launch code chooses kernels by pointer alignment, and the mapped pinned arena is read and written in place
+struct Arena {
+  size_t at = 0;  // the arena's size so far
+  size_t take(size_t bytes) {
+    const size_t o = at;
+    at = (at + bytes + 15) & ~(size_t)15;
+    return o;
+  }
+};

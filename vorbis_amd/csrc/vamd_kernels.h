@@ -1,6 +1,6 @@
 // vamd_kernels.h -- the __global__ shells of libvorbis_amd.so: thin kernels around the wave-level bodies in k_*.h (one
 // section per stage, in pipeline order; then the block-switching detector, stream control, the calibration copy).  Part of
-// the library's single translation unit: included by vamd_hip.hip, once, after the body headers.
+// the library's single translation unit (vamd_hip.hip and its five parts): included by it, once, after the body headers.
 #pragma once
 // ---------------------------------------------------------------------------
 // kernels
@@ -32,7 +32,7 @@ __device__ __forceinline__ void flag_range(const DescP &d, long i) {
 // wave-local), so they drift apart and overlap each other's memory phases.
 #define VAMD_XF_WAVES 8
 // channel-blocks from which the floor stage takes the two channels of a stereo block in one wave (k_floor_pair), per size
-// class.  Measured round 5 (profiles/r05_floor_pair.txt, tools/floor_pair_ab.sh): SHORT blocks gain -- their 128 bins and
+// class.  Measured round 5 (profiles/r05_floor_pair.txt, both forms interleaved on one GPU): SHORT blocks gain -- their 128 bins and
 // 13 / 19 posts leave half of a wave's lanes idle in every phase of k_floor: C5's floor 3.80 -> 3.53 ms, the step
 // 11.38 -> 11.09 ms, at six waves per SIMD (77 registers) -- from a batch that fills the chip; LONG blocks lose at every
 // occupancy (1.96 -> 2.42 ms at best: 12 % fewer vector instructions per channel-block, but 9.6 KB of LDS per wave
@@ -583,7 +583,7 @@ __global__ __launch_bounds__(64 * NoiseGeom<LOGN2>::NW) void k_noise_tone(PsyP P
 // one THREAD per channel-block: the ordered stack walk of seed_chase, VAMD_CHASE_LANES walks per wave.  (Measured
 // round 2: half-filled waves -- twice as many waves for the SIMDs to interleave -- are slower, 1.01 against 0.82 ms per
 // 131 072 stereo blocks; a walk whose stack is a register bit mask fed through coalesced LDS tiles executes three
-// times the instructions once 64 divergent walks share them, 2.96 ms.  tools/pmc_quick.sh has the counters.)
+// times the instructions once 64 divergent walks share them, 2.96 ms.  docs/history/DESIGN_r01-r05.md has the round's account.)
 #define VAMD_CHASE_LANES 64
 __global__ __launch_bounds__(64) void k_tone_chase(int linesper, int nl, int nlp, long ncb, DescP d,
                                                    const float *__restrict__ seed_g,
@@ -687,7 +687,7 @@ __global__ __launch_bounds__(64) void k_tone_fold(PsyP P0, PsyP P1, DescP d, int
 
 // stage 4: offset_and_mix + floor1_fit + floor curve
 // (eight waves per SIMD, i.e. 64 registers: measured against the 73 the compiler would take and six or seven waves --
-// the stage is latency-bound, its time follows the blocks in flight: tools/floor_occ.sh -- 2.14 against 2.24 ms)
+// the stage is latency-bound, its time follows the blocks in flight -- 2.14 against 2.24 ms)
 // With `seed_g` the stage begins with the tone chain's last step (tone_fold_block: paint the chase's survivors,
 // max_seeds' fold) for its own channel-block: the tone curve then goes out and comes straight back through L2 inside
 // one wave instead of through a launch boundary, and the fold's waits sit among thirty-one other waves' floor fits.

@@ -42,7 +42,7 @@ struct Knobs {
   bool env_untiled = false;      // VAMD_ENV_UNTILED: the detector's thread-per-item kernels at every size
   int xf_variant = -1;           // VAMD_XF_VARIANT: transform kernel variant (-1: default)
   long fail_envelope_after = -1; // VAMD_FAIL_ENVELOPE_AFTER: vamd_envelope_search fails (VAMD_EFAULT) from its n-th call on
-  long fail_encode_after = -1;   // VAMD_FAIL_ENCODE_AFTER: the same for vamd_encode_block / vamd_analyze_block*
+  long fail_encode_after = -1;   // VAMD_FAIL_ENCODE_AFTER: the same for vamd_encode_block and for vamd_encode_blocks, each counting its own calls
   long feed_slice = 2048;        // VAMD_FEED_SLICE: blocks per slice of a bitrate-managed vamd_feed group (small: many slices)
   long feed_out_bytes = 0;       // VAMD_FEED_OUT_BYTES: a vamd_feed lane's packet arena to start with (small: it has to grow; 0: the feed's own)
 };

@@ -1,4 +1,4 @@
-// vamd_live.h -- the live feed's plan (vamd_feed_create_live), internal to the library: vamd_hip.hip implements it, the
+// vamd_live.h -- the live feed's plan (vamd_feed_create_live), internal to the library: vamd_plan.h (a part of vamd_hip.hip's translation unit) implements it, the
 // feed (vamd_feed.hip) is its only caller.  Not part of the public ABI.
 #pragma once
 #include <stdint.h>

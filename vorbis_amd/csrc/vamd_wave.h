@@ -166,7 +166,7 @@ struct PhaseClock {
     if (slots) t = clock64();
   }
   VAMD_DEV void mark(int k) {
-#ifdef VAMD_STOP_AFTER  // scratch builds for counting a stage's instructions phase by phase (tools/floor_phases_pmc.sh)
+#ifdef VAMD_STOP_AFTER  // scratch builds for counting a stage's instructions phase by phase
     if (stoppable && k == VAMD_STOP_AFTER) __builtin_amdgcn_endpgm();
 #endif
     if (slots) {
