@@ -258,6 +258,32 @@ VAMD_DEV void fold_fetch(FoldOps<LOGN> &o, const float *in) {
 #ifndef VAMD_XF_HEAD_REGS
 #define VAMD_XF_HEAD_REGS 1
 #endif
+// ---- round 11: three more trips of the 2048-sample transform that never needed LDS ------------------------------
+//   * VAMD_XF_OUT_REGS: the bit-reverse item u = LANE + 64 k holds out[u], out[n2-1-u], out[n4-1-u] and out[n2-n4+u] when it
+//     has rotated them: four runs of 64 consecutive floats per instruction, two ascending and two descending, each a
+//     whole aligned 256 bytes.  They go to HBM (and, where logmdct is wanted, through todB_345 first) from the registers
+//     that hold them, instead of four 4-byte LDS stores, a sync and the quad reads that fed the 16-byte HBM stores.
+//   * VAMD_XF_TAIL_LOGFFT: the fused last radix-4 + radix-2 pass (fft_tail42_wave) ends in exactly the (Re_k, Im_k) pairs
+//     that transform_logfft reloads.  Where nobody taps logfft -- only its run peaks and local_ampmax are wanted, both
+//     maxima -- the tail forms each bin's dB value from its registers and folds it into the run's slot and the lane's
+//     maximum there: no store of the spectrum, no sync, no reload.  A tapped logfft keeps the old hand-over.
+//   * VAMD_XF_P123_REGS: FFT passes 1 + 2 -> 3 through v_permlane32_swap (fft_pass123_wave2048 below).
+//   * VAMD_MD_OUT_REGS: the first of these in k_mdct_only (the HBM-bound kernel: off until a C2 A/B of its own says otherwise).
+// Same arithmetic on the same operands; only where a value is when it is used changes.
+#ifndef VAMD_XF_OUT_REGS
+#define VAMD_XF_OUT_REGS 1
+#endif
+#ifndef VAMD_XF_TAIL_LOGFFT
+#define VAMD_XF_TAIL_LOGFFT 1
+#endif
+#ifndef VAMD_MD_OUT_REGS
+#define VAMD_MD_OUT_REGS 0
+#endif
+template <int LOGN, class Team>
+constexpr bool xf_size_path() {  // the size-specialised 2048-sample path, one wave per channel-block, on the GPU
+  return VAMD_GPU && LOGN == 11 && std::is_same<Team, WaveTeam>::value;
+}
+
 #if VAMD_GPU
 VAMD_DEV void swap_halves32(float &a, float &b) {  // a: [a.lo, b.lo], b: [a.hi, b.hi]  (lo = lanes 0-31)
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
@@ -275,10 +301,15 @@ VAMD_DEV void swap_rows16(float &a, float &b) {  // a's odd rows of sixteen lane
 // detector, k_env_spectrum: its steps overlap by half, so transform t's samples start in_stride = 64 floats after its
 // predecessor's and a windowed copy of every step would be twice the LDS).  x * win[i] is rounded as the separate
 // windowing pass rounds it; the sums the fold takes of such products are the same sums.
-template <int LOGS = 0, int LOGN = 0, class Team = WaveTeam, bool PACKED = false, bool FOLD_AHEAD = false, bool WIN = false>
+// OUT_REGS (VAMD_XF_OUT_REGS above): the spectrum goes from the bit-reverse items' registers to hbm_out [n/2] and its dB twin
+// to hbm_log [n/2] (each may be null); out0 is not written.
+template <int LOGS = 0, int LOGN = 0, class Team = WaveTeam, bool PACKED = false, bool FOLD_AHEAD = false, bool WIN = false,
+          bool OUT_REGS = false>
 VAMD_DEV void mdct_forward_wave(const XformP &P, const float *in0, float *w0, float *out0, PhaseClock &pc,
                                 int in_stride = 0, int w_stride = 0, int out_stride = 0, const Team &tm = Team(),
-                                FoldOps<LOGN> *ahead = nullptr, const float *in_next = nullptr, const float *win = nullptr) {
+                                FoldOps<LOGN> *ahead = nullptr, const float *in_next = nullptr, const float *win = nullptr,
+                                float *__restrict__ hbm_out = nullptr, float *__restrict__ hbm_log = nullptr) {
+  static_assert(!OUT_REGS || LOGS == 0, "the spectrum out of registers: one transform per wave");
   static_assert(!WIN || (!FOLD_AHEAD && !(VAMD_XF_FOLD_QUADS && LOGN >= 10 && LOGS == 0)), "the window in the fold: the generic fold only");
   const int n = LOGN ? (1 << LOGN) : P.n, n2 = n >> 1, n4 = n >> 2, n8 = n >> 3;
   const int log2n = LOGN ? LOGN : P.log2n;
@@ -666,12 +697,22 @@ VAMD_DEV void mdct_forward_wave(const XformP &P, const float *in0, float *w0, fl
     // callers hand over w itself, or a buffer of their own.)
     {
       const F2 Tl = *(const F2 *)(trig + n2 + 2 * u);
-      out_lds[u] = (lo.x * Tl.x + lo.y * Tl.y) * P.mdct_scale;
-      out_lds[n2 - 1 - u] = (lo.x * Tl.y - lo.y * Tl.x) * P.mdct_scale;
+      const float o0 = (lo.x * Tl.x + lo.y * Tl.y) * P.mdct_scale;
+      const float o1 = (lo.x * Tl.y - lo.y * Tl.x) * P.mdct_scale;
       const int i2 = n4 - 1 - u;
       const F2 Th = *(const F2 *)(trig + n2 + 2 * i2);
-      out_lds[i2] = (hi.x * Th.x + hi.y * Th.y) * P.mdct_scale;
-      out_lds[n2 - 1 - i2] = (hi.x * Th.y - hi.y * Th.x) * P.mdct_scale;
+      const float o2 = (hi.x * Th.x + hi.y * Th.y) * P.mdct_scale;
+      const float o3 = (hi.x * Th.y - hi.y * Th.x) * P.mdct_scale;
+      if constexpr (OUT_REGS) {  // neighbouring lanes hold neighbouring bins of all four: whole 256-byte runs per store
+        if (hbm_out) hbm_out[u] = o0, hbm_out[n2 - 1 - u] = o1, hbm_out[i2] = o2, hbm_out[n2 - 1 - i2] = o3;
+        if (hbm_log)  // lib/mapping0.c:384-385
+          hbm_log[u] = todB_345(o0), hbm_log[n2 - 1 - u] = todB_345(o1), hbm_log[i2] = todB_345(o2), hbm_log[n2 - 1 - i2] = todB_345(o3);
+      } else {
+        out_lds[u] = o0;
+        out_lds[n2 - 1 - u] = o1;
+        out_lds[i2] = o2;
+        out_lds[n2 - 1 - i2] = o3;
+      }
     }
   }
   tm.sync();
@@ -801,65 +842,70 @@ VAMD_DEV void radf4_wave(int ido, int l1, const float *__restrict__ cc, float *_
 #define VAMD_F2_POS(t) ((t) + (((t) >> 5) << 1))
 #define VAMD_F3_POS(t) ((t) + (((t) >> 6) << 1))
 
+// passes 1 + 2 on the sixteen values x[m] = c[k + (n/16) m] of unit k: o[0..16) = the ido = 4 pass's outputs 16 k ... 16 k + 15.
+// w1, w2, w3 = the ido = 4 pass's three twiddle pairs.
+VAMD_DEV void fft_pass12_unit(const float *x, float *o, const F2 w1, const F2 w2, const F2 w3) {
+  const float hsqt2 = .70710678118654752f;
+  // dradf4 with ido = 1 (lib/smallft.c:176-193), butterfly k + u*t: its cc[t0+k], cc[3t0+k], cc[k], cc[2t0+k]
+  // are x[t+4], x[t+12], x[t], x[t+8]; y[t][0..3] = its four outputs = the ido = 4 pass's cc[4k + i + (n/4) t]
+  float y[4][4];
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const float c1 = x[t + 4], c2 = x[t + 12], c3 = x[t], c4 = x[t + 8];
+    const float tr1 = c1 + c2, tr2 = c3 + c4;
+    y[t][0] = tr1 + tr2;
+    y[t][1] = c3 - c4;
+    y[t][2] = c2 - c1;
+    y[t][3] = tr2 - tr1;
+  }
+  {  // ido = 4, the i = 0 column (lib/smallft.c:176-193): cc[t1], cc[t2], cc[t3], cc[t4] = y[1][0], y[3][0], y[0][0], y[2][0]
+    const float tr1 = y[1][0] + y[3][0];
+    const float tr2 = y[0][0] + y[2][0];
+    o[0] = tr1 + tr2;
+    o[15] = tr2 - tr1;
+    o[7] = y[0][0] - y[2][0];
+    o[8] = y[3][0] - y[1][0];
+  }
+  {  // the i = ido column (:246-268): cc[t1], cc[t2], cc[t6-1], cc[t1+t0] = y[1][3], y[3][3], y[0][3], y[2][3]
+    const float ti1 = -hsqt2 * (y[1][3] + y[3][3]);
+    const float tr1 = hsqt2 * (y[1][3] - y[3][3]);
+    o[3] = tr1 + y[0][3];
+    o[11] = y[0][3] - tr1;
+    o[4] = ti1 - y[2][3];
+    o[12] = ti1 + y[2][3];
+  }
+  {  // the i = 2 butterfly (:197-243) on the pairs (y[t][1], y[t][2])
+    const float cr2 = w1.x * y[1][1] + w1.y * y[1][2];
+    const float ci2 = w1.x * y[1][2] - w1.y * y[1][1];
+    const float cr3 = w2.x * y[2][1] + w2.y * y[2][2];
+    const float ci3 = w2.x * y[2][2] - w2.y * y[2][1];
+    const float cr4 = w3.x * y[3][1] + w3.y * y[3][2];
+    const float ci4 = w3.x * y[3][2] - w3.y * y[3][1];
+    const float tr1 = cr2 + cr4, tr4 = cr4 - cr2, ti1 = ci2 + ci4, ti4 = ci2 - ci4;
+    const float ti2 = y[0][2] + ci3, ti3 = y[0][2] - ci3;
+    const float tr2 = y[0][1] + cr3, tr3 = y[0][1] - cr3;
+    o[1] = tr1 + tr2;
+    o[2] = ti1 + ti2;
+    o[5] = tr3 - ti4;
+    o[6] = tr4 - ti3;
+    o[9] = ti4 + tr3;
+    o[10] = tr4 + ti3;
+    o[13] = tr2 - tr1;
+    o[14] = ti1 - ti2;
+  }
+}
+
 // passes 1 + 2: c plain [n] -> dst (offset layout, VAMD_F2_POS).  w = the ido = 4 pass's three twiddle pairs.
 template <int LOGN, class Team>
 VAMD_DEV void fft_pass12_wave(const float *__restrict__ c, float *__restrict__ dst, const float *__restrict__ wa1,
                               const float *__restrict__ wa2, const float *__restrict__ wa3, const Team &tm) {
   constexpr int n = 1 << LOGN, u = n / 16;
-  const float hsqt2 = .70710678118654752f;
   const F2 w1 = *(const F2 *)wa1, w2 = *(const F2 *)wa2, w3 = *(const F2 *)wa3;
   TEAM_EACH(k, u, tm) {
-    float x[16];
+    float x[16], o[16];
 #pragma unroll
     for (int m = 0; m < 16; m++) x[m] = c[k + u * m];
-    // dradf4 with ido = 1 (lib/smallft.c:176-193), butterfly k + u*t: its cc[t0+k], cc[3t0+k], cc[k], cc[2t0+k]
-    // are x[t+4], x[t+12], x[t], x[t+8]; y[t][0..3] = its four outputs = the ido = 4 pass's cc[4k + i + (n/4) t]
-    float y[4][4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-      const float c1 = x[t + 4], c2 = x[t + 12], c3 = x[t], c4 = x[t + 8];
-      const float tr1 = c1 + c2, tr2 = c3 + c4;
-      y[t][0] = tr1 + tr2;
-      y[t][1] = c3 - c4;
-      y[t][2] = c2 - c1;
-      y[t][3] = tr2 - tr1;
-    }
-    float o[16];
-    {  // ido = 4, the i = 0 column (lib/smallft.c:176-193): cc[t1], cc[t2], cc[t3], cc[t4] = y[1][0], y[3][0], y[0][0], y[2][0]
-      const float tr1 = y[1][0] + y[3][0];
-      const float tr2 = y[0][0] + y[2][0];
-      o[0] = tr1 + tr2;
-      o[15] = tr2 - tr1;
-      o[7] = y[0][0] - y[2][0];
-      o[8] = y[3][0] - y[1][0];
-    }
-    {  // the i = ido column (:246-268): cc[t1], cc[t2], cc[t6-1], cc[t1+t0] = y[1][3], y[3][3], y[0][3], y[2][3]
-      const float ti1 = -hsqt2 * (y[1][3] + y[3][3]);
-      const float tr1 = hsqt2 * (y[1][3] - y[3][3]);
-      o[3] = tr1 + y[0][3];
-      o[11] = y[0][3] - tr1;
-      o[4] = ti1 - y[2][3];
-      o[12] = ti1 + y[2][3];
-    }
-    {  // the i = 2 butterfly (:197-243) on the pairs (y[t][1], y[t][2])
-      const float cr2 = w1.x * y[1][1] + w1.y * y[1][2];
-      const float ci2 = w1.x * y[1][2] - w1.y * y[1][1];
-      const float cr3 = w2.x * y[2][1] + w2.y * y[2][2];
-      const float ci3 = w2.x * y[2][2] - w2.y * y[2][1];
-      const float cr4 = w3.x * y[3][1] + w3.y * y[3][2];
-      const float ci4 = w3.x * y[3][2] - w3.y * y[3][1];
-      const float tr1 = cr2 + cr4, tr4 = cr4 - cr2, ti1 = ci2 + ci4, ti4 = ci2 - ci4;
-      const float ti2 = y[0][2] + ci3, ti3 = y[0][2] - ci3;
-      const float tr2 = y[0][1] + cr3, tr3 = y[0][1] - cr3;
-      o[1] = tr1 + tr2;
-      o[2] = ti1 + ti2;
-      o[5] = tr3 - ti4;
-      o[6] = tr4 - ti3;
-      o[9] = ti4 + tr3;
-      o[10] = tr4 + ti3;
-      o[13] = tr2 - tr1;
-      o[14] = ti1 - ti2;
-    }
+    fft_pass12_unit(x, o, w1, w2, w3);
     float *d = dst + VAMD_F2_POS(16 * k);  // the sixteen share a group of 32: one pad for all
     d[0] = o[0];
 #pragma unroll
@@ -932,6 +978,95 @@ VAMD_DEV void fft_pass3_wave(const float *__restrict__ cc, float *__restrict__ c
   }
 }
 
+// ---- passes 1 + 2 -> 3 of the 2048-sample FFT without LDS (VAMD_XF_P123_REGS, round 11) ------------------------------------
+// Pass 3's group k3 (< 32) consumes the sixteen outputs of each of the four pass-1+2 units k3 + 32 q, q = 0..3 -- element e
+// of unit k3 + 32 q is its cc[16 k3 + e + (n/4) q].  With the units dealt k = LANE + 64 kk those four are the two units of
+// lane k3 (q = 0, 2) and the two of lane k3 + 32 (q = 1, 3): the exchange crosses lane bit 5 only, v_permlane32_swap, as the
+// MDCT's head does.  The pair of lanes shares group k3's work by element: the lower lane takes elements 0..6 and 15 (the two
+// k-only columns and the butterflies m = 1, 2, 3), the upper one 7..14 (m = 4..7); each swap hands over one register either
+// way, sixteen in all, in place of eighteen LDS stores, a sync and sixteen loads per lane.  Pass 3's butterflies as
+// fft_pass3_wave states them, and its stores: lanes of a half-wave hold 32 different k3 at 66 floats' distance.
+// c and ch may be the same block (they are: pass 3 writes where passes 1 + 2 read) -- every load is consumed before the
+// exchange, every store issued after it.
+#ifndef VAMD_XF_P123_REGS
+#define VAMD_XF_P123_REGS 1
+#endif
+#if VAMD_GPU
+VAMD_DEV void fft_pass123_wave2048(const float *c, float *ch, const float *wa) {
+  constexpr int n = 2048, u = n / 16;
+  const float hsqt2 = .70710678118654752f;
+  float Q[4][8];  // quarter q's elements: slot s = element SLO[s] in the lower lane, SHI[s] in the upper one
+  {
+    const F2 w1 = *(const F2 *)(wa + n - 16), w2 = *(const F2 *)(wa + n - 12), w3 = *(const F2 *)(wa + n - 8);
+    constexpr int SLO[8] = {0, 1, 2, 3, 4, 5, 6, 15}, SHI[8] = {7, 9, 10, 11, 12, 13, 14, 8};
+#pragma unroll
+    for (int kk = 0; kk < 2; kk++) {
+      const int k = LANE + 64 * kk;
+      float x[16], o[16];
+#pragma unroll
+      for (int m = 0; m < 16; m++) x[m] = c[k + u * m];
+      fft_pass12_unit(x, o, w1, w2, w3);
+#pragma unroll
+      for (int s = 0; s < 8; s++) {  // the lower lane keeps o[SLO[s]] and gets its neighbour's; the upper one likewise with SHI
+        float a = o[SLO[s]], b = o[SHI[s]];
+        swap_halves32(a, b);
+        Q[2 * kk][s] = a;
+        Q[2 * kk + 1][s] = b;
+      }
+    }
+  }
+  WAVE_SYNC();
+  const float *wa1 = wa + n - 64, *wa2 = wa + n - 48, *wa3 = wa + n - 32;
+  const bool upper = LANE >= 32;
+  float *d = ch + 66 * (LANE & 31);
+  // the (k, i = 2m) butterfly (lib/smallft.c:197-243) on the pairs in slots sa, sb
+  auto bfly = [&](int m, int sa, int sb) {
+    const int i = 2 * m;
+    const F2 w1 = *(const F2 *)(wa1 + i - 2), w2 = *(const F2 *)(wa2 + i - 2), w3 = *(const F2 *)(wa3 + i - 2);
+    F2 c0, c1, c2, c3;
+    c0.x = Q[0][sa], c0.y = Q[0][sb], c1.x = Q[1][sa], c1.y = Q[1][sb];
+    c2.x = Q[2][sa], c2.y = Q[2][sb], c3.x = Q[3][sa], c3.y = Q[3][sb];
+    const float cr2 = w1.x * c1.x + w1.y * c1.y;
+    const float ci2 = w1.x * c1.y - w1.y * c1.x;
+    const float cr3 = w2.x * c2.x + w2.y * c2.y;
+    const float ci3 = w2.x * c2.y - w2.y * c2.x;
+    const float cr4 = w3.x * c3.x + w3.y * c3.y;
+    const float ci4 = w3.x * c3.y - w3.y * c3.x;
+    const float tr1 = cr2 + cr4, tr4 = cr4 - cr2, ti1 = ci2 + ci4, ti4 = ci2 - ci4;
+    const float ti2 = c0.y + ci3, ti3 = c0.y - ci3;
+    const float tr2 = c0.x + cr3, tr3 = c0.x - cr3;
+    st_pair(d, i, tr1 + tr2, ti1 + ti2);
+    st_pair(d, 32 - i, tr3 - ti4, tr4 - ti3);
+    st_pair(d, 32 + i, ti4 + tr3, tr4 + ti3);
+    st_pair(d, 64 - i, tr2 - tr1, ti1 - ti2);
+  };
+#pragma unroll
+  for (int j = 0; j < 3; j++) bfly((upper ? 5 : 1) + j, 1 + 2 * j, 2 + 2 * j);  // elements (2m - 1, 2m)
+  if (upper) {
+    bfly(4, 0, 7);  // elements 7, 8
+  } else {  // the two k-only columns (elements 0 and 15 of the four quarters)
+    {
+      const float a1 = Q[1][0], a2 = Q[3][0], a3 = Q[0][0], a4 = Q[2][0];
+      const float tr1 = a1 + a2;
+      const float tr2 = a3 + a4;
+      d[0] = tr1 + tr2;
+      d[63] = tr2 - tr1;
+      d[31] = a3 - a4;
+      d[32] = a2 - a1;
+    }
+    {
+      const float b1 = Q[1][7], b2 = Q[3][7], b6 = Q[0][7], b3 = Q[2][7];
+      const float ti1 = -hsqt2 * (b1 + b2);
+      const float tr1 = hsqt2 * (b1 - b2);
+      d[15] = tr1 + b6;
+      d[47] = b6 - tr1;
+      d[16] = ti1 - b3;
+      d[48] = ti1 + b3;
+    }
+  }
+}
+#endif
+
 
 // dradf2, lib/smallft.c:113-166, same flattening
 template <bool AL, class Team>
@@ -979,21 +1114,74 @@ VAMD_DEV void radf2_wave(int ido, int l1, const float *__restrict__ cc, float *_
 // and 4ido-i of those two blocks -- so a thread runs both, then the four radix-2 butterflies on what it holds.
 // Unit 0 takes the two k-only columns of both blocks (values at 0, ido-1, ido, ... 4ido-1) and the radix-2 work
 // they feed (its i = 0 column and the butterflies at ido, 2ido, 3ido).  src, dst: offset layout, plain.
+// SINK (VAMD_XF_TAIL_LOGFFT): nothing is stored.  A pair stored at t is bin t/2's (Re, Im); each is turned into its logfft
+// value (lib/mapping0.c:255-346, as transform_logfft forms it) where it is, and folded into its run's slot of
+// sink.peaks_lds and into sink.amp.  Item g holds the bins tail_bin(g, 0..7).
+template <int LOGN>
+VAMD_DEV int tail_bin(int g, int c) {  // slot c = 2 j + h of item g: the pair of its j-th radix-2 butterfly at t (h = 0) or n - t (h = 1)
+  constexpr int n = 1 << LOGN, ido = n / 8;
+  const int j = c >> 1, i = 2 * g;
+  int t;
+  if (g == 0) {
+    if (j == 0) return (c & 1) ? n / 4 : 0;  // the i = 0 column: bin 0 (R0 alone) and bin n/4 (the values at n/2 - 1, n/2)
+    t = j * ido;
+  } else {
+    t = j == 0 ? i : (j == 1 ? 2 * ido - i : (j == 2 ? 2 * ido + i : 4 * ido - i));
+  }
+  return ((c & 1) ? n - t : t) >> 1;
+}
+struct TailSink {
+  float *peaks_lds;  // [nruns], holding -inf; not the buffer the tail reads
+  const I2 *rid;     // the runs of this lane's bins: item kk's slots 2 j, 2 j + 1 in the halves of word j of rid[2 kk], rid[2 kk + 1]
+  float scale_dB;
+  float amp;         // the lane's maximum so far
+};
+// the run ids the tail wants (fetched once by a persistent kernel: the same for every block, as xf_run_ids')
 template <int LOGN, class Team>
+VAMD_DEV void xf_tail_run_ids(const unsigned short *__restrict__ run_of_bin, I2 *rid, const Team &tm) {
+  constexpr int items = (1 << LOGN) / 16;
+#pragma unroll
+  for (int kk = 0; kk < (items + 63) / 64; kk++) {
+    const int g = tm.tid() + tm.size() * kk;
+    int w[4] = {0, 0, 0, 0};
+    if (g < items)
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        w[j] = (int)run_of_bin[tail_bin<LOGN>(g, 2 * j)] | ((int)run_of_bin[tail_bin<LOGN>(g, 2 * j + 1)] << 16);
+    rid[2 * kk].x = w[0], rid[2 * kk].y = w[1], rid[2 * kk + 1].x = w[2], rid[2 * kk + 1].y = w[3];
+  }
+}
+
+template <int LOGN, bool SINK = false, class Team>
 VAMD_DEV void fft_tail42_wave(const float *__restrict__ cc, float *__restrict__ ch, const float *__restrict__ wa,
-                              const Team &tm) {
+                              const Team &tm, TailSink *sink = nullptr) {
   constexpr int n = 1 << LOGN, ido = n / 8, t0 = n / 4, n2 = n / 2;
   const float hsqt2 = .70710678118654752f;
   const float *__restrict__ wa1 = wa + n2, *__restrict__ wa2 = wa1 + ido, *__restrict__ wa3 = wa2 + ido;  // iw = n/2 + 1
-  // dradf2's butterfly at i (lib/smallft.c:139-163) on the pairs c5 (first block) and c3 (second block)
-  auto radf2_bfly = [&](int i, const F2 c5, const F2 c3) {
+  float amp = -1e30f;
+  // a finished bin (SINK): v as transform_logfft's, into its run `r` and the lane's maximum
+  auto bin_out = [&](float re, float im, int r) {
+    const float temp = re * re + im * im;
+    const float v = (float)((double)(sink->scale_dB + .5f * todB(temp)) + .345);
+    amp = fmaxf(amp, v);
+    lds_atomic_max(sink->peaks_lds + r, v);
+  };
+  // dradf2's butterfly at i (lib/smallft.c:139-163) on the pairs c5 (first block) and c3 (second block); rw = the runs of
+  // the bins i/2 and (n - i)/2 (SINK)
+  auto radf2_bfly = [&](int i, const F2 c5, const F2 c3, int rw) {
     const F2 w1 = *(const F2 *)(wa + i - 2);  // iw = 1
     const float tr2 = w1.x * c3.x + w1.y * c3.y;
     const float ti2 = w1.x * c3.y - w1.y * c3.x;
-    st_pair(ch, i, c5.x + tr2, c5.y + ti2);
-    st_pair(ch, n - i, c5.x - tr2, ti2 - c5.y);
+    if constexpr (SINK) {
+      bin_out(c5.x + tr2, c5.y + ti2, rw & 0xffff);
+      bin_out(c5.x - tr2, ti2 - c5.y, (int)((unsigned)rw >> 16));
+    } else {
+      st_pair(ch, i, c5.x + tr2, c5.y + ti2);
+      st_pair(ch, n - i, c5.x - tr2, ti2 - c5.y);
+    }
   };
-  TEAM_EACH(g, ido / 2, tm) {
+  // item g; rw = the runs of its eight bins (SINK)
+  auto item = [&](int g, const int *rw) {
     if (g == 0) {
       float V[2][8];  // block k's values at 0, ido-1, ido, 2ido-1, 2ido, 3ido-1, 3ido, 4ido-1
 #pragma unroll
@@ -1018,16 +1206,24 @@ VAMD_DEV void fft_tail42_wave(const float *__restrict__ cc, float *__restrict__ 
         }
       }
       // dradf2's i = 0 column (lib/smallft.c:121-136): cc[0], cc[t0] and the two values at ido-1 of its own pass
-      ch[0] = V[0][0] + V[1][0];
-      ch[n - 1] = V[0][0] - V[1][0];
-      ch[n2] = -V[1][7];
-      ch[n2 - 1] = V[0][7];
+      if constexpr (SINK) {
+        // bin 0 is R0 alone (lib/mapping0.c:264); R(n/2) at n - 1 belongs to no bin; bin n/4 = the pair (n/2 - 1, n/2)
+        const float v0 = (float)((double)(sink->scale_dB + todB(V[0][0] + V[1][0])) + .345);
+        amp = fmaxf(amp, v0);
+        lds_atomic_max(sink->peaks_lds + (rw[0] & 0xffff), v0);
+        bin_out(V[0][7], -V[1][7], (int)((unsigned)rw[0] >> 16));
+      } else {
+        ch[0] = V[0][0] + V[1][0];
+        ch[n - 1] = V[0][0] - V[1][0];
+        ch[n2] = -V[1][7];
+        ch[n2 - 1] = V[0][7];
+      }
 #pragma unroll
       for (int j = 1; j < 4; j++) {
         F2 c5, c3;
         c5.x = V[0][2 * j - 1], c5.y = V[0][2 * j];
         c3.x = V[1][2 * j - 1], c3.y = V[1][2 * j];
-        radf2_bfly(j * ido, c5, c3);
+        radf2_bfly(j * ido, c5, c3, rw[j]);
       }
     } else {
       const int i = 2 * g;
@@ -1052,11 +1248,29 @@ VAMD_DEV void fft_tail42_wave(const float *__restrict__ cc, float *__restrict__ 
         Pk[k][2].x = ti4 + tr3, Pk[k][2].y = tr4 + ti3;
         Pk[k][3].x = tr2 - tr1, Pk[k][3].y = ti1 - ti2;
       }
-      radf2_bfly(i, Pk[0][0], Pk[1][0]);
-      radf2_bfly(2 * ido - i, Pk[0][1], Pk[1][1]);
-      radf2_bfly(2 * ido + i, Pk[0][2], Pk[1][2]);
-      radf2_bfly(4 * ido - i, Pk[0][3], Pk[1][3]);
+      radf2_bfly(i, Pk[0][0], Pk[1][0], rw[0]);
+      radf2_bfly(2 * ido - i, Pk[0][1], Pk[1][1], rw[1]);
+      radf2_bfly(2 * ido + i, Pk[0][2], Pk[1][2], rw[2]);
+      radf2_bfly(4 * ido - i, Pk[0][3], Pk[1][3], rw[3]);
     }
+  };
+  if constexpr (SINK) {
+#if VAMD_GPU
+    TEAM_QUADS(kk, g, ido / 2, (ido / 2 + 63) / 64, tm) {  // (a constant trip count: the run ids stay registers)
+      int rw[4] = {sink->rid[2 * kk].x, sink->rid[2 * kk].y, sink->rid[2 * kk + 1].x, sink->rid[2 * kk + 1].y};
+      // (opaque: the sixteen slot addresses are the same for every block, and hoisted out of the block loop they are
+      // sixteen registers held across the whole kernel where the packed ids are eight)
+      asm volatile("" : "+v"(rw[0]), "+v"(rw[1]), "+v"(rw[2]), "+v"(rw[3]));
+      item(g, rw);
+      // one item at a time: interleaved, the two items' pairs, twiddles and fp64 temporaries are 17 registers more than
+      // the kernel has
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    sink->amp = amp;
+#endif
+  } else {
+    const int rw[4] = {0, 0, 0, 0};
+    TEAM_EACH(g, ido / 2, tm) item(g, rw);
   }
 }
 
@@ -1067,8 +1281,11 @@ VAMD_DEV void fft_tail42_wave(const float *__restrict__ cc, float *__restrict__ 
 // LOGN > 0: n = 2^LOGN, whose FFTPACK factorisation is radix 4 throughout with one radix-2 pass at the end
 // when LOGN is odd (drfti1 tries 4 first and moves a leftover 2 to the front of ifac[], which drftf1
 // walks backwards: lib/smallft.c:35-70,572-631); vamd_create() checks the blob's factors against that.
+// sink (VAMD_XF_TAIL_LOGFFT, the sizes with the fused tail): the last trip's bins go into it instead of a buffer -- its
+// peaks_lds is set up here, in the buffer that trip would have written -- and the return value points at nothing.
 template <int LOGN = 0, class Team = WaveTeam>
-VAMD_DEV const float *drft_forward_wave(const XformP &P, float *c, float *ch, const Team &tm = Team()) {
+VAMD_DEV const float *drft_forward_wave(const XformP &P, float *c, float *ch, const Team &tm = Team(), TailSink *sink = nullptr,
+                                        int nruns = 0) {
   const int n = LOGN ? (1 << LOGN) : P.n, nf = LOGN ? (LOGN >> 1) + (LOGN & 1) : P.fft_nf;
   const float *__restrict__ wa = P.wa;
   float *bufc = c + 1, *bufh = ch + 1;  // offset layouts of the two buffers
@@ -1076,9 +1293,18 @@ VAMD_DEV const float *drft_forward_wave(const XformP &P, float *c, float *ch, co
   if (LOGN >= 8) {
     // ido = 1 and 4 in one trip (c -> ch), ido = 16 (ch -> c); twiddles as drftf1 would hand them to dradf4:
     // iw = n - 3 after the first pass, n - 15 for the second, n - 63 for the third
-    fft_pass12_wave<LOGN ? LOGN : 8>(c, bufh, wa + n - 16, wa + n - 12, wa + n - 8, tm);
-    tm.sync();
-    fft_pass3_wave<LOGN ? LOGN : 8>(bufh, bufc, wa + n - 64, wa + n - 48, wa + n - 32, tm);
+    bool done = false;
+#if VAMD_GPU
+    if constexpr (VAMD_XF_P123_REGS && xf_size_path<LOGN, Team>()) {
+      fft_pass123_wave2048(c, bufc, wa);  // (one trip, the hand-over in registers)
+      done = true;
+    }
+#endif
+    if (!done) {
+      fft_pass12_wave<LOGN ? LOGN : 8>(c, bufh, wa + n - 16, wa + n - 12, wa + n - 8, tm);
+      tm.sync();
+      fft_pass3_wave<LOGN ? LOGN : 8>(bufh, bufc, wa + n - 64, wa + n - 48, wa + n - 32, tm);
+    }
     tm.sync();
     na = 1;  // the data is in c: the next pass writes ch
     l2 = n >> 6;
@@ -1115,6 +1341,17 @@ VAMD_DEV const float *drft_forward_wave(const XformP &P, float *c, float *ch, co
   }
   if (TAIL42) {
     na = 1 - na;
+    if constexpr (VAMD_XF_TAIL_LOGFFT && TAIL42 && xf_size_path<LOGN, Team>()) {
+      if (sink) {
+        float *peaks = na ? c : ch;  // the destination: its last reader was the pass before the one that has just synced
+        TEAM_EACH(r, nruns, tm) peaks[r] = f_from_bits(0xff800000u);  // -inf: every run has a bin, and every bin a finite value
+        tm.sync();
+        sink->peaks_lds = peaks;
+        fft_tail42_wave<TAIL42 ? LOGN : 11, true>(na ? bufh : bufc, peaks, wa, tm, sink);
+        tm.sync();
+        return nullptr;
+      }
+    }
     fft_tail42_wave<TAIL42 ? LOGN : 11>(na ? bufh : bufc, na ? bufc : bufh, wa, tm);
     tm.sync();
   }
@@ -1141,21 +1378,27 @@ VAMD_DEV void transform_window(const XformP &P, int W, int lW, int nW, const Pcm
 // is free again and the caller may already put the next block into it.
 template <int LOGN = 0, class Team = WaveTeam>
 VAMD_DEV const float *transform_spectra(const XformP &P, float *A, float *B, float *__restrict__ mdct_out,
-                                        float *__restrict__ logmdct_out, PhaseClock &pc, const Team &tm = Team()) {
+                                        float *__restrict__ logmdct_out, PhaseClock &pc, const Team &tm = Team(),
+                                        TailSink *sink = nullptr, int nruns = 0) {
   const int n = LOGN ? (1 << LOGN) : P.n, n2 = n >> 1;
   // MDCT: spectrum lands in B[0..n2) (LDS), then goes out with its dB twin, 16 bytes per thread and tensor
-  mdct_forward_wave<0, LOGN, Team, LOGN != 0>(P, A, B, B, pc, 0, 0, 0, tm);
-  TEAM_EACH(q, n2 >> 2, tm) {
-    float m[4], l[4];
-    f4_get(((const F4 *)B)[q], m);
-    for (int c = 0; c < 4; c++) l[c] = todB_345(m[c]);  // lib/mapping0.c:384-385
-    if (mdct_out) ((F4 *)mdct_out)[q] = f4_make(m);
-    if (logmdct_out) ((F4 *)logmdct_out)[q] = f4_make(l);
+  // (the 2048-sample path: straight out of the MDCT's last items, VAMD_XF_OUT_REGS)
+  constexpr bool OUT_REGS = VAMD_XF_OUT_REGS && xf_size_path<LOGN, Team>();
+  mdct_forward_wave<0, LOGN, Team, LOGN != 0, false, false, OUT_REGS>(P, A, B, B, pc, 0, 0, 0, tm, nullptr, nullptr, nullptr, mdct_out,
+                                                                      logmdct_out);
+  if constexpr (!OUT_REGS) {
+    TEAM_EACH(q, n2 >> 2, tm) {
+      float m[4], l[4];
+      f4_get(((const F4 *)B)[q], m);
+      for (int c = 0; c < 4; c++) l[c] = todB_345(m[c]);  // lib/mapping0.c:384-385
+      if (mdct_out) ((F4 *)mdct_out)[q] = f4_make(m);
+      if (logmdct_out) ((F4 *)logmdct_out)[q] = f4_make(l);
+    }
+    tm.sync();
   }
-  tm.sync();
   pc.mark(5);
   // FFT of the same windowed block (A), ping-ponging with B
-  const float *spec = drft_forward_wave<LOGN, Team>(P, A, B, tm);
+  const float *spec = drft_forward_wave<LOGN, Team>(P, A, B, tm, sink, nruns);
   pc.mark(6);
   return spec;
 }
@@ -1194,6 +1437,18 @@ VAMD_DEV float transform_logfft(const XformP &P, const float *spec, float *__res
     TEAM_EACH(r, nruns, tm) peaks_lds[r] = f_from_bits(0xff800000u);  // -inf: every run has a bin, and every bin a finite value
     tm.sync();
   }
+#if VAMD_GPU
+  // (the ids opaque once per block, as in fft_tail42_wave: the sixteen slot addresses are not to be held across the block loop)
+  I2 rid_now[VAMD_XF_QPS(LOGN)];
+  if constexpr (VAMD_XF_TAIL_LOGFFT && xf_size_path<LOGN, Team>()) {  // (k_transform: rid is its register array, whatever it holds)
+#pragma unroll
+    for (int k = 0; k < VAMD_XF_QPS(LOGN); k++) {
+      rid_now[k] = rid[k];
+      asm volatile("" : "+v"(rid_now[k].x), "+v"(rid_now[k].y));
+    }
+    rid = rid_now;
+  }
+#endif
   int kq = 0;  // (the size-specialised kernels unroll this loop entirely: rid[kq] is a register)
   TEAM_EACH(q, n2 >> 2, tm) {
     float v[4];
@@ -1233,12 +1488,33 @@ VAMD_DEV float transform_logfft(const XformP &P, const float *spec, float *__res
   return amp;
 }
 
+// whether a block's logfft comes out of the FFT's tail (VAMD_XF_TAIL_LOGFFT): then `rid` holds xf_tail_run_ids', not xf_run_ids'
+template <int LOGN, class Team>
+VAMD_DEV bool xf_tail_fused(const float *logfft_out, const float *peaks_out) {
+  return VAMD_XF_TAIL_LOGFFT && xf_size_path<LOGN, Team>() && !logfft_out && peaks_out;
+}
+
 template <int LOGN = 0, class Team = WaveTeam>
 VAMD_DEV float transform_block(const XformP &P, float *A, float *B, float *__restrict__ mdct_out,
                                float *__restrict__ logmdct_out, float *__restrict__ logfft_out, PhaseClock &pc,
                                const Team &tm = Team(), float *raw_max = nullptr, const I2 *rid = nullptr,
                                const unsigned short *__restrict__ run_of_bin = nullptr, int nruns = 0,
                                float *__restrict__ peaks_out = nullptr) {
+  if constexpr (VAMD_XF_TAIL_LOGFFT && xf_size_path<LOGN, Team>()) {
+    if (xf_tail_fused<LOGN, Team>(logfft_out, peaks_out)) {  // logfft is wanted as run peaks and local_ampmax only: out of the FFT's tail
+      TailSink sink;
+      sink.rid = rid;  // (xf_tail_run_ids')
+      sink.scale_dB = todB_345(4.f / (1 << LOGN));
+      transform_spectra<LOGN, Team>(P, A, B, mdct_out, logmdct_out, pc, tm, &sink, nruns);
+      TEAM_EACH(r, nruns, tm) peaks_out[r] = sink.peaks_lds[r];
+      float amp = wave_max(sink.amp);  // (as transform_logfft ends)
+      if (raw_max) *raw_max = amp;
+      if (amp > 0.f) amp = 0.f;
+      tm.sync();
+      pc.mark(7);
+      return amp;
+    }
+  }
   const float *spec = transform_spectra<LOGN, Team>(P, A, B, mdct_out, logmdct_out, pc, tm);
   // (the spectrum sits in one of the two buffers: the other one is free by now)
   float *lds_free = (spec >= A && spec < A + VAMD_XF_A_FLOATS(P.n)) ? B : A;

@@ -123,9 +123,13 @@ __global__ __launch_bounds__(64 * VAMD_MD_WAVES) void k_mdct_only(XformP G, int 
   PhaseClock pc;
   pc.start(nullptr);
   for (long f = (long)blockIdx.x * nw + (threadIdx.x >> 6); f < nframes; f += (long)gridDim.x * nw) {
-    mdct_forward_wave<0, LOGN, WaveTeam, LOGN != 0, true>(P, in + f * n, B, B, pc);
-    WAVE_FOR(q, n2 >> 2)((F4 *)(out + f * n2))[q] = ((const F4 *)B)[q];
-    WAVE_SYNC();
+    constexpr bool OUT_REGS = VAMD_MD_OUT_REGS && xf_size_path<LOGN, WaveTeam>();  // (k_transform.h, round 11)
+    mdct_forward_wave<0, LOGN, WaveTeam, LOGN != 0, true, false, OUT_REGS>(P, in + f * n, B, B, pc, 0, 0, 0, WaveTeam(), nullptr, nullptr,
+                                                                           nullptr, out + f * n2, nullptr);
+    if constexpr (!OUT_REGS) {
+      WAVE_FOR(q, n2 >> 2)((F4 *)(out + f * n2))[q] = ((const F4 *)B)[q];
+      WAVE_SYNC();
+    }
   }
 }
 
@@ -161,8 +165,15 @@ __global__ __launch_bounds__(64 * VAMD_XF_BOUND_WAVES) __attribute__((amdgpu_num
   // conditional one that is not taken -- makes the wait there a wait for everything outstanding, the stores of the
   // previous block's spectra included.
   int lW = 0, nW = 0;
-  I2 rid[VAMD_XF_QPS(LOGN)];  // which run of bins each of this lane's bins belongs to: the same for every block
-  if (peaks) xf_run_ids<LOGN>(P, run_of_bin, rid, tm);
+  I2 rid[VAMD_XF_QPS(LOGN)] = {};  // which run of bins each of this lane's bins belongs to: the same for every block
+  if constexpr (VAMD_XF_TAIL_LOGFFT && xf_size_path<LOGN, WaveTeam>()) {  // (the same registers either way: logfft is tapped or not for the whole launch)
+    if (xf_tail_fused<LOGN, WaveTeam>(logfft, peaks))
+      xf_tail_run_ids<LOGN>(run_of_bin, rid, tm);
+    else if (peaks)
+      xf_run_ids<LOGN>(P, run_of_bin, rid, tm);
+  } else if (peaks) {
+    xf_run_ids<LOGN>(P, run_of_bin, rid, tm);
+  }
   // where a channel-block's samples start: packed [block][channel][n], or in place (a stream plan's offsets)
   auto samples = [&](long cbi, long blk) -> const float * {
     return d.src ? pcm + d.src[blk] + (cbi - blk * ch) * d.cstride : pcm + cbi * n;
