@@ -642,7 +642,8 @@ int vamd_feed_release(vamd_feed *f, int slot);
 /* the text of the feed's last failure; with f == NULL, of this thread's last vamd_feed_create() that failed */
 const char *vamd_feed_last_error(const vamd_feed *f);
 
-/* ---- the Ogg feed: complete Ogg Vorbis I files beside the packets (whole-stream feeds; still ABI 9: additions only).
+/* ---- the Ogg feed: complete Ogg Vorbis I files beside the packets (whole-stream feeds; a live feed's files come in pieces,
+ * "the live Ogg feed" below; still ABI 9: additions only).
  *     vamd_feed_ogg_headers(f, id, comment, setup)   once, before the first vamd_feed_buffer: the feed is an Ogg feed
  *     slot = vamd_feed_buffer(f, &pcm) ... [vamd_feed_ogg_serials(f, slot, ...)] ... vamd_feed_wrote / _wrote_v
  *     vamd_feed_ogg(f, slot, &files)                 waits as vamd_feed_packets does; one byte range per stream
@@ -650,8 +651,8 @@ const char *vamd_feed_last_error(const vamd_feed *f);
  * The three header packets are what vorbis_analysis_headerout() gives for the encoder setup the blob was packed from (the
  * setup header is libvorbis' codebook packing: the host's, once per setup); they are validated -- packet types 1 / 3 / 5
  * + "vorbis", a 30-byte identification header whose channels, rate and block sizes are the context's -- else VAMD_EINVAL,
- * the reason in vamd_feed_last_error.  A live feed answers VAMD_EIMPL: a page may span two groups, so the open page's
- * packets would have to stay on the device between them (not built yet).  One comment packet serves every stream.
+ * the reason in vamd_feed_last_error.  A live feed answers VAMD_EIMPL here: what it returns are pieces of files, a contract
+ * of its own that the caller opts into by name (vamd_feed_ogg_headers_live).  One comment packet serves every stream.
  * Framing (doc/framing.html, doc/a1-encapsulation-ogg.tex) happens on the device behind the group's last packet: the
  * copy kernels keep a mirror of the packet arena in HBM, k_ogg_plan walks every stream's packet sizes into pages,
  * k_ogg_pages writes each page -- header, lacing, body, CRC -- straight into a second pinned arena; no further host wait.
@@ -669,17 +670,43 @@ const char *vamd_feed_last_error(const vamd_feed *f);
  * NO file -- a hole would decode out of lap: its range is empty, status[s] carries that block's VAMD_STATUS_*; the other
  * streams of the group are untouched.  Serial numbers: stream s of a group gets the feed's running counter (0, 1, 2, ...
  * over all groups in vamd_feed_wrote order) unless vamd_feed_ogg_serials, between vamd_feed_buffer and vamd_feed_wrote*,
- * names the first n streams' itself.  Pinned memory: the file arena is sized from the packet arena (about 7 % more). */
+ * names the first n streams' itself.  Pinned memory: the file arena is sized from the packet arena (about 7 % more).
+ *
+ * THE LIVE OGG FEED: a live feed's streams as Ogg files, in pieces.
+ *     vamd_feed_create_live(...); vamd_feed_ogg_headers_live(f, id, comment, setup)   once, before the first vamd_feed_buffer
+ *     slot = vamd_feed_buffer(f, &pcm) ... [vamd_feed_ogg_serials] ... vamd_feed_wrote_live(f, slot, nstreams, frames, close)
+ *     vamd_feed_ogg(f, slot, &pieces)                 per stream the NEXT BYTES of its file; vamd_feed_packets unchanged
+ * stream_offset[s] .. stream_offset[s + 1] is the next byte range of stream (slot, s)'s file: the pages the stream
+ * completed in this group, a whole number of pages (npages[s] of them), empty where it completed none.  A page is handed
+ * out once it is closed and never before; there is no per-write flush (a silent stream, one one-byte packet per block,
+ * completes a page only every 255 packets).  The ranges of a stream over all its groups, up to and including the group
+ * that closes it, laid end to end are byte for byte the file the whole-stream Ogg feed makes of the same samples and
+ * serial number (where the stream fits one), and in every case the shipped host mux's of its packets: the paging policy
+ * above is unchanged, and the result depends on no cut into pieces, write cadence or slice size.
+ * Between groups the device keeps per stream the paging walk's state (the open page, the next sequence number, the
+ * file offset), its serial number and the CARRY: the packets with a segment on the open page -- at most 255 packets and
+ * 65 025 bytes, of a packet continued from an earlier page only the rest -- so neither stream length nor memory grows
+ * with a stream.  Serial numbers belong to streams: entry s of vamd_feed_ogg_serials names the serial of stream (slot, s)
+ * if that stream BEGINS with this group and is ignored for a stream already open; without the call a stream takes the
+ * feed's running counter when it begins.  After a close the slot's next piece begins a new file: a bos page, sequence
+ * numbers from 0, a new serial.
+ * A stream that loses a packet (bits = -1; a non-finite sample): from that group on its ranges are empty and status[s]
+ * carries that block's VAMD_STATUS_*, in every group until the stream is closed; the packets carried for its open page
+ * are dropped.  Where a whole stream gets NO file, a live stream has already handed pages out: those bytes are a valid
+ * Ogg prefix without an end-of-stream page.  Other streams, and the slot's next stream, are untouched. */
 typedef struct vamd_feed_ogg_result {
   int64_t nstreams;
-  const int64_t *stream_offset;   /* [nstreams + 1]: stream s's file is bytes[stream_offset[s] .. stream_offset[s + 1]) */
-  const int32_t *npages;          /* [nstreams] */
+  const int64_t *stream_offset;   /* [nstreams + 1]: stream s's file (a live feed: its next piece) is bytes[stream_offset[s] .. stream_offset[s + 1]) */
+  const int32_t *npages;          /* [nstreams] pages in that range */
   const uint8_t *status;          /* [nstreams] 0, or the VAMD_STATUS_* of the block that cost the stream its file */
   const uint8_t *bytes;           /* the files, end to end (the lane's pinned file arena; valid until vamd_feed_release) */
   int64_t total_bytes;
 } vamd_feed_ogg_result;
 int vamd_feed_ogg_headers(vamd_feed *f, const void *id, long id_bytes, const void *comment, long comment_bytes,
                           const void *setup, long setup_bytes);
+/* a live feed's (a whole-stream feed answers VAMD_EINVAL); validates as vamd_feed_ogg_headers does */
+int vamd_feed_ogg_headers_live(vamd_feed *f, const void *id, long id_bytes, const void *comment, long comment_bytes,
+                               const void *setup, long setup_bytes);
 int vamd_feed_ogg_serials(vamd_feed *f, int slot, const uint32_t *serials, long n);
 int vamd_feed_ogg(vamd_feed *f, int slot, vamd_feed_ogg_result *out);
 

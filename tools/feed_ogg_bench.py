@@ -5,6 +5,12 @@ group).  One JSON line per feed.  The packet half uses only calls older librarie
 tool can be run beside an earlier checkout for a before/after of the packet feed.
 
     python tools/feed_ogg_bench.py --streams 64 --seconds 20 --reps 3
+
+--live: the same pair as LIVE feeds (vamd_feed_create_live, one lane: a lane's streams are its own) -- the set fed in
+--piece second pieces, every stream closed with its last; the Ogg feed (vamd_feed_ogg_headers_live) returns the files in
+pieces.  Per feed the whole set's blocks/s and bytes/s and the mean time per group (best of --reps passes over the set).
+
+    python tools/feed_ogg_bench.py --live --streams 64 --seconds 20 --piece 1 --reps 3
 """
 import argparse
 import json
@@ -25,6 +31,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--lanes", type=int, default=2)
     ap.add_argument("--only", choices=("packets", "ogg"), default=None, help="one feed only (for a trace of it, or an older library)")
+    ap.add_argument("--live", action="store_true", help="live feeds: the streams in pieces, the Ogg files in pieces")
+    ap.add_argument("--piece", type=float, default=1.0, help="--live: seconds per piece")
     a = ap.parse_args()
     import vorbis_amd
     frames = int(44100 * a.seconds)
@@ -37,6 +45,8 @@ def main():
         pcm[s] = np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)
     blob = vorbis_amd.default_setup_blob("44k_stereo_q4")
     names = [a.only] if a.only else ["packets", "ogg"]
+    if a.live:
+        return live(a, vorbis_amd, blob, pcm, names)
     feeds = {}
     for k in names:
         kw = {}
@@ -66,6 +76,49 @@ def main():
         dt, nb, nbytes, dev, file_bytes = best[k]
         line = {"feed": k, "streams": a.streams, "seconds": a.seconds, "blocks": nb, "wall_s": dt, "device_ms": dev,
                 "blocks_per_s": nb / dt, "packet_bytes_per_s": nbytes / dt}
+        if k == "ogg":
+            line["file_bytes_per_s"] = file_bytes / dt
+            line["file_bytes"] = file_bytes
+        print(json.dumps(line))
+    for f in feeds.values():
+        f.close()
+
+
+def live(a, vorbis_amd, blob, pcm, names):
+    frames, piece = pcm.shape[1], int(44100 * a.piece)
+    feeds = {}
+    for k in names:
+        kw = {}
+        if k == "ogg":
+            from tests import ogg_host
+            kw["ogg_headers"] = ogg_host.reference_headers(2, 44100, 0.4)  # (needs the reference build, oracle/_ref)
+        feeds[k] = vorbis_amd.Feed(blob, lanes_per_device=1, max_streams=a.streams, max_frames=piece, write_frames=1024, **kw)
+    best = {k: None for k in names}
+    for rep in range(a.reps + 1):
+        for k in names:
+            f = feeds[k]
+            dt = dev = 0.0
+            nb = nbytes = file_bytes = groups = 0
+            for at in range(0, frames, piece):
+                flat = np.ascontiguousarray(pcm[:, at:at + piece]).reshape(-1)
+                n = min(piece, frames - at)
+                slot, buf = f.buffer(2)
+                buf[:flat.size] = flat
+                t0 = time.perf_counter()
+                f.wrote_live(slot, [n] * a.streams, [at + piece >= frames] * a.streams)
+                if k == "ogg":
+                    file_bytes += f.ogg(slot, copy=False)["total_bytes"]
+                r = f.packets(slot, copy=False)
+                dt += time.perf_counter() - t0
+                nb, nbytes, dev, groups = nb + r["nblocks"], nbytes + r["total_bytes"], dev + r["device_ms"], groups + 1
+                f.release(slot)
+            if rep and (best[k] is None or dt < best[k][0]):
+                best[k] = (dt, nb, nbytes, dev, file_bytes, groups)
+    for k in names:
+        dt, nb, nbytes, dev, file_bytes, groups = best[k]
+        line = {"feed": "live " + k, "streams": a.streams, "seconds": a.seconds, "piece_s": a.piece, "groups": groups, "blocks": nb,
+                "wall_s": dt, "group_ms": 1e3 * dt / groups, "group_device_ms": dev / groups, "blocks_per_s": nb / dt,
+                "packet_bytes_per_s": nbytes / dt}
         if k == "ogg":
             line["file_bytes_per_s"] = file_bytes / dt
             line["file_bytes"] = file_bytes

@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe",
                     "vamd_feed_create", "vamd_feed_destroy", "vamd_feed_lanes", "vamd_feed_device", "vamd_feed_buffer", "vamd_feed_wrote",
                     "vamd_feed_packets", "vamd_feed_release", "vamd_feed_last_error", "vamd_feed_create_live", "vamd_feed_wrote_live",
                     "vamd_analyze_streams_mixed_managed", "vamd_bitrate_init_states", "vamd_bitrate_walk",
-                    "vamd_feed_ogg_headers", "vamd_feed_ogg_serials", "vamd_feed_ogg"]
+                    "vamd_feed_ogg_headers", "vamd_feed_ogg_serials", "vamd_feed_ogg", "vamd_feed_ogg_headers_live"]
 PACKETBLOBS = 15
 
 _vp = C.c_void_p
@@ -160,6 +160,7 @@ def load_library():
     L.vamd_feed_packets.argtypes = [_vp, C.c_int, C.POINTER(_FeedResult)]
     L.vamd_feed_release.argtypes = [_vp, C.c_int]
     L.vamd_feed_ogg_headers.argtypes = [_vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long]
+    L.vamd_feed_ogg_headers_live.argtypes = [_vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long]
     L.vamd_feed_ogg_serials.argtypes = [_vp, C.c_int, _vp, C.c_long]
     L.vamd_feed_ogg.argtypes = [_vp, C.c_int, C.POINTER(_FeedOggResult)]
     L.vamd_feed_last_error.argtypes = [_vp]
@@ -958,7 +959,9 @@ class Feed:
 
     ogg_headers = (identification, comment, setup), the packets vorbis_analysis_headerout() gives for the blob's encoder
     setup: an OGG feed (vamd_feed_ogg_headers) -- besides packets(), ogg() returns one complete Ogg Vorbis I file per
-    stream, framed on the device: buffer() -> fill -> [ogg_serials()] -> wrote() -> ogg() / packets() -> release()."""
+    stream, framed on the device: buffer() -> fill -> [ogg_serials()] -> wrote() -> ogg() / packets() -> release().
+    With write_frames: a LIVE OGG feed (vamd_feed_ogg_headers_live) -- ogg() returns per stream the next bytes of its file,
+    the pages it completed in the group; a stream's pieces laid end to end are its file (encode_live_ogg)."""
 
     def __init__(self, setup_blob, devices=None, lanes_per_device=2, max_streams=256, max_frames=131072, fmt=FEED_S16,
                  write_frames=None, ogg_headers=None):
@@ -983,7 +986,7 @@ class Feed:
         self.lanes = self.L.vamd_feed_lanes(self.h)
         if ogg_headers is not None:
             try:
-                self.ogg_headers(*ogg_headers)
+                (self.ogg_headers if write_frames is None else self.ogg_headers_live)(*ogg_headers)
             except Exception:
                 self.close()
                 raise
@@ -993,8 +996,14 @@ class Feed:
         pk = [bytes(p) for p in (ident, comment, setup)]
         self._check(self.L.vamd_feed_ogg_headers(self.h, pk[0], len(pk[0]), pk[1], len(pk[1]), pk[2], len(pk[2])))
 
+    def ogg_headers_live(self, ident, comment, setup):
+        """Makes a live feed a live Ogg feed (files in pieces); before the first buffer()."""
+        pk = [bytes(p) for p in (ident, comment, setup)]
+        self._check(self.L.vamd_feed_ogg_headers_live(self.h, pk[0], len(pk[0]), pk[1], len(pk[1]), pk[2], len(pk[2])))
+
     def ogg_serials(self, slot, serials):
-        """The stream serial numbers of the group being filled in `slot` (between buffer() and wrote())."""
+        """The stream serial numbers of the group being filled in `slot` (between buffer() and wrote()).  A live feed: of
+        the streams that begin with this group; an open stream keeps its own."""
         a = np.ascontiguousarray(serials, dtype=np.uint32).reshape(-1)
         self._check(self.L.vamd_feed_ogg_serials(self.h, slot, _vp(a.ctypes.data), a.size))
 
@@ -1151,6 +1160,34 @@ class Feed:
             except VamdError:
                 pass
         return self._rows(r, len(parts))
+
+    def encode_live_ogg(self, pieces, close=None, serials=None):
+        """One group of a live Ogg feed with ONE lane, synchronously: pieces and close as encode_live takes them; serials
+        (optional) as ogg_serials.  -> per stream the next bytes of its Ogg file: the pages it completed in this group
+        (b"" where none, or where the stream has lost a packet: see ogg())."""
+        if self.write_frames is None:
+            raise ValueError("encode_live_ogg needs a live feed (Feed(..., write_frames=..., ogg_headers=...))")
+        if self.lanes != 1:
+            raise ValueError("encode_live_ogg drives a feed with one lane; with more, use buffer / wrote_live / ogg / release")
+        parts = [np.ascontiguousarray(x, dtype=self.dtype) for x in pieces]
+        ch = max(x.shape[1] if x.ndim == 2 else 1 for x in parts)
+        parts = [x.reshape(-1, ch) for x in parts]
+        frames = np.array([x.shape[0] for x in parts], np.int64)
+        slot, buf = self.buffer(ch)
+        try:
+            flat = np.concatenate([x.reshape(-1) for x in parts]) if parts else np.zeros(0, self.dtype)
+            buf[:flat.size] = flat
+            if serials is not None:
+                self.ogg_serials(slot, serials)
+            self.wrote_live(slot, frames, close)
+            r = self.ogg(slot, copy=False)
+            off = r["stream_offset"]
+            return [bytes(r["bytes"][int(off[s]):int(off[s + 1])]) for s in range(len(parts))]
+        finally:
+            try:
+                self.release(slot)
+            except VamdError:
+                pass
 
     def encode(self, pcm):
         """One group, synchronously: pcm [nstreams, frames, ch] of the feed's sample type (host), or a list of [frames_s, ch]

@@ -7,13 +7,17 @@
 //     feed"), in two forms that the CPU suite holds together: a packet at a time (the header runs), and 64 packets at a
 //     time with a page per step (the audio run: prefix sums of the sizes, every packet asked at once where the page ends);
 //   * the kernels: k_ogg_plan (a wave per stream runs the walk, sizes scanned into LDS 64 at a time) and k_ogg_pages (a
-//     wave per page: header, lacing table, body gathered from the packets, CRC, written with aligned dword stores).
+//     wave per page: header, lacing table, body gathered from the packets, CRC, written with aligned dword stores) -- and,
+//     for a live feed, whose files arrive in pieces, k_ogg_carry: what lies on the page still open stays on the device.
 // The CRC functions and the walk are ONE body: the library compiles them for gfx950, the CPU suite compiles this very
 // file with the host compiler (tests/ogg_host.py) together with the host-only mux at the end, which lays the same
 // pages out byte by byte -- the second implementation of the policy that the GPU's files are held against.
 #pragma once
 #include <stdint.h>
 #include <string.h>
+#if !defined(__HIP_DEVICE_COMPILE__)
+#include <vector>
+#endif
 
 #if defined(__HIPCC__)
 #define VAMD_OGG_FN __host__ __device__ inline
@@ -29,7 +33,11 @@ enum {
   OGG_FILL = 4096,       // a page is closed at a packet boundary once its body holds MORE than this ...
   OGG_MIN_PACKETS = 4,   // ... and at least this many packets have been completed on it
   OGG_CRC_LANES = 64,    // k_ogg_pages: chunks a page is summed in
-  OGG_CRC_MIN_CHUNK = 16 // ... none shorter than this (a short page leaves its first lanes empty)
+  OGG_CRC_MIN_CHUNK = 16, // ... none shorter than this (a short page leaves its first lanes empty)
+  // a live stream's carry: the packets with a segment on its open page -- at most 255 of them, 255 * 255 body bytes; on
+  // the device each at a multiple of 4, and 18 bytes behind them that k_ogg_pages' whole-word reads may touch
+  OGG_CARRY_BODY = OGG_MAX_SEGS * OGG_MAX_SEGS,
+  OGG_CARRY_BYTES = OGG_CARRY_BODY + 3 * OGG_MAX_SEGS + 18
 };
 #define VAMD_OGG_POLY 0x04c11db7u
 
@@ -93,9 +101,9 @@ VAMD_OGG_FN int32_t ogg_piece_len(int32_t bytes, int32_t start, int32_t take) {
 // first segment it closes the page if its body holds more than OGG_FILL bytes and OGG_MIN_PACKETS packets have been
 // completed on it; the end of a run closes its page.  A page's granule position is that of the last packet completed
 // on it, -1 where none is.
-// Whole streams start at granule position 0, so a1-encapsulation-ogg's rule for a stream that does not (the second audio
-// packet flushes its page, so that the decoder learns the offset at once) never applies here; a live form that resumes a
-// stream inside a file would have to add it where the audio run begins.
+// Every stream starts at granule position 0, so a1-encapsulation-ogg's rule for a stream that does not (the second audio
+// packet flushes its page, so that the decoder learns the offset at once) never applies here.  A live stream starts at 0
+// as well: it is the FILE that arrives in pieces, one walk interrupted at group boundaries (OggLive, below).
 struct OggPage {
   int64_t file_off;  // where the page starts in its stream's file
   int64_t granule;
@@ -245,6 +253,34 @@ VAMD_OGG_FN int64_t ogg_file_bound(int64_t packet_bytes, int64_t npackets, int64
   return packet_bytes + nstreams * ((int64_t)header_bytes[0] + header_bytes[1] + header_bytes[2]) + pages * (OGG_HEADER + OGG_MAX_SEGS);
 }
 
+
+// ---- a live feed: one walk per stream, interrupted at group boundaries ----
+// At the end of a group every packet has been taken completely, so the walk's state is its OggWalk: the open page, the
+// next sequence number and file_off, which stays absolute in the stream's file (the group's byte range starts at the
+// file_off the group began with).  The packets with a segment on the open page are carried: the next group's list is the
+// carried packets, then its own, and the open page's `first` is rebased to 0.  Of a continued first packet only the part
+// from byte0 on is carried -- byte0 is a multiple of 255, so the remainder laces exactly as a packet of its own (byte0
+// becomes 0; the continued flag stays in pg.flags).
+struct OggLive {
+  OggWalk w;
+  uint32_t serial;
+  int32_t started;  // the stream is open: its headers are out
+  int32_t dead;     // != 0: the VAMD_STATUS_* of the block that had no packet; no page until the stream is closed (0x80: the state is unusable)
+  int32_t ncarry;   // carried packets
+};
+enum { OGG_LIVE_BEGIN = 1, OGG_LIVE_CLOSE = 2, OGG_LIVE_ABSENT = 4 };  // a stream in a group: it starts / ends with it / is not there
+// the open page of a group's end, rebased onto the next group's list
+VAMD_OGG_FN void ogg_walk_rebase(OggWalk &w) { w.pg.first = 0, w.pg.byte0 = 0, w.npages = 0; }
+// Page slots per stream of a live group: the header slots, one for the carried page, and ogg_slots_per_packet per NEW
+// packet (every other page holds new packets only) ...
+VAMD_OGG_FN int64_t ogg_live_slots(const int32_t *header_bytes) { return ogg_header_slots(header_bytes) + 1; }
+// ... and the bytes a live group's pages take at most: ogg_file_bound of the new packets and every stream's full carry,
+// and the carried page's header and lacing
+VAMD_OGG_FN int64_t ogg_live_file_bound(int64_t packet_bytes, int64_t npackets, int64_t nstreams, const int32_t *header_bytes) {
+  return ogg_file_bound(packet_bytes + nstreams * OGG_CARRY_BODY, npackets + nstreams * OGG_MAX_SEGS, nstreams, header_bytes) +
+         nstreams * (OGG_HEADER + OGG_MAX_SEGS);
+}
+
 #if defined(__HIPCC__)
 // ---- the kernels ----
 // What the pager reads: the device mirror of the group's packets (bytes at the offsets of the output arena, each packet at
@@ -264,12 +300,38 @@ struct OggIn {
 };
 __device__ __forceinline__ int64_t ogg_slot_base(const OggIn &I, long s) { return s * I.header_slots + I.slots_per_packet * I.stream_start[s]; }
 
+// A live group (in == null: whole streams): per stream its state and carry as the last group left them, and where this
+// group's go -- the other of two buffers each, swapped by the host once the group has succeeded, so that a group laid out
+// twice advances its streams once.  A stream's carry: rec [2 * OGG_MAX_SEGS] (the packets' bytes, then where each lies in
+// its OGG_CARRY_BYTES of `bytes`, a multiple of 4).  flags: OGG_LIVE_*; gstart: the file_off a stream's group began with
+// (k_ogg_plan -> k_ogg_pages).  OggIn's header_slots are ogg_live_slots, serial[] names the streams that begin.
+struct OggLiveIO {
+  const OggLive *in;
+  OggLive *out;
+  const int32_t *rec_in;
+  const uint8_t *bytes_in;
+  int32_t *rec_out;
+  uint8_t *bytes_out;
+  const uint32_t *flags;
+  int64_t *gstart;
+};
+__device__ __forceinline__ int ogg_live_ncarry(const OggLiveIO &V, long s) {  // packets in front of the group's own in stream s's list
+  if (!V.in || (V.flags[s] & (OGG_LIVE_BEGIN | OGG_LIVE_ABSENT))) return 0;
+  const int n = V.in[s].ncarry;
+  return n < 0 || n > OGG_MAX_SEGS ? 0 : n;
+}
+
 // a wave per stream: its pages into its slots of the page table, the unused slots marked; file_bytes, npages, status.
 // 64 packets at a time: one coalesced load of their sizes and granule positions, a wave-wide scan of bytes and segments
 // into LDS, then a step per PAGE (ogg_stop_at in every lane, one ballot, ogg_walk_join) -- the walk is serial in pages
 // only, and never touches memory.  A stream in which a block has no packet gets no page at all.
+// A live group (V.in set): a stream that begins walks the headers and begins the audio run; an open one loads its walk --
+// the open page already counts the carried packets, which come first in the group's list -- and walks the new packets;
+// only a closing one ends the run.  file_bytes is what the group adds to the file.  A stream that lost a packet writes no
+// page from that group on and reports the block's status until it is closed.  The state behind the group goes to V.out
+// (ncarry and the rebase are k_ogg_carry's).
 __global__ __launch_bounds__(64) void k_ogg_plan(OggIn I, long nstreams, OggPage *__restrict__ pages, int64_t *__restrict__ file_bytes,
-                                                 int32_t *__restrict__ npages, uint8_t *__restrict__ status) {
+                                                 int32_t *__restrict__ npages, uint8_t *__restrict__ status, OggLiveIO V) {
   __shared__ int32_t sz[64], Bx[65], Sx[65];
   __shared__ int64_t gr[64];
   const long s = blockIdx.x;
@@ -285,14 +347,28 @@ __global__ __launch_bounds__(64) void k_ogg_plan(OggIn I, long nstreams, OggPage
     const unsigned long long m = __ballot(mine != 0);
     if (m) st = (unsigned)__shfl((int)mine, __ffsll((long long)m) - 1, 64);
   }
-  const bool none = st || (I.packet_total && *I.packet_total > I.cap);
   // every lane keeps the walk's state (it is the same in all of them); lane 0 alone writes pages
   const int64_t wcap = lane == 0 ? cap : 0;
   OggWalk w;
   ogg_walk_init(w, (int)s);
+  const unsigned lf = V.in ? V.flags[s] : (unsigned)(OGG_LIVE_BEGIN | OGG_LIVE_CLOSE);
+  const bool begin = lf & OGG_LIVE_BEGIN, absent = !begin && (lf & OGG_LIVE_ABSENT);
+  uint32_t serial = I.serial[s];
+  int ncarry = 0;
+  if (V.in && !begin && !absent) {
+    const OggLive old = V.in[s];
+    w = old.w, w.npages = 0, w.pg.stream = (int32_t)s;
+    serial = old.serial, ncarry = ogg_live_ncarry(V, s);
+    if (!old.started) st = 0x80u;  // (an open stream without a state)
+    if (old.dead) st = (unsigned)old.dead;
+  }
+  const int64_t gstart = w.file_off;
+  const bool none = st || absent || (I.packet_total && *I.packet_total > I.cap);
   if (!none) {
-    ogg_walk_headers(w, out, wcap, I.hdr_bytes);
-    ogg_run_begin(w, 2, 0);
+    if (begin) {
+      ogg_walk_headers(w, out, wcap, I.hdr_bytes);
+      ogg_run_begin(w, 2, 0);
+    }
     for (int64_t base = k0; base < k1; base += 64) {
       const int64_t k = base + lane;
       const int n = k1 - base < 64 ? (int)(k1 - base) : 64;
@@ -312,18 +388,25 @@ __global__ __launch_bounds__(64) void k_ogg_plan(OggIn I, long nstreams, OggPage
         const int why = lane >= c && lane < n ? ogg_stop_at(w.pg, Bx, Sx, sz, c, taken, lane) : 0;
         const unsigned long long m = __ballot(why != 0);
         const int j = m ? __ffsll((long long)m) - 1 : n;
-        ogg_walk_join(w, out, wcap, (int32_t)(base - k0), Bx, Sx, gr, &c, &taken, j, m ? __shfl(why, j, 64) : 0);
+        ogg_walk_join(w, out, wcap, ncarry + (int32_t)(base - k0), Bx, Sx, gr, &c, &taken, j, m ? __shfl(why, j, 64) : 0);
       }
     }
-    ogg_run_end(w, out, wcap, 1);
+    if (lf & OGG_LIVE_CLOSE) ogg_run_end(w, out, wcap, 1);
   }
   int np = __shfl(w.npages, 0, 64);
   if (np > cap) np = 0, st |= 0x80u;  // (the slot bound did not hold: no file rather than a cut one)
   for (int64_t i = np + lane; i < cap; i += 64) out[i].run = -1;
   if (lane == 0) {
-    file_bytes[s] = (none || (st & 0x80u)) ? 0 : w.file_off;
+    file_bytes[s] = (none || (st & 0x80u)) ? 0 : w.file_off - gstart;
     npages[s] = (none || (st & 0x80u)) ? 0 : np;
     status[s] = (uint8_t)st;
+    if (V.in) {
+      const bool open = !absent && !(lf & OGG_LIVE_CLOSE);
+      OggLive nx;
+      nx.w = w, nx.serial = serial, nx.started = open, nx.dead = open ? (int32_t)st : 0, nx.ncarry = 0;
+      V.out[s] = nx;
+      V.gstart[s] = gstart;
+    }
   }
 }
 
@@ -346,9 +429,11 @@ struct OggOut {
 //   nothing anyone reads, behind the arena's last page).  So no byte is written twice and no dword in parts.  A dword
 //   inside one piece is two aligned words of the mirror joined by v_alignbyte; one that straddles pieces (packets of a
 //   few bytes), the header or the page's end is put together byte by byte.
+// A live group (V.in set): a page's packets come from two sources -- the first ncarry of the stream's list lie in its
+// carry, the others in the mirror -- the serial number is the stream's own, and the page goes where the group's range has it.
 __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const OggPage *__restrict__ pages,
                                                   const int64_t *__restrict__ stream_off, const int32_t *__restrict__ npages,
-                                                  const uint8_t *__restrict__ status, OggOut O) {
+                                                  const uint8_t *__restrict__ status, OggOut O, OggLiveIO V) {
   __shared__ uint32_t table[256];
   __shared__ __attribute__((aligned(8))) uint8_t head[OGG_HEADER + OGG_MAX_SEGS + 6];
   __shared__ int32_t pdst[OGG_MAX_SEGS + 1];
@@ -365,7 +450,8 @@ __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const 
   const long s = pg.stream;
   for (int e = lane; e < 256; e += 64) table[e] = ogg_crc_entry((uint32_t)e);
   // the pieces and the lacing table
-  const int64_t kbase = I.stream_start[s] + pg.first;
+  const int ncarry = ogg_live_ncarry(V, s);
+  const int64_t kbase = I.stream_start[s] + pg.first - ncarry, kend = I.stream_start[s + 1];
   int carry_s = 0, carry_b = 0;
   bool bad = false;
   for (int j0 = 0; j0 < pg.npackets; j0 += 64) {
@@ -374,11 +460,22 @@ __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const 
     int32_t bytes = 0;
     const uint8_t *src = I.bytes;
     if (valid) {
-      if (pg.run == 2) {
-        const int64_t k = kbase + j, o = I.off[k];
-        bytes = (I.bits[k] + 7) >> 3;
-        if (bytes < 0 || o < 0 || o + bytes > I.cap) bad = true, bytes = 0;
-        else src = I.bytes + o;
+      if (pg.run == 2 && pg.first < 0) bad = true;
+      else if (pg.run == 2 && pg.first + j < ncarry) {
+        const int32_t *rec = V.rec_in + s * (2 * OGG_MAX_SEGS);
+        const int32_t o = rec[OGG_MAX_SEGS + pg.first + j];
+        bytes = rec[pg.first + j];
+        if (bytes < 0 || o < 0 || o + bytes > OGG_CARRY_BYTES - 18) bad = true, bytes = 0;
+        else src = V.bytes_in + s * OGG_CARRY_BYTES + o;
+      } else if (pg.run == 2) {
+        const int64_t k = kbase + j;
+        if (k < I.stream_start[s] || k >= kend) bad = true;
+        else {
+          const int64_t o = I.off[k];
+          bytes = (I.bits[k] + 7) >> 3;
+          if (bytes < 0 || o < 0 || o + bytes > I.cap) bad = true, bytes = 0;
+          else src = I.bytes + o;
+        }
       } else {
         const int h = pg.first + j;
         if (h > 2) bad = true;
@@ -413,7 +510,7 @@ __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const 
   if (__ballot(bad)) return;
   if (lane == 0) {
     pdst[pg.npackets] = pg.body;
-    ogg_page_header(pg, I.serial[s], head);
+    ogg_page_header(pg, V.in && !(V.flags[s] & OGG_LIVE_BEGIN) ? V.in[s].serial : I.serial[s], head);
   }
   __syncthreads();
   const int hlen = OGG_HEADER + pg.nseg, len = hlen + pg.body;
@@ -454,7 +551,7 @@ __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const 
     __syncthreads();
   }
   // stores
-  const int64_t g0 = stream_off[s] + pg.file_off, g1 = g0 + len;
+  const int64_t g0 = stream_off[s] + pg.file_off - (V.in ? V.gstart[s] : 0), g1 = g0 + len;
   const int64_t a0 = (g0 + 3) & ~(int64_t)3, a1 = (g1 + 3) & ~(int64_t)3;
   if (a1 > O.cap) return;
   for (int64_t a = a0 + 4 * lane; a < a1; a += 256) {
@@ -488,6 +585,82 @@ __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const 
     *(uint32_t *)(O.bytes + a) = word;
   }
 }
+
+// A live group, behind k_ogg_pages (which has read the old carry by then), a wave per stream: what lies on the page still
+// open -- of each of its packets the bytes and where they go, of a continued first packet the part from byte0 on -- out
+// of the old carry and the mirror into the other carry; then the rebase and ncarry into the state k_ogg_plan left in V.out.
+// A list that contradicts the page (never seen) costs the stream its state: status 0x80 from the next group on.
+__global__ __launch_bounds__(64) void k_ogg_carry(OggIn I, long nstreams, OggLiveIO V) {
+  __shared__ int32_t cb[OGG_MAX_SEGS], co[OGG_MAX_SEGS];
+  __shared__ const uint8_t *cs[OGG_MAX_SEGS];
+  const long s = blockIdx.x;
+  const int lane = threadIdx.x;
+  if (s >= nstreams || (I.packet_total && *I.packet_total > I.cap)) return;
+  const OggLive nx = V.out[s];
+  if (!nx.started || nx.dead) return;  // (ncarry is 0)
+  const OggPage pg = nx.w.pg;
+  const int ncarry = ogg_live_ncarry(V, s);
+  const int64_t k0 = I.stream_start[s], k1 = I.stream_start[s + 1];
+  const int np = pg.npackets;
+  // (the same in every lane: with it false, every index below is inside its list)
+  const bool bad0 = np < 0 || np > OGG_MAX_SEGS || pg.first < 0 || (np > 0 && pg.first + np != ncarry + (k1 - k0));
+  bool bad = bad0;
+  int at = 0, body = 0;
+  for (int j0 = 0; j0 < np && !bad0; j0 += 64) {
+    const int j = j0 + lane, v = pg.first + j;
+    int32_t bytes = 0;
+    const uint8_t *src = I.bytes;
+    if (j < np) {
+      if (v < ncarry) {
+        const int32_t *rec = V.rec_in + s * (2 * OGG_MAX_SEGS);
+        const int32_t o = rec[OGG_MAX_SEGS + v];
+        bytes = rec[v];
+        if (bytes < 0 || o < 0 || o + bytes > OGG_CARRY_BYTES - 18) bad = true, bytes = 0;
+        else src = V.bytes_in + s * OGG_CARRY_BYTES + o;
+      } else {
+        const int64_t k = k0 + (v - ncarry), o = I.off[k];
+        bytes = (I.bits[k] + 7) >> 3;
+        if (bytes < 0 || o < 0 || o + bytes > I.cap) bad = true, bytes = 0;
+        else src = I.bytes + o;
+      }
+      if (j == 0) {
+        if (pg.byte0 < 0 || pg.byte0 > bytes) bad = true;
+        else src += pg.byte0, bytes -= pg.byte0;
+      }
+    }
+    const int room = (bytes + 3) & ~3;
+    int incl = room, incb = bytes;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64), ub = __shfl_up(incb, d, 64);
+      if (lane >= d) incl += up, incb += ub;
+    }
+    if (j < np) cb[j] = bytes, co[j] = at + incl - room, cs[j] = src;
+    at += __shfl(incl, 63, 64), body += __shfl(incb, 63, 64);
+  }
+  if (body != pg.body || at > OGG_CARRY_BYTES - 18) bad = true;
+  bad = __ballot(bad) != 0;
+  __syncthreads();
+  int32_t *rec = V.rec_out + s * (2 * OGG_MAX_SEGS);
+  uint32_t *dst = (uint32_t *)(V.bytes_out + s * OGG_CARRY_BYTES);
+  if (!bad) {
+    for (int j = lane; j < np; j += 64) rec[j] = cb[j], rec[OGG_MAX_SEGS + j] = co[j];
+    for (int j = 0; j < np; j++) {  // whole words: a source word is two aligned words of the mirror (or the carry) joined
+      const uintptr_t p = (uintptr_t)cs[j];
+      const unsigned sh = (unsigned)(p & 3);
+      const uint32_t *wp = (const uint32_t *)(p & ~(uintptr_t)3);
+      for (int wd = lane; wd < (cb[j] + 3) >> 2; wd += 64) {
+        const uint32_t w0 = wp[wd], w1 = sh ? wp[wd + 1] : 0u;
+        dst[(co[j] >> 2) + wd] = __builtin_amdgcn_alignbyte(w1, w0, sh);
+      }
+    }
+  }
+  if (lane == 0) {
+    OggLive *o = V.out + s;
+    ogg_walk_rebase(o->w);
+    o->ncarry = bad ? 0 : np;
+    if (bad) o->dead = 0x80;
+  }
+}
 #endif  // __HIPCC__
 
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -514,14 +687,11 @@ inline uint32_t ogg_crc_chunked(const uint8_t *data, int64_t n, int min_chunk, i
   return part[0];
 }
 
-// a stream's pages from its packet sizes: pages[] (up to cap of them) <- the walk; returns their number, *file_bytes the file's
-inline int64_t ogg_plan_stream(const int32_t *header_bytes, int64_t npackets, const int32_t *bytes, const int64_t *granule,
-                               OggPage *pages, int64_t cap, int64_t *file_bytes) {
-  OggWalk w;
-  ogg_walk_init(w, 0);
-  if (header_bytes) ogg_walk_headers(w, pages, cap, header_bytes);
-  ogg_run_begin(w, 2, 0);
-  for (int64_t base = 0; base < npackets; base += 64) {  // as k_ogg_plan takes them: 64 packets at a time, a page per step
+// npackets more packets of the audio run, as k_ogg_plan takes them: 64 at a time, a page per step.  first: the place of
+// packet 0 in the list that the pages' `first` counts in.
+inline void ogg_walk_audio(OggWalk &w, OggPage *pages, int64_t cap, int32_t first, int64_t npackets, const int32_t *bytes,
+                           const int64_t *granule) {
+  for (int64_t base = 0; base < npackets; base += 64) {
     const int n = npackets - base < 64 ? (int)(npackets - base) : 64;
     int32_t Bx[65], Sx[65];
     Bx[0] = Sx[0] = 0;
@@ -531,9 +701,19 @@ inline int64_t ogg_plan_stream(const int32_t *header_bytes, int64_t npackets, co
       int j = c, why = 0;
       for (; j < n; j++)
         if ((why = ogg_stop_at(w.pg, Bx, Sx, bytes + base, c, taken, j)) != 0) break;
-      ogg_walk_join(w, pages, cap, (int32_t)base, Bx, Sx, granule + base, &c, &taken, j, why);
+      ogg_walk_join(w, pages, cap, first + (int32_t)base, Bx, Sx, granule + base, &c, &taken, j, why);
     }
   }
+}
+
+// a stream's pages from its packet sizes: pages[] (up to cap of them) <- the walk; returns their number, *file_bytes the file's
+inline int64_t ogg_plan_stream(const int32_t *header_bytes, int64_t npackets, const int32_t *bytes, const int64_t *granule,
+                               OggPage *pages, int64_t cap, int64_t *file_bytes) {
+  OggWalk w;
+  ogg_walk_init(w, 0);
+  if (header_bytes) ogg_walk_headers(w, pages, cap, header_bytes);
+  ogg_run_begin(w, 2, 0);
+  ogg_walk_audio(w, pages, cap, 0, npackets, bytes, granule);
   ogg_run_end(w, pages, cap, 1);
   if (file_bytes) *file_bytes = w.file_off;
   return w.npages;
@@ -570,6 +750,71 @@ inline int64_t ogg_mux(const uint8_t *const *headers, const int32_t *header_byte
     if (pg.run == 2) ogg_write_page(pg, serial, packets, bytes, out + pg.file_off);
     else ogg_write_page(pg, serial, headers, header_bytes, out + pg.file_off);
   }
+  return total;
+}
+
+// ---- a file in pieces (a live feed's groups; the second implementation k_ogg_plan / k_ogg_pages / k_ogg_carry are held
+// against) ----
+// A stream between two pieces: the walk with its open page, and the carried packets end to end
+struct OggPieces {
+  OggWalk w;
+  int32_t ncarry;
+  int32_t cbytes[OGG_MAX_SEGS];
+  uint8_t cdata[OGG_CARRY_BODY];
+};
+// The resumed walk over one group: begin (the stream starts here: T is reset, the headers walked when header_bytes is
+// given), npackets new packets behind the T.ncarry carried ones, close (the run ends).  pages[] <- the pages the group
+// completes, their file_off absolute; returns their number; T.w is the walk at the group's end, not yet rebased.
+inline int64_t ogg_plan_piece(OggPieces &T, int begin, const int32_t *header_bytes, int64_t npackets, const int32_t *bytes,
+                              const int64_t *granule, int close, OggPage *pages, int64_t cap) {
+  if (begin) {
+    ogg_walk_init(T.w, 0);
+    T.ncarry = 0;
+    if (header_bytes) ogg_walk_headers(T.w, pages, cap, header_bytes);
+    ogg_run_begin(T.w, 2, 0);
+  }
+  ogg_walk_audio(T.w, pages, cap, T.ncarry, npackets, bytes, granule);
+  if (close) ogg_run_end(T.w, pages, cap, 1);
+  return T.w.npages;
+}
+// One group of the mux in pieces: the bytes of the pages it completes into out (returned; written when they and the pages
+// fit), the next state and carry into T.  *open_page (optional): the page left open, as it stood before the rebase.
+inline int64_t ogg_mux_piece(OggPieces &T, int begin, const uint8_t *const *headers, const int32_t *header_bytes, int64_t npackets,
+                             const uint8_t *const *packets, const int32_t *bytes, const int64_t *granule, int close, uint32_t serial,
+                             uint8_t *out, int64_t cap, OggPage *pages, int64_t page_cap, int64_t *npages, OggPage *open_page) {
+  const int64_t start = begin ? 0 : T.w.file_off;
+  const int32_t nc = begin ? 0 : T.ncarry;
+  const int64_t np = ogg_plan_piece(T, begin, headers ? header_bytes : nullptr, npackets, bytes, granule, close, pages, page_cap);
+  const int64_t total = T.w.file_off - start;
+  if (npages) *npages = np;
+  if (open_page) *open_page = T.w.pg;
+  // the group's list: the carried packets, then its own
+  std::vector<const uint8_t *> list((size_t)(nc + npackets));
+  std::vector<int32_t> size((size_t)(nc + npackets));
+  int64_t at = 0;
+  for (int32_t v = 0; v < nc; v++) list[(size_t)v] = T.cdata + at, size[(size_t)v] = T.cbytes[v], at += T.cbytes[v];
+  for (int64_t k = 0; k < npackets; k++) list[(size_t)(nc + k)] = packets[k], size[(size_t)(nc + k)] = bytes[k];
+  if (np <= page_cap && total <= cap)
+    for (int64_t p = 0; p < np; p++) {
+      const OggPage &pg = pages[p];
+      if (pg.run == 2) ogg_write_page(pg, serial, list.data(), size.data(), out + (pg.file_off - start));
+      else ogg_write_page(pg, serial, headers, header_bytes, out + (pg.file_off - start));
+    }
+  // the next carry: what lies on the open page
+  const OggPage &pg = T.w.pg;
+  std::vector<uint8_t> data;
+  int32_t nb[OGG_MAX_SEGS];
+  for (int32_t j = 0; j < pg.npackets && j < OGG_MAX_SEGS; j++) {
+    const int32_t skip = j == 0 ? pg.byte0 : 0;
+    nb[j] = size[(size_t)(pg.first + j)] - skip;
+    data.insert(data.end(), list[(size_t)(pg.first + j)] + skip, list[(size_t)(pg.first + j)] + skip + nb[j]);
+  }
+  T.ncarry = close ? 0 : pg.npackets;
+  if (!close && data.size() <= (size_t)OGG_CARRY_BODY) {
+    memcpy(T.cbytes, nb, sizeof(int32_t) * (size_t)pg.npackets);
+    if (!data.empty()) memcpy(T.cdata, data.data(), data.size());
+  }
+  ogg_walk_rebase(T.w);
   return total;
 }
 #endif

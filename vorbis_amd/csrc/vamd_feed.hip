@@ -121,6 +121,12 @@ struct FeedLane {
   Pinned h_serial, h_ogg, h_orec;
   int32_t hdr_off[3] = {0, 0, 0};
   std::vector<uint32_t> serials, user_serials;  // the job's; what vamd_feed_ogg_serials set for it
+  // a live Ogg feed (vamd_feed_ogg_headers_live): per stream the pager's state and its carry -- the packets on the page
+  // still open -- in two buffers each; ogg_cur names the one the last group left, the next group writes the other
+  // (k_ogg.h, OggLiveIO).  ogg_flags: the group's OGG_LIVE_* per stream (run_group_live).
+  Buf d_olive[2], d_crec[2], d_cbytes[2], d_gstart;
+  int ogg_cur = 0;
+  std::vector<uint32_t> ogg_flags;
   vamd_feed_ogg_result ogg_result;
   std::vector<uint8_t> close_of;  // the job's closes (live)
   std::thread worker;
@@ -232,10 +238,26 @@ static size_t orec_status(long ns) { return orec_npages(ns) + (size_t)ns * 4; }
 // sized by ogg_slots_per_packet, the arena by ogg_file_bound of the PACKET arena's size -- packets that fit theirs make
 // files that fit this one.  d_packet_total (VBR): the packets' bytes on the device; beyond the arena nothing was mirrored
 // and nothing is paged (finish_group lays the group out again).
+// A live group (f->write_frames): the streams' states and carries go along (OggLiveIO), k_ogg_carry runs behind the pages;
+// what it and k_ogg_plan write is the OTHER state and carry, which pager_result makes the current ones -- so a group that
+// is laid out twice (finish_group) advances its streams once.
 static int run_pager(vamd_feed *f, FeedLane &L, const int64_t *d_stream_start, long ns, long nb, const int64_t *d_packet_total) {
   hipStream_t st = L.stream;
+  const bool live = f->write_frames != 0;
   int32_t hb[3];
   for (int i = 0; i < 3; i++) hb[i] = (int32_t)f->ogg_hdr[i].size();
+  if (live && !L.d_gstart.p) {  // the streams' states and carries: once per lane, for every stream it may carry
+    const size_t n = (size_t)f->max_streams;
+    for (int b = 0; b < 2; b++) {
+      FEED_TRY(L.d_olive[b].need(n * sizeof(vamd::OggLive)));
+      FEED_TRY(L.d_crec[b].need(n * 2 * vamd::OGG_MAX_SEGS * 4));
+      FEED_TRY(L.d_cbytes[b].need(n * vamd::OGG_CARRY_BYTES + 16));
+      FEED_TRY(hipMemsetAsync(L.d_olive[b].p, 0, L.d_olive[b].bytes, st));
+      FEED_TRY(hipMemsetAsync(L.d_crec[b].p, 0, L.d_crec[b].bytes, st));
+      FEED_TRY(hipMemsetAsync(L.d_cbytes[b].p, 0, L.d_cbytes[b].bytes, st));
+    }
+    FEED_TRY(L.d_gstart.need(n * 8));
+  }
   if (!L.d_hdr.p) {  // the header packets, each at a multiple of 4: once per lane
     size_t at = 0;
     for (int i = 0; i < 3; i++) L.hdr_off[i] = (int32_t)at, at += al((size_t)hb[i], 4);
@@ -244,15 +266,19 @@ static int run_pager(vamd_feed *f, FeedLane &L, const int64_t *d_stream_start, l
     FEED_TRY(L.d_hdr.need(img.size()));
     FEED_TRY(hipMemcpy(L.d_hdr.p, img.data(), img.size(), hipMemcpyHostToDevice));
   }
-  if ((long)L.serials.size() != ns || !L.d_mirror.p) {
+  if (live) L.serials.resize((size_t)ns, 0);  // (the lane's open streams beyond the caller's begin nothing)
+  if ((long)L.serials.size() != ns || !L.d_mirror.p || (live && (long)L.ogg_flags.size() != ns)) {
     L.err = "Ogg feed: the group has no serial numbers or no mirror";
     return VAMD_EFAULT;
   }
-  FEED_TRY(L.h_serial.need((size_t)ns * 4));
-  FEED_TRY(L.d_serial.need((size_t)ns * 4));
+  // [serial (ns) | a live group's flags (ns)]
+  FEED_TRY(L.h_serial.need((size_t)ns * 8));
+  FEED_TRY(L.d_serial.need((size_t)ns * 8));
   memcpy(L.h_serial.p, L.serials.data(), (size_t)ns * 4);
-  FEED_TRY(hipMemcpyAsync(L.d_serial.p, L.h_serial.p, (size_t)ns * 4, hipMemcpyHostToDevice, st));
-  const int64_t hs = vamd::ogg_header_slots(hb), sp = vamd::ogg_slots_per_packet(f->pkcap[0] > f->pkcap[1] ? f->pkcap[0] : f->pkcap[1]);
+  if (live) memcpy((uint32_t *)L.h_serial.p + ns, L.ogg_flags.data(), (size_t)ns * 4);
+  FEED_TRY(hipMemcpyAsync(L.d_serial.p, L.h_serial.p, (size_t)ns * (live ? 8 : 4), hipMemcpyHostToDevice, st));
+  const int64_t hs = live ? vamd::ogg_live_slots(hb) : vamd::ogg_header_slots(hb);
+  const int64_t sp = vamd::ogg_slots_per_packet(f->pkcap[0] > f->pkcap[1] ? f->pkcap[0] : f->pkcap[1]);
   const int64_t nslots = ns * hs + sp * nb;
   FEED_TRY(L.d_pages.need((size_t)nslots * sizeof(vamd::OggPage)));
   FEED_TRY(L.d_fbytes.need((size_t)ns * 8));
@@ -260,7 +286,8 @@ static int run_pager(vamd_feed *f, FeedLane &L, const int64_t *d_stream_start, l
   FEED_TRY(L.d_npages.need((size_t)ns * 4));
   FEED_TRY(L.d_ostatus.need((size_t)ns));
   FEED_TRY(L.h_orec.need(al(orec_status(ns) + (size_t)ns, 16)));
-  FEED_TRY(L.h_ogg.need(al((size_t)vamd::ogg_file_bound((int64_t)L.h_out.bytes, nb, ns, hb) + 16, 4096)));
+  const int64_t bound = live ? vamd::ogg_live_file_bound((int64_t)L.h_out.bytes, nb, ns, hb) : vamd::ogg_file_bound((int64_t)L.h_out.bytes, nb, ns, hb);
+  FEED_TRY(L.h_ogg.need(al((size_t)bound + 16, 4096)));
   void *drec = nullptr, *dbytes = nullptr;
   FEED_TRY(hipHostGetDevicePointer(&drec, L.h_orec.p, 0));
   FEED_TRY(hipHostGetDevicePointer(&dbytes, L.h_ogg.p, 0));
@@ -277,31 +304,49 @@ static int run_pager(vamd_feed *f, FeedLane &L, const int64_t *d_stream_start, l
   uint8_t *dr = (uint8_t *)drec;
   O.total = (int64_t *)dr, O.stream_offset = (int64_t *)(dr + 8), O.npages = (int32_t *)(dr + orec_npages(ns)), O.status = dr + orec_status(ns);
   O.bytes = (uint8_t *)dbytes, O.cap = (int64_t)L.h_ogg.bytes;
+  vamd::OggLiveIO V;
+  memset(&V, 0, sizeof(V));
+  if (live) {
+    const int a = L.ogg_cur, b = 1 - a;
+    V.in = (const vamd::OggLive *)L.d_olive[a].p, V.out = (vamd::OggLive *)L.d_olive[b].p;
+    V.rec_in = (const int32_t *)L.d_crec[a].p, V.rec_out = (int32_t *)L.d_crec[b].p;
+    V.bytes_in = (const uint8_t *)L.d_cbytes[a].p, V.bytes_out = (uint8_t *)L.d_cbytes[b].p;
+    V.flags = (const uint32_t *)L.d_serial.p + ns, V.gstart = (int64_t *)L.d_gstart.p;
+  }
   hipLaunchKernelGGL(vamd::k_ogg_plan, dim3((unsigned)ns), dim3(64), 0, st, I, ns, (vamd::OggPage *)L.d_pages.p, (int64_t *)L.d_fbytes.p,
-                     (int32_t *)L.d_npages.p, (uint8_t *)L.d_ostatus.p);
+                     (int32_t *)L.d_npages.p, (uint8_t *)L.d_ostatus.p, V);
   hipLaunchKernelGGL(k_feed_scan, dim3(1), dim3(1024), 0, st, ns, (const int64_t *)L.d_fbytes.p, (int64_t *)L.d_foff.p);
   hipLaunchKernelGGL(vamd::k_ogg_pages, dim3((unsigned)nslots), dim3(64), 0, st, I, ns, (const vamd::OggPage *)L.d_pages.p,
-                     (const int64_t *)L.d_foff.p, (const int32_t *)L.d_npages.p, (const uint8_t *)L.d_ostatus.p, O);
+                     (const int64_t *)L.d_foff.p, (const int32_t *)L.d_npages.p, (const uint8_t *)L.d_ostatus.p, O, V);
+  if (live) hipLaunchKernelGGL(vamd::k_ogg_carry, dim3((unsigned)ns), dim3(64), 0, st, I, ns, V);
   FEED_TRY(hipGetLastError());
   return VAMD_OK;
 }
 
-// ... and after the group's wait: what vamd_feed_ogg hands out
-static int pager_result(vamd_feed *f, FeedLane &L, long ns) {
-  (void)f;
+// ... and after the group's wait: what vamd_feed_ogg hands out (of a live group's ns streams the caller's first ns_out;
+// the others completed no page), and the live streams' states advance
+static int pager_result(vamd_feed *f, FeedLane &L, long ns, long ns_out) {
   const uint8_t *hr = (const uint8_t *)L.h_orec.p;
   vamd_feed_ogg_result &R = L.ogg_result;
-  R.nstreams = ns;
+  R.nstreams = ns_out;
   R.stream_offset = (const int64_t *)(hr + 8), R.npages = (const int32_t *)(hr + orec_npages(ns)), R.status = hr + orec_status(ns);
   R.bytes = (const uint8_t *)L.h_ogg.p, R.total_bytes = *(const int64_t *)hr;
   for (long s = 0; s < ns; s++)
     if (R.status[s] & 0x80) {
-      L.err = "Ogg feed: a stream needed more pages than its slots of the page table";
+      L.err = f->write_frames ? "Ogg feed: a stream needed more pages than its slots of the page table, or its live state does not hold"
+                              : "Ogg feed: a stream needed more pages than its slots of the page table";
       return VAMD_EFAULT;
     }
   if (R.total_bytes + 4 > (int64_t)L.h_ogg.bytes) {
     L.err = "Ogg feed: the files exceed the bound their arena was sized by";
     return VAMD_EFAULT;
+  }
+  if (f->write_frames) {
+    if (R.stream_offset[ns_out] != R.total_bytes) {
+      L.err = "Ogg feed: a stream outside the group completed a page";
+      return VAMD_EFAULT;
+    }
+    L.ogg_cur = 1 - L.ogg_cur;
   }
   return VAMD_OK;
 }
@@ -525,10 +570,14 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
     FEED_TRY(hipGetLastError());
     base = need;
   }
+  if (f->ogg && sl.empty()) {  // (a live group without a block: no slice has made the mirror the pager is given)
+    FeedOut O;
+    FEED_OWN(feed_out(f, L, R, nb, 0, O));
+  }
   if (f->ogg) FEED_OWN(run_pager(f, L, plan.stream_start, ns, nb, nullptr));
   FEED_TRY(hipEventRecord(L.ev_end, st));
   FEED_TRY(hipEventSynchronize(L.ev_end));
-  if (f->ogg) FEED_OWN(pager_result(f, L, ns));
+  if (f->ogg) FEED_OWN(pager_result(f, L, ns, ns_out));
   uint8_t *hrec = (uint8_t *)L.h_rec.p;  // (the total and stream_start, which a VBR group's copy kernel writes, from here)
   *(int64_t *)hrec = base;
   memcpy(hrec + R.start, start.data(), (size_t)(ns + 1) * 8);
@@ -583,7 +632,7 @@ static int finish_group(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan,
     FEED_TRY(hipEventSynchronize(L.ev_end));
     const int64_t total = *(const int64_t *)L.h_rec.p;
     if (total <= (int64_t)L.h_out.bytes) {
-      if (f->ogg) FEED_OWN(pager_result(f, L, ns));
+      if (f->ogg) FEED_OWN(pager_result(f, L, ns, ns_out));
       feed_result(L, R, ns_out, nb, total);
       return VAMD_OK;
     }
@@ -780,6 +829,13 @@ static int run_group_live(vamd_feed *f, FeedLane &L) {
       return VAMD_EFAULT;
     }
   }
+  if (f->ogg) {  // what the pager needs to know of each stream: it begins with this group, ends with it, or is not there
+    L.ogg_flags.assign((size_t)ns, 0);
+    for (long i = 0; i < ns; i++) {
+      const bool absent = hin[i].fresh && !hin[i].frames;
+      L.ogg_flags[(size_t)i] = absent ? vamd::OGG_LIVE_ABSENT : (hin[i].fresh ? vamd::OGG_LIVE_BEGIN : 0) | (hin[i].close ? vamd::OGG_LIVE_CLOSE : 0);
+    }
+  }
   FeedLive live;
   live.in = d_live, live.nan = (const unsigned long long *)L.d_nan.p;
   const int r = finish_group(f, L, plan, pcm, ns, ss, cs, nullptr, live, nsc);
@@ -934,12 +990,18 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
 
 // an Ogg feed's group (f->m held): its serial numbers -- the next nstreams of the feed's running counter, then what
 // vamd_feed_ogg_serials set for the slot in their place
+// A live group: a serial number belongs to a stream, not to a group -- only a stream that begins with this group (its
+// slot is free and the piece has frames) takes one, the counter's next or the one named for it; an open stream keeps its own.
 static void ogg_job(vamd_feed *f, FeedLane &L, long nstreams) {
   memset(&L.ogg_result, 0, sizeof(L.ogg_result));
   if (!f->ogg) return;
-  L.serials.resize((size_t)nstreams);
-  for (long s = 0; s < nstreams; s++) L.serials[(size_t)s] = f->next_serial++;
-  for (size_t s = 0; s < L.user_serials.size() && s < (size_t)nstreams; s++) L.serials[s] = L.user_serials[s];
+  L.serials.assign((size_t)nstreams, 0);
+  for (long s = 0; s < nstreams; s++)
+    if (!f->write_frames) L.serials[(size_t)s] = f->next_serial++;
+    else if (!L.live[(size_t)s].open && L.frames_of[(size_t)s])
+      L.serials[(size_t)s] = (size_t)s < L.user_serials.size() ? L.user_serials[(size_t)s] : f->next_serial++;
+  if (!f->write_frames)
+    for (size_t s = 0; s < L.user_serials.size() && s < (size_t)nstreams; s++) L.serials[s] = L.user_serials[s];
   L.user_serials.clear();
 }
 
@@ -962,7 +1024,7 @@ static int await_group(vamd_feed *f, int slot, R FeedLane::*result, R *out, bool
   if (!f || !out || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
   std::unique_lock<std::mutex> g(f->m);
   if (ogg && !f->ogg) {
-    f->err = "vamd_feed_ogg: the feed has no Ogg headers (vamd_feed_ogg_headers)";
+    f->err = "vamd_feed_ogg: the feed has no Ogg headers (vamd_feed_ogg_headers / vamd_feed_ogg_headers_live)";
     return VAMD_EINVAL;
   }
   FeedLane &L = f->lanes[(size_t)slot];
@@ -975,18 +1037,11 @@ static int await_group(vamd_feed *f, int slot, R FeedLane::*result, R *out, bool
 
 static uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
-extern "C" {
-
-int vamd_feed_ogg_headers(vamd_feed *f, const void *id, long id_bytes, const void *comment, long comment_bytes, const void *setup,
-                          long setup_bytes) {
-  if (!f) return VAMD_EINVAL;
-  std::lock_guard<std::mutex> g(f->m);
-  if (f->write_frames) {
-    f->err = "Ogg files of a live feed are not implemented (a page may span two groups)";
-    return VAMD_EIMPL;
-  }
+// vamd_feed_ogg_headers / _live (f->m held; `call` names the one): the three packets validated, the feed an Ogg feed
+static int ogg_headers_set(vamd_feed *f, const char *call, const void *id, long id_bytes, const void *comment, long comment_bytes,
+                           const void *setup, long setup_bytes) {
   if (f->turn) {
-    f->err = "vamd_feed_ogg_headers comes before the first vamd_feed_buffer";
+    f->err = std::string(call) + " comes before the first vamd_feed_buffer";
     return VAMD_EINVAL;
   }
   const uint8_t *pk[3] = {(const uint8_t *)id, (const uint8_t *)comment, (const uint8_t *)setup};
@@ -1016,6 +1071,30 @@ int vamd_feed_ogg_headers(vamd_feed *f, const void *id, long id_bytes, const voi
   for (int i = 0; i < 3; i++) f->ogg_hdr[i].assign(pk[i], pk[i] + n[i]);
   f->ogg = true;
   return VAMD_OK;
+}
+
+extern "C" {
+
+int vamd_feed_ogg_headers(vamd_feed *f, const void *id, long id_bytes, const void *comment, long comment_bytes, const void *setup,
+                          long setup_bytes) {
+  if (!f) return VAMD_EINVAL;
+  std::lock_guard<std::mutex> g(f->m);
+  if (f->write_frames) {
+    f->err = "a live feed returns its Ogg files in pieces, a contract of its own: vamd_feed_ogg_headers_live";
+    return VAMD_EIMPL;
+  }
+  return ogg_headers_set(f, "vamd_feed_ogg_headers", id, id_bytes, comment, comment_bytes, setup, setup_bytes);
+}
+
+int vamd_feed_ogg_headers_live(vamd_feed *f, const void *id, long id_bytes, const void *comment, long comment_bytes, const void *setup,
+                               long setup_bytes) {
+  if (!f) return VAMD_EINVAL;
+  std::lock_guard<std::mutex> g(f->m);
+  if (!f->write_frames) {
+    f->err = "vamd_feed_ogg_headers_live is for a live feed (vamd_feed_create_live); a whole-stream feed takes vamd_feed_ogg_headers";
+    return VAMD_EINVAL;
+  }
+  return ogg_headers_set(f, "vamd_feed_ogg_headers_live", id, id_bytes, comment, comment_bytes, setup, setup_bytes);
 }
 
 int vamd_feed_ogg_serials(vamd_feed *f, int slot, const uint32_t *serials, long n) {
@@ -1124,7 +1203,7 @@ int vamd_feed_wrote_live(vamd_feed *f, int slot, long nstreams, const int64_t *f
   L.close_of.assign((size_t)nstreams, 0);
   if (close)
     for (long i = 0; i < nstreams; i++) L.close_of[(size_t)i] = close[i] != 0;
-  return queue_group(f, L, nstreams, f->max_frames);  // (no Ogg files of a live feed: vamd_feed_ogg_headers)
+  return queue_group(f, L, nstreams, f->max_frames);
 }
 
 int vamd_feed_packets(vamd_feed *f, int slot, vamd_feed_result *out) { return await_group(f, slot, &FeedLane::result, out, false); }
