@@ -25,6 +25,38 @@ namespace vamd {
 
 #define VAMD_MAXPOSTS 32
 
+// ---- round 12: what a wave used to redo for every channel-block although it depends on the setup alone ----------------
+// (profiles/r12_floor_phases.txt; each switch can be turned the other way with -D...=0 for an A/B of its own)
+//   * VAMD_FL_TABLES_ONCE: one set of post tables per channel-block (PostTables), handed from the fit to the quantiser
+//     to the curve; every stage used to fetch its own.
+//   * VAMD_FL_GLOBAL_ADDR (vamd_wave.h): the tables behind PsyP / FloorP addressed as device memory.
+//   * VAMD_FL_SEG_ROLLED: the fit's work-list loop rolled (floor_fit_posts): no value spilt to scratch round it.
+//   * VAMD_FL_OFFSET_AHEAD: fold_and_mix_wave asks for a quad's noise offsets together with its noise and spectrum.
+// Same arithmetic on the same operands; only where an operand comes from changes.
+#ifndef VAMD_FL_TABLES_ONCE
+#define VAMD_FL_TABLES_ONCE 1
+#endif
+#ifndef VAMD_FL_OFFSET_AHEAD
+#define VAMD_FL_OFFSET_AHEAD 1
+#endif
+#ifndef VAMD_FL_SEG_ROLLED
+#define VAMD_FL_SEG_ROLLED 1
+#endif
+#if !VAMD_GPU
+#define VAMD_FL_SEG_LOOP
+#elif VAMD_FL_SEG_ROLLED
+#define VAMD_FL_SEG_LOOP _Pragma("unroll 1")
+#else
+#define VAMD_FL_SEG_LOOP _Pragma("unroll 4")
+#endif
+// scratch builds for the phase profile (tools/fl_phases_pmc.sh): -DVAMD_COUNT_CALLS turns the stopwatch's slots into event
+// counters -- slot 0 inspect_error_wave calls, slot 1 fit_line_pair calls of the split loop, summed over the waves
+#if VAMD_GPU && defined(VAMD_COUNT_CALLS)
+#define VAMD_FL_COUNT(pc, k) ((pc).acc[(k)] += 1)
+#else
+#define VAMD_FL_COUNT(pc, k) ((void)0)
+#endif
+
 #include "k_floor.inc"
 
 }  // namespace vamd

@@ -25,12 +25,14 @@ struct FloorScratch {
 // _vp_offset_and_mix with offset_select == 1 (the only select the VBR path uses), for one quad of bins:
 //   nz / tn / md  noise curve, tone curve, spectrum (md is scaled in place: AoTuV M1);  mk  the mask out
 // Returns what the fit reads of the four bins: 16 bits each (see offset_and_mix_wave).
-VAMD_DEV I2 offset_and_mix_quad(const PsyP &P, int q, const float *nz, const float *tn, float *md, float *mk, float twofitatten) {
+//   no_ahead  (optional) the quad of P.noiseoffset1, fetched by the caller beside its own streams
+VAMD_DEV I2 offset_and_mix_quad(const PsyP &P, int q, const float *nz, const float *tn, float *md, float *mk, float twofitatten,
+                                const F4 *no_ahead = nullptr) {
   const float toneatt = P.tone_masteratt1;
   const float cx = P.m_val;
   const float coeffi = -17.2f;  // float coeffi = -17.2 (lib/psy.c:808)
   float no[4], lmv[4];
-  f4_get(((const F4 *)P.noiseoffset1)[q], no);
+  f4_get(no_ahead ? *no_ahead : dm_load_f4(P.noiseoffset1, (unsigned)q << 4), no);
   // logmdct (lib/mapping0.c:384-385) is a function of the spectrum that is read here anyway: recomputed, not
   // fetched -- the transform stage need not write it, nor this one read it (16 KB per stereo block)
   for (int c = 0; c < 4; c++) lmv[c] = todB_345(md[c]);
@@ -67,13 +69,14 @@ VAMD_DEV void offset_and_mix_wave(const PsyP &P, const float *__restrict__ noise
   const int n = P.n;
   WAVE_FOR(q, n >> 2) {
     float nz[4], tn[4], md[4], mk[4];
-    f4_get(((const F4 *)noise)[q], nz);
-    f4_get(((const F4 *)tone)[q], tn);
-    f4_get(((const F4 *)mdct_io_src)[q], md);
+    const unsigned int qo = (unsigned)q << 4;  // the quad's byte offset in every float stream
+    f4_get(dm_load_f4(noise, qo), nz);
+    f4_get(dm_load_f4(tone, qo), tn);
+    f4_get(dm_load_f4(mdct_io_src, qo), md);
     const I2 pk = offset_and_mix_quad(P, q, nz, tn, md, mk, twofitatten);
-    if (logmask_out) ((F4 *)logmask_out)[q] = f4_make(mk);
+    if (logmask_out) dm_store_f4(logmask_out, qo, f4_make(mk));
     ((I2 *)qc)[q] = pk;
-    ((F4 *)mdct_out)[q] = f4_make(md);
+    dm_store_f4(mdct_out, qo, f4_make(md));
   }
   WAVE_SYNC();
   pc.mark(0);
@@ -92,13 +95,21 @@ VAMD_DEV void fold_and_mix_wave(const PsyP &P, float att, const float *seed, con
   I2 keep[VAMD_QPL];
   LANE_QUADS(kq, q, n >> 2) {
     float nz[4], tn[4], md[4], mk[4];
-    f4_get(((const F4 *)noise)[q], nz);
-    f4_get(((const F4 *)mdct_io_src)[q], md);
+    const unsigned int qo = (unsigned)q << 4;  // the quad's byte offset in every float stream
+    f4_get(dm_load_f4(noise, qo), nz);
+    f4_get(dm_load_f4(mdct_io_src, qo), md);
+#if VAMD_FL_OFFSET_AHEAD
+    // (asked for here, with the quad's other streams: behind the fold and the tap's store it was waited for on the spot)
+    const F4 no4 = dm_load_f4(P.noiseoffset1, qo);
+    const F4 *no_ahead = &no4;
+#else
+    const F4 *no_ahead = nullptr;
+#endif
     tone_fold_quad(P, att, seed, gmin, q, tn);
-    if (tone_out) ((F4 *)tone_out)[q] = f4_make(tn);
-    keep[kq] = offset_and_mix_quad(P, q, nz, tn, md, mk, twofitatten);
-    if (logmask_out) ((F4 *)logmask_out)[q] = f4_make(mk);
-    ((F4 *)mdct_out)[q] = f4_make(md);
+    if (tone_out) dm_store_f4(tone_out, qo, f4_make(tn));
+    keep[kq] = offset_and_mix_quad(P, q, nz, tn, md, mk, twofitatten, no_ahead);
+    if (logmask_out) dm_store_f4(logmask_out, qo, f4_make(mk));
+    dm_store_f4(mdct_out, qo, f4_make(md));
   }
   WAVE_SYNC();  // nobody reads seed lines any more
   LANE_QUADS(kq, q, n >> 2)((I2 *)qc)[q] = keep[kq];
@@ -117,10 +128,11 @@ VAMD_DEV void mask_quantise_wave(const PsyP &P, int offset_select, const float *
   const float *__restrict__ noff = offset_select ? P.noiseoffset2 : P.noiseoffset0;
   WAVE_FOR(q, n >> 2) {
     float nz[4], no[4], tn[4], lmv[4];
-    f4_get(((const F4 *)noise)[q], nz);
-    f4_get(((const F4 *)noff)[q], no);
-    f4_get(((const F4 *)tone)[q], tn);
-    f4_get(((const F4 *)mdct_raw_in)[q], lmv);
+    const unsigned int qo = (unsigned)q << 4;
+    f4_get(dm_load_f4(noise, qo), nz);
+    f4_get(dm_load_f4(noff, qo), no);
+    f4_get(dm_load_f4(tone, qo), tn);
+    f4_get(dm_load_f4(mdct_raw_in, qo), lmv);
     for (int c = 0; c < 4; c++) lmv[c] = todB_345(lmv[c]);  // logmdct, lib/mapping0.c:384-385
     uint32_t w[2] = {0, 0};
     for (int c = 0; c < 4; c++) {
@@ -148,8 +160,9 @@ VAMD_DEV void mask_quantise_wave(const PsyP &P, int offset_select, const float *
 // once for all bins and once for class a (mdct + twofitatten >= mask, bit 15); class b is the difference.  With
 // i = base + c:  sum i = base*n + sum c,  sum i*i = base*base*n + 2*base*sum c + sum c*c,  sum i*q = base*sum q +
 // sum c*q -- integer identities, so the totals are the reference's (lib/floor1.c:416-436).
-VAMD_DEV int accumulate_segment(const unsigned int *rec, const unsigned short *qc, FitAcc *acc) {
-  const I4 h = ((const I4 *)rec)[0], m0 = ((const I4 *)rec)[1], m1 = ((const I4 *)rec)[2];
+VAMD_DEV int accumulate_segment(const unsigned int *segs, int sg, const unsigned short *qc, FitAcc *acc) {
+  const unsigned int ro = (unsigned)sg * (4u * VAMD_FITSEG_WORDS);  // record sg of the list
+  const I4 h = dm_load_i4(segs, ro), m0 = dm_load_i4(segs, ro + 16u), m1 = dm_load_i4(segs, ro + 32u);
   const int chunk = h.x;
   const I4 qa = ((const I4 *)qc)[2 * chunk], qb = ((const I4 *)qc)[2 * chunk + 1];
   const unsigned int w[8] = {(unsigned)(qa.x & m0.x), (unsigned)(qa.y & m0.y), (unsigned)(qa.z & m0.z),
@@ -219,7 +232,7 @@ VAMD_DEV LineStep line_step(int x0, int x1, int y0, int y1, const unsigned int *
   const int dy = y1 - y0;
   s.ady = dy < 0 ? -dy : dy;
   s.sgn = dy < 0 ? -1 : 1;
-  s.magic = magic[x1 - x0];
+  s.magic = dm_load<unsigned int>(magic, 4u * (unsigned)(x1 - x0));
   return s;
 }
 VAMD_DEV int line_y(const LineStep &s, int y0, int k) { return y0 + s.sgn * div_magic(mad24(k, s.ady, 0), s.magic); }
@@ -305,9 +318,38 @@ struct PostSteps {
       const int x0 = postlist.gather(lo2.at(i)), x1 = postlist.gather(hi2.at(i));
       if (i >= 2) {
         k.put(i, postlist.at(i) - x0);
-        magic.put(i, (int)F.div_magic[x1 - x0]);
+        magic.put(i, (int)dm_load<unsigned int>(F.div_magic, 4u * (unsigned)(x1 - x0)));
       }
     }
+  }
+};
+
+// The look's tables that the fit, the quantiser and the curve of a channel-block share, one post per lane.  They depend on
+// the setup alone: fetched once per channel-block (VAMD_FL_TABLES_ONCE, k_floor.h) and handed from stage to stage -- the
+// list when the fit begins, the rest when its split loop is through (the loop holds a dozen lane arrays of its own) --
+// where each stage used to fetch its own copy.
+VAMD_DEV void load_post_table(LaneInts &t, const int *p, int shift, int count) {  // LaneInts::load_shifted out of the image
+#if VAMD_GPU
+  t.fill((LANE >= shift && LANE < count) ? dm_load<int>(p, 4u * (unsigned)(LANE - shift)) : 0);
+#else
+  t.load_shifted(p, shift, count);
+#endif
+}
+struct PostTables {
+  LaneInts postlist, forward_index, lo2, hi2, level;
+  PostSteps ps;
+  bool have_steps;
+  VAMD_MEM void load_list(const FloorP &F) {
+    load_post_table(postlist, F.postlist, 0, F.posts);
+    have_steps = false;
+  }
+  VAMD_MEM void load_steps(const FloorP &F, bool with_forward = true) {
+    load_post_table(lo2, F.loneighbor, 2, F.posts);
+    load_post_table(hi2, F.hineighbor, 2, F.posts);
+    load_post_table(level, F.level, 0, F.posts);
+    if (with_forward) load_post_table(forward_index, F.forward_index, 0, F.posts);
+    ps.load(F, postlist, lo2, hi2);
+    have_steps = true;
   }
 };
 
@@ -403,7 +445,7 @@ VAMD_DEV void floor_render_curve(const FloorP &F, int posts, int n2, const LaneI
   pc.mark(3);
   if (ilogmask) {
     WAVE_FOR(q, n2 >> 2) {
-      const unsigned int jq = ((const unsigned int *)F.bin_interval)[q];
+      const unsigned int jq = dm_load<unsigned int>(F.bin_interval, (unsigned)q << 2);
       int v[4];
 #pragma unroll
       for (int c = 0; c < 4; c++) {
@@ -412,7 +454,7 @@ VAMD_DEV void floor_render_curve(const FloorP &F, int posts, int n2, const LaneI
         const int k = 4 * q + c - r.x0;
         v[c] = mad24(div_magic(mad24(k, r.ady, 0), r.magic), r.sgn, r.y0);
       }
-      ((unsigned int *)ilogmask)[q] = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);  // (ilog_t)
+      dm_store<unsigned int>(ilogmask, (unsigned)q << 2, (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24));  // (ilog_t)
     }
   }
 }
@@ -424,16 +466,19 @@ VAMD_DEV void floor_render_curve(const FloorP &F, int posts, int n2, const LaneI
 //   qc    LDS [n2]   quantised mask + class bit, see offset_and_mix_wave
 //   outp  floor1_fit's return, one post per lane (bit 15 = unused flag); untouched when it returns 0
 // Returns 1, or 0 where the reference returns NULL (nothing above the fit's floor).
+//   T     (optional) the block's post tables, the list loaded: the rest is loaded here, after the split loop, unless the
+//         caller has it already; without T the fit fetches its own
 VAMD_DEV int floor_fit_posts(const FloorP &F, const unsigned short *qc, FloorScratch *sc, LaneInts &outp,
-                             PhaseClock &pc) {
-  const int posts = F.posts, n = F.look_n;
+                             PhaseClock &pc, PostTables *T = nullptr) {
+  const int posts = F.posts;
 
-  LaneInts postlist, sorted_index, reverse_index, hineighbor, loneighbor;
-  postlist.load(F.postlist, posts);
-  sorted_index.load(F.sorted_index, posts);
-  reverse_index.load(F.reverse_index, posts);
-  hineighbor.load(F.hineighbor, posts);
-  loneighbor.load(F.loneighbor, posts);
+  PostTables own;
+  if (!T) own.load_list(F);
+  PostTables &tb = T ? *T : own;
+  const LaneInts &postlist = tb.postlist;
+  LaneInts sorted_index, reverse_index;
+  load_post_table(sorted_index, F.sorted_index, 0, posts);
+  load_post_table(reverse_index, F.reverse_index, 0, posts);
   LaneInts fitA, fitB, lon, hin, memo;
   fitA.fill(-200);
   fitB.fill(-200);
@@ -446,7 +491,9 @@ VAMD_DEV int floor_fit_posts(const FloorP &F, const unsigned short *qc, FloorScr
   // accumulate_fit for all post intervals at once, a lane per record of the floor's work list (integer adds
   // commute, so the totals equal the reference's sequential sums)
   int nz = 0;
-  WAVE_FOR(sg, F.fit_nseg) nz += accumulate_segment(F.fit_segs + VAMD_FITSEG_WORDS * sg, qc, sc->acc);
+  // (a lane has one or two records: the list is rolled, not WAVE_FOR's four records a trip -- a body of sixteen bins four
+  // times over held values across it that no longer fitted the stage's 64 registers)
+  VAMD_FL_SEG_LOOP for (int sg = LANE; sg < F.fit_nseg; sg += NLANES) nz += accumulate_segment(F.fit_segs, sg, qc, sc->acc);
   nz = wave_sum(nz);
   WAVE_SYNC();
   // lane i forms interval i's fit_line contribution; the terms go to LDS as rows for fit_line_pair, each over its own
@@ -489,7 +536,9 @@ VAMD_DEV int floor_fit_posts(const FloorP &F, const unsigned short *qc, FloorScr
       const int ly = post_Y(fitA, fitB, ln);
       const int hy = post_Y(fitA, fitB, hn);
       // (ly == -1 || hy == -1 => exit(1) in the reference: unreachable, fits are >= 0 or -200)
+      VAMD_FL_COUNT(pc, 0);  // (scratch builds: inspect_error / fit_line_pair calls per block)
       if (inspect_error_wave(lx, hx, ly, hy, qc, F)) {
+        VAMD_FL_COUNT(pc, 1);
         int ly0 = -200, ly1 = -200, hy0 = -200, hy1 = -200;
         int ret0, ret1;
         fit_line_pair((const double *)sc->acc, sc->pair_sums, lsortpos, sortpos - lsortpos, sorted_index.get(lsortpos),
@@ -528,12 +577,9 @@ VAMD_DEV int floor_fit_posts(const FloorP &F, const unsigned short *qc, FloorScr
   pc.mark(2);
   // ---- posts out, lib/floor1.c:700-724.  Post i is settled from its two fixed neighbours, so
   // the list order of the reference can be replaced by dependency levels: one lane per post.
-  LaneInts lo2, hi2, level;
-  lo2.load_shifted(F.loneighbor, 2, posts);
-  hi2.load_shifted(F.hineighbor, 2, posts);
-  level.load(F.level, posts);
-  PostSteps ps;
-  ps.load(F, postlist, lo2, hi2);
+  if (!tb.have_steps) tb.load_steps(F, T != nullptr);
+  const LaneInts &lo2 = tb.lo2, &hi2 = tb.hi2, &level = tb.level;
+  const PostSteps &ps = tb.ps;
   LaneInts fitted;  // the post's own fit (the mean of its two sides), settled before the levels
   fitted.fill(0);
   WAVE_FOR(i, posts) {
@@ -563,13 +609,18 @@ VAMD_DEV int floor_fit_posts(const FloorP &F, const unsigned short *qc, FloorScr
 //   post     <- quantised values, bit 15 = unused (then the value is the prediction)
 //   wrapped  <- (optional) out[]: what floor1_encode writes for each post -- posts 0/1 verbatim,
 //               the others' deviation from the prediction folded into [0, range) (:805-824)
+//   T        (optional) the block's post tables, all of them loaded; without T they are fetched here
 VAMD_DEV void floor_quantise_predict(const FloorP &F, const LaneInts &outp, const LaneInts &postlist, LaneInts &post,
-                                     LaneInts *wrapped) {
+                                     LaneInts *wrapped, const PostTables *T = nullptr) {
   const int posts = F.posts;
-  LaneInts lo2, hi2, level;
-  lo2.load_shifted(F.loneighbor, 2, posts);
-  hi2.load_shifted(F.hineighbor, 2, posts);
-  level.load(F.level, posts);
+  PostTables own;
+  if (!T) {
+    own.postlist = postlist;
+    own.load_steps(F, false);
+  }
+  const PostTables &tb = T ? *T : own;
+  const LaneInts &lo2 = tb.lo2, &hi2 = tb.hi2, &level = tb.level;
+  const PostSteps &ps = tb.ps;
   post.fill(0);
   WAVE_FOR(i, posts) {
     const int o = outp.at(i);
@@ -583,8 +634,6 @@ VAMD_DEV void floor_quantise_predict(const FloorP &F, const LaneInts &outp, cons
     post.put(i, val | (o & 0x8000));
     if (wrapped) wrapped->put(i, i < 2 ? val | (o & 0x8000) : 0);
   }
-  PostSteps ps;
-  ps.load(F, postlist, lo2, hi2);
   unsigned long long needed = 3ull;  // posts 0 and 1 are always used
   for (int L = 1; L <= F.nlevels; L++) {
     WAVE_FOR(i, posts) {
@@ -625,7 +674,8 @@ VAMD_DEV void floor_quantise_predict(const FloorP &F, const LaneInts &outp, cons
 //   wrapped_out HBM [posts] or null: floor1_encode's out[] (what the packet stage writes for each post), for k_pack
 VAMD_DEV int floor_encode_render(const FloorP &F, int n2, const LaneInts &outp, int valid, FloorScratch *sc,
                                  int *__restrict__ posts_out, int *__restrict__ post_valid,
-                                 ilog_t *__restrict__ ilogmask, PhaseClock &pc, int *__restrict__ wrapped_out = nullptr) {
+                                 ilog_t *__restrict__ ilogmask, PhaseClock &pc, int *__restrict__ wrapped_out = nullptr,
+                                 const PostTables *T = nullptr /* all loaded, or null: fetched here */) {
   const int posts = F.posts;
   if (!valid) {
     // no fit: floor1_encode writes a zero curve (lib/floor1.c:948-952)
@@ -635,20 +685,26 @@ VAMD_DEV int floor_encode_render(const FloorP &F, int n2, const LaneInts &outp, 
     WAVE_SYNC();
     return 0;
   }
-  LaneInts postlist, forward_index, post;
-  postlist.load(F.postlist, posts);
-  forward_index.load(F.forward_index, posts);
+  PostTables own;
+  if (!T) {
+    own.load_list(F);
+    own.load_steps(F);
+  }
+  const PostTables &tb = T ? *T : own;
+  const LaneInts &postlist = tb.postlist, &forward_index = tb.forward_index;
+  LaneInts post;
   WAVE_FOR(i, VAMD_POSTS_STRIDE) if (posts_out) posts_out[i] = i < posts ? outp.at(i) : 0;
   if (post_valid && LANE == 0) *post_valid = 1;
   if (wrapped_out) {
     LaneInts wrapped;
     wrapped.fill(0);
-    floor_quantise_predict(F, outp, postlist, post, &wrapped);
+    floor_quantise_predict(F, outp, postlist, post, &wrapped, &tb);
     WAVE_FOR(i, posts) wrapped_out[i] = wrapped.at(i);
   } else {
-    floor_quantise_predict(F, outp, postlist, post, nullptr);
+    floor_quantise_predict(F, outp, postlist, post, nullptr, &tb);
   }
 
+  pc.mark(7);
   // ---- render the integer curve, lib/floor1.c:923-946
   floor_render_curve(F, posts, n2, forward_index, post, postlist, sc, ilogmask, pc);
   WAVE_SYNC();
@@ -661,8 +717,15 @@ VAMD_DEV int floor_fit_render_block(const FloorP &F, int n2, const unsigned shor
                                     int *__restrict__ posts_out, int *__restrict__ post_valid,
                                     ilog_t *__restrict__ ilogmask, PhaseClock &pc, int *__restrict__ wrapped_out = nullptr) {
   LaneInts outp;
+#if VAMD_FL_TABLES_ONCE
+  PostTables tb;
+  tb.load_list(F);
+  const int valid = floor_fit_posts(F, qc, sc, outp, pc, &tb);  // (a fit that returns 0 leaves the rest unloaded: nobody reads it)
+  return floor_encode_render(F, n2, outp, valid, sc, posts_out, post_valid, ilogmask, pc, wrapped_out, &tb);
+#else
   const int valid = floor_fit_posts(F, qc, sc, outp, pc);
   return floor_encode_render(F, n2, outp, valid, sc, posts_out, post_valid, ilogmask, pc, wrapped_out);
+#endif
 }
 
 // floor1_interpolate_fit, lib/floor1.c:731-750, one post per lane
@@ -694,6 +757,8 @@ VAMD_DEV void floor_managed_block(const PsyP &P, const FloorP &F, int n2, const 
   fmid.fill(0);
   flo.fill(0);
   fhi.fill(0);
+  // (each fit and each curve fetches its own post tables here: one set held across the eighteen of them costs this
+  // kernel, whose two floors arrive by value, 68 bytes of scratch -- profiles/r12_floor_phases.txt)
   const int hmid = floor_fit_posts(F, qc, sc, fmid, pc);
   int hlo = 0, hhi = 0;
   if (hmid) {

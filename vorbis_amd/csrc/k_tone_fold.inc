@@ -73,7 +73,7 @@ VAMD_DEV void tone_fold_prepare(const PsyP &P, float *seed, const float *seed_sr
   WAVE_FOR(g, P.ngroups) gmin[g] = f_from_bits(0x7f800000u);  // +inf = "no real value scanned"
   WAVE_SYNC();
   WAVE_FOR(p, nlines) {
-    const int g = P.line_group[p];
+    const int g = dm_load<unsigned short>(P.line_group, 2u * (unsigned)p);
     const float s = seed[p];
     if (g != 0xffff && s > VAMD_NEGINF) lds_atomic_min(gmin + g, s);
   }
@@ -86,10 +86,10 @@ VAMD_DEV float tone_ath_att(const PsyP &P, float local_ampmax) {
 }
 VAMD_DEV void tone_fold_quad(const PsyP &P, float att, const float *seed, const float *gmin, int q, float *o) {
   const int nlines = P.total_octave_lines;
-  const I4 bf = ((const I4 *)P.bin_fold)[q];
+  const I4 bf = dm_load_i4(P.bin_fold, (unsigned)q << 4);
   const int bfs[4] = {bf.x, bf.y, bf.z, bf.w};
   float av[4];
-  f4_get(((const F4 *)P.ath)[q], av);
+  f4_get(dm_load_f4(P.ath, (unsigned)q << 4), av);
 #pragma unroll
   for (int c = 0; c < 4; c++) {
     const int i = (q << 2) + c;

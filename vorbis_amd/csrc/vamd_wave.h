@@ -169,11 +169,13 @@ struct PhaseClock {
 #ifdef VAMD_STOP_AFTER  // scratch builds for counting a stage's instructions phase by phase
     if (stoppable && k == VAMD_STOP_AFTER) __builtin_amdgcn_endpgm();
 #endif
+#ifndef VAMD_COUNT_CALLS  // (scratch builds whose slots count events instead of ticks: k_floor.h)
     if (slots) {
       const long long now = clock64();
       acc[k & 7] += (unsigned int)(now - t);
       t = now;
     }
+#endif
   }
   VAMD_DEV void flush() {
     if (slots && LANE == 0) {
@@ -278,6 +280,54 @@ VAMD_DEV int div_small(int num, int den, float rcp) {
   if (r < 0) q--;
   if (r >= den) q++;
   return q;
+}
+
+// A table pointer that a kernel reads out of a parameter struct in memory (PsyP, FloorP behind Bound) is a generic
+// pointer to the compiler: flat loads, and a 64-bit address formed per lane on the vector unit for each of them.  Every
+// such pointer points into the setup's image in device memory, and so do a batch's tensors.  dm_*: the access goes
+// through a pointer that says so -- a global load or store off the scalar base with an unsigned 32-bit lane offset in
+// bytes, so that one offset (16 q for quad q) serves every stream of a quad (VAMD_FL_GLOBAL_ADDR, k_floor.h).  Plain
+// pointer arithmetic on the one-lane test build.
+#ifndef VAMD_FL_GLOBAL_ADDR
+#define VAMD_FL_GLOBAL_ADDR 1
+#endif
+#if VAMD_GPU && VAMD_FL_GLOBAL_ADDR
+#define VAMD_DEVMEM __attribute__((address_space(1)))
+typedef float dm_f4_t __attribute__((ext_vector_type(4)));
+typedef int dm_i4_t __attribute__((ext_vector_type(4)));
+#else
+#define VAMD_DEVMEM
+struct alignas(16) dm_f4_t {
+  float x, y, z, w;
+};
+struct alignas(16) dm_i4_t {
+  int x, y, z, w;
+};
+#endif
+template <class T>
+VAMD_DEV T dm_load(const void *row, unsigned int off) {  // T: a scalar type
+  return *(const T VAMD_DEVMEM *)((const char VAMD_DEVMEM *)row + off);
+}
+template <class T>
+VAMD_DEV void dm_store(void *row, unsigned int off, T x) {
+  *(T VAMD_DEVMEM *)((char VAMD_DEVMEM *)row + off) = x;
+}
+VAMD_DEV F4 dm_load_f4(const void *row, unsigned int off) {
+  const dm_f4_t t = dm_load<dm_f4_t>(row, off);
+  F4 v;
+  v.x = t.x, v.y = t.y, v.z = t.z, v.w = t.w;
+  return v;
+}
+VAMD_DEV I4 dm_load_i4(const void *row, unsigned int off) {
+  const dm_i4_t t = dm_load<dm_i4_t>(row, off);
+  I4 v;
+  v.x = t.x, v.y = t.y, v.z = t.z, v.w = t.w;
+  return v;
+}
+VAMD_DEV void dm_store_f4(void *row, unsigned int off, const F4 &v) {
+  dm_f4_t t;
+  t.x = v.x, t.y = v.y, t.z = v.z, t.w = v.w;
+  dm_store<dm_f4_t>(row, off, t);
 }
 
 VAMD_DEV void f4_get(const F4 &v, float *a) { a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w; }
