@@ -645,18 +645,20 @@ const char *vamd_feed_last_error(const vamd_feed *f);
 /* ---- the Ogg feed: complete Ogg Vorbis I files beside the packets (whole-stream feeds; a live feed's files come in pieces,
  * "the live Ogg feed" below; still ABI 9: additions only).
  *     vamd_feed_ogg_headers(f, id, comment, setup)   once, before the first vamd_feed_buffer: the feed is an Ogg feed
- *     slot = vamd_feed_buffer(f, &pcm) ... [vamd_feed_ogg_serials(f, slot, ...)] ... vamd_feed_wrote / _wrote_v
+ *     slot = vamd_feed_buffer(f, &pcm) ... [vamd_feed_ogg_serials(f, slot, ...)] [vamd_feed_ogg_comments(f, slot, ...)] ...
+ *                                              vamd_feed_wrote / _wrote_v
  *     vamd_feed_ogg(f, slot, &files)                 waits as vamd_feed_packets does; one byte range per stream
  *     vamd_feed_packets(f, slot, &out)               unchanged, and still there
  * The three header packets are what vorbis_analysis_headerout() gives for the encoder setup the blob was packed from (the
  * setup header is libvorbis' codebook packing: the host's, once per setup); they are validated -- packet types 1 / 3 / 5
  * + "vorbis", a 30-byte identification header whose channels, rate and block sizes are the context's -- else VAMD_EINVAL,
  * the reason in vamd_feed_last_error.  A live feed answers VAMD_EIMPL here: what it returns are pieces of files, a contract
- * of its own that the caller opts into by name (vamd_feed_ogg_headers_live).  One comment packet serves every stream.
+ * of its own that the caller opts into by name (vamd_feed_ogg_headers_live).  The comment packet given here is the
+ * feed's own: every stream carries it unless its group names another for it (vamd_feed_ogg_comments, below).
  * Framing (doc/framing.html, doc/a1-encapsulation-ogg.tex) happens on the device behind the group's last packet: the
  * copy kernels keep a mirror of the packet arena in HBM, k_ogg_plan walks every stream's packet sizes into pages,
  * k_ogg_pages writes each page -- header, lacing, body, CRC -- straight into a second pinned arena; no further host wait.
- * THE PAGING POLICY is fixed, so a stream's file is a function of its packets and serial number alone:
+ * THE PAGING POLICY is fixed, so a stream's file is a function of its packets, its serial number and its comment packet alone:
  *   - a packet of n bytes is n / 255 lacing values of 255 and one of n % 255;
  *   - page 0 holds the identification header alone (flags 0x02, granule position 0, sequence number 0; 58 bytes);
  *   - the comment and setup headers start on page 1, granule position 0; the page on which the setup header ends is closed;
@@ -671,6 +673,20 @@ const char *vamd_feed_last_error(const vamd_feed *f);
  * streams of the group are untouched.  Serial numbers: stream s of a group gets the feed's running counter (0, 1, 2, ...
  * over all groups in vamd_feed_wrote order) unless vamd_feed_ogg_serials, between vamd_feed_buffer and vamd_feed_wrote*,
  * names the first n streams' itself.  Pinned memory: the file arena is sized from the packet arena (about 7 % more).
+ * A COMMENT HEADER PER STREAM (title, artist, cover art): vamd_feed_ogg_comments, between vamd_feed_buffer and
+ * vamd_feed_wrote*, gives stream s < n of THIS group the comment header comment[s] (bytes[s] long) in place of the feed's
+ * own; comment[s] == NULL, and every stream from n on, keeps the feed's.  The packets are copied before the call returns.
+ * It holds for that group only -- the slot's next group starts with none -- and a later call for the same group replaces
+ * an earlier one.  Each packet is checked as far as its framing goes (Vorbis I 5.2.1): 7 to 2^24 bytes, type 3 + "vorbis",
+ * the vendor length and string, the comment count, that many length + bytes pairs and then a byte with bit 0 set, every
+ * one of them inside the packet; bytes behind the framing byte are allowed (taggers pad there), the strings are not looked
+ * into.  A packet that fails: VAMD_EINVAL, vamd_feed_last_error names the stream's index and what is wrong, and nothing of
+ * the call is kept.  VAMD_EINVAL as well: not an Ogg feed, a slot not between buffer and wrote, n < 0, n > max_streams,
+ * bytes == NULL with n > 0.  The comment goes to the device with the group and is paged there like any packet: it starts
+ * page 1, a long one (a picture) continues over as many pages as it needs, the setup header follows it, and every later
+ * page's offset, sequence number and checksum come out of the same walk -- nothing is retagged on the host.  The page
+ * table is sized from the group's longest comment, the file arena from the SUM of its comments, not from streams times
+ * the longest.  A feed that never makes the call allocates nothing for it and its files are byte for byte what they were.
  *
  * THE LIVE OGG FEED: a live feed's streams as Ogg files, in pieces.
  *     vamd_feed_create_live(...); vamd_feed_ogg_headers_live(f, id, comment, setup)   once, before the first vamd_feed_buffer
@@ -689,7 +705,10 @@ const char *vamd_feed_last_error(const vamd_feed *f);
  * with a stream.  Serial numbers belong to streams: entry s of vamd_feed_ogg_serials names the serial of stream (slot, s)
  * if that stream BEGINS with this group and is ignored for a stream already open; without the call a stream takes the
  * feed's running counter when it begins.  After a close the slot's next piece begins a new file: a bos page, sequence
- * numbers from 0, a new serial.
+ * numbers from 0, a new serial.  Comment headers likewise: entry s of vamd_feed_ogg_comments is the comment header of stream
+ * (slot, s) if that stream BEGINS with this group and is ignored for a stream already open -- a live stream's header pages
+ * all leave with the group that begins it, so nothing of a comment is kept between groups; after a close the slot's next
+ * stream takes a new one, or the feed's own.
  * A stream that loses a packet (bits = -1; a non-finite sample): from that group on its ranges are empty and status[s]
  * carries that block's VAMD_STATUS_*, in every group until the stream is closed; the packets carried for its open page
  * are dropped.  Where a whole stream gets NO file, a live stream has already handed pages out: those bytes are a valid
@@ -708,6 +727,10 @@ int vamd_feed_ogg_headers(vamd_feed *f, const void *id, long id_bytes, const voi
 int vamd_feed_ogg_headers_live(vamd_feed *f, const void *id, long id_bytes, const void *comment, long comment_bytes,
                                const void *setup, long setup_bytes);
 int vamd_feed_ogg_serials(vamd_feed *f, int slot, const uint32_t *serials, long n);
+/* between vamd_feed_buffer and vamd_feed_wrote / _wrote_v / _wrote_live, like vamd_feed_ogg_serials:
+ * comment[s] (bytes[s] long) is the Vorbis comment header of stream s of this group, s < n <= max_streams;
+ * comment[s] == NULL: the feed's own (the one given to vamd_feed_ogg_headers[_live]).  Copied before it returns. */
+int vamd_feed_ogg_comments(vamd_feed *f, int slot, const void *const *comment, const long *bytes, long n);
 int vamd_feed_ogg(vamd_feed *f, int slot, vamd_feed_ogg_result *out);
 
 #ifdef __cplusplus

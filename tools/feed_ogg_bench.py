@@ -11,6 +11,12 @@ tool can be run beside an earlier checkout for a before/after of the packet feed
 pieces.  Per feed the whole set's blocks/s and bytes/s and the mean time per group (best of --reps passes over the set).
 
     python tools/feed_ogg_bench.py --live --streams 64 --seconds 20 --piece 1 --reps 3
+
+--tags BYTES: every stream of the Ogg feed gets a comment header of its own of about BYTES bytes (vamd_feed_ogg_comments;
+a title and a padding tag), handed over inside the timed part of every group -- of a live feed, of the group that begins
+the streams.  wall_s_reps: every timed repetition's wall time, in order (wall_s is their best).
+
+    python tools/feed_ogg_bench.py --streams 64 --seconds 20 --reps 3 --tags 65536
 """
 import argparse
 import json
@@ -33,6 +39,7 @@ def main():
     ap.add_argument("--only", choices=("packets", "ogg"), default=None, help="one feed only (for a trace of it, or an older library)")
     ap.add_argument("--live", action="store_true", help="live feeds: the streams in pieces, the Ogg files in pieces")
     ap.add_argument("--piece", type=float, default=1.0, help="--live: seconds per piece")
+    ap.add_argument("--tags", type=int, default=0, help="the Ogg feed: a comment header of its own per stream, of about this many bytes")
     a = ap.parse_args()
     import vorbis_amd
     frames = int(44100 * a.seconds)
@@ -45,6 +52,10 @@ def main():
         pcm[s] = np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)
     blob = vorbis_amd.default_setup_blob("44k_stereo_q4")
     names = [a.only] if a.only else ["packets", "ogg"]
+    a.comments = None
+    if a.tags:
+        a.comments = [vorbis_amd.comment_packet([("TITLE", "stream %d" % s), ("PAD", "x" * max(0, a.tags - 64))], "vorbis_amd feed_ogg_bench")
+                      for s in range(a.streams)]
     if a.live:
         return live(a, vorbis_amd, blob, pcm, names)
     feeds = {}
@@ -55,6 +66,7 @@ def main():
             kw["ogg_headers"] = ogg_host.reference_headers(2, 44100, 0.4)  # (needs the reference build, oracle/_ref)
         feeds[k] = vorbis_amd.Feed(blob, lanes_per_device=a.lanes, max_streams=a.streams, max_frames=frames, **kw)
     best = {k: None for k in names}
+    walls = {k: [] for k in names}
     flat = pcm.reshape(-1)
     for rep in range(a.reps + 1):
         for k in names:
@@ -62,6 +74,8 @@ def main():
             slot, buf = f.buffer(2)
             buf[:flat.size] = flat
             t0 = time.perf_counter()
+            if k == "ogg" and a.comments:
+                f.ogg_comments(slot, a.comments)
             f.wrote(slot, a.streams, frames)
             file_bytes = 0
             if k == "ogg":
@@ -70,15 +84,18 @@ def main():
             dt = time.perf_counter() - t0
             nb, nbytes, dev = r["nblocks"], r["total_bytes"], r["device_ms"]
             f.release(slot)
+            if rep:
+                walls[k].append(dt)
             if rep and (best[k] is None or dt < best[k][0]):
                 best[k] = (dt, nb, nbytes, dev, file_bytes)
     for k in names:
         dt, nb, nbytes, dev, file_bytes = best[k]
         line = {"feed": k, "streams": a.streams, "seconds": a.seconds, "blocks": nb, "wall_s": dt, "device_ms": dev,
-                "blocks_per_s": nb / dt, "packet_bytes_per_s": nbytes / dt}
+                "blocks_per_s": nb / dt, "packet_bytes_per_s": nbytes / dt, "wall_s_reps": walls[k]}
         if k == "ogg":
             line["file_bytes_per_s"] = file_bytes / dt
             line["file_bytes"] = file_bytes
+            line["tags"] = a.tags
         print(json.dumps(line))
     for f in feeds.values():
         f.close()
@@ -94,6 +111,7 @@ def live(a, vorbis_amd, blob, pcm, names):
             kw["ogg_headers"] = ogg_host.reference_headers(2, 44100, 0.4)  # (needs the reference build, oracle/_ref)
         feeds[k] = vorbis_amd.Feed(blob, lanes_per_device=1, max_streams=a.streams, max_frames=piece, write_frames=1024, **kw)
     best = {k: None for k in names}
+    walls = {k: [] for k in names}
     for rep in range(a.reps + 1):
         for k in names:
             f = feeds[k]
@@ -105,6 +123,8 @@ def live(a, vorbis_amd, blob, pcm, names):
                 slot, buf = f.buffer(2)
                 buf[:flat.size] = flat
                 t0 = time.perf_counter()
+                if k == "ogg" and a.comments and at == 0:
+                    f.ogg_comments(slot, a.comments)
                 f.wrote_live(slot, [n] * a.streams, [at + piece >= frames] * a.streams)
                 if k == "ogg":
                     file_bytes += f.ogg(slot, copy=False)["total_bytes"]
@@ -112,16 +132,19 @@ def live(a, vorbis_amd, blob, pcm, names):
                 dt += time.perf_counter() - t0
                 nb, nbytes, dev, groups = nb + r["nblocks"], nbytes + r["total_bytes"], dev + r["device_ms"], groups + 1
                 f.release(slot)
+            if rep:
+                walls[k].append(dt)
             if rep and (best[k] is None or dt < best[k][0]):
                 best[k] = (dt, nb, nbytes, dev, file_bytes, groups)
     for k in names:
         dt, nb, nbytes, dev, file_bytes, groups = best[k]
         line = {"feed": "live " + k, "streams": a.streams, "seconds": a.seconds, "piece_s": a.piece, "groups": groups, "blocks": nb,
                 "wall_s": dt, "group_ms": 1e3 * dt / groups, "group_device_ms": dev / groups, "blocks_per_s": nb / dt,
-                "packet_bytes_per_s": nbytes / dt}
+                "packet_bytes_per_s": nbytes / dt, "wall_s_reps": walls[k]}
         if k == "ogg":
             line["file_bytes_per_s"] = file_bytes / dt
             line["file_bytes"] = file_bytes
+            line["tags"] = a.tags
         print(json.dumps(line))
     for f in feeds.values():
         f.close()

@@ -2,6 +2,7 @@
 turn follows libvorbis (mapping0_forward's variables and OV_* return codes)."""
 import ctypes as C
 import os
+import struct
 
 import numpy as np
 
@@ -29,7 +30,8 @@ EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe",
                     "vamd_feed_create", "vamd_feed_destroy", "vamd_feed_lanes", "vamd_feed_device", "vamd_feed_buffer", "vamd_feed_wrote",
                     "vamd_feed_packets", "vamd_feed_release", "vamd_feed_last_error", "vamd_feed_create_live", "vamd_feed_wrote_live",
                     "vamd_analyze_streams_mixed_managed", "vamd_bitrate_init_states", "vamd_bitrate_walk",
-                    "vamd_feed_ogg_headers", "vamd_feed_ogg_serials", "vamd_feed_ogg", "vamd_feed_ogg_headers_live"]
+                    "vamd_feed_ogg_headers", "vamd_feed_ogg_serials", "vamd_feed_ogg", "vamd_feed_ogg_headers_live",
+                    "vamd_feed_ogg_comments"]
 PACKETBLOBS = 15
 
 _vp = C.c_void_p
@@ -79,6 +81,41 @@ def packet_bytes(row, bits):
     if nbytes > len(row):
         raise ValueError("packet (%d bits) was cut off at its row length %d" % (bits, len(row)))
     return bytes(bytearray(row[:nbytes]))
+
+
+def comment_packet(tags, vendor):
+    """The Vorbis comment header (Vorbis I 5.2.1) of a vendor string and [(key, value), ...] -- str (UTF-8) or bytes --
+    byte for byte what vorbis_commentheader_out() writes for comments added with vorbis_comment_add_tag(key, value)."""
+    def raw(v):
+        return v.encode("utf-8") if isinstance(v, str) else bytes(v)
+    vendor = raw(vendor)
+    out = [b"\x03vorbis", struct.pack("<I", len(vendor)), vendor, struct.pack("<I", len(tags))]
+    for k, v in tags:
+        entry = raw(k) + b"=" + raw(v)
+        out += [struct.pack("<I", len(entry)), entry]
+    return b"".join(out) + b"\x01"
+
+
+def comment_fields(packet):
+    """-> (vendor, [(key, value), ...]) of a comment header, as str; a comment without "=" comes back as (comment, "")."""
+    p = bytes(packet)
+    if p[:7] != b"\x03vorbis":
+        raise ValueError("not a Vorbis comment header")
+    def take(at):
+        n, = struct.unpack_from("<I", p, at)
+        if at + 4 + n > len(p):
+            raise ValueError("the comment header is cut off")
+        return p[at + 4:at + 4 + n], at + 4 + n
+    vendor, at = take(7)
+    count, = struct.unpack_from("<I", p, at)
+    at, tags = at + 4, []
+    for _ in range(count):
+        entry, at = take(at)
+        k, _, v = entry.partition(b"=")
+        tags.append((k.decode("utf-8"), v.decode("utf-8")))
+    if at >= len(p) or not p[at] & 1:
+        raise ValueError("the comment header's framing bit is missing")
+    return vendor.decode("utf-8"), tags
 
 
 class VamdError(RuntimeError):
@@ -162,6 +199,7 @@ def load_library():
     L.vamd_feed_ogg_headers.argtypes = [_vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long]
     L.vamd_feed_ogg_headers_live.argtypes = [_vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long]
     L.vamd_feed_ogg_serials.argtypes = [_vp, C.c_int, _vp, C.c_long]
+    L.vamd_feed_ogg_comments.argtypes = [_vp, C.c_int, _vp, _vp, C.c_long]
     L.vamd_feed_ogg.argtypes = [_vp, C.c_int, C.POINTER(_FeedOggResult)]
     L.vamd_feed_last_error.argtypes = [_vp]
     L.vamd_feed_last_error.restype = C.c_char_p
@@ -959,7 +997,8 @@ class Feed:
 
     ogg_headers = (identification, comment, setup), the packets vorbis_analysis_headerout() gives for the blob's encoder
     setup: an OGG feed (vamd_feed_ogg_headers) -- besides packets(), ogg() returns one complete Ogg Vorbis I file per
-    stream, framed on the device: buffer() -> fill -> [ogg_serials()] -> wrote() -> ogg() / packets() -> release().
+    stream, framed on the device: buffer() -> fill -> [ogg_serials()] [ogg_comments()] -> wrote() -> ogg() / packets() ->
+    release().  The comment packet given here is the feed's own; ogg_comments() gives a group's streams their own.
     With write_frames: a LIVE OGG feed (vamd_feed_ogg_headers_live) -- ogg() returns per stream the next bytes of its file,
     the pages it completed in the group; a stream's pieces laid end to end are its file (encode_live_ogg)."""
 
@@ -1007,6 +1046,16 @@ class Feed:
         a = np.ascontiguousarray(serials, dtype=np.uint32).reshape(-1)
         self._check(self.L.vamd_feed_ogg_serials(self.h, slot, _vp(a.ctypes.data), a.size))
 
+    def ogg_comments(self, slot, comments):
+        """The comment headers of the group being filled in `slot` (between buffer() and wrote()): comments[s] the packet
+        (bytes, e.g. comment_packet(...)) of stream s, or None for the feed's own; streams beyond the list keep the feed's.
+        For this group only.  A live feed: of the streams that begin with this group."""
+        pk = [None if c is None else bytes(c) for c in comments]
+        n = len(pk)
+        ptr = (C.c_char_p * max(n, 1))(*pk)
+        size = (C.c_long * max(n, 1))(*[0 if c is None else len(c) for c in pk])
+        self._check(self.L.vamd_feed_ogg_comments(self.h, slot, C.cast(ptr, _vp), C.cast(size, _vp), n))
+
     def ogg(self, slot, copy=True):
         """Waits for the group.  -> dict: nstreams, stream_offset [nstreams + 1], npages, status [nstreams], bytes (a view
         over the lane's pinned file arena, or a copy), total_bytes: stream s's file is bytes[stream_offset[s]:stream_offset[s + 1]]
@@ -1024,9 +1073,10 @@ class Feed:
                 "status": view(r.status, C.c_uint8, ns), "bytes": view(r.bytes, C.c_uint8, int(r.total_bytes)),
                 "total_bytes": int(r.total_bytes)}
 
-    def encode_ogg(self, pcm, serials=None):
-        """One group of an Ogg feed, synchronously: pcm as encode() takes it.  -> list[bytes], one complete Ogg Vorbis file
-        per stream (b"" for a stream without one: see ogg())."""
+    def encode_ogg(self, pcm, serials=None, comments=None):
+        """One group of an Ogg feed, synchronously: pcm as encode() takes it; serials and comments (optional) as ogg_serials
+        and ogg_comments take them.  -> list[bytes], one complete Ogg Vorbis file per stream (b"" for a stream without
+        one: see ogg())."""
         if isinstance(pcm, (list, tuple)):
             parts = [np.ascontiguousarray(x, dtype=self.dtype) for x in pcm]
             ns, ch = len(parts), parts[0].shape[1]
@@ -1041,6 +1091,8 @@ class Feed:
             buf[:flat.size] = flat
             if serials is not None:
                 self.ogg_serials(slot, serials)
+            if comments is not None:
+                self.ogg_comments(slot, comments)
             self.wrote(slot, ns, frames)
             r = self.ogg(slot, copy=False)
             off = r["stream_offset"]
@@ -1161,9 +1213,9 @@ class Feed:
                 pass
         return self._rows(r, len(parts))
 
-    def encode_live_ogg(self, pieces, close=None, serials=None):
+    def encode_live_ogg(self, pieces, close=None, serials=None, comments=None):
         """One group of a live Ogg feed with ONE lane, synchronously: pieces and close as encode_live takes them; serials
-        (optional) as ogg_serials.  -> per stream the next bytes of its Ogg file: the pages it completed in this group
+        and comments (optional; this group's) as ogg_serials and ogg_comments take them.  -> per stream the next bytes of its Ogg file: the pages it completed in this group
         (b"" where none, or where the stream has lost a packet: see ogg())."""
         if self.write_frames is None:
             raise ValueError("encode_live_ogg needs a live feed (Feed(..., write_frames=..., ogg_headers=...))")
@@ -1179,6 +1231,8 @@ class Feed:
             buf[:flat.size] = flat
             if serials is not None:
                 self.ogg_serials(slot, serials)
+            if comments is not None:
+                self.ogg_comments(slot, comments)
             self.wrote_live(slot, frames, close)
             r = self.ogg(slot, copy=False)
             off = r["stream_offset"]

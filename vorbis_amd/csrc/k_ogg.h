@@ -253,6 +253,50 @@ VAMD_OGG_FN int64_t ogg_file_bound(int64_t packet_bytes, int64_t npackets, int64
   return packet_bytes + nstreams * ((int64_t)header_bytes[0] + header_bytes[1] + header_bytes[2]) + pages * (OGG_HEADER + OGG_MAX_SEGS);
 }
 
+// A group whose streams carry comment headers of their own (vamd_feed_ogg_comments): the header slots are
+// ogg_header_slots of the group's LONGEST comment (header_bytes[1] set to it), the bytes come from the SUM of the
+// comments -- stream s's header runs take 1 + ceil((segments of its comment + of the setup header) / 255) pages, and a
+// comment of c bytes is c / 255 + 1 segments, so all of them together take at most
+// 2 nstreams + (comment_sum / 255 + nstreams (1 + segments of the setup header)) / 255 pages.
+VAMD_OGG_FN int64_t ogg_file_bound_v(int64_t packet_bytes, int64_t npackets, int64_t nstreams, const int32_t *header_bytes, int64_t comment_sum) {
+  const int64_t pages = packet_bytes / (OGG_FILL + 1) + (npackets + packet_bytes / 255) / 255 + nstreams * 4 +
+                        (comment_sum / 255 + nstreams * (1 + ogg_segments(header_bytes[2]))) / 255 + 1;
+  return packet_bytes + nstreams * ((int64_t)header_bytes[0] + header_bytes[2]) + comment_sum + pages * (OGG_HEADER + OGG_MAX_SEGS);
+}
+
+// A Vorbis comment header as far as its framing goes (Vorbis I 5.2.1; what the reference's vorbis_synthesis_headerin
+// asks of one): type 3 and "vorbis", a little-endian vendor length and that many bytes, a comment count, that many
+// length + bytes pairs, then a byte with bit 0 set -- every one of them inside the packet.  What lies behind the framing
+// byte is not looked at (taggers pad there), nor are the strings.  0: well-formed; else what is wrong (ogg_comment_why).
+enum { OGG_COMMENT_OK = 0, OGG_COMMENT_LENGTH, OGG_COMMENT_TYPE, OGG_COMMENT_VENDOR, OGG_COMMENT_COUNT, OGG_COMMENT_ENTRY, OGG_COMMENT_FRAMING };
+VAMD_OGG_FN uint32_t ogg_le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+VAMD_OGG_FN int ogg_comment_check(const uint8_t *p, int64_t n) {
+  if (!p || n < 7 || n > ((int64_t)1 << 24)) return OGG_COMMENT_LENGTH;
+  if (p[0] != 3 || p[1] != 'v' || p[2] != 'o' || p[3] != 'r' || p[4] != 'b' || p[5] != 'i' || p[6] != 's') return OGG_COMMENT_TYPE;
+  int64_t at = 7;
+  if (n - at < 4 || (int64_t)ogg_le32(p + at) > n - at - 4) return OGG_COMMENT_VENDOR;
+  at += 4 + (int64_t)ogg_le32(p + at);
+  if (n - at < 4) return OGG_COMMENT_COUNT;
+  const int64_t count = (int64_t)ogg_le32(p + at);
+  at += 4;
+  if (count > (n - at) / 4) return OGG_COMMENT_COUNT;  // (every comment takes four bytes at least)
+  for (int64_t i = 0; i < count; i++) {
+    if (n - at < 4 || (int64_t)ogg_le32(p + at) > n - at - 4) return OGG_COMMENT_ENTRY;
+    at += 4 + (int64_t)ogg_le32(p + at);
+  }
+  return at < n && (p[at] & 1) ? OGG_COMMENT_OK : OGG_COMMENT_FRAMING;
+}
+VAMD_OGG_FN const char *ogg_comment_why(int code) {
+  switch (code) {
+    case OGG_COMMENT_OK: return "well-formed";
+    case OGG_COMMENT_LENGTH: return "its length is not 7 to 2^24 bytes";
+    case OGG_COMMENT_TYPE: return "it does not begin with packet type 3 and \"vorbis\"";
+    case OGG_COMMENT_VENDOR: return "the vendor string runs past its end";
+    case OGG_COMMENT_COUNT: return "the comment count is not inside it, or counts more comments than it can hold";
+    case OGG_COMMENT_ENTRY: return "a comment's length or bytes run past its end";
+    default: return "the framing bit behind the last comment is missing or clear";
+  }
+}
 
 // ---- a live feed: one walk per stream, interrupted at group boundaries ----
 // At the end of a group every packet has been taken completely, so the walk's state is its OggWalk: the open page, the
@@ -280,11 +324,18 @@ VAMD_OGG_FN int64_t ogg_live_file_bound(int64_t packet_bytes, int64_t npackets, 
   return ogg_file_bound(packet_bytes + nstreams * OGG_CARRY_BODY, npackets + nstreams * OGG_MAX_SEGS, nstreams, header_bytes) +
          nstreams * (OGG_HEADER + OGG_MAX_SEGS);
 }
+// ... with comment headers per stream (ogg_file_bound_v; the slots: ogg_live_slots of the group's longest comment)
+VAMD_OGG_FN int64_t ogg_live_file_bound_v(int64_t packet_bytes, int64_t npackets, int64_t nstreams, const int32_t *header_bytes,
+                                          int64_t comment_sum) {
+  return ogg_file_bound_v(packet_bytes + nstreams * OGG_CARRY_BODY, npackets + nstreams * OGG_MAX_SEGS, nstreams, header_bytes, comment_sum) +
+         nstreams * (OGG_HEADER + OGG_MAX_SEGS);
+}
 
 #if defined(__HIPCC__)
 // ---- the kernels ----
 // What the pager reads: the device mirror of the group's packets (bytes at the offsets of the output arena, each packet at
-// a multiple of 4, and their records), the three header packets, the streams' serial numbers.
+// a multiple of 4, and their records), the three header packets, the streams' serial numbers, and, where the group names
+// them, the streams' own comment headers.
 struct OggIn {
   const int64_t *stream_start;  // [nstreams + 1] into the packets
   const int64_t *off, *gp;      // [packets] where a packet's bytes lie in `bytes`; its granule position
@@ -297,8 +348,23 @@ struct OggIn {
   int32_t hdr_off[3], hdr_bytes[3];
   const uint32_t *serial;       // [nstreams]
   int64_t header_slots, slots_per_packet;
+  // The group's comment headers per stream (vamd_feed_ogg_comments); null: none, header packet 1 is hdr's for all.  One
+  // buffer, one pointer: [where stream s's lies in it (nstreams, 8 bytes each) | its length (nstreams, 4 each; negative:
+  // the shared one) | the comments, each at a multiple of 4, 8 readable bytes behind the last]
+  const uint8_t *cmt;
 };
 __device__ __forceinline__ int64_t ogg_slot_base(const OggIn &I, long s) { return s * I.header_slots + I.slots_per_packet * I.stream_start[s]; }
+// the length of stream s's comment header: its own where the group has a table and the entry is set, else the shared one's
+__device__ __forceinline__ int32_t ogg_comment_own(const OggIn &I, long nstreams, long s) {  // (I.cmt set) its length, or negative
+  return ((const int32_t *)(I.cmt + nstreams * 8))[s];
+}
+__device__ __forceinline__ int32_t ogg_comment_bytes(const OggIn &I, long nstreams, long s) {
+  if (I.cmt) {
+    const int32_t n = ogg_comment_own(I, nstreams, s);
+    if (n >= 0) return n;
+  }
+  return I.hdr_bytes[1];
+}
 
 // A live group (in == null: whole streams): per stream its state and carry as the last group left them, and where this
 // group's go -- the other of two buffers each, swapped by the host once the group has succeeded, so that a group laid out
@@ -325,6 +391,8 @@ __device__ __forceinline__ int ogg_live_ncarry(const OggLiveIO &V, long s) {  //
 // 64 packets at a time: one coalesced load of their sizes and granule positions, a wave-wide scan of bytes and segments
 // into LDS, then a step per PAGE (ogg_stop_at in every lane, one ballot, ogg_walk_join) -- the walk is serial in pages
 // only, and never touches memory.  A stream in which a block has no packet gets no page at all.
+// A group with comment headers per stream (I.cmt set): the header runs are walked with the stream's own length of
+// header packet 1; nothing else of the walk knows.
 // A live group (V.in set): a stream that begins walks the headers and begins the audio run; an open one loads its walk --
 // the open page already counts the carried packets, which come first in the group's list -- and walks the new packets;
 // only a closing one ends the run.  file_bytes is what the group adds to the file.  A stream that lost a packet writes no
@@ -365,8 +433,9 @@ __global__ __launch_bounds__(64) void k_ogg_plan(OggIn I, long nstreams, OggPage
   const int64_t gstart = w.file_off;
   const bool none = st || absent || (I.packet_total && *I.packet_total > I.cap);
   if (!none) {
-    if (begin) {
-      ogg_walk_headers(w, out, wcap, I.hdr_bytes);
+    if (begin) {  // (header packet 1 is the stream's own comment where the group names one)
+      const int32_t hb[3] = {I.hdr_bytes[0], ogg_comment_bytes(I, nstreams, s), I.hdr_bytes[2]};
+      ogg_walk_headers(w, out, wcap, hb);
       ogg_run_begin(w, 2, 0);
     }
     for (int64_t base = k0; base < k1; base += 64) {
@@ -429,6 +498,8 @@ struct OggOut {
 //   nothing anyone reads, behind the arena's last page).  So no byte is written twice and no dword in parts.  A dword
 //   inside one piece is two aligned words of the mirror joined by v_alignbyte; one that straddles pieces (packets of a
 //   few bytes), the header or the page's end is put together byte by byte.
+// A group with comment headers per stream (I.cmt set): header packet 1 of a stream with an entry lies in I.cmt, not
+// in I.hdr -- the pieces' source and length change, lacing, CRC and stores do not.
 // A live group (V.in set): a page's packets come from two sources -- the first ncarry of the stream's list lie in its
 // carry, the others in the mirror -- the serial number is the stream's own, and the page goes where the group's range has it.
 __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const OggPage *__restrict__ pages,
@@ -454,6 +525,12 @@ __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const 
   const int64_t kbase = I.stream_start[s] + pg.first - ncarry, kend = I.stream_start[s + 1];
   int carry_s = 0, carry_b = 0;
   bool bad = false;
+  int32_t own_bytes = -1;  // the stream's own comment header, where the group names one: the same for the whole wave
+  const uint8_t *own_src = nullptr;
+  if (pg.run == 1 && I.cmt) {
+    own_bytes = ogg_comment_own(I, nstreams, s);
+    own_src = I.cmt + ((const int64_t *)I.cmt)[s];
+  }
   for (int j0 = 0; j0 < pg.npackets; j0 += 64) {
     const int j = j0 + lane;
     const bool valid = j < pg.npackets;
@@ -479,7 +556,10 @@ __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const 
       } else {
         const int h = pg.first + j;
         if (h > 2) bad = true;
-        else bytes = I.hdr_bytes[h], src = I.hdr + I.hdr_off[h];
+        else {
+          bytes = I.hdr_bytes[h], src = I.hdr + I.hdr_off[h];
+          if (h == 1 && own_bytes >= 0) bytes = own_bytes, src = own_src;  // (a packet like any other, continued over pages)
+        }
       }
     }
     const int32_t start = j == 0 ? pg.byte0 : 0;

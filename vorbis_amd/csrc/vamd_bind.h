@@ -317,6 +317,15 @@ inline int build_image(const void *blob_v, size_t bytes, std::vector<unsigned ch
         }
   }
 
+  // the point-stereo amplitudes index the nine stereo thresholds (stereo_threshold, lib/psy.c:1027-1029): bind_params reads
+  // the table through them on the host
+  for (int k = 0; k < VAMD_PACKETBLOBS; k++)
+    if (h.psy_g.coupling_prepointamp[k] < 0 || h.psy_g.coupling_prepointamp[k] > 8 || h.psy_g.coupling_postpointamp[k] < 0 ||
+        h.psy_g.coupling_postpointamp[k] > 8) {
+      *err = "setup blob: coupling point amplitude outside the stereo threshold table";
+      return VAMD_EINVAL;
+    }
+
   if (h.off_bitrate) {
     // the bitrate manager's section (k_bitrate.h): only where the encoder has a manager, and with the values
     // vorbis_bitrate_init can leave (lib/bitrate.c:33-54: reservoir_bits > 0, the floater inside the fifteen candidates)

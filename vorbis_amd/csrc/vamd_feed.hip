@@ -121,6 +121,12 @@ struct FeedLane {
   Pinned h_serial, h_ogg, h_orec;
   int32_t hdr_off[3] = {0, 0, 0};
   std::vector<uint32_t> serials, user_serials;  // the job's; what vamd_feed_ogg_serials set for it
+  // comment headers per stream (vamd_feed_ogg_comments; an empty entry: the feed's own): what the call set for the slot,
+  // and the job's, kept until the group is done -- a group laid out twice is paged twice.  h_cmt / d_cmt: the job's table
+  // and bytes as the pager reads them, [off (ns, 8 bytes each) | bytes (ns, 4 each) | the comments, each at a multiple of 4]
+  std::vector<std::vector<uint8_t>> comments, user_comments;
+  Pinned h_cmt;
+  Buf d_cmt;
   // a live Ogg feed (vamd_feed_ogg_headers_live): per stream the pager's state and its carry -- the packets on the page
   // still open -- in two buffers each; ogg_cur names the one the last group left, the next group writes the other
   // (k_ogg.h, OggLiveIO).  ogg_flags: the group's OGG_LIVE_* per stream (run_group_live).
@@ -238,6 +244,8 @@ static size_t orec_status(long ns) { return orec_npages(ns) + (size_t)ns * 4; }
 // sized by ogg_slots_per_packet, the arena by ogg_file_bound of the PACKET arena's size -- packets that fit theirs make
 // files that fit this one.  d_packet_total (VBR): the packets' bytes on the device; beyond the arena nothing was mirrored
 // and nothing is paged (finish_group lays the group out again).
+// A group with comment headers of its own (L.comments, vamd_feed_ogg_comments): they go up beside the serial numbers, the
+// header slots are those of the group's longest comment and the file arena is sized from their sum (ogg_file_bound_v).
 // A live group (f->write_frames): the streams' states and carries go along (OggLiveIO), k_ogg_carry runs behind the pages;
 // what it and k_ogg_plan write is the OTHER state and carry, which pager_result makes the current ones -- so a group that
 // is laid out twice (finish_group) advances its streams once.
@@ -277,6 +285,37 @@ static int run_pager(vamd_feed *f, FeedLane &L, const int64_t *d_stream_start, l
   memcpy(L.h_serial.p, L.serials.data(), (size_t)ns * 4);
   if (live) memcpy((uint32_t *)L.h_serial.p + ns, L.ogg_flags.data(), (size_t)ns * 4);
   FEED_TRY(hipMemcpyAsync(L.d_serial.p, L.h_serial.p, (size_t)ns * (live ? 8 : 4), hipMemcpyHostToDevice, st));
+  // the group's own comment headers: the table and the bytes in one copy; the slots from the longest, the arena from the sum
+  const bool tagged = !L.comments.empty();
+  int64_t cmt_sum = 0;
+  if (tagged) {
+    auto own = [&](long s) { return (size_t)s < L.comments.size() && !L.comments[(size_t)s].empty() ? &L.comments[(size_t)s] : nullptr; };
+    const size_t table = al((size_t)ns * 12, 8);
+    size_t at = table;
+    int32_t longest = 0;
+    for (long s = 0; s < ns; s++) {
+      const size_t n = own(s) ? own(s)->size() : (size_t)hb[1];
+      if (own(s)) at += al(n, 4);
+      cmt_sum += (int64_t)n;
+      if ((int32_t)n > longest) longest = (int32_t)n;
+    }
+    FEED_TRY(L.h_cmt.need(at + 8));
+    FEED_TRY(L.d_cmt.need(at + 8));
+    uint8_t *img = (uint8_t *)L.h_cmt.p;
+    int64_t *off = (int64_t *)img;
+    int32_t *len = (int32_t *)(img + (size_t)ns * 8);
+    memset(img, 0, at + 8);
+    at = table;
+    for (long s = 0; s < ns; s++) {
+      off[s] = (int64_t)at, len[s] = -1;
+      if (!own(s)) continue;
+      len[s] = (int32_t)own(s)->size();
+      memcpy(img + at, own(s)->data(), own(s)->size());
+      at += al(own(s)->size(), 4);
+    }
+    FEED_TRY(hipMemcpyAsync(L.d_cmt.p, L.h_cmt.p, at + 8, hipMemcpyHostToDevice, st));
+    hb[1] = longest;  // (from here on hb sizes the slots; the pager's own copy of the shared lengths is f->ogg_hdr's)
+  }
   const int64_t hs = live ? vamd::ogg_live_slots(hb) : vamd::ogg_header_slots(hb);
   const int64_t sp = vamd::ogg_slots_per_packet(f->pkcap[0] > f->pkcap[1] ? f->pkcap[0] : f->pkcap[1]);
   const int64_t nslots = ns * hs + sp * nb;
@@ -286,7 +325,9 @@ static int run_pager(vamd_feed *f, FeedLane &L, const int64_t *d_stream_start, l
   FEED_TRY(L.d_npages.need((size_t)ns * 4));
   FEED_TRY(L.d_ostatus.need((size_t)ns));
   FEED_TRY(L.h_orec.need(al(orec_status(ns) + (size_t)ns, 16)));
-  const int64_t bound = live ? vamd::ogg_live_file_bound((int64_t)L.h_out.bytes, nb, ns, hb) : vamd::ogg_file_bound((int64_t)L.h_out.bytes, nb, ns, hb);
+  const int64_t bound = tagged ? (live ? vamd::ogg_live_file_bound_v((int64_t)L.h_out.bytes, nb, ns, hb, cmt_sum)
+                                       : vamd::ogg_file_bound_v((int64_t)L.h_out.bytes, nb, ns, hb, cmt_sum))
+                        : live ? vamd::ogg_live_file_bound((int64_t)L.h_out.bytes, nb, ns, hb) : vamd::ogg_file_bound((int64_t)L.h_out.bytes, nb, ns, hb);
   FEED_TRY(L.h_ogg.need(al((size_t)bound + 16, 4096)));
   void *drec = nullptr, *dbytes = nullptr;
   FEED_TRY(hipHostGetDevicePointer(&drec, L.h_orec.p, 0));
@@ -297,9 +338,10 @@ static int run_pager(vamd_feed *f, FeedLane &L, const int64_t *d_stream_start, l
   I.info = (const uint8_t *)L.d_minfo.p, I.bytes = (const uint8_t *)L.d_mirror.p, I.cap = (int64_t)L.h_out.bytes;
   I.packet_total = d_packet_total;
   I.hdr = (const uint8_t *)L.d_hdr.p;
-  for (int i = 0; i < 3; i++) I.hdr_off[i] = L.hdr_off[i], I.hdr_bytes[i] = hb[i];
+  for (int i = 0; i < 3; i++) I.hdr_off[i] = L.hdr_off[i], I.hdr_bytes[i] = (int32_t)f->ogg_hdr[i].size();
   I.serial = (const uint32_t *)L.d_serial.p;
   I.header_slots = hs, I.slots_per_packet = sp;
+  I.cmt = tagged ? (const uint8_t *)L.d_cmt.p : nullptr;
   vamd::OggOut O;
   uint8_t *dr = (uint8_t *)drec;
   O.total = (int64_t *)dr, O.stream_offset = (int64_t *)(dr + 8), O.npages = (int32_t *)(dr + orec_npages(ns)), O.status = dr + orec_status(ns);
@@ -1003,6 +1045,17 @@ static void ogg_job(vamd_feed *f, FeedLane &L, long nstreams) {
   if (!f->write_frames)
     for (size_t s = 0; s < L.user_serials.size() && s < (size_t)nstreams; s++) L.serials[s] = L.user_serials[s];
   L.user_serials.clear();
+  // ... and its comment headers: what vamd_feed_ogg_comments set for the slot, of a live group only those of the streams
+  // that begin with it; none left: a group like any other
+  L.comments.swap(L.user_comments);
+  L.user_comments.clear();
+  if (L.comments.size() > (size_t)nstreams) L.comments.resize((size_t)nstreams);
+  bool any = false;
+  for (size_t s = 0; s < L.comments.size(); s++) {
+    if (f->write_frames && (L.live[s].open || !L.frames_of[s])) L.comments[s].clear();
+    any |= !L.comments[s].empty();
+  }
+  if (!any) L.comments.clear();
 }
 
 // the tail of vamd_feed_wrote / _wrote_v / _wrote_live (f->m held; the lane's frames_of / close_of are set): the group
@@ -1106,6 +1159,31 @@ int vamd_feed_ogg_serials(vamd_feed *f, int slot, const uint32_t *serials, long 
     return VAMD_EINVAL;
   }
   L.user_serials.assign(serials, serials + n);
+  return VAMD_OK;
+}
+
+int vamd_feed_ogg_comments(vamd_feed *f, int slot, const void *const *comment, const long *bytes, long n) {
+  if (!f || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  std::lock_guard<std::mutex> g(f->m);
+  FeedLane &L = f->lanes[(size_t)slot];
+  if (!f->ogg || L.state != LANE_FILLING || n < 0 || n > f->max_streams || (n && (!comment || !bytes))) {
+    f->err = !f->ogg ? "vamd_feed_ogg_comments: the feed has no Ogg headers (vamd_feed_ogg_headers / vamd_feed_ogg_headers_live)"
+                     : "vamd_feed_ogg_comments: a slot between vamd_feed_buffer and vamd_feed_wrote, 0 to max_streams comments and their lengths";
+    return VAMD_EINVAL;
+  }
+  std::vector<std::vector<uint8_t>> all((size_t)n);
+  for (long s = 0; s < n; s++) {
+    if (!comment[s]) continue;
+    const uint8_t *p = (const uint8_t *)comment[s];
+    const int why = vamd::ogg_comment_check(p, (int64_t)bytes[s]);
+    if (why) {
+      f->err = "vamd_feed_ogg_comments: the comment header of stream " + std::to_string(s) + " (" + std::to_string(bytes[s]) +
+               " bytes) is refused: " + vamd::ogg_comment_why(why);
+      return VAMD_EINVAL;
+    }
+    all[(size_t)s].assign(p, p + bytes[s]);
+  }
+  L.user_comments.swap(all);
   return VAMD_OK;
 }
 
@@ -1214,6 +1292,8 @@ int vamd_feed_release(vamd_feed *f, int slot) {
   FeedLane &L = f->lanes[(size_t)slot];
   if (L.state != LANE_DONE && L.state != LANE_FILLING) return VAMD_EINVAL;
   L.user_serials.clear();
+  L.user_comments.clear();
+  L.comments.clear();
   L.state = LANE_FREE;
   f->cv_done.notify_all();
   return VAMD_OK;
