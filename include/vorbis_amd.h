@@ -578,10 +578,12 @@ vamd_ctx *vamd_batcher_context(vamd_batcher *b);
  * slice), the ampmax chains and the managers carried from slice to slice.  A managed blob without the section (packed
  * before it existed) is refused by vamd_feed_create (VAMD_EIMPL; vamd_feed_last_error(NULL) says why).  Thread rules: one thread drives a feed (or several, each
  * with its own slots); the lanes' threads are the library's.
- * LENGTH CAP of a whole-stream feed: a group's plan holds every detector mark of a stream (one per 64 samples) in one
- * workgroup's LDS, so a stream longer than about (LDS bytes - 16) * 64 - 3 * blocksizes[1] frames (160 KiB: ~10.5 M frames,
- * 3 min 57 s at 44.1 kHz, 1 min 49 s at 96 kHz) fails when its group runs (VAMD_EINVAL, "streams too long for one plan").
- * Longer streams, and sources that produce a stream while it plays, take a LIVE feed:
+ * LENGTH of a whole-stream feed's streams: anything up to 0x3fffffff samples per channel, head room and padding included
+ * (blocksizes[1]/2 in front, 3 * blocksizes[1] behind: some 6 h 45 min at 44.1 kHz) -- the bound of a block's position, a
+ * 32-bit int in the plan.  The block walk reads a stream's detector marks (one per 64 samples) through a window in LDS that
+ * slides along the stream, so nothing on the path grows with a workgroup's LDS; what does grow with
+ * max_frames is memory: each lane pins a whole group's samples and keeps them, their detector workspaces and their blocks in
+ * HBM.  Sources that produce a stream while it plays, and callers that would rather not hold a whole recording, take a LIVE feed:
  *     vamd_feed_create_live(..., write_frames)   the same lanes; each keeps max_streams CONTINUING streams
  *     slot = vamd_feed_buffer(f, &pcm)           the next pieces of that lane's streams 0 .. nstreams-1, back to back
  *     vamd_feed_wrote_live(f, slot, nstreams, frames, close)

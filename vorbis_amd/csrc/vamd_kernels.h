@@ -1436,9 +1436,10 @@ __global__ __launch_bounds__(64) void k_env_walk(int ch, long nstreams, long nst
 }
 
 // ---- device-resident stream control (k_blockout.h) ----------------------------------------------------
-// one wave per stream: the lanes turn the stream's flags into its mark bytes in LDS (coalesced reads, ve->mark[] as
-// mark_at defines it), then one lane does the walk out of LDS -- a dependent chain of a few thousand steps that would
-// otherwise pay a trip to HBM at each of them
+// one wave per stream: the lanes turn the stream's flags into mark bytes in LDS (coalesced reads, ve->mark[] as mark_at
+// defines it), then the wave does the walk out of LDS -- a dependent chain of a few thousand steps that would otherwise pay
+// a trip to HBM at each of them.  The LDS is a window of `window` marks (MarkWindow, k_blockout.h): a stream that is longer
+// has it refilled further on whenever the walk steps out of it, so that a stream's length is not bounded by a workgroup's LDS.
 // flags: row s of `flags` holds the steps [0, split) at stride stride1, row s of `flags2` the steps from split on at stride2 (the
 // steps of a stream's end-of-stream padding are taken in a second detector pass, vamd_plan_streams_whole; split == B.nsteps:
 // one array).  pending != null: a dry run -- nothing is emitted, pending[s] = centerW of the block the walk stopped in front of.
@@ -1451,10 +1452,8 @@ __global__ __launch_bounds__(64) void k_plan_streams(BlockoutP B, long nstreams,
                                                      long split, const unsigned char *__restrict__ flags2, long stride2,
                                                      PlannedBlock *__restrict__ blocks, int *__restrict__ counts,
                                                      long long *__restrict__ pending, const PlanGeo *__restrict__ geo,
-                                                     int with_eof) {
-  unsigned char *marks = (unsigned char *)vamd_smem;  // [nsteps + 4]
+                                                     int with_eof, long window) {
   const long s = blockIdx.x;
-  const long lds_steps = B.nsteps;  // (the launch's LDS holds this many marks + 4)
   if (geo) {
     B.nsamples = geo[s].nsamples;
     B.eof = geo[s].eof;
@@ -1466,19 +1465,8 @@ __global__ __launch_bounds__(64) void k_plan_streams(BlockoutP B, long nstreams,
       B.nsteps = split;
     }
   }
-  const long last = blockout_steps(B);
-  const unsigned char *f = flags + s * stride1, *f2 = flags2 + s * stride2;
-  auto flag = [&](long p) -> int { return p < split ? f[p] : f2[p - split]; };
-  for (long p = threadIdx.x; p < lds_steps + 4; p += 64) {
-    int m = 0;  // mark_at(), over the two pieces
-    if (p < last) {
-      if (p >= 1) m |= flag(p - 1) & 1;
-      m |= flag(p) & 3;
-      if (p + 1 < last) m |= flag(p + 1) & 2;
-    }
-    marks[p] = (unsigned char)(m != 0);
-  }
-  __syncthreads();
+  MarkWindow marks;
+  marks.open((unsigned char *)vamd_smem, window, flags + s * stride1, split, flags2 + s * stride2, blockout_steps(B));
   int n0 = 0, n1 = 0;
   long pc = 0;
   plan_stream(B, marks, pending ? nullptr : blocks + s * B.maxblocks, &n0, &n1, &pc);  // (the whole wave: it looks at 64 marks at a time)

@@ -210,11 +210,12 @@ static int plan_streams(vamd_ctx *c, float *pcm, long stream_stride, long channe
   int r;
   if ((r = plan_ws(c, nstreams, (size_t)nstreams * (steps_all ? steps_all : 1), B.maxblocks, &ws))) return r;
   hipStream_t s = c->stream;
-  const size_t plan_lds = (size_t)((steps_all + 4 + 15) & ~15L);
-  if (plan_lds > c->lds_per_block) return fail(c, VAMD_EINVAL, "streams too long for one plan (their marks must fit a workgroup's LDS)");
-  // (above the default 64 KB of dynamic LDS the launch needs the opt-in, and a launch that fails leaves counts[] --
-  // which sizes everything below -- uninitialised: hence the checks straight after it)
-  HIP_TRY(c, hipFuncSetAttribute((const void *)k_plan_streams, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block));
+  // the walk's LDS: a window of marks (MarkWindow), the whole of a stream that is shorter.  The default fits the 64 KB of
+  // dynamic LDS a launch gets without an opt-in; a window from the test knob is held to what a workgroup has.
+  long window = plan_window_clamp(B, c->K.plan_window > 0 ? c->K.plan_window : VAMD_PLAN_WINDOW_DEFAULT);
+  if (window > 65536) window = 65536;
+  if (window > steps_all + 4) window = steps_all + 4;
+  const size_t plan_lds = (size_t)((window + 15) & ~15L);
   unsigned char *flags1 = (unsigned char *)ws.flags, *flags2 = flags1 + (size_t)nstreams * steps1;
   const PlanGeo *geo = nullptr;      // streams of unequal length: their own sample counts, step counts and first padding steps
   const int *count1 = nullptr, *count2 = nullptr;
@@ -267,7 +268,7 @@ static int plan_streams(vamd_ctx *c, float *pcm, long stream_stride, long channe
       return r;
     // where every stream's walk stands when the data runs out: the reference's buffer begins blocksizes[1]/2 before it
     hipLaunchKernelGGL(k_plan_streams, dim3((unsigned)nstreams), dim3(64), plan_lds, s, B, nstreams, flags1, steps1, steps1, flags2, steps2,
-                       (PlannedBlock *)nullptr, (int *)nullptr, (long long *)ws.pending, geo, 0);
+                       (PlannedBlock *)nullptr, (int *)nullptr, (long long *)ws.pending, geo, 0, window);
     hipLaunchKernelGGL(k_lpc_tail, dim3((unsigned)(nstreams * ch)), dim3(64), lds_lpc, s, ch, nstreams, pcm, stream_stride,
                        channel_stride, nsamples, c->B.bs[1], pad, (const long long *)ws.pending, geo);
     HIP_TRY(c, hipGetLastError());
@@ -282,7 +283,7 @@ static int plan_streams(vamd_ctx *c, float *pcm, long stream_stride, long channe
     return r;
   HIP_TRY(c, hipMemsetAsync(ws.counts, 0, (size_t)nstreams * 2 * sizeof(int), s));
   hipLaunchKernelGGL(k_plan_streams, dim3((unsigned)nstreams), dim3(64), plan_lds, s, B, nstreams, flags1, steps1, steps1, flags2, steps2,
-                     (PlannedBlock *)ws.blocks, (int *)ws.counts, (long long *)nullptr, geo, 1);
+                     (PlannedBlock *)ws.blocks, (int *)ws.counts, (long long *)nullptr, geo, 1, window);
   HIP_TRY(c, hipGetLastError());
   return plan_emit(c, B, nstreams, stream_stride, ws, plan);
 }
