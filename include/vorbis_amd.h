@@ -692,15 +692,16 @@ const char *vamd_feed_last_error(const vamd_feed *f);
  *
  * THE LIVE OGG FEED: a live feed's streams as Ogg files, in pieces.
  *     vamd_feed_create_live(...); vamd_feed_ogg_headers_live(f, id, comment, setup)   once, before the first vamd_feed_buffer
- *     slot = vamd_feed_buffer(f, &pcm) ... [vamd_feed_ogg_serials] ... vamd_feed_wrote_live(f, slot, nstreams, frames, close)
+ *     slot = vamd_feed_buffer(f, &pcm) ... [vamd_feed_ogg_serials] [vamd_feed_ogg_flush] ... vamd_feed_wrote_live(f, slot, nstreams, frames, close)
  *     vamd_feed_ogg(f, slot, &pieces)                 per stream the NEXT BYTES of its file; vamd_feed_packets unchanged
  * stream_offset[s] .. stream_offset[s + 1] is the next byte range of stream (slot, s)'s file: the pages the stream
  * completed in this group, a whole number of pages (npages[s] of them), empty where it completed none.  A page is handed
- * out once it is closed and never before; there is no per-write flush (a silent stream, one one-byte packet per block,
- * completes a page only every 255 packets).  The ranges of a stream over all its groups, up to and including the group
- * that closes it, laid end to end are byte for byte the file the whole-stream Ogg feed makes of the same samples and
- * serial number (where the stream fits one), and in every case the shipped host mux's of its packets: the paging policy
- * above is unchanged, and the result depends on no cut into pieces, write cadence or slice size.
+ * out once it is closed and never before; unless the caller flushes (below), nothing closes a page but the policy (a
+ * silent stream, one one-byte packet per block, completes a page only every 255 packets).  The ranges of a stream over all
+ * its groups, up to and including the group that closes it, laid end to end are byte for byte the file the whole-stream Ogg
+ * feed makes of the same samples and serial number (where the stream fits one), and in every case the shipped host mux's of
+ * its packets: the paging policy above is unchanged, and the result depends on no cut into pieces, write cadence or slice
+ * size -- for a feed that never flushes.
  * Between groups the device keeps per stream the paging walk's state (the open page, the next sequence number, the
  * file offset), its serial number and the CARRY: the packets with a segment on the open page -- at most 255 packets and
  * 65 025 bytes, of a packet continued from an earlier page only the rest -- so neither stream length nor memory grows
@@ -714,7 +715,31 @@ const char *vamd_feed_last_error(const vamd_feed *f);
  * A stream that loses a packet (bits = -1; a non-finite sample): from that group on its ranges are empty and status[s]
  * carries that block's VAMD_STATUS_*, in every group until the stream is closed; the packets carried for its open page
  * are dropped.  Where a whole stream gets NO file, a live stream has already handed pages out: those bytes are a valid
- * Ogg prefix without an end-of-stream page.  Other streams, and the slot's next stream, are untouched. */
+ * Ogg prefix without an end-of-stream page.  Other streams, and the slot's next stream, are untouched.
+ * A FLUSH PER WRITE (what ogg_stream_flush() is to a libogg user; a source that plays while it is made): vamd_feed_ogg_flush,
+ * between vamd_feed_buffer and vamd_feed_wrote_live, names the streams of THIS group whose open page leaves with the group:
+ * flush[s] != 0, s < n <= max_streams, flushes stream (slot, s) behind this group's packets; flush == NULL with n > 0 flushes
+ * every one of the first n; streams from n on are not flushed.  A later call for the same group replaces an earlier one, and
+ * the slot's next group starts with none.  What a flush does: if the stream's open page holds at least one segment after
+ * the group's last packet has been walked, the page is closed there -- exactly as the end of the run closes it, but without
+ * flag 0x04.  Its granule position is that of the last packet completed on it, never -1: at a group's end every packet on
+ * the open page is complete (so its last lacing value is below 255).  The page leaves with this group's range and
+ * npages[s] counts it; the next packet starts a fresh page with the next sequence number.  A flush that finds the open page
+ * empty hands out nothing; a flushed 0-frame piece of an open stream hands out the carried packets' page.  Precedence: a
+ * close in the same group wins -- the end-of-stream page is what it always was; a stream that begins with the group gets its
+ * header pages, then its audio pages, then the flushed one; a stream that is absent, dead (it lost a packet) or not yet
+ * begun is untouched, and flushing it is no error.
+ * What is claimed of the bytes.  A feed that never makes the call, or flushes no stream, returns byte for byte what it
+ * returned before the call existed: its files depend on no cut.  With flushes the file DOES depend on where the flushes fall:
+ * it is the shipped host mux's of the same packets with the same flush points (k_ogg.h, ogg_mux_piece), a valid Ogg Vorbis I
+ * stream that holds the same packets in the same order as the unflushed file, decodes to the same samples, and is longer by
+ * one page header and lacing table per flush that closed a page.  After a flushing group the stream's ranges so far, laid end
+ * to end, hold every packet vamd_feed_packets has reported for it, whole: what is still out is only what the encoder itself
+ * has not yet determined, fewer than the live feed's retention bound (3 200 samples at 44.1 kHz).  Page table and file arena are sized
+ * as before: the flushed page takes the place that the run's last page has in both bounds (k_ogg.h, ogg_live_slots).
+ * VAMD_EINVAL, the reason in vamd_feed_last_error: a whole-stream feed, a live feed without Ogg headers, a slot not between
+ * buffer and wrote, n < 0, n > max_streams.  The flags ride to the device in the word that already names each stream's begin
+ * and close: no copy, launch or wait more. */
 typedef struct vamd_feed_ogg_result {
   int64_t nstreams;
   const int64_t *stream_offset;   /* [nstreams + 1]: stream s's file (a live feed: its next piece) is bytes[stream_offset[s] .. stream_offset[s + 1]) */
@@ -733,6 +758,9 @@ int vamd_feed_ogg_serials(vamd_feed *f, int slot, const uint32_t *serials, long 
  * comment[s] (bytes[s] long) is the Vorbis comment header of stream s of this group, s < n <= max_streams;
  * comment[s] == NULL: the feed's own (the one given to vamd_feed_ogg_headers[_live]).  Copied before it returns. */
 int vamd_feed_ogg_comments(vamd_feed *f, int slot, const void *const *comment, const long *bytes, long n);
+/* between vamd_feed_buffer and vamd_feed_wrote_live, like vamd_feed_ogg_serials; this group only: stream s < n is flushed
+ * behind the group's packets where flush[s] != 0 (flush == NULL: all of the first n).  A live Ogg feed's only. */
+int vamd_feed_ogg_flush(vamd_feed *f, int slot, const uint8_t *flush, long n);
 int vamd_feed_ogg(vamd_feed *f, int slot, vamd_feed_ogg_result *out);
 
 #ifdef __cplusplus

@@ -17,6 +17,12 @@ a title and a padding tag), handed over inside the timed part of every group -- 
 the streams.  wall_s_reps: every timed repetition's wall time, in order (wall_s is their best).
 
     python tools/feed_ogg_bench.py --streams 64 --seconds 20 --reps 3 --tags 65536
+
+--flush (with --live): the Ogg feed flushes every stream in every group (vamd_feed_ogg_flush, inside the timed part), so
+each group returns every stream's open page too; `pages` counts all pages the set handed out (with and without --flush, so
+the difference is the flushed ones), file_bytes shows the growth.
+
+    python tools/feed_ogg_bench.py --live --streams 64 --seconds 20 --piece 0.1 --reps 3 --flush
 """
 import argparse
 import json
@@ -40,7 +46,10 @@ def main():
     ap.add_argument("--live", action="store_true", help="live feeds: the streams in pieces, the Ogg files in pieces")
     ap.add_argument("--piece", type=float, default=1.0, help="--live: seconds per piece")
     ap.add_argument("--tags", type=int, default=0, help="the Ogg feed: a comment header of its own per stream, of about this many bytes")
+    ap.add_argument("--flush", action="store_true", help="--live: the Ogg feed flushes every stream in every group")
     a = ap.parse_args()
+    if a.flush and not a.live:
+        ap.error("--flush goes with --live: a whole stream's file has no open page to flush")
     import vorbis_amd
     frames = int(44100 * a.seconds)
     rng = np.random.default_rng(1)
@@ -116,7 +125,7 @@ def live(a, vorbis_amd, blob, pcm, names):
         for k in names:
             f = feeds[k]
             dt = dev = 0.0
-            nb = nbytes = file_bytes = groups = 0
+            nb = nbytes = file_bytes = groups = pages = 0
             for at in range(0, frames, piece):
                 flat = np.ascontiguousarray(pcm[:, at:at + piece]).reshape(-1)
                 n = min(piece, frames - at)
@@ -125,9 +134,13 @@ def live(a, vorbis_amd, blob, pcm, names):
                 t0 = time.perf_counter()
                 if k == "ogg" and a.comments and at == 0:
                     f.ogg_comments(slot, a.comments)
+                if k == "ogg" and a.flush:
+                    f.ogg_flush(slot, True)
                 f.wrote_live(slot, [n] * a.streams, [at + piece >= frames] * a.streams)
                 if k == "ogg":
-                    file_bytes += f.ogg(slot, copy=False)["total_bytes"]
+                    o = f.ogg(slot, copy=False)
+                    file_bytes += o["total_bytes"]
+                    pages += int(np.sum(o["npages"]))
                 r = f.packets(slot, copy=False)
                 dt += time.perf_counter() - t0
                 nb, nbytes, dev, groups = nb + r["nblocks"], nbytes + r["total_bytes"], dev + r["device_ms"], groups + 1
@@ -135,9 +148,9 @@ def live(a, vorbis_amd, blob, pcm, names):
             if rep:
                 walls[k].append(dt)
             if rep and (best[k] is None or dt < best[k][0]):
-                best[k] = (dt, nb, nbytes, dev, file_bytes, groups)
+                best[k] = (dt, nb, nbytes, dev, file_bytes, groups, pages)
     for k in names:
-        dt, nb, nbytes, dev, file_bytes, groups = best[k]
+        dt, nb, nbytes, dev, file_bytes, groups, pages = best[k]
         line = {"feed": "live " + k, "streams": a.streams, "seconds": a.seconds, "piece_s": a.piece, "groups": groups, "blocks": nb,
                 "wall_s": dt, "group_ms": 1e3 * dt / groups, "group_device_ms": dev / groups, "blocks_per_s": nb / dt,
                 "packet_bytes_per_s": nbytes / dt, "wall_s_reps": walls[k]}
@@ -145,6 +158,8 @@ def live(a, vorbis_amd, blob, pcm, names):
             line["file_bytes_per_s"] = file_bytes / dt
             line["file_bytes"] = file_bytes
             line["tags"] = a.tags
+            line["flush"] = bool(a.flush)
+            line["pages"] = pages
         print(json.dumps(line))
     for f in feeds.values():
         f.close()

@@ -1,4 +1,4 @@
-"""Code-object resource summary of the product kernels: VGPRs / SGPRs / spills / scratch / occupancy as hipcc reports
+"""Code-object resource summary of the product kernels: VGPRs / SGPRs / spills / scratch / LDS / occupancy as hipcc reports
 them (-Rpass-analysis=kernel-resource-usage), one line per kernel whose demangled name matches the pattern.
 
     python tools/kernel_resources.py ['k_noise|k_floor']
@@ -15,7 +15,7 @@ cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ff
 err = subprocess.run(cmd, capture_output=True, text=True, stdin=subprocess.DEVNULL, timeout=900).stderr
 cur, rows = None, []
 for line in err.splitlines():
-    m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill): (\S+)", line)
+    m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\S+)", line)
     if not m:
         continue
     k, v = m.groups()
@@ -27,9 +27,9 @@ for line in err.splitlines():
 if not rows:  # the compile failed (c++filt without arguments would wait on stdin)
     sys.exit("no kernels reported:\n" + "\n".join(l for l in err.splitlines() if "error" in l)[:4000])
 names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True, stdin=subprocess.DEVNULL).stdout.splitlines()
-print("%-44s %5s %5s %7s %7s %7s %4s" % ("kernel", "VGPR", "SGPR", "vspill", "sspill", "scratch", "occ"))
+print("%-44s %5s %5s %7s %7s %7s %6s %4s" % ("kernel", "VGPR", "SGPR", "vspill", "sspill", "scratch", "LDS", "occ"))
 for r, nm in zip(rows, names):
     nm = re.sub(r"\(.*$", "", nm.replace("(anonymous namespace)::", "")).replace("void ", "")
     if pat.search(nm):
-        print("%-44s %5s %5s %7s %7s %7s %4s" % (nm, r.get("VGPRs"), r.get("TotalSGPRs"), r.get("VGPRs Spill"), r.get("SGPRs Spill"),
-                                                 r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]")))
+        print("%-44s %5s %5s %7s %7s %7s %6s %4s" % (nm, r.get("VGPRs"), r.get("TotalSGPRs"), r.get("VGPRs Spill"), r.get("SGPRs Spill"),
+                                                     r.get("ScratchSize [bytes/lane]"), r.get("LDS Size [bytes/block]"), r.get("Occupancy [waves/SIMD]")))

@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe",
                     "vamd_feed_packets", "vamd_feed_release", "vamd_feed_last_error", "vamd_feed_create_live", "vamd_feed_wrote_live",
                     "vamd_analyze_streams_mixed_managed", "vamd_bitrate_init_states", "vamd_bitrate_walk",
                     "vamd_feed_ogg_headers", "vamd_feed_ogg_serials", "vamd_feed_ogg", "vamd_feed_ogg_headers_live",
-                    "vamd_feed_ogg_comments"]
+                    "vamd_feed_ogg_comments", "vamd_feed_ogg_flush"]
 PACKETBLOBS = 15
 
 _vp = C.c_void_p
@@ -200,6 +200,7 @@ def load_library():
     L.vamd_feed_ogg_headers_live.argtypes = [_vp, _vp, C.c_long, _vp, C.c_long, _vp, C.c_long]
     L.vamd_feed_ogg_serials.argtypes = [_vp, C.c_int, _vp, C.c_long]
     L.vamd_feed_ogg_comments.argtypes = [_vp, C.c_int, _vp, _vp, C.c_long]
+    L.vamd_feed_ogg_flush.argtypes = [_vp, C.c_int, _vp, C.c_long]
     L.vamd_feed_ogg.argtypes = [_vp, C.c_int, C.POINTER(_FeedOggResult)]
     L.vamd_feed_last_error.argtypes = [_vp]
     L.vamd_feed_last_error.restype = C.c_char_p
@@ -1056,6 +1057,16 @@ class Feed:
         size = (C.c_long * max(n, 1))(*[0 if c is None else len(c) for c in pk])
         self._check(self.L.vamd_feed_ogg_comments(self.h, slot, C.cast(ptr, _vp), C.cast(size, _vp), n))
 
+    def ogg_flush(self, slot, flags=True):
+        """A live Ogg feed: the streams of the group being filled in `slot` (between buffer() and wrote_live()) whose open
+        page leaves with this group.  flags: a sequence, stream s is flushed where flags[s] is true and streams beyond it
+        are not; True: every stream the feed can hold; False or None: none.  For this group only."""
+        if flags is True:
+            self._check(self.L.vamd_feed_ogg_flush(self.h, slot, None, self.max_streams))
+            return
+        a = np.ascontiguousarray([] if flags is None or flags is False else [bool(v) for v in flags], dtype=np.uint8).reshape(-1)
+        self._check(self.L.vamd_feed_ogg_flush(self.h, slot, _vp(a.ctypes.data) if a.size else None, a.size))
+
     def ogg(self, slot, copy=True):
         """Waits for the group.  -> dict: nstreams, stream_offset [nstreams + 1], npages, status [nstreams], bytes (a view
         over the lane's pinned file arena, or a copy), total_bytes: stream s's file is bytes[stream_offset[s]:stream_offset[s + 1]]
@@ -1213,10 +1224,11 @@ class Feed:
                 pass
         return self._rows(r, len(parts))
 
-    def encode_live_ogg(self, pieces, close=None, serials=None, comments=None):
-        """One group of a live Ogg feed with ONE lane, synchronously: pieces and close as encode_live takes them; serials
-        and comments (optional; this group's) as ogg_serials and ogg_comments take them.  -> per stream the next bytes of its Ogg file: the pages it completed in this group
-        (b"" where none, or where the stream has lost a packet: see ogg())."""
+    def encode_live_ogg(self, pieces, close=None, serials=None, comments=None, flush=None):
+        """One group of a live Ogg feed with ONE lane, synchronously: pieces and close as encode_live takes them; serials,
+        comments and flush (optional; this group's) as ogg_serials, ogg_comments and ogg_flush take them.  -> per stream the
+        next bytes of its Ogg file: the pages it completed in this group, with a flush its open page too (b"" where none,
+        or where the stream has lost a packet: see ogg())."""
         if self.write_frames is None:
             raise ValueError("encode_live_ogg needs a live feed (Feed(..., write_frames=..., ogg_headers=...))")
         if self.lanes != 1:
@@ -1233,6 +1245,8 @@ class Feed:
                 self.ogg_serials(slot, serials)
             if comments is not None:
                 self.ogg_comments(slot, comments)
+            if flush is not None:
+                self.ogg_flush(slot, flush)
             self.wrote_live(slot, frames, close)
             r = self.ogg(slot, copy=False)
             off = r["stream_offset"]

@@ -8,7 +8,8 @@
 //     time with a page per step (the audio run: prefix sums of the sizes, every packet asked at once where the page ends);
 //   * the kernels: k_ogg_plan (a wave per stream runs the walk, sizes scanned into LDS 64 at a time) and k_ogg_pages (a
 //     wave per page: header, lacing table, body gathered from the packets, CRC, written with aligned dword stores) -- and,
-//     for a live feed, whose files arrive in pieces, k_ogg_carry: what lies on the page still open stays on the device.
+//     for a live feed, whose files arrive in pieces, k_ogg_carry: what lies on the page still open stays on the device,
+//     unless the group flushes the stream (vamd_feed_ogg_flush): then the open page leaves with the group.
 // The CRC functions and the walk are ONE body: the library compiles them for gfx950, the CPU suite compiles this very
 // file with the host compiler (tests/ogg_host.py) together with the host-only mux at the end, which lays the same
 // pages out byte by byte -- the second implementation of the policy that the GPU's files are held against.
@@ -214,6 +215,7 @@ VAMD_OGG_FN void ogg_walk_join(OggWalk &w, OggPage *out, int64_t cap, int32_t kb
   if (why) ogg_page_close(w, out, cap, 0);
 }
 
+// (eos = 0: the end of a header run -- and a live stream's FLUSH, ogg_flush below: the page is closed, the run goes on)
 VAMD_OGG_FN void ogg_run_end(OggWalk &w, OggPage *out, int64_t cap, int eos) {
   if (w.pg.nseg > 0) ogg_page_close(w, out, cap, eos ? 0x04 : 0);
 }
@@ -312,19 +314,44 @@ struct OggLive {
   int32_t dead;     // != 0: the VAMD_STATUS_* of the block that had no packet; no page until the stream is closed (0x80: the state is unusable)
   int32_t ncarry;   // carried packets
 };
-enum { OGG_LIVE_BEGIN = 1, OGG_LIVE_CLOSE = 2, OGG_LIVE_ABSENT = 4 };  // a stream in a group: it starts / ends with it / is not there
+// a stream in a group: it starts / ends with it / is not there / is flushed behind it (vamd_feed_ogg_flush)
+enum { OGG_LIVE_BEGIN = 1, OGG_LIVE_CLOSE = 2, OGG_LIVE_ABSENT = 4, OGG_LIVE_FLUSH = 8 };
 // the open page of a group's end, rebased onto the next group's list
 VAMD_OGG_FN void ogg_walk_rebase(OggWalk &w) { w.pg.first = 0, w.pg.byte0 = 0, w.npages = 0; }
+// A FLUSH (a group's end, behind its last packet; the stream goes on): the open page, if it holds a segment, is closed as
+// the end of the run closes it, without the end-of-stream flag, and the run goes on -- the next packet starts a fresh page
+// with the next sequence number.  Every packet on the page is complete there, so its granule position is the last one's,
+// never -1, and its last lacing value is below 255.  Nothing lies on the open page afterwards: the carry is empty.  A
+// close in the same group wins (the page ends the run, with its flag), and an empty open page hands out nothing.
+// The case a feed never meets -- a close with no new packet onto an EMPTY open page, which a flush in the group before
+// makes possible for this walk's callers: ogg_run_end writes no page there, so the file ends on the flushed page without
+// an end-of-stream flag (no empty page is invented; RFC 3533 allows one, the policy above does not name one).  The feed
+// cannot get there: a closing piece always yields the e_o_s packet, so its closing group always has a new packet.
+VAMD_OGG_FN void ogg_flush(OggWalk &w, OggPage *out, int64_t cap) { ogg_run_end(w, out, cap, 0); }
 // Page slots per stream of a live group: the header slots, one for the carried page, and ogg_slots_per_packet per NEW
-// packet (every other page holds new packets only) ...
+// packet (every other page holds new packets only).  The count, flushes included -- a group's pages of stream s, n new
+// packets of at most cap bytes: where the stream begins, at most ogg_header_slots - 2 header pages; the carried page (one slot: it is the only page with carried packets
+// on it, flushed or not, since a flush leaves no carry); pages of new packets alone that are closed by the fill rule or at
+// 255 segments, at most n / 4 + n (1 + cap / 255) / 255 <= n ogg_slots_per_packet(cap) of them; and ONE page that is
+// neither -- the run's last (a close) or the flushed one, never both, since a close wins.  That one is among the two
+// spare slots of ogg_header_slots, as the run's last always was: a flush adds no page that the close did not already
+// have a slot for.  With n = 0 (a flushed 0-frame piece, a list of one-byte packets flushed one per group) the carried
+// page's slot is the flushed page's.  So a flush needs no slot more, and the page table is the size it was without it.
 VAMD_OGG_FN int64_t ogg_live_slots(const int32_t *header_bytes) { return ogg_header_slots(header_bytes) + 1; }
-// ... and the bytes a live group's pages take at most: ogg_file_bound of the new packets and every stream's full carry,
-// and the carried page's header and lacing
+// The bytes a live group's pages take at most: ogg_file_bound of the new packets and every stream's full carry, and the
+// carried page's header and lacing.  It holds with flushes as well: ogg_file_bound counts per page a full header and lacing table (282 bytes), and
+// its pages are: those with more than OGG_FILL body bytes, those with 255 segments, and per stream 2 + ogg_header_slots,
+// of which the header runs use ogg_header_slots - 2 at most -- four pages per stream and group that are neither full nor
+// header pages.  A whole stream uses one of them (the run's last); a live group the same one for its close OR its
+// flush, and the carried page has a header of its own on top (the last term).  The flushed page's body is packet bytes
+// that are counted in any case (new ones, or the carry's).  ogg_live_file_bound_v: ogg_file_bound_v counts 4 pages per
+// stream and the comments' segments / 255, of which the header runs use 2 per stream and that quotient -- two spare per
+// stream, one of them the run's last or the flushed page.  So the pinned arena does not grow with a flush.
 VAMD_OGG_FN int64_t ogg_live_file_bound(int64_t packet_bytes, int64_t npackets, int64_t nstreams, const int32_t *header_bytes) {
   return ogg_file_bound(packet_bytes + nstreams * OGG_CARRY_BODY, npackets + nstreams * OGG_MAX_SEGS, nstreams, header_bytes) +
          nstreams * (OGG_HEADER + OGG_MAX_SEGS);
 }
-// ... with comment headers per stream (ogg_file_bound_v; the slots: ogg_live_slots of the group's longest comment)
+// The same with comment headers per stream (ogg_file_bound_v; the slots: ogg_live_slots of the group's longest comment)
 VAMD_OGG_FN int64_t ogg_live_file_bound_v(int64_t packet_bytes, int64_t npackets, int64_t nstreams, const int32_t *header_bytes,
                                           int64_t comment_sum) {
   return ogg_file_bound_v(packet_bytes + nstreams * OGG_CARRY_BODY, npackets + nstreams * OGG_MAX_SEGS, nstreams, header_bytes, comment_sum) +
@@ -395,9 +422,11 @@ __device__ __forceinline__ int ogg_live_ncarry(const OggLiveIO &V, long s) {  //
 // header packet 1; nothing else of the walk knows.
 // A live group (V.in set): a stream that begins walks the headers and begins the audio run; an open one loads its walk --
 // the open page already counts the carried packets, which come first in the group's list -- and walks the new packets;
-// only a closing one ends the run.  file_bytes is what the group adds to the file.  A stream that lost a packet writes no
-// page from that group on and reports the block's status until it is closed.  The state behind the group goes to V.out
-// (ncarry and the rebase are k_ogg_carry's).
+// only a closing one ends the run; a flushed one (OGG_LIVE_FLUSH, and no close) closes its open page behind the last
+// packet and goes on (ogg_flush): one more page in its slots, an empty open page in the state.  file_bytes is what the
+// group adds to the file.  A stream that lost a packet writes no page from that group on and reports the block's status
+// until it is closed; it, an absent one and one that has not begun are not flushed either.  The state behind the group
+// goes to V.out (ncarry and the rebase are k_ogg_carry's).
 __global__ __launch_bounds__(64) void k_ogg_plan(OggIn I, long nstreams, OggPage *__restrict__ pages, int64_t *__restrict__ file_bytes,
                                                  int32_t *__restrict__ npages, uint8_t *__restrict__ status, OggLiveIO V) {
   __shared__ int32_t sz[64], Bx[65], Sx[65];
@@ -461,6 +490,7 @@ __global__ __launch_bounds__(64) void k_ogg_plan(OggIn I, long nstreams, OggPage
       }
     }
     if (lf & OGG_LIVE_CLOSE) ogg_run_end(w, out, wcap, 1);
+    else if (lf & OGG_LIVE_FLUSH) ogg_flush(w, out, wcap);
   }
   int np = __shfl(w.npages, 0, 64);
   if (np > cap) np = 0, st |= 0x80u;  // (the slot bound did not hold: no file rather than a cut one)
@@ -502,6 +532,11 @@ struct OggOut {
 // in I.hdr -- the pieces' source and length change, lacing, CRC and stores do not.
 // A live group (V.in set): a page's packets come from two sources -- the first ncarry of the stream's list lie in its
 // carry, the others in the mirror -- the serial number is the stream's own, and the page goes where the group's range has it.
+// A flushed page is a page like any other here: its packets are pg.first .. pg.first + npackets - 1 of the stream's list,
+// whether all of them lie in the carry (a 0-frame piece: first = 0, npackets = ncarry, k never reaches the mirror), in
+// the carry and then the mirror (the per-packet choice below), or it begins inside a packet of this group (byte0 > 0:
+// the first piece starts byte0 into its packet, as on every continued page; a continued page that was CARRIED has
+// byte0 = 0 and the flag 0x01 in pg.flags, its first packet being the carried rest).
 __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const OggPage *__restrict__ pages,
                                                   const int64_t *__restrict__ stream_off, const int32_t *__restrict__ npages,
                                                   const uint8_t *__restrict__ status, OggOut O, OggLiveIO V) {
@@ -670,6 +705,8 @@ __global__ __launch_bounds__(64) void k_ogg_pages(OggIn I, long nstreams, const 
 // open -- of each of its packets the bytes and where they go, of a continued first packet the part from byte0 on -- out
 // of the old carry and the mirror into the other carry; then the rebase and ncarry into the state k_ogg_plan left in V.out.
 // A list that contradicts the page (never seen) costs the stream its state: status 0x80 from the next group on.
+// Behind a flush the open page is empty (np = 0): bad0 is false, no loop runs, body = pg.body = 0, nothing is copied, and
+// the state stays alive with ncarry = 0.
 __global__ __launch_bounds__(64) void k_ogg_carry(OggIn I, long nstreams, OggLiveIO V) {
   __shared__ int32_t cb[OGG_MAX_SEGS], co[OGG_MAX_SEGS];
   __shared__ const uint8_t *cs[OGG_MAX_SEGS];
@@ -845,8 +882,9 @@ struct OggPieces {
 // The resumed walk over one group: begin (the stream starts here: T is reset, the headers walked when header_bytes is
 // given), npackets new packets behind the T.ncarry carried ones, close (the run ends).  pages[] <- the pages the group
 // completes, their file_off absolute; returns their number; T.w is the walk at the group's end, not yet rebased.
+// flush (without close): the open page leaves with the group (ogg_flush); T.w.pg is empty then.
 inline int64_t ogg_plan_piece(OggPieces &T, int begin, const int32_t *header_bytes, int64_t npackets, const int32_t *bytes,
-                              const int64_t *granule, int close, OggPage *pages, int64_t cap) {
+                              const int64_t *granule, int close, OggPage *pages, int64_t cap, int flush = 0) {
   if (begin) {
     ogg_walk_init(T.w, 0);
     T.ncarry = 0;
@@ -855,16 +893,20 @@ inline int64_t ogg_plan_piece(OggPieces &T, int begin, const int32_t *header_byt
   }
   ogg_walk_audio(T.w, pages, cap, T.ncarry, npackets, bytes, granule);
   if (close) ogg_run_end(T.w, pages, cap, 1);
+  else if (flush) ogg_flush(T.w, pages, cap);
   return T.w.npages;
 }
 // One group of the mux in pieces: the bytes of the pages it completes into out (returned; written when they and the pages
 // fit), the next state and carry into T.  *open_page (optional): the page left open, as it stood before the rebase.
+// flush (default: none): the stream is flushed behind this group's packets -- the open page is among the group's pages,
+// the page left open and the carry are empty.
 inline int64_t ogg_mux_piece(OggPieces &T, int begin, const uint8_t *const *headers, const int32_t *header_bytes, int64_t npackets,
                              const uint8_t *const *packets, const int32_t *bytes, const int64_t *granule, int close, uint32_t serial,
-                             uint8_t *out, int64_t cap, OggPage *pages, int64_t page_cap, int64_t *npages, OggPage *open_page) {
+                             uint8_t *out, int64_t cap, OggPage *pages, int64_t page_cap, int64_t *npages, OggPage *open_page,
+                             int flush = 0) {
   const int64_t start = begin ? 0 : T.w.file_off;
   const int32_t nc = begin ? 0 : T.ncarry;
-  const int64_t np = ogg_plan_piece(T, begin, headers ? header_bytes : nullptr, npackets, bytes, granule, close, pages, page_cap);
+  const int64_t np = ogg_plan_piece(T, begin, headers ? header_bytes : nullptr, npackets, bytes, granule, close, pages, page_cap, flush);
   const int64_t total = T.w.file_off - start;
   if (npages) *npages = np;
   if (open_page) *open_page = T.w.pg;

@@ -129,10 +129,13 @@ struct FeedLane {
   Buf d_cmt;
   // a live Ogg feed (vamd_feed_ogg_headers_live): per stream the pager's state and its carry -- the packets on the page
   // still open -- in two buffers each; ogg_cur names the one the last group left, the next group writes the other
-  // (k_ogg.h, OggLiveIO).  ogg_flags: the group's OGG_LIVE_* per stream (run_group_live).
+  // (k_ogg.h, OggLiveIO).  ogg_flags: the group's OGG_LIVE_* per stream (run_group_live).  flush: the streams the job
+  // flushes behind its packets (vamd_feed_ogg_flush; user_flush: what the call set for the slot), kept like the comments
+  // until the group is done; it rides in ogg_flags as OGG_LIVE_FLUSH.
   Buf d_olive[2], d_crec[2], d_cbytes[2], d_gstart;
   int ogg_cur = 0;
   std::vector<uint32_t> ogg_flags;
+  std::vector<uint8_t> flush, user_flush;
   vamd_feed_ogg_result ogg_result;
   std::vector<uint8_t> close_of;  // the job's closes (live)
   std::thread worker;
@@ -876,6 +879,7 @@ static int run_group_live(vamd_feed *f, FeedLane &L) {
     for (long i = 0; i < ns; i++) {
       const bool absent = hin[i].fresh && !hin[i].frames;
       L.ogg_flags[(size_t)i] = absent ? vamd::OGG_LIVE_ABSENT : (hin[i].fresh ? vamd::OGG_LIVE_BEGIN : 0) | (hin[i].close ? vamd::OGG_LIVE_CLOSE : 0);
+      if ((size_t)i < L.flush.size() && L.flush[(size_t)i]) L.ogg_flags[(size_t)i] |= vamd::OGG_LIVE_FLUSH;  // (the pager decides whom it concerns)
     }
   }
   FeedLive live;
@@ -1056,6 +1060,10 @@ static void ogg_job(vamd_feed *f, FeedLane &L, long nstreams) {
     any |= !L.comments[s].empty();
   }
   if (!any) L.comments.clear();
+  // ... and the streams it flushes (vamd_feed_ogg_flush), of the caller's streams only
+  L.flush.swap(L.user_flush);
+  L.user_flush.clear();
+  if (L.flush.size() > (size_t)nstreams) L.flush.resize((size_t)nstreams);
 }
 
 // the tail of vamd_feed_wrote / _wrote_v / _wrote_live (f->m held; the lane's frames_of / close_of are set): the group
@@ -1187,6 +1195,22 @@ int vamd_feed_ogg_comments(vamd_feed *f, int slot, const void *const *comment, c
   return VAMD_OK;
 }
 
+int vamd_feed_ogg_flush(vamd_feed *f, int slot, const uint8_t *flush, long n) {
+  if (!f || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  std::lock_guard<std::mutex> g(f->m);
+  FeedLane &L = f->lanes[(size_t)slot];
+  if (!f->write_frames || !f->ogg || L.state != LANE_FILLING || n < 0 || n > f->max_streams) {
+    f->err = !f->write_frames ? "vamd_feed_ogg_flush is for a live Ogg feed (vamd_feed_create_live, vamd_feed_ogg_headers_live): a whole stream's file has no open page to flush"
+             : !f->ogg        ? "vamd_feed_ogg_flush: the feed has no Ogg headers (vamd_feed_ogg_headers_live)"
+                              : "vamd_feed_ogg_flush: a slot between vamd_feed_buffer and vamd_feed_wrote_live, 0 to max_streams flags";
+    return VAMD_EINVAL;
+  }
+  L.user_flush.assign((size_t)n, 1);  // (flush == NULL: every one of the first n)
+  if (flush)
+    for (long s = 0; s < n; s++) L.user_flush[(size_t)s] = flush[s] != 0;
+  return VAMD_OK;
+}
+
 int vamd_feed_ogg(vamd_feed *f, int slot, vamd_feed_ogg_result *out) { return await_group(f, slot, &FeedLane::ogg_result, out, true); }
 
 int vamd_feed_create(vamd_feed **out, const void *setup_blob, size_t blob_bytes, const int *devices, int ndevices,
@@ -1294,6 +1318,8 @@ int vamd_feed_release(vamd_feed *f, int slot) {
   L.user_serials.clear();
   L.user_comments.clear();
   L.comments.clear();
+  L.user_flush.clear();
+  L.flush.clear();
   L.state = LANE_FREE;
   f->cv_done.notify_all();
   return VAMD_OK;
