@@ -644,6 +644,62 @@ int vamd_feed_release(vamd_feed *f, int slot);
 /* the text of the feed's last failure; with f == NULL, of this thread's last vamd_feed_create() that failed */
 const char *vamd_feed_last_error(const vamd_feed *f);
 
+/* ---- device-fed groups: streams that are ALREADY in device memory (still ABI 9: additions only).  A model, a resampler or
+ * a decoder on the same GPU leaves its waveforms in HBM as (batch, channels, frames) tensors -- fp32, fp16 or bf16, ragged,
+ * often a view of a larger buffer.  Such a group names its samples where they lie instead of filling the pinned arena:
+ *     slot = vamd_feed_buffer(f, &pcm)  or  vamd_feed_buffer_on(f, device, &pcm)      (the arena is simply not filled)
+ *     ... [vamd_feed_ogg_serials] [vamd_feed_ogg_comments] [vamd_feed_ogg_flush] ...
+ *     vamd_feed_wrote_device(f, slot, nstreams, frames, &src)                  in place of vamd_feed_wrote_v
+ *     vamd_feed_wrote_live_device(f, slot, nstreams, frames, close, &src)      in place of vamd_feed_wrote_live
+ *     [vamd_feed_source_done(f, slot, consumer, wait_on_host)]                 when the source may be overwritten
+ *     vamd_feed_packets / vamd_feed_ogg / vamd_feed_release                    unchanged
+ * Stream s of the group has frames[s] frames (1 .. max_frames on a whole-stream feed, 0 .. max_frames on a live one; no bound
+ * on their sum: nothing is laid back to back) and its element (channel c, frame k) at base[s] + c * channel_stride +
+ * k * frame_stride, in elements of `dtype`.  base[s] may be NULL where frames[s] == 0.  The samples that reach the stream
+ * buffers are bit for bit what a host-fed VAMD_FEED_F32 / _S16 group of the same values puts there (a 16-bit float is
+ * converted exactly), and everything behind the ingest -- plan, analysis, bitrate manager, packets, Ogg paging -- is the
+ * same code: the packets and files are those of the host-fed group (tests/test_feed_device.py).  A non-finite sample is
+ * treated as a host-fed VAMD_FEED_F32 group treats it.  A feed may alternate host-fed and device-fed groups, and a live
+ * stream may take one piece from the arena and the next from a tensor; the group's dtype is its own, whatever the feed's
+ * format.  Measured: profiles/r16_feed_device.txt.
+ * LIFETIME: base, frames and close are copied before the call returns.  The source memory must stay valid and unwritten
+ * until vamd_feed_source_done, vamd_feed_packets or vamd_feed_ogg has returned for the slot.
+ * ORDERING: the lanes' streams are non-blocking streams, so nothing orders them against the work that produces the source.
+ * The call records an event -- the lane's own, on the lane's device, which the call makes current for the record and then
+ * restores the caller's -- on `producer`, and the lane's stream waits for it before the ingest.  upload_ms of such a group
+ * is 0, device_ms runs from the ingest on, and the device's upload turn is not taken: the link is not used.
+ * VALIDATION, before anything is enqueued (VAMD_EINVAL, the reason in vamd_feed_last_error, the slot still being filled and
+ * the feed usable): dtype known and base non-NULL; every non-NULL base[s] a multiple of the element size and DEVICE memory on
+ * vamd_feed_device(slot) as hipPointerGetAttributes tells (pinned or managed host memory is refused); the whole extent
+ * stream s reads -- the minimum and the maximum of c * channel_stride + k * frame_stride over c < channels, k < frames[s],
+ * plus one element, negative strides counted as such -- inside the allocation hipMemGetAddressRange reports for base[s] (a
+ * pointer whose range cannot be had is refused).  So a bad stride is an error code and never a fault.  The allocation may
+ * be larger than the caller's tensor (a caching allocator's segment): what is guaranteed is that nothing outside it is read.
+ * vamd_feed_wrote_device refuses a live feed and vamd_feed_wrote_live_device a whole-stream one. */
+#define VAMD_SRC_S16  0   /* int16_t,  sample = x / 32768.f              */
+#define VAMD_SRC_F32  1   /* float,    already +-1                       */
+#define VAMD_SRC_F16  2   /* IEEE binary16, converted exactly to float   */
+#define VAMD_SRC_BF16 3   /* bfloat16, converted exactly to float        */
+/* or'ed into vamd_feed_create[_live]'s format: the lanes allocate no pinned input arena -- vamd_feed_buffer[_on] returns the
+ * slot with *pcm = NULL and vamd_feed_wrote / _wrote_v / _wrote_live answer VAMD_EINVAL; device-fed groups only */
+#define VAMD_FEED_NO_ARENA 0x100
+typedef struct vamd_feed_source {
+  const void *const *base;     /* HOST array [nstreams] of DEVICE pointers: stream s, channel 0, frame 0 */
+  int dtype;                   /* VAMD_SRC_* : of this group, whatever the feed's own format is */
+  int64_t channel_stride;      /* in elements; any sign, 0 allowed (one channel shown to all) */
+  int64_t frame_stride;        /* in elements; 1 = planar rows, ch = interleaved, anything else = a view */
+  void *producer;              /* hipStream_t whose work enqueued so far must precede the read; 0 = the device's default stream */
+} vamd_feed_source;
+/* vamd_feed_buffer restricted to the lanes on `device` (a HIP ordinal): waits for one of those; VAMD_EINVAL if the feed has
+ * no lane there.  vamd_feed_buffer's round robin may hand out a lane on any device; a tensor is on one. */
+int vamd_feed_buffer_on(vamd_feed *f, int device, void **pcm);
+int vamd_feed_wrote_device(vamd_feed *f, int slot, long nstreams, const int64_t *frames, const vamd_feed_source *src);
+int vamd_feed_wrote_live_device(vamd_feed *f, int slot, long nstreams, const int64_t *frames, const uint8_t *close, const vamd_feed_source *src);
+/* Of a slot whose group is device-fed (VAMD_EINVAL otherwise): waits until the lane's thread has enqueued the group's ingest;
+ * then, with consumer != NULL, makes that stream wait for the ingest (hipStreamWaitEvent: work enqueued on it afterwards may
+ * overwrite the source, no host wait needed); with wait_on_host != 0 also blocks until the ingest has finished. */
+int vamd_feed_source_done(vamd_feed *f, int slot, void *consumer /* hipStream_t */, int wait_on_host);
+
 /* ---- the Ogg feed: complete Ogg Vorbis I files beside the packets (whole-stream feeds; a live feed's files come in pieces,
  * "the live Ogg feed" below; still ABI 9: additions only).
  *     vamd_feed_ogg_headers(f, id, comment, setup)   once, before the first vamd_feed_buffer: the feed is an Ogg feed

@@ -31,7 +31,8 @@ EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe",
                     "vamd_feed_packets", "vamd_feed_release", "vamd_feed_last_error", "vamd_feed_create_live", "vamd_feed_wrote_live",
                     "vamd_analyze_streams_mixed_managed", "vamd_bitrate_init_states", "vamd_bitrate_walk",
                     "vamd_feed_ogg_headers", "vamd_feed_ogg_serials", "vamd_feed_ogg", "vamd_feed_ogg_headers_live",
-                    "vamd_feed_ogg_comments", "vamd_feed_ogg_flush"]
+                    "vamd_feed_ogg_comments", "vamd_feed_ogg_flush",
+                    "vamd_feed_buffer_on", "vamd_feed_wrote_device", "vamd_feed_wrote_live_device", "vamd_feed_source_done"]
 PACKETBLOBS = 15
 
 _vp = C.c_void_p
@@ -46,6 +47,10 @@ class _FeedResult(C.Structure):  # vamd_feed_result
     _fields_ = [("nstreams", C.c_int64), ("nblocks", C.c_int64), ("stream_start", _vp), ("offset", _vp), ("bits", _vp),
                 ("granulepos", _vp), ("info", _vp), ("bytes", _vp), ("total_bytes", C.c_int64), ("upload_ms", C.c_double),
                 ("device_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class _FeedSource(C.Structure):  # vamd_feed_source
+    _fields_ = [("base", _vp), ("dtype", C.c_int), ("channel_stride", C.c_int64), ("frame_stride", C.c_int64), ("producer", _vp)]
 
 
 class _FeedOggResult(C.Structure):  # vamd_feed_ogg_result
@@ -202,6 +207,10 @@ def load_library():
     L.vamd_feed_ogg_comments.argtypes = [_vp, C.c_int, _vp, _vp, C.c_long]
     L.vamd_feed_ogg_flush.argtypes = [_vp, C.c_int, _vp, C.c_long]
     L.vamd_feed_ogg.argtypes = [_vp, C.c_int, C.POINTER(_FeedOggResult)]
+    L.vamd_feed_buffer_on.argtypes = [_vp, C.c_int, C.POINTER(_vp)]
+    L.vamd_feed_wrote_device.argtypes = [_vp, C.c_int, C.c_long, _vp, C.POINTER(_FeedSource)]
+    L.vamd_feed_wrote_live_device.argtypes = [_vp, C.c_int, C.c_long, _vp, _vp, C.POINTER(_FeedSource)]
+    L.vamd_feed_source_done.argtypes = [_vp, C.c_int, _vp, C.c_int]
     L.vamd_feed_last_error.argtypes = [_vp]
     L.vamd_feed_last_error.restype = C.c_char_p
     L.vamd_analyze_streams_mixed_managed.argtypes = [_vp, C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO), C.POINTER(_Desc),
@@ -985,6 +994,69 @@ class EnvelopeState(C.Structure):
 
 
 FEED_S16, FEED_F32 = 0, 1
+FEED_NO_ARENA = 0x100                       # or'ed into fmt: no pinned input arena, device-fed groups only
+SRC_S16, SRC_F32, SRC_F16, SRC_BF16 = 0, 1, 2, 3   # VAMD_SRC_*: a device-fed group's element type
+
+
+class DeviceSource:
+    """A device-fed group's source spelled out, as vamd_feed_source has it: base = one device pointer per stream (ints; 0
+    where the stream has no frames), dtype = SRC_*, the strides in elements.  keep: whatever owns the memory."""
+
+    def __init__(self, base, dtype, channel_stride, frame_stride, keep=None):
+        self.base, self.dtype, self.channel_stride, self.frame_stride, self.keep = list(base), dtype, channel_stride, frame_stride, keep
+
+
+def _torch_src_dtype(t):
+    import torch
+    table = {torch.int16: SRC_S16, torch.float32: SRC_F32, torch.float16: SRC_F16, torch.bfloat16: SRC_BF16}
+    if t.dtype not in table:
+        raise ValueError("a device-fed group takes int16, float32, float16 or bfloat16 tensors, not %s" % t.dtype)
+    return table[t.dtype]
+
+
+def device_source(source, frames=None, layout="scf"):
+    """-> (DeviceSource, frames [nstreams] int64, device index or None) of what Feed.wrote_device takes: one tensor
+    (streams, channels, frames) -- (streams, frames, channels) with layout="sfc" -- or a list of per-stream tensors (channels,
+    frames_s) -- (frames_s, channels) with "sfc".  The strides are the tensors' own: nothing is made contiguous, nothing copied."""
+    if isinstance(source, DeviceSource):
+        if frames is None:
+            raise ValueError("a DeviceSource needs frames")
+        return source, np.ascontiguousarray(frames, dtype=np.int64).reshape(-1), None
+    if layout not in ("scf", "sfc"):
+        raise ValueError("layout is 'scf' or 'sfc'")
+    ci, fi = (0, 1) if layout == "scf" else (1, 0)
+    if isinstance(source, (list, tuple)):
+        if not source:
+            raise ValueError("no streams")
+        for t in source:
+            if t.dim() != 2:
+                raise ValueError("a list holds one 2-d tensor per stream")
+        # (the stride of an axis of length 1 is never used, and a stream without frames reads nothing: its strides are no one's)
+        sig = lambda t: (t.dtype, t.device, t.shape[ci], t.stride(ci) if t.shape[ci] > 1 and t.shape[fi] else None,
+                         t.stride(fi) if t.shape[fi] > 1 else None)
+        first = next((t for t in source if t.shape[fi] > 1), next((t for t in source if t.shape[fi]), source[0]))
+        for t in source:
+            a, b = sig(t), sig(first)
+            if a[:3] != b[:3] or any(x is not None and y is not None and x != y for x, y in zip(a[3:], b[3:])):
+                raise ValueError("the tensors of a device-fed group must agree in dtype, device, channels and strides")
+        have = np.array([t.shape[fi] for t in source], np.int64)
+        base = [t.data_ptr() if t.shape[fi] else 0 for t in source]
+        t0 = first
+    else:
+        t0 = source
+        if t0.dim() != 3:
+            raise ValueError("a tensor source is (streams, channels, frames), or (streams, frames, channels) with layout='sfc'")
+        ci, fi = ci + 1, fi + 1
+        have = np.full(t0.shape[0], t0.shape[fi], np.int64)
+        base = [t0.data_ptr() + s * t0.stride(0) * t0.element_size() for s in range(t0.shape[0])]
+    if not t0.is_cuda:
+        raise ValueError("a device-fed group reads device memory: the tensors must be on the GPU (a host array goes through buffer() / wrote())")
+    fr = have if frames is None else np.ascontiguousarray(frames, dtype=np.int64).reshape(-1)
+    if fr.shape != have.shape or (fr > have).any() or (fr < 0).any():
+        raise ValueError("frames must hold one length per stream, none longer than its tensor")
+    src = DeviceSource(base, _torch_src_dtype(t0), t0.stride(ci) if t0.shape[ci] > 1 and t0.shape[fi] else 0, t0.stride(fi) if t0.shape[fi] > 1 else 1,
+                       keep=source)
+    return src, fr, t0.device.index
 
 
 class Feed:
@@ -1001,7 +1073,13 @@ class Feed:
     stream, framed on the device: buffer() -> fill -> [ogg_serials()] [ogg_comments()] -> wrote() -> ogg() / packets() ->
     release().  The comment packet given here is the feed's own; ogg_comments() gives a group's streams their own.
     With write_frames: a LIVE OGG feed (vamd_feed_ogg_headers_live) -- ogg() returns per stream the next bytes of its file,
-    the pages it completed in the group; a stream's pieces laid end to end are its file (encode_live_ogg)."""
+    the pages it completed in the group; a stream's pieces laid end to end are its file (encode_live_ogg).
+
+    DEVICE-fed groups (vamd_feed_wrote_device): streams that are already in device memory, as torch tensors of int16 /
+    float32 / float16 / bfloat16 with any strides, read where they lie: buffer() or buffer_on(device) -> wrote_device() /
+    wrote_live_device() in wrote()'s / wrote_live()'s place -> [source_done()] -> packets() / ogg() -> release(); the
+    synchronous helpers are encode_tensors, encode_ogg_tensors, encode_live_tensors and encode_live_ogg_tensors.
+    fmt | FEED_NO_ARENA: a feed for such groups only, without pinned input arenas."""
 
     def __init__(self, setup_blob, devices=None, lanes_per_device=2, max_streams=256, max_frames=131072, fmt=FEED_S16,
                  write_frames=None, ogg_headers=None):
@@ -1021,6 +1099,9 @@ class Feed:
             why = self.L.vamd_feed_last_error(None).decode()
             raise VamdError(r, "vamd_feed_create failed: " + (why or "setup without GPU-assembled packets, bad arguments, or a HIP failure"))
         self.h = h
+        self.no_arena = bool(fmt & FEED_NO_ARENA)
+        fmt &= ~FEED_NO_ARENA
+        self._held = {}   # slot -> the tensors of its device-fed group, kept alive until the group has read them
         self.max_streams, self.max_frames, self.fmt = max_streams, max_frames, fmt
         self.dtype = np.int16 if fmt == FEED_S16 else np.float32
         self.lanes = self.L.vamd_feed_lanes(self.h)
@@ -1072,7 +1153,10 @@ class Feed:
         over the lane's pinned file arena, or a copy), total_bytes: stream s's file is bytes[stream_offset[s]:stream_offset[s + 1]]
         (empty, with status[s] = the VAMD_STATUS_* bits, where a block of the stream has no packet)."""
         r = _FeedOggResult()
-        self._check(self.L.vamd_feed_ogg(self.h, slot, C.byref(r)))
+        try:
+            self._check(self.L.vamd_feed_ogg(self.h, slot, C.byref(r)))
+        finally:
+            self._held.pop(slot, None)
         ns = int(r.nstreams)
 
         def view(p, ct, n):
@@ -1133,10 +1217,20 @@ class Feed:
     def device(self, slot):
         return self._check(self.L.vamd_feed_device(self.h, slot))
 
-    def buffer(self, channels):
-        """-> (slot, array [max_streams * max_frames * channels] of the feed's sample type over the lane's pinned input arena)"""
+    def buffer(self, channels=None):
+        """-> (slot, array [max_streams * max_frames * channels] of the feed's sample type over the lane's pinned input arena;
+        None on a FEED_NO_ARENA feed, and where channels is None: a slot for a device-fed group)"""
         p = _vp()
-        slot = self._check(self.L.vamd_feed_buffer(self.h, C.byref(p)))
+        return self._arena(self._check(self.L.vamd_feed_buffer(self.h, C.byref(p))), p, channels)
+
+    def buffer_on(self, device, channels=None):
+        """buffer() restricted to the lanes on `device` (an ordinal): waits for one of those."""
+        p = _vp()
+        return self._arena(self._check(self.L.vamd_feed_buffer_on(self.h, int(device), C.byref(p))), p, channels)
+
+    def _arena(self, slot, p, channels):
+        if not p.value or channels is None:
+            return slot, None
         n = self.max_streams * self.max_frames * channels
         ct = C.c_int16 if self.fmt == FEED_S16 else C.c_float
         arr = np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape=(n,))
@@ -1163,12 +1257,58 @@ class Feed:
                 raise ValueError("close must hold one flag per stream")
         self._check(self.L.vamd_feed_wrote_live(self.h, slot, fr.size, _vp(fr.ctypes.data), _vp(cl.ctypes.data) if cl is not None else None))
 
+    def _source(self, source, frames, layout, stream, slot):
+        src, fr, dev = device_source(source, frames, layout)
+        lane_dev = self.device(slot)
+        if dev is not None and dev != lane_dev:
+            raise ValueError("the tensors are on device %d, the slot's lane on device %d (buffer_on)" % (dev, lane_dev))
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(lane_dev).cuda_stream
+        ptrs = (_vp * max(1, len(src.base)))(*[_vp(int(b) or None) for b in src.base])
+        cs = _FeedSource(C.cast(ptrs, _vp), int(src.dtype), int(src.channel_stride), int(src.frame_stride), _vp(int(stream) or None))
+        if fr.size != len(src.base):
+            raise ValueError("frames must hold one length per stream")
+        return src, fr, cs, ptrs
+
+    def wrote_device(self, slot, source, frames=None, stream=None, layout="scf"):
+        """A group from DEVICE memory (vamd_feed_wrote_device) in wrote()'s place: source as device_source() takes it -- one
+        tensor, a list of per-stream tensors, or a DeviceSource -- read where it lies with its own strides; frames: one length
+        per stream (default: the tensors').  stream: the HIP stream (a handle, an int) whose work so far produces the samples;
+        default torch's current stream on the lane's device.  The tensors stay referenced until packets() / ogg() /
+        source_done(wait=True) has returned for the slot."""
+        src, fr, cs, ptrs = self._source(source, frames, layout, stream, slot)
+        self._check(self.L.vamd_feed_wrote_device(self.h, slot, fr.size, _vp(fr.ctypes.data), C.byref(cs)))
+        self._held[slot] = src
+
+    def wrote_live_device(self, slot, source, frames=None, close=None, stream=None, layout="scf"):
+        """A live feed's pieces from DEVICE memory (vamd_feed_wrote_live_device) in wrote_live()'s place."""
+        src, fr, cs, ptrs = self._source(source, frames, layout, stream, slot)
+        cl = None
+        if close is not None:
+            cl = np.ascontiguousarray(close, dtype=np.uint8).reshape(-1)
+            if cl.shape != fr.shape:
+                raise ValueError("close must hold one flag per stream")
+        self._check(self.L.vamd_feed_wrote_live_device(self.h, slot, fr.size, _vp(fr.ctypes.data), _vp(cl.ctypes.data) if cl is not None else None,
+                                                       C.byref(cs)))
+        self._held[slot] = src
+
+    def source_done(self, slot, stream=None, wait=False):
+        """Of a device-fed group: returns once its ingest is enqueued; stream (a HIP stream handle): work enqueued on it from
+        now on runs behind the ingest and may overwrite the source; wait: blocks until the ingest has finished."""
+        self._check(self.L.vamd_feed_source_done(self.h, slot, _vp(int(stream)) if stream else None, 1 if wait else 0))
+        if wait:
+            self._held.pop(slot, None)
+
     def packets(self, slot, copy=True):
         """Waits for the group.  -> dict: nstreams, nblocks, stream_start, offset, bits, granulepos, info (numpy views over
         the lane's pinned output arena, or copies), choice (info >> 4: the bitrate manager's candidate, 0 on a VBR setup),
         bytes, total_bytes, upload_ms, device_ms, total_ms."""
         r = _FeedResult()
-        self._check(self.L.vamd_feed_packets(self.h, slot, C.byref(r)))
+        try:
+            self._check(self.L.vamd_feed_packets(self.h, slot, C.byref(r)))
+        finally:
+            self._held.pop(slot, None)
         nb, ns = int(r.nblocks), int(r.nstreams)
 
         def view(p, ct, n):
@@ -1185,6 +1325,80 @@ class Feed:
 
     def release(self, slot):
         self._check(self.L.vamd_feed_release(self.h, slot))
+        self._held.pop(slot, None)
+
+    def _slot_for(self, source, layout):
+        src, _, dev = device_source(source, [0] * len(source.base) if isinstance(source, DeviceSource) else None, layout)
+        return self.buffer()[0] if dev is None else self.buffer_on(dev)[0]
+
+    def _release_quietly(self, slot):
+        try:
+            self.release(slot)
+        except VamdError:
+            pass
+
+    def encode_tensors(self, source, frames=None, stream=None, layout="scf"):
+        """encode() of streams that are in DEVICE memory: source, frames, stream and layout as wrote_device takes them.
+        -> per stream a list of (packet bytes, granulepos, W, e_o_s)."""
+        slot = self._slot_for(source, layout)
+        try:
+            self.wrote_device(slot, source, frames, stream, layout)
+            r = self.packets(slot)
+        finally:
+            self._release_quietly(slot)
+        return self._rows(r, r["nstreams"])
+
+    def encode_ogg_tensors(self, source, frames=None, serials=None, comments=None, stream=None, layout="scf"):
+        """encode_ogg() of streams that are in DEVICE memory.  -> list[bytes], one Ogg Vorbis file per stream."""
+        slot = self._slot_for(source, layout)
+        try:
+            if serials is not None:
+                self.ogg_serials(slot, serials)
+            if comments is not None:
+                self.ogg_comments(slot, comments)
+            self.wrote_device(slot, source, frames, stream, layout)
+            r = self.ogg(slot, copy=False)
+            off = r["stream_offset"]
+            return [bytes(r["bytes"][int(off[s]):int(off[s + 1])]) for s in range(r["nstreams"])]
+        finally:
+            self._release_quietly(slot)
+
+    def encode_live_tensors(self, source, frames=None, close=None, stream=None, layout="scf"):
+        """encode_live() of pieces that are in DEVICE memory (a live feed with ONE lane): stream s of the lane gets frames[s]
+        frames (default: the tensors') from source; close[s] true ends it after its piece."""
+        if self.write_frames is None:
+            raise ValueError("encode_live_tensors needs a live feed (Feed(..., write_frames=...))")
+        if self.lanes != 1:
+            raise ValueError("encode_live_tensors drives a feed with one lane; with more, use buffer_on / wrote_live_device / packets / release")
+        slot = self._slot_for(source, layout)
+        try:
+            self.wrote_live_device(slot, source, frames, close, stream, layout)
+            r = self.packets(slot)
+        finally:
+            self._release_quietly(slot)
+        return self._rows(r, r["nstreams"])
+
+    def encode_live_ogg_tensors(self, source, frames=None, close=None, serials=None, comments=None, flush=None, stream=None, layout="scf"):
+        """encode_live_ogg() of pieces that are in DEVICE memory (a live Ogg feed with ONE lane).  -> per stream the next
+        bytes of its Ogg file."""
+        if self.write_frames is None:
+            raise ValueError("encode_live_ogg_tensors needs a live feed (Feed(..., write_frames=..., ogg_headers=...))")
+        if self.lanes != 1:
+            raise ValueError("encode_live_ogg_tensors drives a feed with one lane; with more, use buffer_on / wrote_live_device / ogg / release")
+        slot = self._slot_for(source, layout)
+        try:
+            if serials is not None:
+                self.ogg_serials(slot, serials)
+            if comments is not None:
+                self.ogg_comments(slot, comments)
+            if flush is not None:
+                self.ogg_flush(slot, flush)
+            self.wrote_live_device(slot, source, frames, close, stream, layout)
+            r = self.ogg(slot, copy=False)
+            off = r["stream_offset"]
+            return [bytes(r["bytes"][int(off[s]):int(off[s + 1])]) for s in range(r["nstreams"])]
+        finally:
+            self._release_quietly(slot)
 
     @staticmethod
     def _rows(r, ns):

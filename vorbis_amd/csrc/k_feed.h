@@ -1,5 +1,6 @@
 // k_feed.h -- the kernels of the host-fed farm (vamd_feed.hip is their host side): the ingest of a group's samples (whole
-// streams: k_feed_ingest; a live lane's continuing streams: k_live_begin, k_live_ingest) and the packet hand-over -- the
+// streams: k_feed_ingest; a live lane's continuing streams: k_live_begin, k_live_ingest; either from tensors that already lie
+// in HBM: k_feed_ingest_dev, k_live_ingest_dev over k_feed_src.h) and the packet hand-over -- the
 // analysis' packets laid end to end into the pinned output arena, their records beside them: per-stream sizes (a wave per
 // stream), a scan over the streams, and a wave per packet that copies its words across the link.  The hand-over takes a run
 // of packets in stream order (FeedSlice): a whole VBR group, or one slice of a bitrate-managed group.
@@ -7,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "vorbis_amd.h"
+#include "k_feed_src.h"
 
 namespace vamd {
 
@@ -127,6 +129,71 @@ __global__ void k_live_ingest(const T *__restrict__ in, int ch, long nstreams, l
       }
       ((float4 *)(pcm + s * ss + (long)c * cs))[p0 >> 2] = make_float4(v[0], v[1], v[2], v[3]);
       if (bad) atomicMin(nan + s, (unsigned long long)(L.origin + badp));
+    }
+  }
+}
+
+// ---- a DEVICE-fed group (vamd_feed_wrote_device / _wrote_live_device): the same buffers from a caller's tensors ----
+// T: int16_t, float, src_f16 or src_bf16 (k_feed_src.h); stream s reads element (c, k) at base + c * cstride + k * fstride.
+// k_feed_ingest's layout and work split: a thread owns four frames of every channel and stores 16 bytes per channel;
+// consecutive threads own consecutive quads, so with fstride == 1 a wave reads 64 quads of one channel row back to back
+// (1 KB of floats, 512 B of a 16-bit type), each quad in one load where its address is aligned to it (src_quad).  The
+// streams' lengths and base pointers come in one list, [frames_of (nstreams) | base_of (nstreams)] (the lane's d_len).
+template <typename T>
+__global__ void k_feed_ingest_dev(int ch, long nstreams, long frames, int head, int pad, float *__restrict__ pcm, long ss, long cs,
+                                  float *__restrict__ amp, vamd_envelope_state *__restrict__ states, const long long *__restrict__ frames_of,
+                                  const long long *__restrict__ base_of, int64_t cstride, int64_t fstride) {
+  const long per = (head >> 2) + ((frames + 3) >> 2) + (pad >> 2), total = nstreams * per;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x)
+    feed_ingest_dev_item<T>(t, ch, frames, head, pad, pcm, ss, cs, amp, VAMD_AMPMAX_FLOOR, frames_of, base_of, cstride, fstride, true);
+  // a fresh detector state per stream (all-zero == a stream's start, include/vorbis_amd.h)
+  const long words = nstreams * (long)(sizeof(vamd_envelope_state) / 4);
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < words; t += (long)gridDim.x * blockDim.x) ((uint32_t *)states)[t] = 0u;
+}
+
+// k_live_ingest with the piece of stream s at the base pointer that LiveIn::first carries (frame 0 of the piece, channel 0).
+// The float types: the first non-finite sample of each stream is recorded, as for VAMD_FEED_F32.  A quad that lies whole in
+// the piece goes through src_quad (one load where consecutive and aligned); a quad across an edge is put together by element.
+template <typename T>
+__global__ void k_live_ingest_dev(int ch, long nstreams, long quads, int room, const LiveIn *__restrict__ li, const float *__restrict__ old,
+                                  float *__restrict__ pcm, long ss, long cs, unsigned long long *__restrict__ nan, int *__restrict__ status,
+                                  int64_t cstride, int64_t fstride) {
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < nstreams * quads; t += (long)gridDim.x * blockDim.x) {
+    const long s = t / quads, p0 = (t - s * quads) << 2;
+    const LiveIn L = li[s];
+    const long data = L.keep + L.frames, end = data + room < cs ? data + room : cs;
+    if (data + room > cs || L.keep < 0 || L.shift < 0 || L.shift + L.keep > cs) {
+      if (p0 == 0) *(volatile int *)status = 1;  // (host memory, mapped: a plain store)
+      continue;
+    }
+    if (p0 >= end) continue;
+    const T *base = (const T *)(uintptr_t)L.first;
+    for (int c = 0; c < ch; c++) {
+      float v[4];
+      const T *row = base + (int64_t)c * cstride;
+      if (p0 >= L.keep && p0 + 4 <= data) src_quad(row, (int64_t)(p0 - L.keep), fstride, 4, true, v);
+      else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const long p = p0 + k;
+          float x = 0.f;
+          if (p < L.keep) {
+            if (!L.fresh) x = old[s * ss + (long)c * cs + L.shift + p];
+          } else if (p < data) x = src_float(row[(int64_t)(p - L.keep) * fstride]);
+          v[k] = x;
+        }
+      }
+      src_store4(pcm + s * ss + (long)c * cs + p0, v[0], v[1], v[2], v[3]);
+      if (src_has_non_finite<T>()) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const long p = p0 + k;
+          if (p >= L.keep && p < data && src_non_finite(v[k])) {
+            atomicMin(nan + s, (unsigned long long)(L.origin + p));
+            break;
+          }
+        }
+      }
     }
   }
 }

@@ -16,6 +16,10 @@
 //     pinned output arena (mapped into the device's address space: the packets cross the link inside that kernel, no
 //     copy command, no second wait).  Lanes are independent: while one computes, another's upload is on the wire.
 //   * the call sequence is libvorbis' own, for a group: vamd_feed_buffer / _wrote / _packets / _release.
+//   * DEVICE-FED GROUPS (vamd_feed_wrote_device / _wrote_live_device): the samples already lie in HBM as a caller's tensors.
+//     Such a group skips the arena, d_in and the upload turn: the call checks every base pointer and extent on the caller's
+//     thread (source_check: an error code, never a fault), records an event on the producer's stream, and the lane's stream
+//     waits for it in front of k_feed_ingest_dev / k_live_ingest_dev (k_feed_src.h); from the plan on it is any group.
 // Built on the public C ABI only (a context is used by one thread: its lane's), like vamd_batcher.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -138,6 +142,15 @@ struct FeedLane {
   std::vector<uint8_t> flush, user_flush;
   vamd_feed_ogg_result ogg_result;
   std::vector<uint8_t> close_of;  // the job's closes (live)
+  // a device-fed job (vamd_feed_wrote_device / _wrote_live_device): the streams' base pointers and what else the call named;
+  // ev_src: recorded on the producer's stream by the call, waited for by the lane's stream before the ingest; ev_ingest:
+  // recorded behind the ingest, what vamd_feed_source_done hands out.  ingest_queued / ingest_recorded (guarded by
+  // vamd_feed::m): the lane's thread is past the ingest's launch; ev_ingest stands for this group's ingest.
+  bool src_dev = false, ingest_queued = false, ingest_recorded = false;
+  std::vector<const void *> src_base;
+  int src_dtype = 0;
+  int64_t src_cstride = 0, src_fstride = 0;
+  hipEvent_t ev_src = nullptr, ev_ingest = nullptr;
   std::thread worker;
   std::mutex *upload_turn = nullptr;  // its device's (vamd_feed::upload_turns)
   // the job (guarded by vamd_feed::m)
@@ -159,6 +172,8 @@ struct FeedLane {
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev_up) (void)hipEventDestroy(ev_up);
     if (ev_end) (void)hipEventDestroy(ev_end);
+    if (ev_src) (void)hipEventDestroy(ev_src);
+    if (ev_ingest) (void)hipEventDestroy(ev_ingest);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -172,6 +187,7 @@ struct vamd_feed {
   long pkcap[2] = {0, 0};
   long max_streams = 0, max_frames = 0;
   int format = VAMD_FEED_S16;
+  bool no_arena = false;            // VAMD_FEED_NO_ARENA: the lanes have no pinned input arena (device-fed groups only)
   int write_frames = 0;             // > 0: a live feed (vamd_feed_create_live), the reference's frames per write
   long live_cs = 0, row_stride = 0, retain = 0;  // its buffers' samples per channel, flag rows, the retention bound
   bool ogg = false;                 // an Ogg feed (vamd_feed_ogg_headers): files beside the packets
@@ -431,7 +447,7 @@ static void feed_result(FeedLane &L, const RecLayout &R, long ns_out, long nb, i
   float up = 0.f, dev = 0.f;
   (void)hipEventElapsedTime(&up, L.ev0, L.ev_up);
   (void)hipEventElapsedTime(&dev, L.ev0, L.ev_end);
-  out.upload_ms = up, out.device_ms = dev;
+  out.upload_ms = L.src_dev ? 0. : up, out.device_ms = dev;  // (a device-fed group: nothing went up, ev0 stands before the ingest)
 }
 
 // the analysis' batch of size class W: blocks [i0, i0 + n) of the plan's, read where they lie in pcm
@@ -717,8 +733,74 @@ static void launch_ingest(const FeedLane &L, K16 *k16, K32 *k32, long items, A..
   else hipLaunchKernelGGL(k32, dim3((unsigned)blocks), dim3(256), 0, L.stream, (const float *)L.d_in.p, args...);
 }
 
+// A device-fed group's start, in upload()'s place: the lane's stream waits for the producer's event (recorded by
+// vamd_feed_wrote_device on the caller's thread), the side list goes up, and the timing events stand where the ingest begins.
+// No upload turn: the link carries a few bytes per stream.
+static int source_begin(FeedLane &L, void *side_dst = nullptr, const void *side_src = nullptr, size_t side_bytes = 0) {
+  FEED_TRY(hipStreamWaitEvent(L.stream, L.ev_src, 0));
+  if (side_bytes) FEED_TRY(hipMemcpyAsync(side_dst, side_src, side_bytes, hipMemcpyHostToDevice, L.stream));
+  FEED_TRY(hipEventRecord(L.ev0, L.stream));
+  FEED_TRY(hipEventRecord(L.ev_up, L.stream));
+  return VAMD_OK;
+}
+
+// ... and behind its ingest's launch: the event vamd_feed_source_done hands out, and the word that it stands
+static int source_ingested(vamd_feed *f, FeedLane &L) {
+  const hipError_t e = hipEventRecord(L.ev_ingest, L.stream);
+  {
+    std::lock_guard<std::mutex> g(f->m);
+    L.ingest_queued = true, L.ingest_recorded = e == hipSuccess;
+  }
+  f->cv_done.notify_all();
+  FEED_TRY(e);
+  return VAMD_OK;
+}
+
+// a device-fed group's ingest kernel by the group's element type (args: the kernel's)
+#define FEED_LAUNCH_DEV(kernel, L, items, ...)                                                                                      \
+  do {                                                                                                                              \
+    long blocks__ = ((items) + 255) / 256;                                                                                          \
+    if (blocks__ > 256L * 32) blocks__ = 256L * 32;                                                                                 \
+    if (blocks__ < 1) blocks__ = 1;                                                                                                 \
+    const dim3 g__((unsigned)blocks__), b__(256);                                                                                   \
+    switch ((L).src_dtype) {                                                                                                        \
+      case VAMD_SRC_S16: hipLaunchKernelGGL(kernel<int16_t>, g__, b__, 0, (L).stream, __VA_ARGS__); break;                          \
+      case VAMD_SRC_F32: hipLaunchKernelGGL(kernel<float>, g__, b__, 0, (L).stream, __VA_ARGS__); break;                            \
+      case VAMD_SRC_F16: hipLaunchKernelGGL(kernel<vamd::src_f16>, g__, b__, 0, (L).stream, __VA_ARGS__); break;                    \
+      default: hipLaunchKernelGGL(kernel<vamd::src_bf16>, g__, b__, 0, (L).stream, __VA_ARGS__); break;                             \
+    }                                                                                                                               \
+  } while (0)
+
+// a whole-stream group from device memory: run_group with the streams' base pointers in first_of's place ([frames_of |
+// base_of], one copy), no d_in and no upload; the plan is always the one of streams of unequal length
+static int run_group_device(vamd_feed *f, FeedLane &L) {
+  const long ns = L.nstreams, frames = L.frames;
+  const int ch = f->ch, head = f->bs[1] / 2, pad = 3 * f->bs[1];
+  const long cs = (long)al((size_t)head + ((frames + 3) & ~3L) + pad, 64), ss = cs * ch;
+  FEED_TRY(L.d_pcm.need((size_t)ns * ss * 4));
+  FEED_TRY(L.d_states.need((size_t)ns * sizeof(vamd_envelope_state)));
+  FEED_TRY(L.d_amp.need((size_t)ns * 4));
+  FEED_TRY(L.h_len.need((size_t)ns * 16));
+  FEED_TRY(L.d_len.need((size_t)ns * 16));
+  long long *h = (long long *)L.h_len.p;
+  for (long i = 0; i < ns; i++) h[i] = L.frames_of[(size_t)i], h[ns + i] = (long long)(uintptr_t)L.src_base[(size_t)i];
+  const long long *d_frames_of = (const long long *)L.d_len.p, *d_base_of = d_frames_of + ns;
+  FEED_OWN(source_begin(L, L.d_len.p, h, (size_t)ns * 16));
+  FEED_LAUNCH_DEV(k_feed_ingest_dev, L, ns * ((long)(head >> 2) + ((frames + 3) >> 2) + (pad >> 2)), ch, ns, frames, head, pad, (float *)L.d_pcm.p,
+                  ss, cs, (float *)L.d_amp.p, (vamd_envelope_state *)L.d_states.p, d_frames_of, d_base_of, L.src_cstride, L.src_fstride);
+  const hipError_t launched = hipGetLastError();
+  FEED_OWN(source_ingested(f, L));
+  FEED_TRY(launched);
+  vamd_stream_plan plan;
+  FEED_CALL(vamd_plan_streams_whole_v(L.ctx, (float *)L.d_pcm.p, ss, cs, ns, frames, L.frames_of.data(), (vamd_envelope_state *)L.d_states.p, &plan));
+  FeedLive none;
+  none.in = nullptr, none.nan = nullptr;
+  return finish_group(f, L, plan, (const float *)L.d_pcm.p, ns, ss, cs, d_frames_of, none, ns);
+}
+
 // one group through its lane (the lane's own thread; its device is current)
 static int run_group(vamd_feed *f, FeedLane &L) {
+  if (L.src_dev) return run_group_device(f, L);
   const long ns = L.nstreams, frames = L.frames;
   const int ch = f->ch, head = f->bs[1] / 2, pad = 3 * f->bs[1];
   const size_t sample = L.format == VAMD_FEED_S16 ? 2 : 4;
@@ -793,6 +875,7 @@ static int run_group_live(vamd_feed *f, FeedLane &L) {
     memset(&in, 0, sizeof(in));
     memset(&g, 0, sizeof(g));
     in.first = first, in.frames = n;
+    if (L.src_dev) in.first = i < nsc ? (int64_t)(uintptr_t)L.src_base[(size_t)i] : 0;  // (a device-fed piece: where it lies)
     first += n;
     in.fresh = !m.open;
     if (!m.open && !n) {  // (a stream starts with its first frame: until then it is not there, and nothing of it is planned)
@@ -834,8 +917,11 @@ static int run_group_live(vamd_feed *f, FeedLane &L) {
     if (q > quads) quads = q;
   }
   const size_t in_bytes = (size_t)first * ch * sample;
-  FEED_TRY(L.d_in.need(in_bytes ? in_bytes : 16));
-  FEED_OWN(upload(L, in_bytes, L.d_live.p, hin, (size_t)ns * sizeof(LiveIn)));
+  if (L.src_dev) FEED_OWN(source_begin(L, L.d_live.p, hin, (size_t)ns * sizeof(LiveIn)));
+  else {
+    FEED_TRY(L.d_in.need(in_bytes ? in_bytes : 16));
+    FEED_OWN(upload(L, in_bytes, L.d_live.p, hin, (size_t)ns * sizeof(LiveIn)));
+  }
   const LiveIn *d_live = (const LiveIn *)L.d_live.p;
   vamd_bitrate_state *bst = f->managed ? (vamd_bitrate_state *)L.d_bstate.p : nullptr;
   if (f->managed && !L.btmpl_ready) {
@@ -849,9 +935,17 @@ static int run_group_live(vamd_feed *f, FeedLane &L) {
     *(volatile int *)L.h_lstatus.p = 0;
     void *d_lstatus = nullptr;
     FEED_TRY(hipHostGetDevicePointer(&d_lstatus, L.h_lstatus.p, 0));
-    launch_ingest(L, k_live_ingest<int16_t>, k_live_ingest<float>, ns * (long)quads, ch, ns, (long)quads, pad + 256, d_live,
-                  (const float *)L.d_buf[L.cur].p, (float *)L.d_buf[1 - L.cur].p, ss, cs, (unsigned long long *)L.d_nan.p, (int *)d_lstatus);
-    FEED_TRY(hipGetLastError());
+    if (L.src_dev) {
+      FEED_LAUNCH_DEV(k_live_ingest_dev, L, ns * (long)quads, ch, ns, (long)quads, pad + 256, d_live, (const float *)L.d_buf[L.cur].p,
+                      (float *)L.d_buf[1 - L.cur].p, ss, cs, (unsigned long long *)L.d_nan.p, (int *)d_lstatus, L.src_cstride, L.src_fstride);
+      const hipError_t launched = hipGetLastError();
+      FEED_OWN(source_ingested(f, L));
+      FEED_TRY(launched);
+    } else {
+      launch_ingest(L, k_live_ingest<int16_t>, k_live_ingest<float>, ns * (long)quads, ch, ns, (long)quads, pad + 256, d_live,
+                    (const float *)L.d_buf[L.cur].p, (float *)L.d_buf[1 - L.cur].p, ss, cs, (unsigned long long *)L.d_nan.p, (int *)d_lstatus);
+      FEED_TRY(hipGetLastError());
+    }
   }
   L.cur = 1 - L.cur;
   float *pcm = (float *)L.d_buf[L.cur].p;
@@ -935,6 +1029,8 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
                        int lanes_per_device, long max_streams, long max_frames, int format, int write_frames) {
   if (!out) return VAMD_EINVAL;
   *out = nullptr;
+  const bool no_arena = (format & VAMD_FEED_NO_ARENA) != 0;
+  format &= ~VAMD_FEED_NO_ARENA;
   if (!setup_blob || lanes_per_device < 1 || lanes_per_device > 8 || max_streams < 1 || max_frames < 1 || ndevices < 0 ||
       ndevices > 64 || (ndevices > 0 && !devices) || (format != VAMD_FEED_S16 && format != VAMD_FEED_F32) || write_frames < 0)
     return VAMD_EINVAL;
@@ -955,6 +1051,7 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
   for (int i = 0; i < ndevices; i++) devs.push_back(devices[i] >= 0 ? devices[i] : cur);
   vamd_feed *f = new vamd_feed;
   f->max_streams = max_streams, f->max_frames = max_frames, f->format = format, f->write_frames = write_frames;
+  f->no_arena = no_arena;
   f->managed = h.managed && h.off_bitrate;
   f->rate = h.rate;
   {
@@ -977,6 +1074,8 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
     if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev0, hipEventDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev_up, hipEventBlockingSync);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev_end, hipEventBlockingSync);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev_src, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev_ingest, hipEventDisableTiming | hipEventBlockingSync);
     if (e == hipSuccess && vamd_set_stream(L.ctx, L.stream) != VAMD_OK) e = hipErrorUnknown;
     if (e == hipSuccess && l == 0) {
       f->ch = vamd_channels(L.ctx);
@@ -1009,7 +1108,7 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
     // the arenas: the group's samples; packets: half the samples' size AS 16-BIT to start with (a q 0.4 stream is a
     // tenth of that, q 1.0 on noise a third; run_group grows the arena when a group needs more)
     const size_t in_cap = (size_t)max_streams * max_frames * f->ch * (format == VAMD_FEED_S16 ? 2 : 4);
-    if (e == hipSuccess && !r) e = L.h_in.need(in_cap);
+    if (e == hipSuccess && !r && !no_arena) e = L.h_in.need(in_cap);
     const size_t out_cap = f->out_bytes ? (size_t)f->out_bytes : (size_t)max_streams * max_frames * f->ch + (size_t)max_streams * 65536;
     if (e == hipSuccess && !r) e = L.h_out.need(al(out_cap, 4096));
     if (e != hipSuccess) r = VAMD_EFAULT;
@@ -1068,8 +1167,9 @@ static void ogg_job(vamd_feed *f, FeedLane &L, long nstreams) {
 
 // the tail of vamd_feed_wrote / _wrote_v / _wrote_live (f->m held; the lane's frames_of / close_of are set): the group
 // goes to its lane's thread
-static int queue_group(vamd_feed *f, FeedLane &L, long nstreams, long frames) {
+static int queue_group(vamd_feed *f, FeedLane &L, long nstreams, long frames, bool src_dev = false) {
   L.nstreams = nstreams, L.frames = frames, L.format = f->format;
+  L.src_dev = src_dev, L.ingest_queued = L.ingest_recorded = false;
   L.status = 0;
   memset(&L.result, 0, sizeof(L.result));
   ogg_job(f, L, nstreams);
@@ -1239,14 +1339,24 @@ int vamd_feed_device(const vamd_feed *f, int slot) {
   return (f && slot >= 0 && slot < (int)f->lanes.size()) ? f->lanes[(size_t)slot].device : VAMD_EINVAL;
 }
 
-int vamd_feed_buffer(vamd_feed *f, void **pcm) {
+// vamd_feed_buffer (device < 0: a lane anywhere) and vamd_feed_buffer_on (a lane on `device`)
+static int feed_buffer(vamd_feed *f, int device, void **pcm) {
   if (!f || !pcm) return VAMD_EINVAL;
   std::unique_lock<std::mutex> g(f->m);
+  auto mine = [&](const FeedLane &L) { return device < 0 || L.device == device; };
+  if (device >= 0) {
+    bool any = false;
+    for (const FeedLane &L : f->lanes) any |= mine(L);
+    if (!any) {
+      f->err = "vamd_feed_buffer_on: the feed has no lane on device " + std::to_string(device);
+      return VAMD_EINVAL;
+    }
+  }
   for (;;) {
     if (f->stop) return VAMD_EFAULT;
     int best = -1;
     for (size_t l = 0; l < f->lanes.size(); l++)
-      if (f->lanes[l].state == LANE_FREE && (best < 0 || f->lanes[l].served < f->lanes[(size_t)best].served)) best = (int)l;
+      if (mine(f->lanes[l]) && f->lanes[l].state == LANE_FREE && (best < 0 || f->lanes[l].served < f->lanes[(size_t)best].served)) best = (int)l;
     if (best >= 0) {
       FeedLane &L = f->lanes[(size_t)best];
       L.state = LANE_FILLING;
@@ -1257,14 +1367,182 @@ int vamd_feed_buffer(vamd_feed *f, void **pcm) {
     // every lane is out: wait for a release -- unless nothing can release one (all handed out and none queued or done
     // would be the caller waiting for itself)
     bool hope = false;
-    for (const FeedLane &L : f->lanes) hope |= L.state == LANE_QUEUED || L.state == LANE_DONE;
+    for (const FeedLane &L : f->lanes) hope |= mine(L) && (L.state == LANE_QUEUED || L.state == LANE_DONE);
     if (!hope) return VAMD_EINVAL;
     f->cv_done.wait(g);
   }
 }
 
+// what vamd_feed_wrote_device / _wrote_live_device check of their source before anything is enqueued (f->m held; the lane's
+// device current): the reason in f->err
+static int source_check(vamd_feed *f, const FeedLane &L, long nstreams, const int64_t *frames, const vamd_feed_source *src) {
+  if (!src || !src->base) {
+    f->err = "device-fed group: no source, or no base pointers";
+    return VAMD_EINVAL;
+  }
+  if (src->dtype < 0 || src->dtype >= vamd::SRC_TYPES) {
+    f->err = "device-fed group: unknown dtype " + std::to_string(src->dtype) + " (VAMD_SRC_S16 / _F32 / _F16 / _BF16)";
+    return VAMD_EINVAL;
+  }
+  const int eb = vamd::src_elem_bytes(src->dtype);
+  for (long s = 0; s < nstreams; s++) {
+    const void *p = src->base[s];
+    const std::string who = "device-fed group: stream " + std::to_string(s);
+    if (!p) {
+      if (frames[s]) {
+        f->err = who + " has frames and no base pointer";
+        return VAMD_EINVAL;
+      }
+      continue;
+    }
+    if ((uintptr_t)p % (uintptr_t)eb) {
+      f->err = who + ": the base pointer is not a multiple of the element size";
+      return VAMD_EINVAL;
+    }
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+      (void)hipGetLastError();
+      f->err = who + ": the base pointer is not memory the HIP runtime knows (host memory?)";
+      return VAMD_EINVAL;
+    }
+    if (at.type != hipMemoryTypeDevice || at.isManaged) {
+      f->err = who + ": the base pointer is " + (at.isManaged || at.type == hipMemoryTypeManaged ? "managed" : at.type == hipMemoryTypeHost ? "pinned host" : "not device") +
+               " memory; a device-fed group reads device memory";
+      return VAMD_EINVAL;
+    }
+    if (at.device != L.device) {
+      f->err = who + ": the base pointer is on device " + std::to_string(at.device) + ", the slot's lane on device " + std::to_string(L.device) +
+               " (vamd_feed_buffer_on)";
+      return VAMD_EINVAL;
+    }
+    hipDeviceptr_t abase = nullptr;
+    size_t abytes = 0;
+    if (hipMemGetAddressRange(&abase, &abytes, (hipDeviceptr_t)p) != hipSuccess || !abase || (uintptr_t)p < (uintptr_t)abase) {
+      (void)hipGetLastError();
+      f->err = who + ": the allocation of the base pointer cannot be had (hipMemGetAddressRange)";
+      return VAMD_EINVAL;
+    }
+    int64_t lo = 0, hi = 0;
+    const int64_t off = (int64_t)((uintptr_t)p - (uintptr_t)abase);
+    const int why = vamd::source_extent(f->ch, frames[s], src->channel_stride, src->frame_stride, eb, off, (int64_t)abytes, &lo, &hi);
+    if (why) {
+      f->err = who + (why == 1 ? ": the extent of its strides does not fit 64-bit arithmetic"
+                               : ": it reads elements [" + std::to_string(lo) + ", " + std::to_string(hi) + ") of " + std::to_string(eb) +
+                                     " bytes from its base pointer, which lies " + std::to_string(off) + " bytes into an allocation of " +
+                                     std::to_string(abytes) + " bytes: out of range");
+      return VAMD_EINVAL;
+    }
+  }
+  return VAMD_OK;
+}
+
+// the tail of the two: the source is the lane's, the producer's event recorded (the lane's device current), the group queued
+static int queue_group_device(vamd_feed *f, FeedLane &L, long nstreams, long frames, const vamd_feed_source *src) {
+  const hipError_t e = hipEventRecord(L.ev_src, (hipStream_t)src->producer);
+  if (e != hipSuccess) {
+    f->err = std::string("device-fed group: hipEventRecord on the producer's stream: ") + hipGetErrorString(e);
+    return VAMD_EINVAL;
+  }
+  L.src_base.assign(src->base, src->base + nstreams);
+  L.src_dtype = src->dtype, L.src_cstride = src->channel_stride, L.src_fstride = src->frame_stride;
+  return queue_group(f, L, nstreams, frames, true);
+}
+
+// the lane's device current for a call's checks and its event, the caller's restored behind them
+struct DeviceScope {
+  int before = -1;
+  explicit DeviceScope(int device) {
+    if (hipGetDevice(&before) != hipSuccess) before = -1;
+    if (before != device) (void)hipSetDevice(device);
+    else before = -1;
+  }
+  ~DeviceScope() {
+    if (before >= 0) (void)hipSetDevice(before);
+  }
+};
+
+int vamd_feed_buffer(vamd_feed *f, void **pcm) { return feed_buffer(f, -1, pcm); }
+
+int vamd_feed_buffer_on(vamd_feed *f, int device, void **pcm) { return device < 0 ? VAMD_EINVAL : feed_buffer(f, device, pcm); }
+
+int vamd_feed_wrote_device(vamd_feed *f, int slot, long nstreams, const int64_t *frames, const vamd_feed_source *src) {
+  if (!f || !frames || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  std::lock_guard<std::mutex> g(f->m);
+  if (f->write_frames) {
+    f->err = "vamd_feed_wrote_device is for a whole-stream feed; a live feed takes vamd_feed_wrote_live_device";
+    return VAMD_EINVAL;
+  }
+  FeedLane &L = f->lanes[(size_t)slot];
+  if (nstreams < 1 || nstreams > f->max_streams || L.state != LANE_FILLING) {
+    f->err = "vamd_feed_wrote_device: a slot between vamd_feed_buffer and its group, 1 to max_streams streams";
+    return VAMD_EINVAL;
+  }
+  long longest = 0;
+  for (long i = 0; i < nstreams; i++) {
+    if (frames[i] < 1 || frames[i] > f->max_frames) {
+      f->err = "vamd_feed_wrote_device: stream " + std::to_string(i) + " has " + std::to_string(frames[i]) + " frames, not 1 to max_frames";
+      return VAMD_EINVAL;
+    }
+    if (frames[i] > longest) longest = (long)frames[i];
+  }
+  DeviceScope on(L.device);
+  FEED_OWN(source_check(f, L, nstreams, frames, src));
+  L.frames_of.assign(frames, frames + nstreams);
+  return queue_group_device(f, L, nstreams, longest, src);
+}
+
+int vamd_feed_wrote_live_device(vamd_feed *f, int slot, long nstreams, const int64_t *frames, const uint8_t *close, const vamd_feed_source *src) {
+  if (!f || !frames || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  std::lock_guard<std::mutex> g(f->m);
+  if (!f->write_frames) {
+    f->err = "vamd_feed_wrote_live_device is for a live feed (vamd_feed_create_live); a whole-stream feed takes vamd_feed_wrote_device";
+    return VAMD_EINVAL;
+  }
+  FeedLane &L = f->lanes[(size_t)slot];
+  if (nstreams < 1 || nstreams > f->max_streams || L.state != LANE_FILLING) {
+    f->err = "vamd_feed_wrote_live_device: a slot between vamd_feed_buffer and its group, 1 to max_streams streams";
+    return VAMD_EINVAL;
+  }
+  for (long i = 0; i < nstreams; i++) {
+    if (frames[i] < 0 || frames[i] > f->max_frames) {
+      f->err = "vamd_feed_wrote_live_device: stream " + std::to_string(i) + " has " + std::to_string(frames[i]) + " frames, not 0 to max_frames";
+      return VAMD_EINVAL;
+    }
+    if (close && close[i] && !frames[i] && !L.live[(size_t)i].open) {  // (closing a stream that never had a frame)
+      f->err = "vamd_feed_wrote_live_device: stream " + std::to_string(i) + " is closed and never had a frame";
+      return VAMD_EINVAL;
+    }
+  }
+  DeviceScope on(L.device);
+  FEED_OWN(source_check(f, L, nstreams, frames, src));
+  L.frames_of.assign(frames, frames + nstreams);
+  L.close_of.assign((size_t)nstreams, 0);
+  if (close)
+    for (long i = 0; i < nstreams; i++) L.close_of[(size_t)i] = close[i] != 0;
+  return queue_group_device(f, L, nstreams, f->max_frames, src);
+}
+
+int vamd_feed_source_done(vamd_feed *f, int slot, void *consumer, int wait_on_host) {
+  if (!f || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  std::unique_lock<std::mutex> g(f->m);
+  FeedLane &L = f->lanes[(size_t)slot];
+  if ((L.state != LANE_QUEUED && L.state != LANE_DONE) || !L.src_dev) {
+    f->err = "vamd_feed_source_done: the slot holds no device-fed group";
+    return VAMD_EINVAL;
+  }
+  f->cv_done.wait(g, [&] { return f->stop || L.ingest_queued || L.state == LANE_DONE; });
+  if (f->stop) return VAMD_EFAULT;
+  if (!L.ingest_recorded) return VAMD_OK;  // (the group failed before its ingest: nothing of the lane's reads the source)
+  const hipEvent_t ev = L.ev_ingest;
+  g.unlock();  // (the event is this group's until the slot is released, which is the caller's to do)
+  if (consumer && hipStreamWaitEvent((hipStream_t)consumer, ev, 0) != hipSuccess) return VAMD_EFAULT;
+  if (wait_on_host && hipEventSynchronize(ev) != hipSuccess) return VAMD_EFAULT;
+  return VAMD_OK;
+}
+
 int vamd_feed_wrote(vamd_feed *f, int slot, long nstreams, long frames) {
-  if (!f || slot < 0 || slot >= (int)f->lanes.size() || f->write_frames) return VAMD_EINVAL;
+  if (!f || slot < 0 || slot >= (int)f->lanes.size() || f->write_frames || f->no_arena) return VAMD_EINVAL;
   if (nstreams < 1 || nstreams > f->max_streams || frames < 1 || frames > f->max_frames) return VAMD_EINVAL;
   std::lock_guard<std::mutex> g(f->m);
   FeedLane &L = f->lanes[(size_t)slot];
@@ -1274,7 +1552,7 @@ int vamd_feed_wrote(vamd_feed *f, int slot, long nstreams, long frames) {
 }
 
 int vamd_feed_wrote_v(vamd_feed *f, int slot, long nstreams, const int64_t *frames) {
-  if (!f || !frames || slot < 0 || slot >= (int)f->lanes.size() || f->write_frames) return VAMD_EINVAL;
+  if (!f || !frames || slot < 0 || slot >= (int)f->lanes.size() || f->write_frames || f->no_arena) return VAMD_EINVAL;
   if (nstreams < 1 || nstreams > f->max_streams) return VAMD_EINVAL;
   long longest = 0;
   long long total = 0;
@@ -1292,7 +1570,7 @@ int vamd_feed_wrote_v(vamd_feed *f, int slot, long nstreams, const int64_t *fram
 }
 
 int vamd_feed_wrote_live(vamd_feed *f, int slot, long nstreams, const int64_t *frames, const uint8_t *close) {
-  if (!f || !frames || slot < 0 || slot >= (int)f->lanes.size() || !f->write_frames) return VAMD_EINVAL;
+  if (!f || !frames || slot < 0 || slot >= (int)f->lanes.size() || !f->write_frames || f->no_arena) return VAMD_EINVAL;
   if (nstreams < 1 || nstreams > f->max_streams) return VAMD_EINVAL;
   std::lock_guard<std::mutex> g(f->m);
   FeedLane &L = f->lanes[(size_t)slot];
