@@ -12,8 +12,10 @@
 //    the two top-of-stack entries held in registers so the common path never
 //    waits on LDS; its second half (painting each surviving entry over its span)
 //    is a prefix-max over the entries' end positions and is done by all lanes.
-//  * max_seeds' pointer walk over (octave line, bin) is static too: per bin the
-//    span of seed lines it folds is precomputed, every lane folds its own bins.
+//  * max_seeds' pointer walk over (octave line, bin) is static too: the lines each
+//    of its outer-loop iterations ("group") scans and the bins that take the outcome
+//    are precomputed; lanes fold runs of lines into their groups' minima, every bin then
+//    combines its group's start value and minimum.
 //
 // The stage is three kernels so that the ordered stack walk -- one useful lane if a
 // wave owned a single block -- can instead run with one *lane* per channel-block
@@ -89,6 +91,31 @@ VAMD_DEV void seed_curve_scatter(float *seed, const float *__restrict__ band_row
 //             therefore lines further on (linesper <= 16).  The one-lane test build, whose chunks are single entries,
 //             hands over a copy of the unpainted lines instead.
 //   posstack  the survivor list (HBM);  head  its first two chunks as fetched ahead by surv_head_load (optional)
+//
+// ---- round 17: max_seeds' fold by groups (profiles/r17_tone_fold_groups.txt; each switch can be turned the other way
+// with -D...=0 / =1 for an A/B of its own, the tables are derived in both forms) ------------------------------------------
+//   * VAMD_TF_MIN_RUNS (on): the groups' minima from runs of VAMD_TF_RUN_LINES (4 or 8) consecutive lines per lane, one
+//     LDS float min per group a run touches, instead of one per line.
+//   * VAMD_TF_GROUP_FOLD (off): max_seeds' start value, cap and compares once per group; a bin looks its group's value up.
+// Same compares and selects on the same operands; a min is order-free.
+#ifndef VAMD_TF_MIN_RUNS
+#define VAMD_TF_MIN_RUNS 1
+#endif
+#ifndef VAMD_TF_RUN_LINES
+#define VAMD_TF_RUN_LINES 8
+#endif
+#ifndef VAMD_TF_GROUP_FOLD
+#define VAMD_TF_GROUP_FOLD 0  // measured slower than the per-bin form it replaces (a phase more, behind a table fetch): off
+#endif
+// the smaller of two real seed values (> VAMD_NEGINF, +inf allowed, no NaN): the median of the two and a value below
+// both, one instruction -- fminf() quiets signalling NaNs first (three), a compare and a select are two
+#if VAMD_GPU
+VAMD_DEV float tone_min(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, VAMD_NEGINF); }
+#define VAMD_TF_RUN_LOOP _Pragma("unroll 1")
+#else
+VAMD_DEV float tone_min(float a, float b) { return b < a ? b : a; }
+#define VAMD_TF_RUN_LOOP
+#endif
 #include "k_tone_fold.inc"  // SurvHead, surv_head_load, seed_chase_paint, tone_fold_prepare, tone_ath_att, tone_fold_quad
 
 // Thread-per-block form of seed_chase part 1.  Only the top ~9 stack entries can
@@ -464,7 +491,7 @@ VAMD_DEV void tone_seed_block(const PsyP &P, const float *__restrict__ peaks, fl
 #endif
 
 VAMD_DEV void tone_fold_block(const PsyP &P, float local_ampmax, float *seed, const float *seed_src,
-                              const unsigned short *__restrict__ surv, int nsurv, float *gmin /* LDS [ngroups] */,
+                              const unsigned short *__restrict__ surv, int nsurv, float *gmin /* LDS [ngroups + 1] */,
                               float *__restrict__ out, PhaseClock &pc) {
   const float att = tone_ath_att(P, local_ampmax);
   tone_fold_prepare(P, seed, seed_src, surv, nsurv, gmin, pc);

@@ -56,34 +56,112 @@ VAMD_DEV void seed_chase_paint(float *seeds, const float *src, int linesper, int
 // list -> tone curve
 // ... in two steps, so that a caller can take the curve quad by quad (k_floor mixes it without a trip through memory):
 // tone_fold_prepare leaves the painted lines and the groups' minima in LDS, tone_fold_quad forms four bins from them.
+//
+// max_seeds' fold, lib/psy.c:522-543.  Each outer-loop iteration ("group") of the reference starts from seed[p0]
+// (capped at tone_abs_limit) and then keeps the lowest real (> NEGINF) value among the lines it scans -- a min, hence
+// order-free -- and every bin the iteration covers takes that value.  Static tables (vamd_derive.h):
+//   line_slot[line]  the group whose scan covers the line (`ngroups` where none does), as a byte offset into gmin[]
+//   bin_fold[bin]    p0 | group << 16 (bins below tail_linpos; the bins of the tail loop, :539-543, take seed[nlines - 1])
+//   group_p0[g]      the line group g starts from; g = ngroups stands for the bins of the tail loop
+//   bin_group[bin]   a bin's group, 16 bits
+// gmin[ngroups + 1] (LDS): the groups' scanned minima; slot `ngroups` takes the lines that no group scans.
+//  * VAMD_TF_MIN_RUNS (on): a lane takes VAMD_TF_RUN_LINES consecutive lines, reduces them in registers and sends one LDS
+//    float min per group its run touches (a group's lines are one run, so a change of group ends a segment).  Before,
+//    a lane sent one line: in the low octaves a group spans up to 101 lines, all 64 lanes of an instruction hit one or
+//    two addresses and the LDS unit took them one after the other.  No test for a line without a group: its slot is
+//    nobody's.
+//  * VAMD_TF_GROUP_FOLD (off: fewer instructions, measured slower): start value, cap and the three compares once per
+//    group (315 at 1024 bins) instead of once per bin, stored over gmin[g]; tone_fold_quad is then group_p0 / bin_group
+//    look-ups -- a table load, the ATH quad, four LDS reads, add, max -- and does not read seed[].
+// With a switch at 0 that piece is the per-line / per-bin form it replaces (profiles/r17_tone_fold_groups.txt).
+#if VAMD_TF_MIN_RUNS
+static_assert(VAMD_TF_RUN_LINES == 4 || VAMD_TF_RUN_LINES == 8, "a run is one or two 16-byte LDS reads");
+VAMD_DEV void tone_group_minima(const PsyP &P, const float *seed, float *gmin) {
+  constexpr int R = VAMD_TF_RUN_LINES;
+  const float inf = f_from_bits(0x7f800000u);
+  const int nruns = (P.total_octave_lines + R - 1) / R;  // (seed[] and line_slot[] are padded to whole runs)
+  // (two trips of the loop at 777 lines: not unrolled, eight ends of a segment are code enough)
+  VAMD_TF_RUN_LOOP for (int r = LANE; r < nruns; r += NLANES) {
+    float s[R];
+    int g[R];  // the lines' slots as byte offsets into gmin[]
+    f4_get(((const F4 *)seed)[(R / 4) * r], s);
+    const I4 w0 = dm_load_i4(P.line_slot, (unsigned)r * (4u * R));
+    g[0] = w0.x, g[1] = w0.y, g[2] = w0.z, g[3] = w0.w;
+    if (R == 8) {
+      f4_get(((const F4 *)seed)[2 * r + 1], s + R - 4);
+      const I4 w1 = dm_load_i4(P.line_slot, (unsigned)r * (4u * R) + 16u);
+      g[R - 4] = w1.x, g[R - 3] = w1.y, g[R - 2] = w1.z, g[R - 1] = w1.w;
+    }
+    float acc = inf;
+#pragma unroll
+    for (int c = 0; c < R; c++) {
+      const float v = s[c] > VAMD_NEGINF ? s[c] : inf;
+      acc = c == 0 ? v : tone_min(acc, v);
+      if (c == R - 1 || g[c] != g[c + 1]) {  // the last of this group's lines in the run (+inf: nothing real, a no-op)
+        lds_atomic_min((float *)((char *)gmin + g[c]), acc);
+        acc = inf;
+      }
+    }
+  }
+}
+#endif
 VAMD_DEV void tone_fold_prepare(const PsyP &P, float *seed, const float *seed_src,
-                                const unsigned short *__restrict__ surv, int nsurv, float *gmin /* LDS [ngroups] */,
+                                const unsigned short *__restrict__ surv, int nsurv, float *gmin /* LDS [ngroups + 1] */,
                                 PhaseClock &pc, int slot = 3, const SurvHead *head = nullptr) {
   const int nlines = P.total_octave_lines;
   seed_chase_paint(seed, seed_src, P.eighth_octave_lines, nlines, nsurv, surv, head);
   WAVE_SYNC();
   pc.mark(slot);
 
-  // max_seeds' fold, lib/psy.c:522-543.  Each outer-loop iteration ("group") of the
-  // reference starts from seed[p0] (capped at tone_abs_limit) and then keeps the lowest
-  // real (> NEGINF) value among the lines it scans -- a min, hence order-free: every
-  // line is folded into its group with an LDS float min, then every bin combines its
-  // group's start value and scanned minimum.  Work is balanced over lines and bins
-  // instead of leaving the few low bins with 70-line spans to single lanes.
-  WAVE_FOR(g, P.ngroups) gmin[g] = f_from_bits(0x7f800000u);  // +inf = "no real value scanned"
+  // the groups' minima: work is balanced over lines instead of leaving the few low bins with 70-line spans to
+  // single lanes
+  WAVE_FOR(g, P.ngroups + 1) gmin[g] = f_from_bits(0x7f800000u);  // +inf = "no real value scanned"
   WAVE_SYNC();
+#if VAMD_TF_MIN_RUNS
+  tone_group_minima(P, seed, gmin);
+#else
   WAVE_FOR(p, nlines) {
     const int g = dm_load<unsigned short>(P.line_group, 2u * (unsigned)p);
     const float s = seed[p];
     if (g != 0xffff && s > VAMD_NEGINF) lds_atomic_min(gmin + g, s);
   }
+#endif
   WAVE_SYNC();
   pc.mark(slot + 1);
+#if VAMD_TF_GROUP_FOLD
+  // what the bins of group g get (a lane reads and writes its own groups' slots only)
+  WAVE_FOR(g, P.ngroups + 1) {
+    float minV = seed[dm_load<int>(P.group_p0, 4u * (unsigned)g)];
+    if (g < P.ngroups) {
+      if (minV > P.tone_abs_limit) minV = P.tone_abs_limit;
+      const float rest = gmin[g];
+      if (rest < f_from_bits(0x7f800000u)) {
+        if (minV == VAMD_NEGINF || rest < minV) minV = rest;
+      }
+    }
+    gmin[g] = minV;
+  }
+  WAVE_SYNC();
+#endif
 }
 VAMD_DEV float tone_ath_att(const PsyP &P, float local_ampmax) {
   float att = local_ampmax + P.ath_adjatt;
   return att < P.ath_maxatt ? P.ath_maxatt : att;
 }
+#if VAMD_TF_GROUP_FOLD
+VAMD_DEV void tone_fold_quad(const PsyP &P, float att, const float *, const float *gmin, int q, float *o) {
+  const unsigned long long gq = dm_load<unsigned long long>(P.bin_group, (unsigned)q << 3);  // the quad's four groups
+  float av[4];
+  f4_get(dm_load_f4(P.ath, (unsigned)q << 4), av);
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    const float minV = gmin[(int)(gq >> (16 * c)) & 0xffff];
+    float v = av[c] + att;
+    if (v < minV) v = minV;
+    o[c] = v;
+  }
+}
+#else
 VAMD_DEV void tone_fold_quad(const PsyP &P, float att, const float *seed, const float *gmin, int q, float *o) {
   const int nlines = P.total_octave_lines;
   const I4 bf = dm_load_i4(P.bin_fold, (unsigned)q << 4);
@@ -109,3 +187,4 @@ VAMD_DEV void tone_fold_quad(const PsyP &P, float att, const float *seed, const 
     o[c] = v;
   }
 }
+#endif

@@ -381,6 +381,11 @@ static void launch_couple(vamd_ctx *c, BatchRun *R, hipStream_t s, int blob_base
 // saves -- one stereo block 192 us with it, 181 without)
 static bool masks_overlap(const vamd_ctx *c, const BatchRun *R) { return c->overlap && (unsigned)(R->nb * c->B.channels) > 64; }
 static hipEvent_t join_event(const vamd_ctx *c, const BatchRun *R) { return R->W ? c->ev_join : c->ev_join2; }
+// the fold's LDS: the seed lines, then a float per group and one for the tail bins' group (k_tone_fold.inc); whole 16
+// bytes, so that the second half of a paired wave (k_floor_pair) starts aligned as well
+static size_t fold_lds_bytes(int nlp, const PsyP &P0, const PsyP &P1) {
+  return ((size_t)(nlp + (P0.ngroups > P1.ngroups ? P0.ngroups : P1.ngroups) + 1) * 4 + 15) & ~(size_t)15;
+}
 // the VBR path's floor stage takes the tone chain's last step with it (k_floor)
 static bool fold_in_floor(const vamd_ctx *c, const BatchRun *R, int level) {
   const bool fold_env = !c->K.fold_separate;
@@ -490,7 +495,7 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
                            P0.eighth_octave_lines, nl, nlp, (long)gcb, d, p.seed, p.surv, p.nsurv);
     }
     if (!fold_later)
-      hipLaunchKernelGGL(k_tone_fold, dim3(gcb), dim3(64), (size_t)(nlp + (P0.ngroups > P1.ngroups ? P0.ngroups : P1.ngroups)) * 4, s, P0, P1, d, ch, nlp, p.seed, p.surv,
+      hipLaunchKernelGGL(k_tone_fold, dim3(gcb), dim3(64), fold_lds_bytes(nlp, P0, P1), s, P0, P1, d, ch, nlp, p.seed, p.surv,
                          p.nsurv, p.local, p.tone);
   }
   if (overlap) (void)hipEventRecord(join_event(c, R), c->side);
@@ -509,7 +514,7 @@ static void launch_floor_on(vamd_ctx *c, BatchRun *R, int level) {
   const unsigned gcb = (unsigned)(R->nb * ch), gb = (unsigned)R->nb;
   hipStream_t s = c->stream;
   const bool fold_here = fold_in_floor(c, R, level);
-  const size_t fold_lds = (size_t)(nlp_all + (P0.ngroups > P1.ngroups ? P0.ngroups : P1.ngroups)) * 4;
+  const size_t fold_lds = fold_lds_bytes(nlp_all, P0, P1);
   if (level >= VAMD_LEVEL_PSY) {
     if (masks_overlap(c, R)) (void)hipStreamWaitEvent(s, join_event(c, R), 0);  // join
     prof_mark(c, VAMD_ST_TONE);

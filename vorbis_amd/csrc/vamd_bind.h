@@ -468,6 +468,16 @@ inline int build_image(const void *blob_v, size_t bytes, std::vector<unsigned ch
       const unsigned char *a = (const unsigned char *)tab.data();
       image->insert(image->end(), a, a + 4 * tab.size());
     }
+  for (int p = 0; p < 4; p++) {  // slots 43 + 3 p ..: per psy group_p0[], bin_group[] and line_slot[] (the fold per group)
+    const PsyDerived &d = (*derived)[p];
+    const void *src[3] = {d.group_p0.data(), d.bin_group.data(), d.line_slot.data()};
+    const size_t len[3] = {4 * d.group_p0.size(), 2 * d.bin_group.size(), 4 * d.line_slot.size()};
+    for (int k = 0; k < 3; k++) {
+      while (image->size() & 15) image->push_back(0);
+      derived_off->push_back((uint32_t)image->size());
+      image->insert(image->end(), (const unsigned char *)src[k], (const unsigned char *)src[k] + len[k]);
+    }
+  }
   while (image->size() & 15) image->push_back(0);
   return VAMD_OK;
 }
@@ -844,6 +854,9 @@ inline void bind_params(const std::vector<unsigned char> &image, const std::vect
     P.line_group = (const unsigned short *)(base + derived_off[16 + 2 * p + 1]);
     P.ngroups = d.ngroups;
     P.tail_linpos = d.tail_linpos;
+    P.group_p0 = (const int *)(base + derived_off[43 + 3 * p]);
+    P.bin_group = (const unsigned short *)(base + derived_off[43 + 3 * p + 1]);
+    P.line_slot = (const int *)(base + derived_off[43 + 3 * p + 2]);
     P.normal_p = t.normal_p;
     P.normal_start = t.normal_start;
     P.normal_partition = t.normal_partition;

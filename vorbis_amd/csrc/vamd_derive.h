@@ -3,6 +3,12 @@
 // depend only on the setup blob (octave[], bark[], n, window widths), never on
 // audio, so vamd_create() computes them once and ships them to HBM next to the
 // blob.  Pure integer walks; each cites the loop it freezes.
+//
+// max_seeds' walk (lib/psy.c:512-545) is frozen three ways.  Per bin: seed_span, bin_fold (p0 | group << 16).  Per
+// octave line: line_group, line_slot (the group whose scan covers the line).  Per group: group_p0 (the line the group
+// starts from) with bin_group (a bin's group, 16 bits) -- the form the kernels read (k_tone_fold.inc): the fold's
+// outcome is a function of the group, so it is formed once per group and a bin only looks it up.  Groups are numbered
+// in walk order; their scans (p0_g, p1_g] are ascending and adjacent (p0_{g+1} = p1_g), so a group's lines are one run.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -34,6 +40,15 @@ struct PsyDerived {
   std::vector<int32_t> bin_fold;     // [n]   p0 | group << 16  (bins below tail_linpos)
   std::vector<uint16_t> line_group;  // [nl padded to 16] group whose scan covers the line, 0xffff = none
   int ngroups;
+  // ... and organised per GROUP (k_tone_fold.inc: the fold's result is one value per group, not per bin).  p0 and the
+  // group number are assigned in the same iteration of the walk, so a bin needs its group number only.  The bins of
+  // max_seeds' tail loop (:539-543), which all take seed[nlines - 1] as it is, form one more group: number `ngroups`.
+  std::vector<int32_t> group_p0;     // [ngroups + 1] the line a group starts from; [ngroups] = nlines - 1
+  std::vector<uint16_t> bin_group;   // [n padded to 8] a bin's group; `ngroups` from tail_linpos on and in the padding
+  // line_group with `ngroups` for "none": while the minima are taken the tail group's slot is nobody's yet, so the
+  // lines no group scans are folded into it unconditionally and need no test (the per-group fold then sets that slot)
+  std::vector<int32_t> line_slot;    // [nl padded to 16] the slot's byte offset, 4 * group
+  int longest_group;                 // lines of the longest scan (a figure for the profile, not read by kernels)
 };
 
 inline PsyDerived derive_psy(const vamd_psy_tab &t, const unsigned char *blob) {
@@ -122,6 +137,7 @@ inline PsyDerived derive_psy(const vamd_psy_tab &t, const unsigned char *blob) {
   d.bin_fold.assign((size_t)n, 0);
   d.line_group.assign((size_t)((t.total_octave_lines + 15) & ~15), 0xffff);
   d.ngroups = 0;
+  d.longest_group = 0;
   {
     const int linesper = t.eighth_octave_lines;
     long linpos = 0;
@@ -137,9 +153,17 @@ inline PsyDerived derive_psy(const vamd_psy_tab &t, const unsigned char *blob) {
         d.seed_span[2 * linpos + 1] = (int32_t)pos;
         d.bin_fold[(size_t)linpos] = (int32_t)(p0 | ((long)d.ngroups << 16));
       }
+      d.group_p0.push_back((int32_t)p0);
+      if ((int)(pos - p0) > d.longest_group) d.longest_group = (int)(pos - p0);
       d.ngroups++;
     }
     d.tail_linpos = (int)linpos;
+    d.group_p0.push_back(t.total_octave_lines - 1);
+    d.bin_group.assign((size_t)((n + 7) & ~7), (uint16_t)d.ngroups);
+    for (int b = 0; b < d.tail_linpos; b++) d.bin_group[(size_t)b] = (uint16_t)(d.bin_fold[(size_t)b] >> 16);
+    d.line_slot.resize(d.line_group.size());
+    for (size_t p = 0; p < d.line_slot.size(); p++)
+      d.line_slot[p] = 4 * (d.line_group[p] == 0xffff ? d.ngroups : (int32_t)d.line_group[p]);
   }
   return d;
 }

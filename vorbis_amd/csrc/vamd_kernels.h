@@ -687,7 +687,7 @@ __global__ __launch_bounds__(64) void k_tone_fold(PsyP P0, PsyP P1, DescP d, int
   const PsyP &P = d_bt(d, blk) ? P1 : P0;
   const int n2 = P.n;
   float *seed = (float *)vamd_smem;  // [nlp]
-  float *gmin = seed + nlp;          // [ngroups]
+  float *gmin = seed + nlp;          // [ngroups + 1]
   PhaseClock pc;
   pc.start(d.dbg ? d.dbg + 32 : nullptr);
   WAVE_FOR(q, nlp >> 2)((F4 *)seed)[q] = ((const F4 *)(seed_g + cb * nlp))[q];

@@ -64,6 +64,9 @@ struct PsyP {
   const unsigned short *line_group;  // [nl16] group of each octave line, 0xffff = none
   int ngroups;
   int tail_linpos;           // first bin handled by max_seeds' tail loop (lib/psy.c:539-543)
+  const int *group_p0;       // [ngroups + 1] the line a group starts from; group `ngroups` = the tail bins, line nlines - 1
+  const unsigned short *bin_group;   // [n8] a bin's group
+  const int *line_slot;      // [nl16] line_group with `ngroups` for "none", as byte offsets (4 * group) into the minima
   int normal_p, normal_start, normal_partition;
   double normal_thresh;
 };
