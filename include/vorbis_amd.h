@@ -514,6 +514,38 @@ int vamd_plan_streams_whole_v(vamd_ctx *ctx, float *pcm, long stream_stride, lon
 int vamd_plan_fetch(vamd_ctx *ctx, const vamd_stream_plan *plan, int32_t *const lW[2], int32_t *const nW[2],
                     int32_t *const blocktype[2], int64_t *const src[2], int32_t *order, int64_t *stream_start);
 
+/* ---- synthesis: the decoded signal beside the packets (still ABI 9: additions only).  The decoder's per-block, data-parallel
+ * back half -- _01inverse's vector adds, the inverse coupling, floor1_inverse2, mdct_backward (lib/mapping0.c:698-799) and
+ * vorbis_synthesis_blockin's windowed overlap-add (lib/block.c:779-823) -- run from what the encoder holds of a block in
+ * HBM: the floor's integer curve and flags, the residue classes and codebook entries.  No bitstream is read; the entropy
+ * decode, the only serial part of vorbis_synthesis(), is not needed.  Bit for bit (signed zeros included) what libvorbis'
+ * decoder computes from the packets of the same blocks (tests/test_synth_cpu.py, tests/test_synth_gpu.py).
+ *   vamd_analyze_batch_synth   vamd_analyze_batch(level FULL) with the residue search on whether or not `io` takes its
+ *     outputs, then synth [nb][ch][n] (device): vb->pcm as vorbis_synthesis() leaves it for each block's packet, un-windowed.
+ *     VAMD_EIMPL where vamd_residue_capacity() is 0, where a block's spectrum and butterfly vectors do not fit a workgroup's
+ *     LDS, and for a floor of more than two posts whose range (postlist[1]) is no power of two: floor1_pack writes the range
+ *     as a bit count and a decoder rebuilds 1 << bits (lib/floor1.c:102-103,160), so such a floor is drawn differently by the
+ *     two sides.  libvorbisenc ships one kind, the 5.1 setups' LFE floor (two posts, range 12, decoded as 16): its one line is
+ *     drawn the decoder's way here, which is NOT the integer curve the encoder quantised against (the `ilogmask` tap).
+ *   vamd_synth_streams         the decoded samples of the streams of a plan, out of the tensors the context's LAST
+ *     vamd_analyze_streams_mixed left (a VBR run with packets or residue outputs on, of exactly the plan's blocks; else
+ *     VAMD_EINVAL): k_synth per size class into scratch_short / scratch_long ([nblocks[W]][ch][blocksizes[W]] floats, device;
+ *     NULL where the class has no blocks), then the lap: stream s, channel c, frame k at pcm[offset[s] + c * frames[s] + k]
+ *     (frames, offset: DEVICE arrays [nstreams]; max_frames: the longest, sizes the launch).  Frame 0 is the first block's
+ *     centre, the stream's first sample; a stream yields no more frames than its blocks' centres span, which is what the last
+ *     packet's granule position cuts a decoder's output to.  Enqueued on the context's stream; no host wait.  The call reads the
+ *     run's floor flags, integer curves and residue rows where the run had them: output buffers the caller gave that run
+ *     (post_valid, res_class / res_entries / res_count) must still be alive and unwritten; anything that grows the context's
+ *     workspace in between (vamd_reserve, another call) makes the call answer VAMD_EINVAL rather than read what has moved.  A
+ *     run of another plan with the same block counts cannot be told apart: analyse, then synthesise.  (Public because the
+ *     feed, which is built on this ABI alone, is its caller.)
+ *   vamd_synth_check           VAMD_OK where size class W's blocks can be synthesised, else VAMD_EIMPL as above (vamd_last_error
+ *     says why). */
+int vamd_synth_check(vamd_ctx *ctx, int W);
+int vamd_analyze_batch_synth(vamd_ctx *ctx, const vamd_batch_desc *desc, const vamd_batch_io *io, float *synth);
+int vamd_synth_streams(vamd_ctx *ctx, const vamd_stream_plan *plan, long nstreams, long max_frames, const int64_t *frames,
+                       const int64_t *offset, float *scratch_short, float *scratch_long, float *pcm);
+
 /* ---- the host shim for encoders that submit ONE block at a time from many threads.
  * libvorbis' unit of work is one block of one stream (mapping0_forward, reference lib/mapping0.c:233-687); a
  * batcher coalesces concurrent vamd_batcher_encode_block() calls -- same contract as vamd_encode_block() for a VBR
@@ -699,6 +731,40 @@ int vamd_feed_wrote_live_device(vamd_feed *f, int slot, long nstreams, const int
  * then, with consumer != NULL, makes that stream wait for the ingest (hipStreamWaitEvent: work enqueued on it afterwards may
  * overwrite the source, no host wait needed); with wait_on_host != 0 also blocks until the ingest has finished. */
 int vamd_feed_source_done(vamd_feed *f, int slot, void *consumer /* hipStream_t */, int wait_on_host);
+
+/* ---- the decoded feed: the signal a listener gets back from the packets, on the device (still ABI 9: additions only).
+ * Callers whose audio already lives in HBM -- a model, a resampler, a decoder -- also want what the codec makes of it, aligned
+ * sample for sample with the input: Vorbis at quality q as an augmentation of device tensors, a quality check of a
+ * rendition before the files leave the box, a self-check of a farm's output without a CPU decoder.  VAMD_FEED_DECODED,
+ * or'ed into vamd_feed_create's format beside VAMD_FEED_NO_ARENA, gives every group that signal:
+ *     ... vamd_feed_wrote / _wrote_v / _wrote_device ...
+ *     vamd_feed_packets(f, slot, &out)        unchanged, and no later than without the flag
+ *     vamd_feed_decoded(f, slot, &dec)        waits as vamd_feed_packets does, then for the decoded signal
+ *     vamd_feed_release(f, slot)
+ * Stream s's pcm is bit for bit what libvorbis' decoder returns for the feed's packets of that stream -- vorbis_synthesis +
+ * vorbis_synthesis_blockin + vorbis_synthesis_pcmout, the packets' own granule positions given -- frames[s] samples per
+ * channel, planar: as many as the stream had frames in, sample k the listener's sample k (tests/test_feed_decoded.py).
+ * Nothing is decoded: behind the group's packet hand-over the lane's stream runs vamd_synth_streams over what the analysis
+ * left in HBM ("synthesis", above) and records a second event; vamd_feed_decoded waits for that one.
+ * A stream with a block that has no packet (bits = -1) gets no signal, exactly as it gets no file: frames[s] = 0 and
+ * status[s] says why (frames[s] = 0 is the sign, whatever status[s] holds); the others are untouched.  Host-fed and device-fed groups alike, and together with the Ogg feed.
+ * A feed without the flag behaves and allocates exactly as before: its packets and files are byte for byte what they were.
+ * A lane of a decoded feed also holds, in HBM, the decoded arena (channels * max_streams * max_frames floats) and k_synth's
+ * scratch (about twice that).  VAMD_EINVAL: vamd_feed_decoded on a feed without the flag; a slot that is not ready is
+ * treated as vamd_feed_packets treats it.  VAMD_EIMPL from vamd_feed_create with the flag and a bitrate-managed blob (the
+ * manager may CUT the chosen packet, and a decoder that runs out of bits stops in mid-residue: eopbreak, lib/res0.c:686,701),
+ * from vamd_feed_create_live with the flag (the overlap would have to be carried between groups), and for a setup
+ * vamd_analyze_batch_synth refuses; vamd_feed_last_error(NULL) says which. */
+#define VAMD_FEED_DECODED 0x200
+typedef struct vamd_feed_decoded_result {
+  int64_t nstreams; int32_t channels;
+  const int64_t *frames;   /* host [nstreams]: decoded frames == the stream's input frames; 0 where status[s] != 0 */
+  const int64_t *offset;   /* host [nstreams + 1], in floats: stream s, channel c, frame k at pcm[offset[s] + c * frames[s] + k] */
+  const uint8_t *status;   /* host [nstreams]: 0, or the VAMD_STATUS_* of the block that cost the stream its signal */
+  const float   *pcm;      /* DEVICE memory on vamd_feed_device(slot); complete when the call returns; valid until vamd_feed_release */
+  int64_t total_floats;
+} vamd_feed_decoded_result;
+int vamd_feed_decoded(vamd_feed *f, int slot, vamd_feed_decoded_result *out);   /* waits as vamd_feed_packets does */
 
 /* ---- the Ogg feed: complete Ogg Vorbis I files beside the packets (whole-stream feeds; a live feed's files come in pieces,
  * "the live Ogg feed" below; still ABI 9: additions only).

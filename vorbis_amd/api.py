@@ -32,7 +32,8 @@ EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe",
                     "vamd_analyze_streams_mixed_managed", "vamd_bitrate_init_states", "vamd_bitrate_walk",
                     "vamd_feed_ogg_headers", "vamd_feed_ogg_serials", "vamd_feed_ogg", "vamd_feed_ogg_headers_live",
                     "vamd_feed_ogg_comments", "vamd_feed_ogg_flush",
-                    "vamd_feed_buffer_on", "vamd_feed_wrote_device", "vamd_feed_wrote_live_device", "vamd_feed_source_done"]
+                    "vamd_feed_buffer_on", "vamd_feed_wrote_device", "vamd_feed_wrote_live_device", "vamd_feed_source_done",
+                    "vamd_analyze_batch_synth", "vamd_synth_streams", "vamd_synth_check", "vamd_feed_decoded"]
 PACKETBLOBS = 15
 
 _vp = C.c_void_p
@@ -56,6 +57,18 @@ class _FeedSource(C.Structure):  # vamd_feed_source
 class _FeedOggResult(C.Structure):  # vamd_feed_ogg_result
     _fields_ = [("nstreams", C.c_int64), ("stream_offset", _vp), ("npages", _vp), ("status", _vp), ("bytes", _vp),
                 ("total_bytes", C.c_int64)]
+
+
+class _FeedDecodedResult(C.Structure):  # vamd_feed_decoded_result
+    _fields_ = [("nstreams", C.c_int64), ("channels", C.c_int32), ("frames", _vp), ("offset", _vp), ("status", _vp), ("pcm", _vp),
+                ("total_floats", C.c_int64)]
+
+
+class _DeviceFloats:
+    """`count` floats of device memory at `ptr`, for torch.as_tensor (the CUDA array interface: a view, no copy)"""
+
+    def __init__(self, ptr, count):
+        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
 
 
 class _Desc(C.Structure):
@@ -183,6 +196,9 @@ def load_library():
     L.vamd_residue_capacity.argtypes = [_vp, C.c_int]
     L.vamd_analyze_block_res.argtypes = [_vp, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float] + [_vp] * 10
     L.vamd_analyze_batch_managed.argtypes = [_vp, C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO)]
+    L.vamd_analyze_batch_synth.argtypes = [_vp, C.POINTER(_Desc), C.POINTER(_IO), _vp]
+    L.vamd_synth_check.argtypes = [_vp, C.c_int]
+    L.vamd_synth_streams.argtypes = [_vp, C.POINTER(_Plan), C.c_long, C.c_long, _vp, _vp, _vp, _vp, _vp]
     L.vamd_analyze_block_managed.argtypes = [_vp, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float] + [_vp] * 9
     L.vamd_plan_streams.argtypes = [_vp, _vp, C.c_long, C.c_long, C.c_long, C.c_long, _vp, C.POINTER(_Plan)]
     L.vamd_gather_blocks.argtypes = [_vp, C.POINTER(_Plan), C.c_int, _vp, C.c_long, _vp]
@@ -211,6 +227,7 @@ def load_library():
     L.vamd_feed_wrote_device.argtypes = [_vp, C.c_int, C.c_long, _vp, C.POINTER(_FeedSource)]
     L.vamd_feed_wrote_live_device.argtypes = [_vp, C.c_int, C.c_long, _vp, _vp, C.POINTER(_FeedSource)]
     L.vamd_feed_source_done.argtypes = [_vp, C.c_int, _vp, C.c_int]
+    L.vamd_feed_decoded.argtypes = [_vp, C.c_int, C.POINTER(_FeedDecodedResult)]
     L.vamd_feed_last_error.argtypes = [_vp]
     L.vamd_feed_last_error.restype = C.c_char_p
     L.vamd_analyze_streams_mixed_managed.argtypes = [_vp, C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO), C.POINTER(_Desc),
@@ -447,6 +464,8 @@ class Analyzer:
                 o[k] = t.zeros((nb,), dtype=t.int32, device=dev)
             elif k == "status":      # STATUS_* bits: the channel-block was outside the input domain (vorbis_amd.h)
                 o[k] = t.zeros((nb, ch), dtype=t.uint8, device=dev)
+            elif k == "synth":       # vb->pcm of the block's packet, un-windowed (vamd_analyze_batch_synth)
+                o[k] = t.empty((nb, ch, 2 * n2), dtype=t.float32, device=dev)
             else:
                 raise KeyError(k)
         return o
@@ -488,11 +507,14 @@ class Analyzer:
             return t.uint8
         return t.int32
 
-    def _io(self, pcm, outs, nb=None):
+    def _io(self, pcm, outs, nb=None, synth_ok=False):
         io = _IO()
         io.pcm = _vp(pcm.data_ptr())
         nb = pcm.shape[0] if nb is None else nb
         for k, v in outs.items():
+            if k == "synth":  # (not a field of vamd_batch_io: vamd_analyze_batch_synth's own argument)
+                self._need(synth_ok, "the synth output is analyze()'s alone (vamd_analyze_batch_synth)")
+                continue
             self._need(hasattr(io, k), "unknown output %r" % (k,))
             self._need_tensor(v, self._out_dtype(k), "outs[%r]" % k)
             self._need(v.dim() >= 1 and v.shape[0] == nb, "outs[%r] must have one row per block (%d)" % (k, nb))
@@ -507,7 +529,9 @@ class Analyzer:
 
     def analyze(self, pcm, W=1, lW=1, nW=1, blocktype=BLOCKTYPE_LONG, ampmax_in=-9999.0, level=LEVEL_FULL,
                 want=None, outs=None):
-        """vamd_analyze_batch.  pcm: cuda float32 [nblocks, ch, n].  Returns dict name -> tensor."""
+        """vamd_analyze_batch.  pcm: cuda float32 [nblocks, ch, n].  Returns dict name -> tensor.  With "synth" among the
+        outputs (level FULL): vamd_analyze_batch_synth, synth [nblocks, ch, n] = what a decoder's vorbis_synthesis() leaves
+        in vb->pcm for each block's packet."""
         t = self.torch
         n = self.blocksizes[W]
         self._need(W in (0, 1), "W must be 0 or 1")
@@ -519,9 +543,14 @@ class Analyzer:
             outs = self.alloc_outputs(W, nb, self._DEFAULT_WANT[level] if want is None else want)
         keep = []
         d = self._desc(W, nb, lW, nW, blocktype, ampmax_in, keep)
-        io = self._io(pcm, outs)
+        io = self._io(pcm, outs, synth_ok=True)
         self._bind_stream()
-        self._check(self.L.vamd_analyze_batch(self.h, C.byref(d), C.byref(io), level))
+        if "synth" in outs:
+            self._need(level == LEVEL_FULL, "synth needs level FULL")
+            self._need_tensor(outs["synth"], t.float32, "outs['synth']", shape=(nb, self.channels, n))
+            self._check(self.L.vamd_analyze_batch_synth(self.h, C.byref(d), C.byref(io), _vp(outs["synth"].data_ptr())))
+        else:
+            self._check(self.L.vamd_analyze_batch(self.h, C.byref(d), C.byref(io), level))
         return outs
 
     def analyze_stream(self, pcm, ampmax_state, W=1, lW=1, nW=1, blocktype=BLOCKTYPE_LONG, want=None, outs=None):
@@ -995,6 +1024,7 @@ class EnvelopeState(C.Structure):
 
 FEED_S16, FEED_F32 = 0, 1
 FEED_NO_ARENA = 0x100                       # or'ed into fmt: no pinned input arena, device-fed groups only
+FEED_DECODED = 0x200                        # or'ed into fmt: the decoded signal beside the packets (Feed(decoded=True))
 SRC_S16, SRC_F32, SRC_F16, SRC_BF16 = 0, 1, 2, 3   # VAMD_SRC_*: a device-fed group's element type
 
 
@@ -1079,10 +1109,16 @@ class Feed:
     float32 / float16 / bfloat16 with any strides, read where they lie: buffer() or buffer_on(device) -> wrote_device() /
     wrote_live_device() in wrote()'s / wrote_live()'s place -> [source_done()] -> packets() / ogg() -> release(); the
     synchronous helpers are encode_tensors, encode_ogg_tensors, encode_live_tensors and encode_live_ogg_tensors.
-    fmt | FEED_NO_ARENA: a feed for such groups only, without pinned input arenas."""
+    fmt | FEED_NO_ARENA: a feed for such groups only, without pinned input arenas.
+
+    decoded=True (vamd_feed_create with VAMD_FEED_DECODED): every group also leaves, in device memory, the signal a listener
+    gets back from its packets -- bit for bit libvorbis' decoder's, aligned sample for sample with the input: decoded(slot)
+    beside packets(slot); roundtrip_tensors for device tensors in, (packets, decoded tensors) out."""
 
     def __init__(self, setup_blob, devices=None, lanes_per_device=2, max_streams=256, max_frames=131072, fmt=FEED_S16,
-                 write_frames=None, ogg_headers=None):
+                 write_frames=None, ogg_headers=None, decoded=False):
+        if decoded:
+            fmt |= FEED_DECODED
         self.L = load_library()
         blob = np.ascontiguousarray(setup_blob, dtype=np.uint8)
         devs = list(devices) if devices else []
@@ -1100,7 +1136,8 @@ class Feed:
             raise VamdError(r, "vamd_feed_create failed: " + (why or "setup without GPU-assembled packets, bad arguments, or a HIP failure"))
         self.h = h
         self.no_arena = bool(fmt & FEED_NO_ARENA)
-        fmt &= ~FEED_NO_ARENA
+        self.is_decoded = bool(fmt & FEED_DECODED)
+        fmt &= ~(FEED_NO_ARENA | FEED_DECODED)
         self._held = {}   # slot -> the tensors of its device-fed group, kept alive until the group has read them
         self.max_streams, self.max_frames, self.fmt = max_streams, max_frames, fmt
         self.dtype = np.int16 if fmt == FEED_S16 else np.float32
@@ -1323,6 +1360,29 @@ class Feed:
                 "bytes": view(r.bytes, C.c_uint8, int(r.total_bytes)), "total_bytes": int(r.total_bytes),
                 "upload_ms": r.upload_ms, "device_ms": r.device_ms, "total_ms": r.total_ms}
 
+    def decoded(self, slot, copy=True, with_status=False):
+        """Waits for the group and its decoded signal (vamd_feed_decoded).  -> per stream a float32 torch tensor (channels,
+        frames) on the lane's device: what libvorbis' decoder returns for the stream's packets.  A stream that lost a packet
+        has no frames.  copy=True: clones, which survive release(); else views of the lane's decoded arena, valid until
+        release().  with_status: -> (tensors, status), status[s] the STATUS_* that cost stream s its signal, or 0."""
+        import torch
+        r = _FeedDecodedResult()
+        self._check(self.L.vamd_feed_decoded(self.h, slot, C.byref(r)))
+        ns, ch = int(r.nstreams), int(r.channels)
+        frames = np.ctypeslib.as_array(C.cast(r.frames, C.POINTER(C.c_int64)), shape=(ns,)).copy()
+        offset = np.ctypeslib.as_array(C.cast(r.offset, C.POINTER(C.c_int64)), shape=(ns + 1,)).copy()
+        status = np.ctypeslib.as_array(C.cast(r.status, C.POINTER(C.c_uint8)), shape=(ns,)).copy()
+        dev = torch.device("cuda", self.device(slot))
+        total = int(r.total_floats)
+        arena = torch.as_tensor(_DeviceFloats(r.pcm, total), device=dev) if total else torch.empty(0, dtype=torch.float32, device=dev)
+        out = []
+        for s in range(ns):
+            v = arena[int(offset[s]):int(offset[s]) + ch * int(frames[s])].view(ch, int(frames[s]))
+            out.append(v.clone() if copy else v)
+        if copy:
+            torch.cuda.synchronize(dev)  # (the clones are done before release() lets the lane's next group at the arena)
+        return (out, status) if with_status else out
+
     def release(self, slot):
         self._check(self.L.vamd_feed_release(self.h, slot))
         self._held.pop(slot, None)
@@ -1347,6 +1407,18 @@ class Feed:
         finally:
             self._release_quietly(slot)
         return self._rows(r, r["nstreams"])
+
+    def roundtrip_tensors(self, source, frames=None, stream=None, layout="scf"):
+        """encode_tensors() of a decoded feed: -> (packets, decoded): per stream the list of (packet bytes, granulepos, W,
+        e_o_s), and per stream the decoded (channels, frames) tensor on the lane's device (decoded(), copy=True)."""
+        slot = self._slot_for(source, layout)
+        try:
+            self.wrote_device(slot, source, frames, stream, layout)
+            r = self.packets(slot)
+            dec = self.decoded(slot, copy=True)
+        finally:
+            self._release_quietly(slot)
+        return self._rows(r, r["nstreams"]), dec
 
     def encode_ogg_tensors(self, source, frames=None, serials=None, comments=None, stream=None, layout="scf"):
         """encode_ogg() of streams that are in DEVICE memory.  -> list[bytes], one Ogg Vorbis file per stream."""

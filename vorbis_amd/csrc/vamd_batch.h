@@ -146,6 +146,7 @@ struct BatchRun {
   ResBufs rb;
   float *couple_state;  // [units][4][ch][n2] or null (alloc_couple_state)
   bool make_ampmax;     // the block ampmax is formed by k_tone_seed (independent blocks at the psy level or above: no k_ampmax launch)
+  bool want_res;        // the residue search runs whether or not the caller takes its outputs (vamd_analyze_batch_synth)
 };
 
 // what a mode's setup may leave uncovered (vamd_bind.h)
@@ -199,8 +200,10 @@ static int alloc_couple_state(vamd_ctx *c, BatchRun *R) {
 
 // M: the run is bitrate-managed (the caller has checked it: check_managed), `io` then holds the shared tensors only
 static int prepare_run(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io, int level, BatchRun *R,
-                       const vamd_managed_io *M = nullptr) {
+                       const vamd_managed_io *M = nullptr, bool want_res = false) {
   memset(R, 0, sizeof(*R));
+  c->synth_src[desc->W].nb = -1;  // (the run's tensors replace the last run's)
+  R->want_res = want_res;
   int r;
   if (io && (io->res_class || io->res_entries || io->res_count)) {
     if (!(io->res_class && io->res_entries && io->res_count)) return fail(c, VAMD_EINVAL, "res_class / res_entries / res_count go together");
@@ -217,7 +220,7 @@ static int prepare_run(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batc
   R->units = M ? R->nb * VAMD_PACKETBLOBS : R->nb;
   if (R->nb == 0) return VAMD_OK;
   if ((r = plan(c, R->W, R->nb, io, level, &R->p))) return r;
-  if (io && level >= VAMD_LEVEL_FULL && (io->res_entries || io->packets) &&
+  if (io && level >= VAMD_LEVEL_FULL && (io->res_entries || io->packets || want_res) &&
       (r = res_bufs(c, R->W, R->units, io->res_class, io->res_entries, io->res_count, &R->rb)))
     return r;
   if (M) {  // the fifteen integer floor curves live in workspace only
@@ -556,16 +559,22 @@ static void launch_floor_on(vamd_ctx *c, BatchRun *R, int level) {
     prof_mark(c, VAMD_ST_FLOOR);
     launch_couple(c, R, s, VAMD_PACKETBLOBS / 2, 1, p.mdct, p.ilogmask, p.iwork, p.nonzero);
     prof_mark(c, VAMD_ST_COUPLE);
-    if (R->io && (R->io->res_entries || R->io->packets))
+    if (R->io && (R->io->res_entries || R->io->packets || R->want_res)) {
       launch_residue_pack(c, R, s, 1, p.posts, p.wrapped, p.post_valid, p.iwork, p.nonzero, rb, R->io->packets, R->io->packet_stride,
                           R->io->packet_bits);
+      vamd_ctx::SynthSrc &y = c->synth_src[W];
+      y.nb = R->nb, y.post_valid = p.post_valid, y.ilogmask = p.ilogmask;
+      y.res_class = rb.cls, y.res_entries = rb.entries, y.res_count = rb.count;
+    }
   }
 }
 
+static int launch_synth(vamd_ctx *c, int W, float *synth);
+
 static int run_batch(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io, int level, bool stream_mode,
-                     float *ampmax_state, const vamd_managed_io *M = nullptr) {
+                     float *ampmax_state, const vamd_managed_io *M = nullptr, float *synth = nullptr) {
   BatchRun R;
-  int r = prepare_run(c, desc, io, level, &R, M);
+  int r = prepare_run(c, desc, io, level, &R, M, synth != nullptr);
   if (r) return r;
   if (R.nb == 0) return VAMD_OK;
   const int ch = c->B.channels;
@@ -587,6 +596,7 @@ static int run_batch(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_
   launch_floor_on(c, &R, level);
   if (c->profile) c->prof_runs++;
   HIP_TRY(c, hipGetLastError());
+  if (synth && (r = launch_synth(c, R.W, synth))) return r;
   if (stream_mode) {
     // new state = ampmax_out of the last block
     HIP_TRY(c, hipMemcpyAsync(ampmax_state, R.p.ampglob + (R.nb - 1), sizeof(float), hipMemcpyDeviceToHost, s));
@@ -601,6 +611,82 @@ int vamd_analyze_batch(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batc
   if (r) return r;
   if (level < VAMD_LEVEL_TRANSFORM || level > VAMD_LEVEL_FULL) return fail(c, VAMD_EINVAL, "bad level");
   return run_batch(c, desc, io, level, false, nullptr);
+}
+
+// ---- the decoder's back half (k_synth.h): vb->pcm per block, the streams' decoded samples ----
+static size_t synth_lds_bytes(const vamd_ctx *c, int W) {
+  return synth_lds_words(c->B.channels, c->B.bs[W] / 2, c->B.channels, c->B.res_off_ints[W]) * 4;
+}
+// what k_synth needs of a size class's setup beyond the residue back-end: floors it can draw the decoder's way, and a
+// workgroup's LDS for the block's spectrum and a butterfly vector per channel
+static int synth_covered(vamd_ctx *c, int W, SynthFloorP *S) {
+  int r = res_covered(c, W);
+  if (r) return r;
+  const int ch = c->B.channels, n2 = c->B.bs[W] / 2;
+  if (!synth_floor_ranges(c->B.floor[W][0], c->B.floor[W][1], c->B.chmap[W].submaps, n2, S))
+    return fail(c, VAMD_EIMPL, "synthesis: a floor of more than two posts whose range is no power of two (a decoder rebuilds the range from its bit count, lib/floor1.c:160)");
+  if (synth_lds_bytes(c, W) > c->lds_per_block)
+    return fail(c, VAMD_EIMPL, "synthesis: a block's spectrum and butterfly vectors do not fit a workgroup's LDS");
+  return VAMD_OK;
+}
+// k_synth over the blocks the last run of size class W left (vamd_ctx::synth_src), on the context's stream
+static int launch_synth(vamd_ctx *c, int W, float *synth) {
+  SynthFloorP S;
+  int r = synth_covered(c, W, &S);
+  if (r) return r;
+  const vamd_ctx::SynthSrc &y = c->synth_src[W];
+  if (y.nb < 1) return VAMD_OK;
+  const int ch = c->B.channels, n2 = c->B.bs[W] / 2;
+  hipLaunchKernelGGL(k_synth, dim3((unsigned)y.nb), dim3(64 * ch), synth_lds_bytes(c, W), c->stream,
+                     c->B.xf[W], c->B.res[W][0], c->B.res[W][1], c->B.chmap[W], c->B.couple[W], S, ch, c->B.res_cap[W], c->B.res_off_ints[W],
+                     c->d_dbg ? c->d_dbg + 8 : nullptr, y.post_valid, y.ilogmask, y.res_class, y.res_entries, y.res_count, synth);
+  HIP_TRY(c, hipGetLastError());
+  return VAMD_OK;
+}
+
+int vamd_synth_check(vamd_ctx *c, int W) {
+  if (!c || (W != 0 && W != 1)) return VAMD_EINVAL;
+  SynthFloorP S;
+  return synth_covered(c, W, &S);
+}
+
+int vamd_analyze_batch_synth(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io, float *synth) {
+  DeviceGuard dev_guard(c);
+  int r = check_desc(c, desc, io);
+  if (r) return r;
+  SynthFloorP S;
+  if ((r = synth_covered(c, desc->W, &S))) return r;
+  if (!synth && desc->nblocks) return fail(c, VAMD_EINVAL, "null synth buffer");
+  if (!desc->nblocks) return run_batch(c, desc, io, VAMD_LEVEL_FULL, false, nullptr);
+  return run_batch(c, desc, io, VAMD_LEVEL_FULL, false, nullptr, nullptr, synth);
+}
+
+int vamd_synth_streams(vamd_ctx *c, const vamd_stream_plan *plan, long nstreams, long max_frames, const int64_t *frames,
+                       const int64_t *offset, float *scratch_short, float *scratch_long, float *pcm) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  if (!plan || nstreams < 1 || plan->nstreams != nstreams || max_frames < 1 || !frames || !offset || !pcm)
+    return fail(c, VAMD_EINVAL, "plan / max_frames / frames / offset / pcm");
+  float *scratch[2] = {scratch_short, scratch_long};
+  for (int W = 0; W < 2; W++) {
+    if (!plan->nblocks[W]) continue;
+    if (!scratch[W]) return fail(c, VAMD_EINVAL, "null scratch for a size class with blocks");
+    if (c->synth_src[W].nb != (long)plan->nblocks[W])
+      return fail(c, VAMD_EINVAL, "vamd_synth_streams: the context's last analysis is not the plan's (a VBR vamd_analyze_streams_mixed with packets or residue outputs)");
+    int r = launch_synth(c, W, scratch[W]);
+    if (r) return r;
+  }
+  LapP L;
+  L.ch = c->B.channels, L.bs0 = c->B.bs[0], L.bs1 = c->B.bs[1];
+  L.win0 = c->B.xf[0].win_short, L.win1 = c->B.xf[0].win_long;
+  L.order = plan->order, L.stream_start = (const long long *)plan->stream_start;
+  L.src0 = (const long long *)plan->src[0], L.src1 = (const long long *)plan->src[1];
+  L.synth0 = scratch_short, L.synth1 = scratch_long;
+  const long per_stream = (max_frames + 1023) / 1024;  // workgroups a stream: four frames a thread, at most 1024 of them (the kernel strides)
+  hipLaunchKernelGGL(k_lap, dim3((unsigned)(per_stream < 1024 ? per_stream : 1024), (unsigned)(nstreams < 1024 ? nstreams : 1024)), dim3(256), 0, c->stream, L, nstreams,
+                     (const long long *)frames, (const long long *)offset, pcm);
+  HIP_TRY(c, hipGetLastError());
+  return VAMD_OK;
 }
 
 // a bitrate-managed call's outputs, of size class W

@@ -51,6 +51,16 @@ struct vamd_ctx {
   size_t ev_used = 0;
   std::vector<int> ev_stage;  // per recorded event: the stage whose interval it closes (VAMD_ST_BEGIN = none)
   int prof_runs = 0;          // batches recorded since the last vamd_stage_ms()
+  // what the last VBR run of each size class left for k_synth (vamd_synth_streams): its blocks (-1: none) and where their
+  // floor flags, integer curves and residue rows are -- the caller's buffers or workspace, as the run had them
+  struct SynthSrc {
+    long nb = -1;
+    const int32_t *post_valid = nullptr;
+    const ilog_t *ilogmask = nullptr;
+    const int32_t *res_class = nullptr;
+    const uint16_t *res_entries = nullptr;
+    const int32_t *res_count = nullptr;
+  } synth_src[2];
 };
 
 // stage ids of vamd_stage_ms(); a mark closes the interval of the stage it names (VAMD_ST_BEGIN: opens one)
@@ -123,6 +133,7 @@ struct DeviceGuard {
 static int ws_get(vamd_ctx *c, int W, int which, size_t bytes, void **out) {
   DevBuf &b = c->ws[W][which];
   if (b.bytes < bytes) {
+    c->synth_src[W].nb = -1;  // (what the last run left for k_synth may have lived here)
     if (b.p) HIP_TRY(c, hipFree(b.p));
     b.p = nullptr;
     b.bytes = 0;

@@ -151,6 +151,14 @@ struct FeedLane {
   int src_dtype = 0;
   int64_t src_cstride = 0, src_fstride = 0;
   hipEvent_t ev_src = nullptr, ev_ingest = nullptr;
+  // a decoded feed (VAMD_FEED_DECODED): k_synth's scratch per size class, the decoded arena, the streams' [frames | offset]
+  // (d_dgeo: h_dgeo's copy); ev_dec: recorded behind the lap, what vamd_feed_decoded waits for; what it hands out
+  Buf d_synth[2], d_dec, d_dgeo;
+  Pinned h_dgeo;
+  hipEvent_t ev_dec = nullptr;
+  std::vector<int64_t> dec_frames, dec_offset;
+  std::vector<uint8_t> dec_status;
+  vamd_feed_decoded_result dec_result;
   std::thread worker;
   std::mutex *upload_turn = nullptr;  // its device's (vamd_feed::upload_turns)
   // the job (guarded by vamd_feed::m)
@@ -174,6 +182,7 @@ struct FeedLane {
     if (ev_end) (void)hipEventDestroy(ev_end);
     if (ev_src) (void)hipEventDestroy(ev_src);
     if (ev_ingest) (void)hipEventDestroy(ev_ingest);
+    if (ev_dec) (void)hipEventDestroy(ev_dec);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -188,6 +197,7 @@ struct vamd_feed {
   long max_streams = 0, max_frames = 0;
   int format = VAMD_FEED_S16;
   bool no_arena = false;            // VAMD_FEED_NO_ARENA: the lanes have no pinned input arena (device-fed groups only)
+  bool decoded = false;             // VAMD_FEED_DECODED: the decoded signal beside the packets (vamd_feed_decoded)
   int write_frames = 0;             // > 0: a live feed (vamd_feed_create_live), the reference's frames per write
   long live_cs = 0, row_stride = 0, retain = 0;  // its buffers' samples per channel, flag rows, the retention bound
   bool ogg = false;                 // an Ogg feed (vamd_feed_ogg_headers): files beside the packets
@@ -646,6 +656,49 @@ static int run_group_managed(vamd_feed *f, FeedLane &L, const vamd_stream_plan &
   return VAMD_OK;
 }
 
+// A decoded feed's group, behind its packets' hand-over: the streams' geometry up, k_synth per size class and the lap
+// (vamd_synth_streams: out of what the analysis left in the lane's context), ev_dec behind them.  Stream s takes
+// ch * frames[s] floats of the arena whether or not it gets a signal.
+static int enqueue_decoded(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, long ns) {
+  L.dec_frames.resize((size_t)ns), L.dec_offset.resize((size_t)ns + 1);
+  FEED_TRY(L.h_dgeo.need((size_t)ns * 16));
+  FEED_TRY(L.d_dgeo.need((size_t)ns * 16));
+  int64_t *h = (int64_t *)L.h_dgeo.p, at = 0;
+  for (long s = 0; s < ns; s++) {
+    const int64_t fr = L.frames_of.empty() ? L.frames : L.frames_of[(size_t)s];
+    h[s] = L.dec_frames[(size_t)s] = fr;
+    h[ns + s] = L.dec_offset[(size_t)s] = at;
+    at += fr * f->ch;
+  }
+  L.dec_offset[(size_t)ns] = at;
+  for (int W = 0; W < 2; W++) FEED_TRY(L.d_synth[W].need(((size_t)plan.nblocks[W] * f->ch * (size_t)f->bs[W] + 4) * 4));
+  FEED_TRY(L.d_dec.need(((size_t)at + 4) * 4));
+  FEED_TRY(hipMemcpyAsync(L.d_dgeo.p, h, (size_t)ns * 16, hipMemcpyHostToDevice, L.stream));
+  FEED_CALL(vamd_synth_streams(L.ctx, &plan, ns, L.frames, (const int64_t *)L.d_dgeo.p, (const int64_t *)L.d_dgeo.p + ns,
+                               plan.nblocks[0] ? (float *)L.d_synth[0].p : nullptr, plan.nblocks[1] ? (float *)L.d_synth[1].p : nullptr,
+                               (float *)L.d_dec.p));
+  FEED_TRY(hipEventRecord(L.ev_dec, L.stream));
+  return VAMD_OK;
+}
+
+// ... and what vamd_feed_decoded hands out, once the group's record is home: a stream that lost a packet has no signal
+static void decoded_result(vamd_feed *f, FeedLane &L, long ns) {
+  L.dec_status.assign((size_t)ns, 0);
+  const vamd_feed_result &r = L.result;
+  for (long s = 0; s < ns; s++) {
+    for (int64_t k = r.stream_start[s]; k < r.stream_start[s + 1]; k++)
+      if (r.bits[k] < 0) {  // no packet, no signal -- whatever the block's status bits say
+        L.dec_status[(size_t)s] = (uint8_t)((r.info[k] >> 2) & 3);
+        L.dec_frames[(size_t)s] = 0;
+        break;
+      }
+  }
+  vamd_feed_decoded_result &o = L.dec_result;
+  o.nstreams = ns, o.channels = f->ch;
+  o.frames = L.dec_frames.data(), o.offset = L.dec_offset.data(), o.status = L.dec_status.data();
+  o.pcm = (const float *)L.d_dec.p, o.total_floats = L.dec_offset[(size_t)ns];
+}
+
 // a group from its plan on (whole or live): the analysis, the packets end to end into the pinned arena
 static int finish_group(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan, const float *pcm, long ns, long ss, long cs,
                         const long long *d_frames_of, FeedLive live, long ns_out) {
@@ -690,11 +743,15 @@ static int finish_group(vamd_feed *f, FeedLane &L, const vamd_stream_plan &plan,
     FEED_TRY(hipGetLastError());
     if (f->ogg) FEED_OWN(run_pager(f, L, plan.stream_start, ns, nb, (const int64_t *)L.d_soff.p + ns));
     FEED_TRY(hipEventRecord(L.ev_end, st));
+    // (the decoded signal is enqueued behind the hand-over's event and ahead of the wait for it: the packets are ready no
+    // later than without it, and the lane's stream goes on while the host looks at them)
+    if (f->decoded && !attempt) FEED_OWN(enqueue_decoded(f, L, plan, ns));
     FEED_TRY(hipEventSynchronize(L.ev_end));
     const int64_t total = *(const int64_t *)L.h_rec.p;
     if (total <= (int64_t)L.h_out.bytes) {
       if (f->ogg) FEED_OWN(pager_result(f, L, ns, ns_out));
       feed_result(L, R, ns_out, nb, total);
+      if (f->decoded) decoded_result(f, L, ns);
       return VAMD_OK;
     }
     if (attempt) {
@@ -1029,8 +1086,8 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
                        int lanes_per_device, long max_streams, long max_frames, int format, int write_frames) {
   if (!out) return VAMD_EINVAL;
   *out = nullptr;
-  const bool no_arena = (format & VAMD_FEED_NO_ARENA) != 0;
-  format &= ~VAMD_FEED_NO_ARENA;
+  const bool no_arena = (format & VAMD_FEED_NO_ARENA) != 0, decoded = (format & VAMD_FEED_DECODED) != 0;
+  format &= ~(VAMD_FEED_NO_ARENA | VAMD_FEED_DECODED);
   if (!setup_blob || lanes_per_device < 1 || lanes_per_device > 8 || max_streams < 1 || max_frames < 1 || ndevices < 0 ||
       ndevices > 64 || (ndevices > 0 && !devices) || (format != VAMD_FEED_S16 && format != VAMD_FEED_F32) || write_frames < 0)
     return VAMD_EINVAL;
@@ -1044,6 +1101,16 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
     feed_create_err = "bitrate-managed setup blob without the bitrate manager's section (packed before it existed): repack it with vamd_pack_setup";
     return VAMD_EIMPL;
   }
+  // the decoded signal: not of a live feed (the overlap would have to be carried between groups), not of a managed one (the
+  // manager may cut the chosen packet, and a decoder that runs out of bits stops in mid-residue)
+  if (decoded && write_frames) {
+    feed_create_err = "VAMD_FEED_DECODED: a live feed has no decoded signal (whole-stream feeds only)";
+    return VAMD_EIMPL;
+  }
+  if (decoded && h.managed) {
+    feed_create_err = "VAMD_FEED_DECODED: a bitrate-managed setup has no decoded signal (the manager may cut a packet short of its residue)";
+    return VAMD_EIMPL;
+  }
   int cur = 0;
   if (hipGetDevice(&cur) != hipSuccess) return VAMD_EFAULT;
   std::vector<int> devs;
@@ -1051,7 +1118,7 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
   for (int i = 0; i < ndevices; i++) devs.push_back(devices[i] >= 0 ? devices[i] : cur);
   vamd_feed *f = new vamd_feed;
   f->max_streams = max_streams, f->max_frames = max_frames, f->format = format, f->write_frames = write_frames;
-  f->no_arena = no_arena;
+  f->no_arena = no_arena, f->decoded = decoded;
   f->managed = h.managed && h.off_bitrate;
   f->rate = h.rate;
   {
@@ -1076,11 +1143,18 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
     if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev_end, hipEventBlockingSync);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev_src, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&L.ev_ingest, hipEventDisableTiming | hipEventBlockingSync);
+    if (e == hipSuccess && decoded) e = hipEventCreateWithFlags(&L.ev_dec, hipEventDisableTiming | hipEventBlockingSync);
     if (e == hipSuccess && vamd_set_stream(L.ctx, L.stream) != VAMD_OK) e = hipErrorUnknown;
     if (e == hipSuccess && l == 0) {
       f->ch = vamd_channels(L.ctx);
       for (int W = 0; W < 2; W++) f->bs[W] = vamd_blocksize(L.ctx, W), f->pkcap[W] = vamd_packet_capacity(L.ctx, W);
       if (f->pkcap[0] <= 0 || f->pkcap[1] <= 0) r = VAMD_EIMPL;  // packets of this mode are not assembled on the GPU
+      for (int W = 0; W < 2 && !r && decoded; W++) {  // ... or its blocks not synthesised
+        if (vamd_synth_check(L.ctx, W) != VAMD_OK) {
+          feed_create_err = std::string("VAMD_FEED_DECODED: ") + vamd_last_error(L.ctx);
+          r = VAMD_EIMPL;
+        }
+      }
       if (!r && write_frames) {
         const char *why = vamd_live_check(L.ctx, write_frames, max_frames);
         if (why) {
@@ -1111,6 +1185,11 @@ static int feed_create(vamd_feed **out, const void *setup_blob, size_t blob_byte
     if (e == hipSuccess && !r && !no_arena) e = L.h_in.need(in_cap);
     const size_t out_cap = f->out_bytes ? (size_t)f->out_bytes : (size_t)max_streams * max_frames * f->ch + (size_t)max_streams * 65536;
     if (e == hipSuccess && !r) e = L.h_out.need(al(out_cap, 4096));
+    if (decoded && !r) {  // the decoded arena, and k_synth's scratch for a group of long blocks (half overlapped: twice its samples)
+      const size_t group = (size_t)max_streams * max_frames * f->ch;
+      if (e == hipSuccess) e = L.d_dec.need((group + 4) * 4);
+      if (e == hipSuccess) e = L.d_synth[1].need((2 * group + (size_t)max_streams * 4 * f->bs[1] * f->ch) * 4);
+    }
     if (e != hipSuccess) r = VAMD_EFAULT;
   }
   (void)hipSetDevice(cur);
@@ -1172,6 +1251,7 @@ static int queue_group(vamd_feed *f, FeedLane &L, long nstreams, long frames, bo
   L.src_dev = src_dev, L.ingest_queued = L.ingest_recorded = false;
   L.status = 0;
   memset(&L.result, 0, sizeof(L.result));
+  memset(&L.dec_result, 0, sizeof(L.dec_result));
   ogg_job(f, L, nstreams);
   L.t_wrote = now_s();
   L.state = LANE_QUEUED;
@@ -1587,6 +1667,29 @@ int vamd_feed_wrote_live(vamd_feed *f, int slot, long nstreams, const int64_t *f
 }
 
 int vamd_feed_packets(vamd_feed *f, int slot, vamd_feed_result *out) { return await_group(f, slot, &FeedLane::result, out, false); }
+
+int vamd_feed_decoded(vamd_feed *f, int slot, vamd_feed_decoded_result *out) {
+  if (!f || !out || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;
+  memset(out, 0, sizeof(*out));
+  if (!f->decoded) {
+    std::lock_guard<std::mutex> g(f->m);
+    f->err = "vamd_feed_decoded: the feed was not created with VAMD_FEED_DECODED";
+    return VAMD_EINVAL;
+  }
+  const int r = await_group(f, slot, &FeedLane::dec_result, out, false);
+  if (r) {
+    memset(out, 0, sizeof(*out));
+    return r;
+  }
+  FeedLane &L = f->lanes[(size_t)slot];
+  if (hipEventSynchronize(L.ev_dec) != hipSuccess) {
+    std::lock_guard<std::mutex> g(f->m);
+    f->err = "vamd_feed_decoded: the decoded signal's kernels failed";
+    memset(out, 0, sizeof(*out));
+    return VAMD_EFAULT;
+  }
+  return VAMD_OK;
+}
 
 int vamd_feed_release(vamd_feed *f, int slot) {
   if (!f || slot < 0 || slot >= (int)f->lanes.size()) return VAMD_EINVAL;

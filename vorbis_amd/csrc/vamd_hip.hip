@@ -39,6 +39,7 @@
 #include "k_blockout.h"
 #include "k_lpc.h"
 #include "k_bitrate.h"
+#include "k_synth.h"
 
 using namespace vamd;
 
@@ -101,6 +102,7 @@ int vamd_create_abi(vamd_ctx **out, const void *setup_blob, size_t blob_bytes, i
                             (int)c->lds_per_block);
       VAMD_OPT_IN(0) VAMD_OPT_IN(8) VAMD_OPT_IN(9) VAMD_OPT_IN(10) VAMD_OPT_IN(11) VAMD_OPT_IN(12)
 #undef VAMD_OPT_IN
+      (void)hipFuncSetAttribute((const void *)k_synth, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block);
       (void)hipGetLastError();
       if (c->K.verbose)
         fprintf(stderr, "vamd_create: %d CUs, %zu B LDS per workgroup\n", c->num_cus, c->lds_per_block);

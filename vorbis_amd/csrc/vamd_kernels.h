@@ -1651,3 +1651,42 @@ __global__ void k_gather_blocks(int ch, int n, long nb, const long long *__restr
 __global__ __launch_bounds__(256) void k_calib_copy(const F4 *__restrict__ src, F4 *__restrict__ dst, long n16) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x) dst[i] = src[i];
 }
+
+// ---- the decoder's back half (k_synth.h) ----
+// One workgroup per block, a wave per channel: vb->pcm [ch][n] of the block's packet out of the batch's own tensors.
+//   ent_row = the row length of res_entries (vamd_residue_capacity); off_ints = Bound::res_off_ints of the size class
+//   dbg = the phase stopwatch's slots (null = off): the upper half of the transform stage's row, marks as synth_block names them
+__global__ __launch_bounds__(64 * VAMD_MAX_CH) void k_synth(XformP X, ResP R0, ResP R1, ChMap cm, CoupleP C, SynthFloorP S, int ch, int ent_row,
+                                                          int off_ints, unsigned long long *dbg, const int *__restrict__ post_valid,
+                                                          const ilog_t *__restrict__ ilogmask, const int *__restrict__ res_class,
+                                                          const unsigned short *__restrict__ res_entries,
+                                                          const int *__restrict__ res_count, float *__restrict__ synth) {
+  const long u = blockIdx.x;
+  const int n = X.n, n2 = n >> 1;
+  PhaseClock pc;
+  pc.start(dbg);
+  synth_block(X, R0, R1, cm, C, S, ch, off_ints, post_valid + u * ch, ilogmask + u * ch * n2,
+              res_class + u * (cm.submaps * VAMD_RES_CLASS_STRIDE), res_entries + u * (long)ent_row, res_count + u * cm.submaps * 2,
+              (float *)vamd_smem, synth + u * ch * n, pc);
+  pc.flush();
+}
+
+// The streams' decoded samples out of their blocks' vb->pcm: a thread per four consecutive frames (one search for the
+// block pair of the first, a step along order[] where a later one lies past the pair's end), all channels.  frames[s] frames of stream
+// s, channel c at out + offset[s] + c * frames[s]; never more than its blocks' centres span.
+__global__ __launch_bounds__(256) void k_lap(LapP L, long nstreams, const long long *__restrict__ frames,
+                                             const long long *__restrict__ offset, float *__restrict__ out) {
+  for (long s = blockIdx.y; s < nstreams; s += gridDim.y) {
+    const long long k0 = L.stream_start[s], k1 = L.stream_start[s + 1], F = frames[s];
+    if (k1 - k0 < 2) continue;
+    const long long first = lap_centre(L, k0), span = lap_centre(L, k1 - 1) - first;
+    const long long count = F < span ? F : span;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; 4 * q < count; q += (long long)gridDim.x * blockDim.x) {
+      long long k = lap_find(L, k0, k1, first + 4 * q), end = lap_centre(L, k);
+      for (long long t = 4 * q; t < 4 * q + 4 && t < count; t++) {
+        while (first + t >= end && k < k1 - 1) end = lap_centre(L, ++k);
+        for (int c = 0; c < L.ch; c++) out[offset[s] + c * F + t] = lap_sample(L, k, first + t, c);
+      }
+    }
+  }
+}
