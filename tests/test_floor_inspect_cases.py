@@ -1,0 +1,33 @@
+"""CPU: inspect_error_wave (k_floor.inc) on crafted ranges against a serial restatement of inspect_error.
+
+tests/c/floor_inspect_cases.cpp, a program of its own built with -fsanitize=address,undefined against the one-lane
+vocabulary (tests/emul): ranges of 1, 2, 63, 64, 65, 128 and 1024 points; ascending, flat and descending lines; the only
+failing point at the first, the last and an interior place of every chunk of 64; candidate points that must not count
+(class bit clear; a zero past the first point) and the zero first point that must; no failing point with the squared
+error one below, at and one above (floor(maxerr) + 1) * cnt; the count thresholds against a large error; the integer and
+the float form of the point tests.  Each range is a heap block of exactly the points visited, so a read past either end
+is the sanitizer's to report.
+
+This pins the logic of the walk that ends at the first failing chunk (VAMD_FL_INSPECT_STOP) and of the walk it
+replaces; a chunk is one point in this build.  The 64-lane and the half-wave forms are tests/test_floor_split_gpu.py's.
+"""
+import os
+import subprocess
+
+import pytest
+
+from tests import checker
+
+ROOT = checker.ROOT
+
+
+@pytest.mark.parametrize("stop", [1, 0])
+def test_inspect_error_wave_against_the_serial_walk(tmp_path, stop):
+    exe = str(tmp_path / "floor_inspect_cases")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-ffp-contract=off", "-Wno-unknown-pragmas", "-DVAMD_FL_INSPECT_STOP=%d" % stop,
+                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"),
+                           "-I" + os.path.join(ROOT, "tests", "emul"),
+                           os.path.join(ROOT, "tests", "c", "floor_inspect_cases.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith(": ok"), r.stdout[-4000:] + r.stderr[-4000:]

@@ -49,12 +49,34 @@ namespace vamd {
 #else
 #define VAMD_FL_SEG_LOOP _Pragma("unroll 4")
 #endif
+// ---- round 19: the greedy split loop of floor1_fit (profiles/r19_floor_split.txt; -D...=0 restores the earlier code) ---
+//   * VAMD_FL_INSPECT_STOP: inspect_error_wave asks after every chunk of NLANES points whether a point of it failed the
+//     over / under test and returns 1 there, as the reference's inspect_error does at the point itself
+//     (lib/floor1.c:537-538); it used to walk the whole range and ask once.  A call without a failing point runs every
+//     trip and reaches the count thresholds and the mse sum as before.
+//   * VAMD_FL_FIT_LANES (off): fit_line_pair's two fp64 quotients of a side, aa and bb, formed side by side in two lanes --
+//     one division expansion a call where every lane of a group evaluates both -- and handed over with one DPP shift per
+//     word before rint(aa + bb * x).  The same IEEE divisions on the same operands, and the same results on the GPU; the
+//     stage gained 0.018 ms with it alone, inside three spreads of the parent, and nothing beside the early stop, so it
+//     stays at 0 with its figures in the profile file.
+// Which lane evaluates an expression and how many trips run after the outcome is settled: no expression changes.
+#ifndef VAMD_FL_INSPECT_STOP
+#define VAMD_FL_INSPECT_STOP 1
+#endif
+#ifndef VAMD_FL_FIT_LANES
+#define VAMD_FL_FIT_LANES 0
+#endif
 // scratch builds for the phase profile (tools/fl_phases_pmc.sh): -DVAMD_COUNT_CALLS turns the stopwatch's slots into event
-// counters -- slot 0 inspect_error_wave calls, slot 1 fit_line_pair calls of the split loop, summed over the waves
+// counters, summed over the waves -- slot 0 inspect_error_wave calls, slot 1 fit_line_pair calls of the split loop (= calls
+// that return 1), slot 2 chunks of NLANES points walked by inspect_error_wave, slot 3 its returns of 1 on the point test,
+// slot 4 its returns of 0 on the count thresholds, slot 5 split-loop trips that end at the memo test, slot 6 the sum of
+// `most` over the split loop's fit_line_pair calls (tools/fl_calls.py)
 #if VAMD_GPU && defined(VAMD_COUNT_CALLS)
 #define VAMD_FL_COUNT(pc, k) ((pc).acc[(k)] += 1)
+#define VAMD_FL_COUNT_N(pc, k, n) ((pc).acc[(k)] += (unsigned int)(n))
 #else
 #define VAMD_FL_COUNT(pc, k) ((void)0)
+#define VAMD_FL_COUNT_N(pc, k, n) ((void)0)
 #endif
 
 #include "k_floor.inc"

@@ -237,8 +237,15 @@ VAMD_DEV LineStep line_step(int x0, int x1, int y0, int y1, const unsigned int *
 }
 VAMD_DEV int line_y(const LineStep &s, int y0, int k) { return y0 + s.sgn * div_magic(mad24(k, s.ady, 0), s.magic); }
 
-// inspect_error, lib/floor1.c:516-565, wave-parallel over x in [x0, x1)
-VAMD_DEV int inspect_error_wave(int x0, int x1, int y0, int y1, const unsigned short *qc, const FloorP &F) {
+// inspect_error, lib/floor1.c:516-565, wave-parallel over x in [x0, x1).  The reference returns 1 AT the first point that
+// fails the over / under test (:537-538); here the points go by in chunks of NLANES, and the walk ends with the chunk that
+// holds a failing one (VAMD_FL_INSPECT_STOP, k_floor.h).  The whole chunks come first: every lane of the wave (of the
+// half, in the pair form: a half that stops sits out the other's remaining trips) has a point in them, so the question is
+// asked with all of them active, of a lane mask the compares leave in scalar registers -- a scalar compare and branch a
+// trip.  The lanes that have a point in the rest of the range take it last, and the question is asked once more, where
+// they meet the others again.
+VAMD_DEV int inspect_error_wave(int x0, int x1, int y0, int y1, const unsigned short *qc, const FloorP &F, PhaseClock &pc) {
+  (void)pc;
   LineStep s;  // (line_step with wave-uniform operands)
   s.ady = y1 < y0 ? y0 - y1 : y1 - y0;
   s.sgn = y1 < y0 ? -1 : 1;
@@ -246,6 +253,9 @@ VAMD_DEV int inspect_error_wave(int x0, int x1, int y0, int y1, const unsigned s
   const int cnt = (x1 - x0) > 1 ? (x1 - x0) : 1;  // points visited: x0, then x0+1 .. x1-1
   int mse = 0;
   bool bad = false;
+#if !VAMD_FL_INSPECT_STOP
+  VAMD_FL_COUNT_N(pc, 2, (cnt + NLANES - 1) / NLANES);
+#endif
   if (F.int_tests) {
     // The two tests in integers (floor_derive_tests), as one range check on d = val - y: the point is bad when d is
     // outside (-under_i, over_i).  They apply to a point of class a (bit 15 of qc: mdct + twofitatten >= mask) that
@@ -256,6 +266,34 @@ VAMD_DEV int inspect_error_wave(int x0, int x1, int y0, int y1, const unsigned s
     unsigned int first = LANE == 0 ? 1u : 0u;
     int nsgn = -s.sgn;
     keep_opaque(nsgn);  // (a known +-1 would turn the multiply-add into negate + select)
+#if VAMD_FL_INSPECT_STOP
+    // point k: its squared error into mse; whether it is one the tests apply to, and whether it lies outside them
+    const auto point = [&](int k, bool &applies, bool &outside) {
+      const int q = div_magic(mad24(k, s.ady, 0), s.magic);
+      const unsigned int qv = qc[x0 + k];
+      const int d = mad24(q, nsgn, (int)(qv & 0x7fffu) - y0);  // val - y
+      mse = mad24(d, d, mse);
+      applies = (qv | first) > 0x8000u;
+      outside = (unsigned int)(d + bias) >= span;
+      first = 0;
+    };
+    int k0 = 0;
+    for (; k0 + NLANES <= cnt; k0 += NLANES) {  // the whole chunks
+      bool applies, outside;
+      point(k0 + LANE, applies, outside);
+      VAMD_FL_COUNT(pc, 2);
+      if (wave_flags_any(wave_flags(applies) & wave_flags(outside))) {
+        VAMD_FL_COUNT(pc, 3);
+        return 1;
+      }
+    }
+    if (k0 < cnt) VAMD_FL_COUNT(pc, 2);
+    if (LANE < cnt - k0) {  // the rest of the range
+      bool applies, outside;
+      point(k0 + LANE, applies, outside);
+      bad = applies && outside;
+    }
+#else
     for (int k = LANE; k < cnt; k += NLANES) {
       const int q = div_magic(mad24(k, s.ady, 0), s.magic);
       const unsigned int qv = qc[x0 + k];
@@ -264,8 +302,9 @@ VAMD_DEV int inspect_error_wave(int x0, int x1, int y0, int y1, const unsigned s
       bad = bad || (((qv | first) > 0x8000u) && ((unsigned int)(d + bias) >= span));
       first = 0;
     }
+#endif
   } else {
-    WAVE_FOR(k, cnt) {
+    const auto point = [&](int k) {
       const int x = x0 + k;
       const int y = line_y(s, y0, k);
       const int qv = qc[x];
@@ -275,11 +314,32 @@ VAMD_DEV int inspect_error_wave(int x0, int x1, int y0, int y1, const unsigned s
         if ((float)y + F.maxover < (float)val) bad = true;
         if ((float)y - F.maxunder > (float)val) bad = true;
       }
+    };
+#if VAMD_FL_INSPECT_STOP
+    int k0 = 0;
+    for (; k0 + NLANES <= cnt; k0 += NLANES) {  // the whole chunks
+      point(k0 + LANE);
+      VAMD_FL_COUNT(pc, 2);
+      if (wave_any(bad)) {
+        VAMD_FL_COUNT(pc, 3);
+        return 1;
+      }
     }
+    if (k0 < cnt) VAMD_FL_COUNT(pc, 2);
+    if (LANE < cnt - k0) point(k0 + LANE);  // the rest of the range
+#else
+    WAVE_FOR(k, cnt) point(k);
+#endif
   }
-  if (wave_any(bad)) return 1;
+  if (wave_any(bad)) {
+    VAMD_FL_COUNT(pc, 3);
+    return 1;
+  }
   // maxover^2 / cnt > maxerr, maxunder^2 / cnt > maxerr (:556-557), as thresholds on cnt (floor_derive_tests)
-  if (cnt <= F.cnt_over || cnt <= F.cnt_under) return 0;
+  if (cnt <= F.cnt_over || cnt <= F.cnt_under) {
+    VAMD_FL_COUNT(pc, 4);
+    return 0;
+  }
   mse = wave_sum(mse);
   // (float)(mse / cnt) > maxerr, without the integer divide: the quotient q is an integer, so for
   // maxerr >= 0 the test is q >= floor(maxerr) + 1, i.e. mse >= (floor(maxerr) + 1) * cnt.  (q >= 2^24,
@@ -377,6 +437,44 @@ VAMD_DEV void fit_line_pair(const double *term, double *sums, int firstL, int fi
     sums[grp * 8 + q] = acc;
   }
   WAVE_SYNC();
+#if VAMD_FL_FIT_LANES
+  // The two quotients of a side in two lanes: the odd lanes of a group form aa = (yb*x2b - xyb*xb) / denom, the even lanes
+  // bb = (bn*xyb - xb*yb) / denom -- each picks its four operands out of the side's row by index, so the wave issues ONE
+  // division expansion -- and lane 1 (9) takes bb over from lane 0 (8) with a DPP shift per word.  The sides' results are
+  // then lane 1's and lane 9's.
+  const double *row = sums + grp * 8;
+  const bool odd = (LANE & 1) != 0;
+  const double xb = row[0], x2b = row[2], bn = row[4];
+  const double p = row[odd ? 1 : 4], q2 = row[odd ? 2 : 3], r2 = row[odd ? 3 : 0], s2 = row[odd ? 0 : 1];
+  const int x0 = grp ? x0R : x0L, x1 = grp ? x1R : x1L;
+  const double denom = (bn * x2b - xb * xb);
+  double quot = 0.;
+  if (denom > 0.) quot = (p * q2 - r2 * s2) / denom;
+  long long qbits;
+  memcpy(&qbits, &quot, 8);
+  const unsigned int blo = (unsigned int)wave_shift_up1((int)(unsigned int)qbits, 0);
+  const unsigned int bhi = (unsigned int)wave_shift_up1((int)(unsigned int)((unsigned long long)qbits >> 32), 0);
+  const long long bbits = (long long)(((unsigned long long)bhi << 32) | blo);
+  int r = 1, y0 = 0, y1 = 0;
+  if (denom > 0.) {
+    const double aa = quot;  // (an odd lane's)
+    double bb;               // (the even lane's below it)
+    memcpy(&bb, &bbits, 8);
+    y0 = (int)rint(aa + bb * x0);
+    y1 = (int)rint(aa + bb * x1);
+    if (y0 > 1023) y0 = 1023;
+    if (y1 > 1023) y1 = 1023;
+    if (y0 < 0) y0 = 0;
+    if (y1 < 0) y1 = 0;
+    r = 0;
+  }
+  *ret0 = wave_read(r, 1);
+  *ly0 = wave_read(y0, 1);
+  *ly1 = wave_read(y1, 1);
+  *ret1 = wave_read(r, 9);
+  *hy0 = wave_read(y0, 9);
+  *hy1 = wave_read(y1, 9);
+#else
   const double xb = sums[grp * 8], yb = sums[grp * 8 + 1], x2b = sums[grp * 8 + 2], xyb = sums[grp * 8 + 3],
                bn = sums[grp * 8 + 4];
   const int x0 = grp ? x0R : x0L, x1 = grp ? x1R : x1L;
@@ -399,6 +497,7 @@ VAMD_DEV void fit_line_pair(const double *term, double *sums, int firstL, int fi
   *ret1 = wave_read(r, 8);
   *hy0 = wave_read(y0, 8);
   *hy1 = wave_read(y1, 8);
+#endif
   WAVE_SYNC();  // sums[] is rewritten by the next split
 }
 
@@ -537,10 +636,11 @@ VAMD_DEV int floor_fit_posts(const FloorP &F, const unsigned short *qc, FloorScr
       const int hy = post_Y(fitA, fitB, hn);
       // (ly == -1 || hy == -1 => exit(1) in the reference: unreachable, fits are >= 0 or -200)
       VAMD_FL_COUNT(pc, 0);  // (scratch builds: inspect_error / fit_line_pair calls per block)
-      if (inspect_error_wave(lx, hx, ly, hy, qc, F)) {
+      if (inspect_error_wave(lx, hx, ly, hy, qc, F, pc)) {
         VAMD_FL_COUNT(pc, 1);
         int ly0 = -200, ly1 = -200, hy0 = -200, hy1 = -200;
         int ret0, ret1;
+        VAMD_FL_COUNT_N(pc, 6, sortpos - lsortpos > hsortpos - sortpos ? sortpos - lsortpos : hsortpos - sortpos);
         fit_line_pair((const double *)sc->acc, sc->pair_sums, lsortpos, sortpos - lsortpos, sorted_index.get(lsortpos),
                       sorted_index.get(sortpos), sortpos, hsortpos - sortpos, sorted_index.get(sortpos),
                       sorted_index.get(hsortpos), &ret0, &ly0, &ly1, &ret1, &hy0, &hy1);
@@ -571,6 +671,8 @@ VAMD_DEV int floor_fit_posts(const FloorP &F, const unsigned short *qc, FloorScr
         fitA.set(i, -200);
         fitB.set(i, -200);
       }
+    } else {
+      VAMD_FL_COUNT(pc, 5);
     }
   }
 

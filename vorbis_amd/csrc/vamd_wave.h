@@ -113,6 +113,11 @@ VAMD_DEV int wave_scan_sum(int v) {  // inclusive prefix sum over the lanes
   return v;
 }
 VAMD_DEV int wave_any(int pred) { return __any(pred); }
+// a condition as a lane mask in scalar registers, straight out of the compare that forms it, and the question whether a
+// mask gathered from such has a lane of this wave in it: a scalar compare (wave_any's int is made in a vector register
+// and compared there).  Lanes that are not active leave their bits clear.
+VAMD_DEV unsigned long long wave_flags(bool pred) { return __builtin_amdgcn_ballot_w64(pred); }
+VAMD_DEV bool wave_flags_any(unsigned long long m) { return m != 0ull; }
 // the lanes for which `pred` holds, bit l = lane l; a value of lane `lane` (wave-uniform index: one v_readlane); a value
 // of a lane of each lane's own choosing (ds_bpermute)
 VAMD_DEV unsigned long long wave_ballot(bool pred) { return __ballot(pred); }
@@ -254,6 +259,7 @@ VAMD_DEV void keep_opaque(int &v) { asm volatile("" : "+s"(v)); }
 #else
 #define VAMD_GPU 0
 #include "vamd_wave_host.h"  // the one-lane test vocabulary: tests/emul only, see the note at the top
+#include "vamd_wave_flags_host.h"
 #endif
 
 namespace vamd {

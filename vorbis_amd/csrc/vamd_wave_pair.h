@@ -68,6 +68,9 @@ VAMD_DEV unsigned long long wave_ballot(bool pred) {  // bit l = lane l of this 
   return VAMD_PAIR_HALF ? (b >> 32) : (b & 0xffffffffull);
 }
 VAMD_DEV int wave_any(int pred) { return wave_ballot(pred != 0) != 0ull; }
+// (wave_flags keeps the lanes' places in the wave; each half asks about its own word)
+VAMD_DEV unsigned long long wave_flags(bool pred) { return __builtin_amdgcn_ballot_w64(pred); }
+VAMD_DEV bool wave_flags_any(unsigned long long m) { return (VAMD_PAIR_HALF ? (unsigned int)(m >> 32) : (unsigned int)m) != 0u; }
 VAMD_DEV unsigned long long wave_or64(unsigned long long x) {  // (posts <= 32: the low word holds everything the floor ors)
   int lo = (int)(unsigned int)x, hi = (int)(unsigned int)(x >> 32);
   VAMD_DPP_SCAN32_SELF(lo, VAMD_OP_OR)
