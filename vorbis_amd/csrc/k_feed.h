@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include "vorbis_amd.h"
 #include "k_feed_src.h"
+#include "vamd_feed_host.h"
 
 namespace vamd {
 
@@ -58,18 +59,7 @@ __global__ void k_feed_ingest(const T *__restrict__ in, int ch, long nstreams, l
 }
 
 // ---- the live feed (vamd_feed_create_live): continuing streams, their state on the device between groups ----
-// A live lane keeps every stream in one of two buffers [stream][channel][cs], swapped each group: a stream's samples from
-// where the reference's buffer begins (walk_rebase) on, then the group's piece, then zeroes (the end-of-stream padding's
-// room and the detector's reads).  Per stream and group, built by the lane's host mirror:
-struct LiveIn {
-  int64_t first, frames;  // the piece: its first frame in the arena, its frames
-  int64_t keep, shift;    // samples carried over from the other buffer, taken from sample `shift` of it on
-  int64_t origin;         // the stream's position (head room included) of buffer sample 0: granule positions go on from it
-  int64_t eof;            // a closing stream: its end in buffer coordinates; else LIVE_OPEN
-  int32_t fresh, close;   // the stream starts / ends in this group
-};
-#define LIVE_OPEN (1LL << 60)
-#define LIVE_NO_NAN (~0ull)
+// (LiveIn, LIVE_OPEN, LIVE_NO_NAN: vamd_feed_host.h, beside the host mirror that builds them)
 
 // a fresh stream's states: the detector's (all zero), the ampmax chain's, the bitrate manager's (a copy of `tmpl`), no
 // non-finite sample yet.  A stream that goes on keeps all of them.
