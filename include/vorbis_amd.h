@@ -100,6 +100,14 @@ int vamd_stage_ms(vamd_ctx *ctx, float *ms, int nstages, int *runs);
  * the slots accumulated so far are copied out first. */
 int vamd_debug_cycles(vamd_ctx *ctx, int enable, unsigned long long *out80);
 
+/* Test aid (no libvorbis counterpart): what the last batch of size class W at the masking level or above left of the tone
+ * chain's first two steps, copied to host memory after the stream has drained -- for each of the first `channel_blocks`
+ * channel-blocks the seed lines seed_chase walks (`seed`, rows of *row_lines floats of which *lines are lines), the lines
+ * that survive the walk (`surv`, rows of *row_lines, ascending) and their number (`nsurv`).  Any of the three may be NULL;
+ * with all three NULL only the two sizes are returned.  OV_EINVAL if no such batch has run or it was smaller. */
+int vamd_debug_survivors(vamd_ctx *ctx, int W, long channel_blocks, float *seed, uint16_t *surv, int32_t *nsurv,
+                         int32_t *row_lines, int32_t *lines);
+
 /* Measurement aid (no libvorbis counterpart): the shader clock while the chip is busy.  While `acc3` (device memory,
  * three 64-bit words zeroed by the caller) is set, every batch of more than a few thousand blocks at the masking level
  * or above has the first wave of its tone stack walk -- which runs beside the noise mask, the path's longest stage --

@@ -20,7 +20,7 @@ BLOCKTYPE_IMPULSE, BLOCKTYPE_PADDING, BLOCKTYPE_TRANSITION, BLOCKTYPE_LONG = 0, 
 EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe", "vamd_quant_limit", "vamd_config_string", "vamd_destroy", "vamd_last_error", "vamd_set_stream", "vamd_reserve",
                     "vamd_channels", "vamd_blocksize", "vamd_posts", "vamd_mdct_forward_batch",
                     "vamd_analyze_batch", "vamd_analyze_stream", "vamd_analyze_block", "vamd_profile",
-                    "vamd_stage_ms", "vamd_debug_cycles", "vamd_analyze_stream_mixed", "vamd_envelope_search_batch",
+                    "vamd_stage_ms", "vamd_debug_cycles", "vamd_debug_survivors", "vamd_analyze_stream_mixed", "vamd_envelope_search_batch",
                     "vamd_envelope_search", "vamd_envelope_geometry", "vamd_residue_capacity", "vamd_analyze_block_res", "vamd_analyze_batch_managed", "vamd_analyze_block_managed",
                     "vamd_packet_capacity", "vamd_encode_block", "vamd_submaps", "vamd_residue_offset", "vamd_analyze_streams_mixed",
                     "vamd_plan_streams", "vamd_gather_blocks", "vamd_plan_fetch",
@@ -185,6 +185,7 @@ def load_library():
     L.vamd_analyze_block.argtypes = [_vp, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _vp, _vp,
                                      _vp, _vp, _vp, _vp, C.POINTER(C.c_float)]
     L.vamd_debug_cycles.argtypes = [_vp, C.c_int, _vp]
+    L.vamd_debug_survivors.argtypes = [_vp, C.c_int, C.c_long, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.vamd_calib_copy.argtypes = [_vp, _vp, _vp, C.c_size_t]
     L.vamd_analyze_stream_mixed.argtypes = [_vp, C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_Desc), C.POINTER(_IO), _vp,
                                             C.c_long, C.POINTER(C.c_float)]
@@ -346,6 +347,17 @@ class Analyzer:
         out = np.zeros(80, dtype=np.uint64)
         self._check(self.L.vamd_debug_cycles(self.h, 1 if enable else 0, _vp(out.ctypes.data) if read else None))
         return out.reshape(5, 16)
+
+    def debug_survivors(self, W, channel_blocks):
+        """vamd_debug_survivors(): (seed [cb][row], surv [cb][row] uint16, nsurv [cb], lines) of the last batch of size class W."""
+        row, nl = C.c_int32(), C.c_int32()
+        self._check(self.L.vamd_debug_survivors(self.h, W, 0, None, None, None, C.byref(row), C.byref(nl)))
+        seed = np.zeros((channel_blocks, row.value), np.float32)
+        surv = np.zeros((channel_blocks, row.value), np.uint16)
+        nsurv = np.zeros(channel_blocks, np.int32)
+        self._check(self.L.vamd_debug_survivors(self.h, W, channel_blocks, _vp(seed.ctypes.data), _vp(surv.ctypes.data),
+                                                _vp(nsurv.ctypes.data), None, None))
+        return seed, surv, nsurv, nl.value
 
     def calib_copy(self, dst, src):
         """vamd_calib_copy(): src -> dst (device tensors of equal byte size) with the library's named copy kernel."""

@@ -121,14 +121,53 @@ VAMD_DEV float tone_min(float a, float b) { return b < a ? b : a; }
 // Thread-per-block form of seed_chase part 1.  Only the top ~9 stack entries can
 // ever be popped or inspected (an entry more than `linesper` lines behind the
 // current line fails both position tests for good), so the stack lives in a
-// 16-slot ring per lane; an entry pushed out of the ring is final and its line
-// index is appended to the survivor list.  Ring layout [slot][lane] keeps the 64
-// lanes on distinct LDS banks.
+// ring of RING slots per lane, RING >= linesper; an entry pushed out of the ring
+// is final and its line index is appended to the survivor list.  Ring layout
+// [slot][lane] keeps the 64 lanes on distinct LDS banks.
 //   seeds   this block's seed[] (HBM, read 32 lines -- a cache line -- at a time)
 //   surv    out: surviving line indices, ascending (uint16), returns their count
+//
+// ---- round 21: the walk's share of a CU beside the noise mask (profiles/r21_chase_ring.txt) ------------------------------
+// k_tone_chase runs beside k_noise's persistent teams and its speed there follows the waves it has resident.  Two switches
+// decide how many fit, each with the parent's form at its other setting:
+//   * VAMD_CHASE_RING (8; 16 as before): slots of the ring where linesper <= 8 -- every libvorbisenc setup; longer windows
+//     always have VAMD_RING = 16, which is also what a caller that does not know linesper sizes a ring for.  Eight slots of
+//     (amplitude, position) are 4 KB a wave of 64 walks where sixteen are 8.
+//   * VAMD_CHASE_PREFETCH (0; 1 as before): a row's next 32 lines in flight while 32 are walked.  That is 64 registers of row
+//     data and a kernel of 94 VGPRs -- one wave a SIMD in the 128 that six noise teams leave; without it the kernel has 62
+//     and two fit.  A lane still asks for whole 128-byte lines, once each; what the prefetch hid is now hidden by the other
+//     resident waves (215 k wave cycles alone against 205 k).
+// Beside six teams (8 wave slots, 40 KB, 128 VGPRs a SIMD) that makes 8 walk waves a CU where there were 4, and six teams
+// are then ahead of five (vamd_batch.h: noise_teams_per_cu).  Either switch alone loses.
+//
+// Why RING = linesper slots are enough, although the slot of index k is written again by index k + RING while entry k may
+// still be on the stack.  Positions on the stack are distinct and ascending, so when index k + RING is written, at line L,
+// the entries k+1 .. k+RING lie on RING distinct lines <= L: pos(k+1) <= L - RING + 1.  Entry k is read back only as the
+// new second-from-top, after a pop of index k+2 -- and that pop wanted the then second-from-top, entry k+1, within reach:
+// i < pos(k+1) + linesper <= L + 1 + (linesper - RING), which no later line i > L satisfies for linesper <= RING.  Entry k+1
+// cannot have moved to a later line in between either: that takes a pop of k+1, hence first the same pop of k+2.  So
+// once index k + RING has been written, indices <= k + 2 are never popped and index k is never read again: the walk reads
+// no stale slot, a test on `hmax > (stack - 2) + RING` at the read-back would never fire, and there is none (the switch
+// VAMD_CHASE_GUARD compiles it in with a counter for tests/test_chase_ring_cases.py, which finds zero hits on rings of 8
+// and of 16).  The same bound makes an entry one ring-length below a first write final (the emission rule) and keeps
+// chase_chunk's window() from reaching a reused slot: it walks down from the top and stops at entry k+1, which is out of
+// its window.
 #define VAMD_RING 16
-VAMD_DEV int tone_chase_thread(const float *__restrict__ seeds, int linesper, int n, float *ring_amp, int *ring_pos,
-                               int rstride, int rlane, unsigned short *__restrict__ surv) {
+#ifndef VAMD_CHASE_RING
+#define VAMD_CHASE_RING 8
+#endif
+#ifndef VAMD_CHASE_GUARD
+#define VAMD_CHASE_GUARD 0
+#endif
+#ifndef VAMD_CHASE_PREFETCH
+#define VAMD_CHASE_PREFETCH 0
+#endif
+static_assert(VAMD_CHASE_RING == 8 || VAMD_CHASE_RING == VAMD_RING, "VAMD_CHASE_RING is 8 or 16");
+// slots of the ring for windows of `linesper` lines
+constexpr int chase_ring_slots(int linesper) { return linesper <= 8 ? VAMD_CHASE_RING : VAMD_RING; }
+template <int RING>
+VAMD_DEV int tone_chase_ring(const float *__restrict__ seeds, int linesper, int n, float *ring_amp, int *ring_pos,
+                             int rstride, int rlane, unsigned short *__restrict__ surv) {
   int stack = 0, hmax = 0;  // hmax = highest stack index ever written
   // survivors leave in index order, 0, 1, 2, ...: eight at a time as one 16-byte store (a lane per block means every
   // lane stores into a cache line of its own: with 2-byte stores the stage took 0.75 ms, with these 0.5)
@@ -152,16 +191,24 @@ VAMD_DEV int tone_chase_thread(const float *__restrict__ seeds, int linesper, in
   const F4 *q = (const F4 *)seeds;
   const int nblk = (n + 31) >> 5;
   F4 w[8];
+#if VAMD_CHASE_PREFETCH
 #pragma unroll
   for (int k = 0; k < 8; k++) w[k] = q[k];  // the next 32 lines load while these are walked
+#endif
   for (int b = 0; b < nblk; b++) {
     float blk[32];
+#if !VAMD_CHASE_PREFETCH
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = q[8 * b + k];
+#endif
 #pragma unroll
     for (int k = 0; k < 8; k++) blk[4 * k] = w[k].x, blk[4 * k + 1] = w[k].y, blk[4 * k + 2] = w[k].z, blk[4 * k + 3] = w[k].w;
+#if VAMD_CHASE_PREFETCH
     if (b + 1 < nblk) {
 #pragma unroll
       for (int k = 0; k < 8; k++) w[k] = q[8 * b + 8 + k];
     }
+#endif
 #pragma unroll
     for (int j = 0; j < 32; j++) {
       const int i = (b << 5) + j;
@@ -173,16 +220,22 @@ VAMD_DEV int tone_chase_thread(const float *__restrict__ seeds, int linesper, in
             a1 = a2;
             p1 = p2;
             if (stack < 2) break;
-            const int slot = (stack - 2) & (VAMD_RING - 1);
+            const int slot = (stack - 2) & (RING - 1);
             a2 = ring_amp[slot * rstride + rlane];
             p2 = ring_pos[slot * rstride + rlane];
+#if VAMD_CHASE_GUARD
+            if (hmax > stack - 2 + RING) {  // the slot has been reused: the entry it held is out of reach
+              VAMD_CHASE_GUARD_HIT();
+              p2 = -(1 << 24);
+            }
+#endif
           }
         }
-        const int slot = stack & (VAMD_RING - 1);
+        const int slot = stack & (RING - 1);
         if (stack == hmax) {
           // first write of this index: the entry one ring-length below is final, emit it
           // before its slot is reused (re-pushes of an index already seen emit nothing)
-          if (stack >= VAMD_RING) emit(ring_pos[slot * rstride + rlane]);
+          if (stack >= RING) emit(ring_pos[slot * rstride + rlane]);
           hmax++;
         }
         ring_amp[slot * rstride + rlane] = s;
@@ -195,12 +248,18 @@ VAMD_DEV int tone_chase_thread(const float *__restrict__ seeds, int linesper, in
       }
     }
   }
-  for (int k = hmax > VAMD_RING ? hmax - VAMD_RING : 0; k < stack; k++) emit(ring_pos[(k & (VAMD_RING - 1)) * rstride + rlane]);
+  for (int k = hmax > RING ? hmax - RING : 0; k < stack; k++) emit(ring_pos[(k & (RING - 1)) * rstride + rlane]);
   for (int k = nw & ~7; k < nw; k++) {  // the last one to seven
     const int sh = 16 * (8 - (nw & 7) + (k & 7));
     surv[k] = (unsigned short)(sh < 64 ? wlo >> sh : whi >> (sh - 64));
   }
   return stack;
+}
+// (the ring's depth from linesper: a caller that knows it at compile time names tone_chase_ring itself)
+VAMD_DEV int tone_chase_thread(const float *__restrict__ seeds, int linesper, int n, float *ring_amp, int *ring_pos,
+                               int rstride, int rlane, unsigned short *__restrict__ surv) {
+  if (chase_ring_slots(linesper) == VAMD_CHASE_RING) return tone_chase_ring<VAMD_CHASE_RING>(seeds, linesper, n, ring_amp, ring_pos, rstride, rlane, surv);
+  return tone_chase_ring<VAMD_RING>(seeds, linesper, n, ring_amp, ring_pos, rstride, rlane, surv);
 }
 
 // ---- seed_chase part 1 for ONE block spread over a wave (small batches, the per-block entry points) -------------
@@ -226,8 +285,9 @@ struct ChaseChunk {
 //   warm >= 0: cold start `warm` lines before s.  warm < 0: start AT s from the state `enter` (an alive mask of the
 //   window before s, e.g. the predecessor's sig_out): the stack is rebuilt as one entry far out of reach -- standing
 //   for everything older, which can neither be popped nor pass a position test -- plus the window's alive lines.
-VAMD_DEV ChaseChunk chase_chunk(const float *seeds, int linesper, int n, int s, int e, int warm, uint32_t enter,
-                                float *ring_amp, int *ring_pos, int rstride, int rlane) {
+template <int RING>
+VAMD_DEV ChaseChunk chase_chunk_ring(const float *seeds, int linesper, int n, int s, int e, int warm, uint32_t enter,
+                                     float *ring_amp, int *ring_pos, int rstride, int rlane) {
   ChaseChunk out;
   out.popped = out.sig_in = out.sig_out = 0;
   const int ws = warm < 0 ? s : (s - warm > 0 ? s - warm : 0);
@@ -238,7 +298,7 @@ VAMD_DEV ChaseChunk chase_chunk(const float *seeds, int linesper, int n, int s, 
   int p1 = 0, p2 = 0;
   if (warm < 0 && s > 0) {
     auto push = [&](float a, int pos) {
-      const int slot = stack & (VAMD_RING - 1);
+      const int slot = stack & (RING - 1);
       ring_amp[slot * rstride + rlane] = a;
       ring_pos[slot * rstride + rlane] = pos;
       stack++;
@@ -257,7 +317,7 @@ VAMD_DEV ChaseChunk chase_chunk(const float *seeds, int linesper, int n, int s, 
     uint32_t m = 0;
     const int lo = t - linesper + 1;
     for (int k = stack - 1; k >= 0 && k >= stack - linesper; k--) {
-      const int pos = k == stack - 1 ? p1 : (k == stack - 2 ? p2 : ring_pos[(k & (VAMD_RING - 1)) * rstride + rlane]);
+      const int pos = k == stack - 1 ? p1 : (k == stack - 2 ? p2 : ring_pos[(k & (RING - 1)) * rstride + rlane]);
       if (pos < lo) break;
       m |= 1u << (pos - lo);
     }
@@ -274,12 +334,12 @@ VAMD_DEV ChaseChunk chase_chunk(const float *seeds, int linesper, int n, int s, 
         a1 = a2;
         p1 = p2;
         if (stack < 2) break;
-        const int slot = (stack - 2) & (VAMD_RING - 1);
+        const int slot = (stack - 2) & (RING - 1);
         a2 = ring_amp[slot * rstride + rlane];
         p2 = ring_pos[slot * rstride + rlane];
       }
     }
-    const int slot = stack & (VAMD_RING - 1);
+    const int slot = stack & (RING - 1);
     ring_amp[slot * rstride + rlane] = sv;
     ring_pos[slot * rstride + rlane] = i;
     stack++;
@@ -289,6 +349,11 @@ VAMD_DEV ChaseChunk chase_chunk(const float *seeds, int linesper, int n, int s, 
     p1 = i;
   }
   return out;
+}
+VAMD_DEV ChaseChunk chase_chunk(const float *seeds, int linesper, int n, int s, int e, int warm, uint32_t enter,
+                                float *ring_amp, int *ring_pos, int rstride, int rlane) {
+  if (chase_ring_slots(linesper) == VAMD_CHASE_RING) return chase_chunk_ring<VAMD_CHASE_RING>(seeds, linesper, n, s, e, warm, enter, ring_amp, ring_pos, rstride, rlane);
+  return chase_chunk_ring<VAMD_RING>(seeds, linesper, n, s, e, warm, enter, ring_amp, ring_pos, rstride, rlane);
 }
 
 // The same walk with its state in registers.  What a step can pop or look at are the lines within linesper of it, so the

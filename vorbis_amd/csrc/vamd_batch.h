@@ -72,6 +72,25 @@ int vamd_reserve(vamd_ctx *c, int W, long max_blocks) {
   return plan(c, W, max_blocks, nullptr, VAMD_LEVEL_FULL, &p);
 }
 
+// (test aid) the seed lines, survivor lists and counts the last run of size class W left in the workspace
+int vamd_debug_survivors(vamd_ctx *c, int W, long ncb, float *seed, uint16_t *surv, int32_t *nsurv, int32_t *row_lines,
+                         int32_t *lines) {
+  DeviceGuard dev_guard(c);
+  if (!c || (W != 0 && W != 1) || ncb < 0) return VAMD_EINVAL;
+  const size_t nl = (size_t)c->B.psy[2 * W].total_octave_lines, nlp = (size_t)VAMD_LINES_PAD(nl);
+  if (row_lines) *row_lines = (int32_t)nlp;
+  if (lines) *lines = (int32_t)nl;
+  if (!seed && !surv && !nsurv) return VAMD_OK;
+  const DevBuf &bs = c->ws[W][vamd_ctx::WS_SEED], &bv = c->ws[W][vamd_ctx::WS_SURV], &bn = c->ws[W][vamd_ctx::WS_NSURV];
+  if (bs.bytes < (size_t)ncb * nlp * 4 || bv.bytes < (size_t)ncb * nlp * 2 || bn.bytes < (size_t)ncb * 4)
+    return fail(c, VAMD_EINVAL, "no batch of that size has left survivor lists");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (seed) HIP_TRY(c, hipMemcpy(seed, bs.p, (size_t)ncb * nlp * 4, hipMemcpyDeviceToHost));
+  if (surv) HIP_TRY(c, hipMemcpy(surv, bv.p, (size_t)ncb * nlp * 2, hipMemcpyDeviceToHost));
+  if (nsurv) HIP_TRY(c, hipMemcpy(nsurv, bn.p, (size_t)ncb * 4, hipMemcpyDeviceToHost));
+  return VAMD_OK;
+}
+
 // from a run-time size to a template argument: the call site defines VAMD_GO(arg) as its launch
 #define VAMD_SWITCH_LOGN(logn)   \
   switch (logn) {                \
@@ -419,7 +438,14 @@ static long noise_teams_per_cu(const vamd_ctx *c, int n2, size_t lds, bool overl
     // visible tone tail per 131 072 stereo blocks 2.77 + 0.01 ms against 2.51 + 0.32 with six, 2.34 + 0.54 with seven,
     // 2.16 + 0.93 with eight; a mixed run, whose chains also have the other class's masks and floor fits to run
     // beside, keeps six: C5 11.25 ms against 11.34 with five.  profiles/r06_noise_teams.txt)
-    const int beside = c->K.noise_waves > 0 ? c->K.noise_waves : (alone ? 20 : 24);
+    // (round 21, profiles/r21_chase_ring.txt: six for both.  What stood against the sixth team in a run of one size class
+    // was k_tone_chase: 94 VGPRs and 8 KB of ring a wave, so beside six teams -- 8 wave slots, 40 KB and 128 VGPRs a SIMD
+    // left -- 4 of its waves fit a CU.  With 62 VGPRs and a ring of 4 KB (k_tone.h: VAMD_CHASE_PREFETCH, VAMD_CHASE_RING)
+    // 8 fit.  Noise mask + visible tone tail per 131 072 stereo blocks: the parent, five teams, 2.78 + 0.01 ms; the new
+    // walk with five 2.79 + 0.01, with six 2.51 + 0.19, with seven 2.37 + 0.54.  What is left of the tail is k_tone_seed,
+    // 8 of whose waves fit beside six teams for 12 beside five.  C5: 10.12 ms against 10.17, 10.51 with 28 waves.)
+    // (a run of smaller blocks alone was not measured again: as before)
+    const int beside = c->K.noise_waves > 0 ? c->K.noise_waves : (alone && n2 < 1024 ? 20 : 24);
     const long cap = (fold_later ? beside : 16) / nw;
     if (per_cu > cap) per_cu = cap > 0 ? cap : 1;
   }
@@ -451,11 +477,14 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
   const long wave_max_cb = c->K.chase_wave_max;
   const bool by_wave = (long)gcb <= wave_max_cb && P0.eighth_octave_lines <= 16 && nl <= 2048;
   const bool lp8 = P0.eighth_octave_lines == 8 && P1.eighth_octave_lines == 8;
+  // the stack walk's ring: VAMD_CHASE_RING slots where no window is longer than 8 lines, 16 otherwise (k_tone.h)
+  const bool ring8 = P0.eighth_octave_lines <= 8 && P1.eighth_octave_lines <= 8 && VAMD_CHASE_RING < VAMD_RING;
+  const size_t ring_slots = ring8 ? VAMD_CHASE_RING : VAMD_RING;
   // a handful of blocks, no second stream: both masks in one launch, side by side (k_noise_tone)
   const bool merge_env = !c->K.masks_separate;
   const bool merged = merge_env && !overlap && by_wave && lp8;
   if (merged) {
-    const size_t nlds = (size_t)5 * VAMD_NZ_STRIDE(n2) * 4, tlds = seed_lds + (size_t)VAMD_RING * 8;
+    const size_t nlds = (size_t)5 * VAMD_NZ_STRIDE(n2) * 4, tlds = seed_lds + (size_t)chase_ring_slots(8) * 8;
 #define VAMD_GO(L)                                                                                                          \
   hipLaunchKernelGGL((k_noise_tone<L, 8>), dim3(2 * gcb), dim3(64 * NoiseGeom<L>::NW), nlds > tlds ? nlds : tlds, s, P0, P1, d, ch, \
                      (long)gcb, p.mdct_raw, p.noise, nlp, run_peaks_stride(P0), p.peaks, p.local, p.ampglob,                  \
@@ -479,7 +508,7 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
     if (merged) {
       // (launched with the noise stage)
     } else if (by_wave && lp8) {  // ... and seed + chase in one launch (k_tone_seed_chase)
-      hipLaunchKernelGGL(k_tone_seed_chase<8>, dim3(gcb), dim3(64), seed_lds + (size_t)VAMD_RING * 8, s, P0, P1, d, ch, nlp,
+      hipLaunchKernelGGL(k_tone_seed_chase<8>, dim3(gcb), dim3(64), seed_lds + (size_t)chase_ring_slots(8) * 8, s, P0, P1, d, ch, nlp,
                          run_peaks_stride(P0), p.peaks, p.local, p.ampglob, R->make_ampmax ? p.ampglob : nullptr, p.seed, p.surv,
                          p.nsurv);
     } else {
@@ -489,13 +518,21 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
       else
         hipLaunchKernelGGL(k_tone_seed<0>, dim3(gcb), dim3(64), seed_lds, s, P0, P1, d, ch, nlp, run_peaks_stride(P0), p.peaks, p.local,
                            p.ampglob, R->make_ampmax ? p.ampglob : nullptr, p.seed);
-      if (by_wave)
-        hipLaunchKernelGGL(k_tone_chase_wave, dim3(gcb), dim3(64), (size_t)nlp * 4 + (size_t)VAMD_RING * 64 * 8, s,
-                           P0.eighth_octave_lines, nl, nlp, d, p.seed, p.surv, p.nsurv);
-      else
-        hipLaunchKernelGGL(k_tone_chase, dim3((gcb + VAMD_CHASE_LANES - 1) / VAMD_CHASE_LANES), dim3(VAMD_CHASE_LANES),
-                           (size_t)VAMD_RING * VAMD_CHASE_LANES * 8, s,
-                           P0.eighth_octave_lines, nl, nlp, (long)gcb, d, p.seed, p.surv, p.nsurv);
+      const size_t chase_pad = (size_t)c->K.chase_lds_pad;  // (experiment: the walk's waves per CU beside the noise mask)
+#define VAMD_GO(RING)                                                                                                          \
+  if (by_wave)                                                                                                                 \
+    hipLaunchKernelGGL(k_tone_chase_wave<RING>, dim3(gcb), dim3(64), (size_t)nlp * 4 + (size_t)RING * 64 * 8, s,               \
+                       P0.eighth_octave_lines, nl, nlp, d, p.seed, p.surv, p.nsurv);                                           \
+  else                                                                                                                         \
+    hipLaunchKernelGGL(k_tone_chase<RING>, dim3((gcb + VAMD_CHASE_LANES - 1) / VAMD_CHASE_LANES), dim3(VAMD_CHASE_LANES),      \
+                       (size_t)RING * VAMD_CHASE_LANES * 8 + chase_pad, s, P0.eighth_octave_lines, nl, nlp, (long)gcb, d, p.seed, \
+                       p.surv, p.nsurv)
+      if (ring_slots == VAMD_RING) {
+        VAMD_GO(VAMD_RING);
+      } else {
+        VAMD_GO(VAMD_CHASE_RING);
+      }
+#undef VAMD_GO
     }
     if (!fold_later)
       hipLaunchKernelGGL(k_tone_fold, dim3(gcb), dim3(64), fold_lds_bytes(nlp, P0, P1), s, P0, P1, d, ch, nlp, p.seed, p.surv,

@@ -509,7 +509,8 @@ __device__ __forceinline__ void tone_seed_chase_run(const PsyP &P0, const PsyP &
   const int nl = P.total_octave_lines;
   float *seed = (float *)vamd_smem + seed_pad_lo(LP);
   float *ring_amp = seed + nlp + seed_pad_hi(LP);
-  int *ring_pos = (int *)(ring_amp + VAMD_RING);
+  constexpr int RING = chase_ring_slots(LP);
+  int *ring_pos = (int *)(ring_amp + RING);
   PhaseClock pc;
   pc.start(d.dbg ? d.dbg + 32 : nullptr);
   tone_seed_block<LP>(P, peaks + cb * nrp, g_amp, local_ampmax[cb], seed, pc);
@@ -556,7 +557,7 @@ __device__ __forceinline__ void tone_seed_chase_run(const PsyP &P0, const PsyP &
     for (uint32_t m = alive; m; m &= m - 1) out[at++] = (unsigned short)(s0 + __builtin_ctz(m));
     if (LANE == 63) nsurv[cb] = incl;
   } else if (LANE == 0) {
-    nsurv[cb] = tone_chase_thread(seed, LP, nl, ring_amp, ring_pos, 1, 0, out);
+    nsurv[cb] = tone_chase_ring<RING>(seed, LP, nl, ring_amp, ring_pos, 1, 0, out);
   }
   pc.mark(2);
   pc.flush();
@@ -595,12 +596,14 @@ __global__ __launch_bounds__(64 * NoiseGeom<LOGN2>::NW) void k_noise_tone(PsyP P
 // round 2: half-filled waves -- twice as many waves for the SIMDs to interleave -- are slower, 1.01 against 0.82 ms per
 // 131 072 stereo blocks; a walk whose stack is a register bit mask fed through coalesced LDS tiles executes three
 // times the instructions once 64 divergent walks share them, 2.96 ms.  docs/history/DESIGN_r01-r05.md has the round's account.)
+// RING: the slots of a lane's ring, chase_ring_slots(linesper) (chosen by the launch)
 #define VAMD_CHASE_LANES 64
+template <int RING>
 __global__ __launch_bounds__(64) void k_tone_chase(int linesper, int nl, int nlp, long ncb, DescP d,
                                                    const float *__restrict__ seed_g,
                                                    unsigned short *__restrict__ surv, int *__restrict__ nsurv) {
   float *ring_amp = (float *)vamd_smem;
-  int *ring_pos = (int *)(ring_amp + VAMD_RING * VAMD_CHASE_LANES);
+  int *ring_pos = (int *)(ring_amp + RING * VAMD_CHASE_LANES);
   const long cb = (long)blockIdx.x * VAMD_CHASE_LANES + threadIdx.x;
   PhaseClock pc;
   pc.start(d.dbg ? d.dbg + 32 : nullptr);
@@ -614,7 +617,7 @@ __global__ __launch_bounds__(64) void k_tone_chase(int linesper, int nl, int nlp
   long long t0 = 0;
   if (probe) w0 = wall_clock64(), t0 = clock64();
   if (cb < ncb)
-    nsurv[cb] = tone_chase_thread(seed_g + cb * nlp, linesper, nl, ring_amp, ring_pos, VAMD_CHASE_LANES, threadIdx.x, surv + cb * nlp);
+    nsurv[cb] = tone_chase_ring<RING>(seed_g + cb * nlp, linesper, nl, ring_amp, ring_pos, VAMD_CHASE_LANES, threadIdx.x, surv + cb * nlp);
   if (probe) {
     atomicAdd(d.clk, (unsigned long long)(clock64() - t0));
     atomicAdd(d.clk + 1, wall_clock64() - w0);
@@ -625,13 +628,14 @@ __global__ __launch_bounds__(64) void k_tone_chase(int linesper, int nl, int nlp
 }
 
 // the same for a small batch: one WAVE per channel-block, the walk cut into one chunk per lane (chase_chunk, k_tone.h)
-// LDS: the block's seed lines [nlp], then the rings [VAMD_RING][64] x 2
+// LDS: the block's seed lines [nlp], then the rings [RING][64] x 2, RING = chase_ring_slots(linesper)
+template <int RING>
 __global__ __launch_bounds__(64) void k_tone_chase_wave(int linesper, int nl, int nlp, DescP d,
                                                         const float *__restrict__ seed_g,
                                                         unsigned short *__restrict__ surv, int *__restrict__ nsurv) {
   float *seed = (float *)vamd_smem;
   float *ring_amp = seed + nlp;
-  int *ring_pos = (int *)(ring_amp + VAMD_RING * 64);
+  int *ring_pos = (int *)(ring_amp + RING * 64);
   const long cb = blockIdx.x;
   WAVE_FOR(q, nlp >> 2)((F4 *)seed)[q] = ((const F4 *)(seed_g + cb * nlp))[q];
   WAVE_SYNC();
@@ -647,7 +651,7 @@ __global__ __launch_bounds__(64) void k_tone_chase_wave(int linesper, int nl, in
   int longest = 0;
   for (; fm && longest <= VAMD_CHASE_FLAT_MAX; longest++) fm &= fm << 1;
   if (longest <= VAMD_CHASE_FLAT_MAX) {
-    if (s0 < nl) r = chase_chunk(seed, linesper, nl, s0, e0, VAMD_CHASE_WARM * linesper, 0, ring_amp, ring_pos, 64, LANE);
+    if (s0 < nl) r = chase_chunk_ring<RING>(seed, linesper, nl, s0, e0, VAMD_CHASE_WARM * linesper, 0, ring_amp, ring_pos, 64, LANE);
     uint32_t used = r.sig_in;
     for (int rd = 0; rd <= VAMD_CHASE_ROUNDS; rd++) {
       const uint32_t prev_out = (uint32_t)wave_shift_up1((int)r.sig_out, 0);
@@ -658,7 +662,7 @@ __global__ __launch_bounds__(64) void k_tone_chase_wave(int linesper, int nl, in
       }
       if (rd == VAMD_CHASE_ROUNDS) break;
       if (need) {  // walked again, started exactly in the predecessor's exit state
-        const ChaseChunk t = chase_chunk(seed, linesper, nl, s0, e0, -1, prev_out, ring_amp, ring_pos, 64, LANE);
+        const ChaseChunk t = chase_chunk_ring<RING>(seed, linesper, nl, s0, e0, -1, prev_out, ring_amp, ring_pos, 64, LANE);
         used = prev_out;
         r.popped = t.popped;
         r.sig_out = t.sig_out;
@@ -673,7 +677,7 @@ __global__ __launch_bounds__(64) void k_tone_chase_wave(int linesper, int nl, in
     for (uint32_t m = alive; m; m &= m - 1) out[at++] = (unsigned short)(s0 + __builtin_ctz(m));
     if (LANE == 63) nsurv[cb] = incl;
   } else if (LANE == 0) {
-    nsurv[cb] = tone_chase_thread(seed, linesper, nl, ring_amp, ring_pos, 64, 0, out);
+    nsurv[cb] = tone_chase_ring<RING>(seed, linesper, nl, ring_amp, ring_pos, 64, 0, out);
   }
 }
 
