@@ -554,6 +554,57 @@ int vamd_analyze_batch_synth(vamd_ctx *ctx, const vamd_batch_desc *desc, const v
 int vamd_synth_streams(vamd_ctx *ctx, const vamd_stream_plan *plan, long nstreams, long max_frames, const int64_t *frames,
                        const int64_t *offset, float *scratch_short, float *scratch_long, float *pcm);
 
+/* ---- the packet decoder: audio packets in, PCM out (still ABI 9: additions only).  The front half the synthesis above
+ * lacked -- the packet head (lib/synthesis.c:25-88), floor1_inverse1, the phrase words and codebook entries in the order
+ * _01inverse / res2_inverse read them, every codeword by table (lib/codebook.c:264-365) -- as a kernel of its own, k_unpack,
+ * one lane per packet; it writes exactly the rows the synthesis reads, and k_synth and the lap run on them unchanged.  Bit
+ * for bit libvorbis' decoder on the same packets (tests/test_unpack_cpu.py, tests/test_decode_gpu.py).
+ *
+ * The context's setup blob IS the setup: the packets must come from an encoder of that setup (ours or libvorbis'); header
+ * packets are not read.  `bytes` holds the audio packets of all streams back to back in HOST memory, packet p at
+ * [offset[p], offset[p+1]), stream s = packets [stream_start[s], stream_start[s+1]).  end_granule (or NULL): per stream
+ * the granule position of its last packet, -1 = none; the last block's frames are cut to it as vorbis_synthesis_blockin
+ * cuts them (lib/block.c:906-935) for a stream that begins at granule 0.
+ *
+ *   vamd_decode_plan     host only, nothing is enqueued: frames[s] (host [nstreams]) = the frames stream s decodes to --
+ *     the span of its blocks' centres (bs[lW]/4 + bs[W]/4 apart, lib/block.c:840-842; W from each packet's mode bits), cut
+ *     as above; zero or one packet gives 0 -- and nblocks[2], the blocks per size class.  VAMD_EINVAL with the reason in
+ *     vamd_last_error for a bad descriptor (counts, offsets or stream_start not monotone or out of range); VAMD_EIMPL for a
+ *     setup vamd_synth_check refuses, with its text.
+ *   vamd_decode_streams  plans again, then on the context's stream: the packets and the plan go up (one copy each),
+ *     k_unpack, k_synth per size class, the lap into pcm (DEVICE) -- stream s, channel c, frame k at
+ *     pcm[offset_out[s] + c * frames[s] + k], frames as vamd_decode_plan gave them -- and status[s] (host) comes back; the
+ *     call returns when it has (one stream synchronisation).  A bad descriptor launches nothing.
+ *
+ * status[s] is 0, or the VAMD_STATUS_* of the stream's flagged packets or-ed: such a stream has NO frames -- what its part
+ * of pcm holds is not its signal -- and the other streams are untouched.
+ *   VAMD_STATUS_NOTAUDIO   the packet-type bit is set, or the mode number names no mode
+ *   VAMD_STATUS_BADCODE    bits that are no codeword of the book they are read with, or a phrase word beyond the classes
+ *   VAMD_STATUS_TRUNCATED  the packet ends before its block is complete (an empty packet too)
+ * A DELIBERATE DEVIATION: libvorbis decodes what a truncated packet still holds (a floor that meets the end is no floor, a
+ * residue keeps what it has -- eopbreak, lib/res0.c:650,709) and returns 0; here the stream is flagged, as a decoded feed's
+ * stream with a missing packet is.  The packets a bitrate-managed encoder CUT to fit its reservoir are such packets.
+ *
+ * Workspace: in the context, grown on demand, released with it -- per block 4 ch + ch n/2 + 2048 S + 2 *
+ * vamd_residue_capacity + 8 S bytes of rows, 4 ch n of vb->pcm and 29 of plan (ch channels, n the block's size, S its
+ * submaps), and the packets themselves.
+ *
+ * Out of scope: header packets and setups other than the context's; Ogg demultiplexing; packets in device memory; streams
+ * that begin at a nonzero granule (the first page's trim); eopbreak semantics (above). */
+#define VAMD_STATUS_NOTAUDIO  4
+#define VAMD_STATUS_BADCODE   8
+#define VAMD_STATUS_TRUNCATED 16
+typedef struct vamd_decode_desc {
+  int64_t nstreams, npackets;
+  const uint8_t *bytes;          /* HOST: the audio packets, back to back */
+  const int64_t *offset;         /* host [npackets + 1], bytes */
+  const int64_t *stream_start;   /* host [nstreams + 1], into packets */
+  const int64_t *end_granule;    /* host [nstreams] or NULL: the last packet's granule position, -1 = none */
+} vamd_decode_desc;
+int vamd_decode_plan(vamd_ctx *ctx, const vamd_decode_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
+int vamd_decode_streams(vamd_ctx *ctx, const vamd_decode_desc *desc, const int64_t *offset_out /* host [nstreams] */,
+                        float *pcm /* device */, uint8_t *status /* host [nstreams] */);
+
 /* ---- the host shim for encoders that submit ONE block at a time from many threads.
  * libvorbis' unit of work is one block of one stream (mapping0_forward, reference lib/mapping0.c:233-687); a
  * batcher coalesces concurrent vamd_batcher_encode_block() calls -- same contract as vamd_encode_block() for a VBR

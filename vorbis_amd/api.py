@@ -12,6 +12,7 @@ VAMD_OK, VAMD_EFAULT, VAMD_EIMPL, VAMD_EINVAL, VAMD_EVERSION, VAMD_EDOMAIN, VAMD
 ABI_VERSION = 9             # VAMD_ABI_VERSION of the header this mirror was written against
 QUANT_LIMIT_SQUARE, QUANT_LIMIT_INT = 46340, 0x7fffff80
 STATUS_RANGE, STATUS_NONFINITE = 1, 2   # bits of the `status` output (vorbis_amd.h, "Input domain")
+STATUS_NOTAUDIO, STATUS_BADCODE, STATUS_TRUNCATED = 4, 8, 16  # a decoded stream's status (vorbis_amd.h, "the packet decoder")
 LEVEL_TRANSFORM, LEVEL_PSY, LEVEL_FULL = 1, 2, 3
 POSTS_STRIDE = 32
 BLOCKTYPE_IMPULSE, BLOCKTYPE_PADDING, BLOCKTYPE_TRANSITION, BLOCKTYPE_LONG = 0, 1, 0, 1
@@ -33,7 +34,8 @@ EXPORTED_SYMBOLS = ["vamd_create_abi", "vamd_encode_blocks", "vamd_clock_probe",
                     "vamd_feed_ogg_headers", "vamd_feed_ogg_serials", "vamd_feed_ogg", "vamd_feed_ogg_headers_live",
                     "vamd_feed_ogg_comments", "vamd_feed_ogg_flush",
                     "vamd_feed_buffer_on", "vamd_feed_wrote_device", "vamd_feed_wrote_live_device", "vamd_feed_source_done",
-                    "vamd_analyze_batch_synth", "vamd_synth_streams", "vamd_synth_check", "vamd_feed_decoded"]
+                    "vamd_analyze_batch_synth", "vamd_synth_streams", "vamd_synth_check", "vamd_feed_decoded",
+                    "vamd_decode_plan", "vamd_decode_streams"]
 PACKETBLOBS = 15
 
 _vp = C.c_void_p
@@ -62,6 +64,10 @@ class _FeedOggResult(C.Structure):  # vamd_feed_ogg_result
 class _FeedDecodedResult(C.Structure):  # vamd_feed_decoded_result
     _fields_ = [("nstreams", C.c_int64), ("channels", C.c_int32), ("frames", _vp), ("offset", _vp), ("status", _vp), ("pcm", _vp),
                 ("total_floats", C.c_int64)]
+
+
+class _DecodeDesc(C.Structure):  # vamd_decode_desc
+    _fields_ = [("nstreams", C.c_int64), ("npackets", C.c_int64), ("bytes", _vp), ("offset", _vp), ("stream_start", _vp), ("end_granule", _vp)]
 
 
 class _DeviceFloats:
@@ -200,6 +206,8 @@ def load_library():
     L.vamd_analyze_batch_synth.argtypes = [_vp, C.POINTER(_Desc), C.POINTER(_IO), _vp]
     L.vamd_synth_check.argtypes = [_vp, C.c_int]
     L.vamd_synth_streams.argtypes = [_vp, C.POINTER(_Plan), C.c_long, C.c_long, _vp, _vp, _vp, _vp, _vp]
+    L.vamd_decode_plan.argtypes = [_vp, C.POINTER(_DecodeDesc), _vp, _vp]
+    L.vamd_decode_streams.argtypes = [_vp, C.POINTER(_DecodeDesc), _vp, _vp, _vp]
     L.vamd_analyze_block_managed.argtypes = [_vp, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float] + [_vp] * 9
     L.vamd_plan_streams.argtypes = [_vp, _vp, C.c_long, C.c_long, C.c_long, C.c_long, _vp, C.POINTER(_Plan)]
     L.vamd_gather_blocks.argtypes = [_vp, C.POINTER(_Plan), C.c_int, _vp, C.c_long, _vp]
@@ -847,6 +855,66 @@ class Analyzer:
         self._check(self.L.vamd_bitrate_walk(self.h, _vp(order.data_ptr()), _vp(stream_start.data_ptr()), stream_start.numel() - 1,
                                              pb, st, _vp(states.data_ptr()), ch_p, fb_p))
         return choice, final
+
+    def decode_prepare(self, streams, granules=None, offset=None, stream_start=None):
+        """The descriptor of decode_streams()'s group (vamd_decode_desc) with the host arrays it points into."""
+        ns = len(streams)
+        for row in streams:
+            for p in row:
+                self._need(isinstance(p, (bytes, bytearray, memoryview)), "decode_streams: a packet must be bytes (a missing packet is not decodable)")
+        flat = [bytes(p) for row in streams for p in row]
+        data = np.frombuffer(b"".join(flat) + b"\0" * 8, np.uint8)
+        off = np.zeros(len(flat) + 1, np.int64)
+        np.cumsum([len(p) for p in flat], out=off[1:])
+        start = np.zeros(ns + 1, np.int64)
+        np.cumsum([len(row) for row in streams], out=start[1:])
+        if offset is not None:
+            off = np.ascontiguousarray(offset, np.int64)
+            self._need(off.size == len(flat) + 1, "decode_streams: offset must hold npackets + 1 values")
+        if stream_start is not None:
+            start = np.ascontiguousarray(stream_start, np.int64)
+            self._need(start.size == ns + 1, "decode_streams: stream_start must hold nstreams + 1 values")
+        gran = None
+        if granules is not None:
+            self._need(len(granules) == ns, "decode_streams: one granule position per stream")
+            gran = np.array([-1 if g is None else int(g) for g in granules], np.int64)
+        d = _DecodeDesc(ns, len(flat), _vp(data.ctypes.data), _vp(off.ctypes.data), _vp(start.ctypes.data), _vp(gran.ctypes.data) if gran is not None else None)
+        return dict(desc=d, keep=(data, off, start, gran), nstreams=ns, npackets=len(flat))
+
+    def decode_run(self, prep, pcm=None):
+        """vamd_decode_plan + vamd_decode_streams over decode_prepare()'s descriptor.  pcm: a float32 tensor on the context's
+        device to decode into (at least the planned frames x channels floats), or None: one is made.
+        -> (pcm, frames, offset, status): stream s, channel c, frame k at pcm[offset[s] + c * frames[s] + k]"""
+        t = self.torch
+        ns, d = prep["nstreams"], prep["desc"]
+        frames, nblocks = np.zeros(max(ns, 1), np.int64), np.zeros(2, np.int64)
+        self._check(self.L.vamd_decode_plan(self.h, C.byref(d), _vp(frames.ctypes.data), _vp(nblocks.ctypes.data)))
+        out_off = np.zeros(max(ns, 1), np.int64)
+        if ns > 1:
+            out_off[1:ns] = np.cumsum(frames[:ns - 1] * self.channels)
+        total = int((frames[:ns] * self.channels).sum())
+        if pcm is None:
+            pcm = t.zeros(total + 4, dtype=t.float32, device=self._dev())
+        self._need_tensor(pcm, t.float32, "pcm")
+        self._need(pcm.numel() >= total, "pcm must hold %d floats" % total)
+        status = np.zeros(max(ns, 1), np.uint8)
+        self._bind_stream()
+        self._check(self.L.vamd_decode_streams(self.h, C.byref(d), _vp(out_off.ctypes.data), _vp(pcm.data_ptr()), _vp(status.ctypes.data)))
+        return pcm, frames[:ns], out_off[:ns], status[:ns]
+
+    def decode_streams(self, streams, granules=None, with_status=False, offset=None, stream_start=None):
+        """vamd_decode_plan + vamd_decode_streams: audio packets of this context's setup in, PCM out -- k_unpack, k_synth and
+        the lap on the GPU.  streams: a list of lists of `bytes`, one list per stream (a Feed's rows plug in as
+        [[p for p, _, _, _ in row] for row in rows]); granules: per stream the last packet's granule position (None or -1:
+        none), which cuts the last block's frames.  offset / stream_start: test hooks, the descriptor's arrays as given
+        instead of as derived.  -> a list of float32 tensors [ch, frames] on the context's device; with_status, also the
+        streams' status bytes (numpy uint8): a flagged stream -- STATUS_NOTAUDIO / _BADCODE / _TRUNCATED -- has no frames."""
+        pcm, frames, out_off, status = self.decode_run(self.decode_prepare(streams, granules, offset, stream_start))
+        out = []
+        for s in range(len(streams)):
+            f = 0 if status[s] else int(frames[s])
+            out.append(pcm[int(out_off[s]):int(out_off[s]) + self.channels * f].view(self.channels, f))
+        return (out, status.copy()) if with_status else out
 
     def analyze_block(self, pcm, lW=1, W=1, nW=1, blocktype=BLOCKTYPE_LONG, ampmax_in=-9999.0):
         """vamd_analyze_block: host numpy pcm[ch][n] in, host numpy results out (the per-block
@@ -1587,6 +1655,16 @@ class Feed:
                 row.append((data, int(r["granulepos"][k]), int(r["info"][k]) & 1, (int(r["info"][k]) >> 1) & 1))
             out.append(row)
         return out
+
+
+def decode(setup_blob, streams, granules=None, with_status=False, device=None):
+    """Analyzer(setup_blob).decode_streams(...) for a caller who holds packets and no context: the packets must come from an
+    encoder of that setup."""
+    a = Analyzer(setup_blob, device)
+    try:
+        return a.decode_streams(streams, granules, with_status)
+    finally:
+        a.close()
 
 
 def envelope_marks(ret, first=0, marks=None):

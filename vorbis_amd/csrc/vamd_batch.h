@@ -606,7 +606,7 @@ static void launch_floor_on(vamd_ctx *c, BatchRun *R, int level) {
   }
 }
 
-static int launch_synth(vamd_ctx *c, int W, float *synth);
+static int launch_synth(vamd_ctx *c, int W, const vamd_ctx::SynthSrc &y, float *synth);
 
 static int run_batch(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io, int level, bool stream_mode,
                      float *ampmax_state, const vamd_managed_io *M = nullptr, float *synth = nullptr) {
@@ -633,7 +633,7 @@ static int run_batch(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_
   launch_floor_on(c, &R, level);
   if (c->profile) c->prof_runs++;
   HIP_TRY(c, hipGetLastError());
-  if (synth && (r = launch_synth(c, R.W, synth))) return r;
+  if (synth && (r = launch_synth(c, R.W, c->synth_src[R.W], synth))) return r;
   if (stream_mode) {
     // new state = ampmax_out of the last block
     HIP_TRY(c, hipMemcpyAsync(ampmax_state, R.p.ampglob + (R.nb - 1), sizeof(float), hipMemcpyDeviceToHost, s));
@@ -666,12 +666,12 @@ static int synth_covered(vamd_ctx *c, int W, SynthFloorP *S) {
     return fail(c, VAMD_EIMPL, "synthesis: a block's spectrum and butterfly vectors do not fit a workgroup's LDS");
   return VAMD_OK;
 }
-// k_synth over the blocks the last run of size class W left (vamd_ctx::synth_src), on the context's stream
-static int launch_synth(vamd_ctx *c, int W, float *synth) {
+// k_synth over y's blocks of size class W -- what the last run left (vamd_ctx::synth_src), or the rows k_unpack wrote
+// (vamd_decode.h) -- on the context's stream
+static int launch_synth(vamd_ctx *c, int W, const vamd_ctx::SynthSrc &y, float *synth) {
   SynthFloorP S;
   int r = synth_covered(c, W, &S);
   if (r) return r;
-  const vamd_ctx::SynthSrc &y = c->synth_src[W];
   if (y.nb < 1) return VAMD_OK;
   const int ch = c->B.channels, n2 = c->B.bs[W] / 2;
   hipLaunchKernelGGL(k_synth, dim3((unsigned)y.nb), dim3(64 * ch), synth_lds_bytes(c, W), c->stream,
@@ -710,7 +710,7 @@ int vamd_synth_streams(vamd_ctx *c, const vamd_stream_plan *plan, long nstreams,
     if (!scratch[W]) return fail(c, VAMD_EINVAL, "null scratch for a size class with blocks");
     if (c->synth_src[W].nb != (long)plan->nblocks[W])
       return fail(c, VAMD_EINVAL, "vamd_synth_streams: the context's last analysis is not the plan's (a VBR vamd_analyze_streams_mixed with packets or residue outputs)");
-    int r = launch_synth(c, W, scratch[W]);
+    int r = launch_synth(c, W, c->synth_src[W], scratch[W]);
     if (r) return r;
   }
   LapP L;

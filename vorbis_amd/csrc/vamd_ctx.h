@@ -61,6 +61,17 @@ struct vamd_ctx {
     const uint16_t *res_entries = nullptr;
     const int32_t *res_count = nullptr;
   } synth_src[2];
+  // the packet decoder (vamd_decode.h): the codebooks' decode tables, built at first use, and its workspace, grown on
+  // demand -- the packets and the plan as they go up, per size class the rows k_unpack writes and k_synth's output
+  struct Decode {
+    bool ready = false;
+    int lanes = VAMD_UNPACK_LANES;  // packets a wave of k_unpack
+    unsigned char *d_tab = nullptr;
+    UnpackP U = {};
+    DevBuf bytes, plan, status;
+    DevBuf post_valid[2], ilogmask[2], res_class[2], res_entries[2], res_count[2], synth[2];
+    HostBuf h_plan;
+  } dec;
 };
 
 // stage ids of vamd_stage_ms(); a mark closes the interval of the stage it names (VAMD_ST_BEGIN: opens one)

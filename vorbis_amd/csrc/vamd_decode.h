@@ -1,0 +1,174 @@
+// vamd_decode.h -- the packet decoder's host side (include/vorbis_amd.h: vamd_decode_plan, vamd_decode_streams): audio
+// packets in host memory to PCM in device memory.  Part of the library's single translation unit, after vamd_batch.h
+// (launch_synth, synth_covered).  The plan is made on the host before anything is enqueued (vamd_decode_plan.h); then, on
+// the context's stream: the packets and the plan go up, one copy each; k_unpack turns every packet into its block's rows
+// (k_unpack.h); k_synth runs per size class on those rows (k_synth.h, the launch the encoder's tensors take); k_lap
+// gathers the streams' samples; the statuses come back.
+//
+// Workspace per block, in the context, grown on demand and released with it (ch channels, n the block's size, S submaps):
+//   rows     4 ch (post_valid) + ch n/2 (the integer curves) + S * 2048 (res_class) + 2 * vamd_residue_capacity
+//            (res_entries) + 8 S (res_count)
+//   k_synth  4 ch n (vb->pcm)
+//   plan     4 (order) + 8 (src) + 16 (the packet's bits) + 1 (status), and the packet itself
+// -- for a stereo block of 2048 some 29 KiB, of which vb->pcm is 16.
+#pragma once
+#include "vamd_decode_plan.h"
+
+static int dev_need(vamd_ctx *c, DevBuf &b, size_t bytes) {
+  if (b.bytes < bytes) {
+    if (b.p) HIP_TRY(c, hipFree(b.p));
+    b.p = nullptr;
+    b.bytes = 0;
+    const size_t want = bytes + bytes / 4;
+    HIP_TRY(c, hipMalloc(&b.p, want));
+    b.bytes = want;
+  }
+  return VAMD_OK;
+}
+
+static void decode_release(vamd_ctx *c) {
+  vamd_ctx::Decode &D = c->dec;
+  DevBuf *all[] = {&D.bytes, &D.plan, &D.status, &D.post_valid[0], &D.post_valid[1], &D.ilogmask[0], &D.ilogmask[1], &D.res_class[0], &D.res_class[1],
+                   &D.res_entries[0], &D.res_entries[1], &D.res_count[0], &D.res_count[1], &D.synth[0], &D.synth[1]};
+  for (DevBuf *b : all)
+    if (b->p) (void)hipFree(b->p);
+  if (D.h_plan.p) (void)hipHostFree(D.h_plan.p);
+  if (D.d_tab) (void)hipFree(D.d_tab);
+}
+
+// what the decoder refuses: the setups vamd_synth_check refuses, with its text; a setup k_unpack's walk is not safe on.
+// At first use it also builds the codebooks' decode tables, from the image as the device holds it.
+static int decode_ready(vamd_ctx *c) {
+  vamd_ctx::Decode &D = c->dec;
+  if (!D.ready) {
+    std::vector<unsigned char> image(c->image_bytes), tab;
+    HIP_TRY(c, hipMemcpy(image.data(), c->d_image, image.size(), hipMemcpyDeviceToHost));
+    std::string err;
+    if (!unpack_check_setup(image, &err)) return fail(c, VAMD_EIMPL, err.c_str());
+    UnpackP U;
+    unpack_build_tables(image, &tab, &U);
+    HIP_TRY(c, hipMalloc((void **)&D.d_tab, tab.size()));
+    HIP_TRY(c, hipMemcpy(D.d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    U.tab = D.d_tab;
+    D.U = U;
+    // (a test knob, honoured beside VAMD_TEST_KNOBS=1 only as vamd_knobs.h's are: packets a wave, 1 .. 64; profiles/r22_decode.txt)
+    const char *t = getenv("VAMD_TEST_KNOBS"), *e = getenv("VAMD_UNPACK_LANES");
+    const int lanes = t && atoi(t) == 1 && e ? atoi(e) : 0;
+    if (lanes >= 1 && lanes <= 64) D.lanes = lanes;
+    D.ready = true;
+  }
+  for (int W = 0; W < D.U.modes; W++) {
+    SynthFloorP S;
+    int r = synth_covered(c, W, &S);
+    if (r) return r;
+  }
+  return VAMD_OK;
+}
+
+static int decode_plan(vamd_ctx *c, const vamd_decode_desc *d, DecodePlan *P) {
+  if (!d) return fail(c, VAMD_EINVAL, "decode: null descriptor");
+  int r = decode_ready(c);
+  if (r) return r;
+  std::string err;
+  if (!decode_plan_build(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->nstreams, d->npackets, d->bytes, d->offset, d->stream_start, d->end_granule, P,
+                         &err))
+    return fail(c, VAMD_EINVAL, err.c_str());
+  return VAMD_OK;
+}
+
+int vamd_decode_plan(vamd_ctx *c, const vamd_decode_desc *d, int64_t *frames, int64_t *nblocks) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  DecodePlan P;
+  int r = decode_plan(c, d, &P);
+  if (r) return r;
+  for (int64_t s = 0; frames && s < d->nstreams; s++) frames[s] = P.frames[(size_t)s];
+  if (nblocks) nblocks[0] = P.nblocks[0], nblocks[1] = P.nblocks[1];
+  return VAMD_OK;
+}
+
+int vamd_decode_streams(vamd_ctx *c, const vamd_decode_desc *d, const int64_t *offset_out, float *pcm, uint8_t *status) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  DecodePlan P;
+  int r = decode_plan(c, d, &P);
+  if (r) return r;
+  const int64_t ns = d->nstreams;
+  if (ns && !status) return fail(c, VAMD_EINVAL, "decode: null status");
+  if (P.max_frames > 0 && (!offset_out || !pcm)) return fail(c, VAMD_EINVAL, "decode: null offset_out / pcm");
+  for (int64_t s = 0; s < ns; s++) {
+    if (P.frames[(size_t)s] > 0 && offset_out[s] < 0) return fail(c, VAMD_EINVAL, "decode: negative offset_out");
+    status[s] = P.status[(size_t)s];
+  }
+  const size_t nb = P.order.size();
+  if (!nb) return VAMD_OK;
+  vamd_ctx::Decode &D = c->dec;
+  const int ch = c->B.channels;
+  // the workspace
+  const int64_t byte0 = d->offset[0], nbytes = d->offset[d->npackets] - byte0;
+  const long long nwords = (long long)((nbytes + 3) / 4);
+  if ((r = dev_need(c, D.bytes, (size_t)nwords * 4 + 16))) return r;
+  if ((r = dev_need(c, D.status, nb + 16))) return r;
+  UnpackRows rows[2];
+  vamd_ctx::SynthSrc src[2];
+  for (int W = 0; W < 2; W++) {
+    const size_t n = (size_t)P.nblocks[W], n2 = (size_t)c->B.bs[W] / 2, S = (size_t)c->B.chmap[W].submaps;
+    if ((r = dev_need(c, D.post_valid[W], n * ch * 4 + 16))) return r;
+    if ((r = dev_need(c, D.ilogmask[W], n * ch * n2 + 16))) return r;
+    if ((r = dev_need(c, D.res_class[W], n * S * VAMD_RES_CLASS_STRIDE * 4 + 16))) return r;
+    if ((r = dev_need(c, D.res_entries[W], n * (size_t)c->B.res_cap[W] * 2 + 16))) return r;
+    if ((r = dev_need(c, D.res_count[W], n * S * 8 + 16))) return r;
+    if ((r = dev_need(c, D.synth[W], n * ch * n2 * 8 + 16))) return r;
+    rows[W].post_valid = (int *)D.post_valid[W].p, rows[W].ilogmask = (ilog_t *)D.ilogmask[W].p, rows[W].res_class = (int *)D.res_class[W].p;
+    rows[W].res_entries = (unsigned short *)D.res_entries[W].p, rows[W].res_count = (int *)D.res_count[W].p;
+    src[W].nb = (long)n, src[W].post_valid = rows[W].post_valid, src[W].ilogmask = rows[W].ilogmask, src[W].res_class = rows[W].res_class;
+    src[W].res_entries = rows[W].res_entries, src[W].res_count = rows[W].res_count;
+  }
+  // the plan, one piece: order | stream_start | src per size class | the packets' bits | frames | offset_out
+  Arena a;
+  const size_t o_order = a.take(4 * nb), o_start = a.take(8 * ((size_t)ns + 1)), o_src0 = a.take(8 * P.src[0].size() + 8),
+               o_src1 = a.take(8 * P.src[1].size() + 8), o_bits = a.take(16 * nb), o_frames = a.take(8 * (size_t)ns), o_off = a.take(8 * (size_t)ns);
+  const size_t plan_bytes = a.at, o_status = a.take(nb);
+  if ((r = pinned_get(c, D.h_plan, a.at, true))) return r;
+  if ((r = dev_need(c, D.plan, plan_bytes))) return r;
+  unsigned char *h = (unsigned char *)D.h_plan.p, *dp = (unsigned char *)D.plan.p;
+  memcpy(h + o_order, P.order.data(), 4 * nb);
+  memcpy(h + o_start, P.lap_start.data(), 8 * ((size_t)ns + 1));
+  if (!P.src[0].empty()) memcpy(h + o_src0, P.src[0].data(), 8 * P.src[0].size());
+  if (!P.src[1].empty()) memcpy(h + o_src1, P.src[1].data(), 8 * P.src[1].size());
+  for (size_t k = 0; k < nb; k++) {
+    const int64_t p = P.packet[k];
+    ((int64_t *)(h + o_bits))[2 * k] = 8 * (d->offset[p] - byte0);
+    ((int64_t *)(h + o_bits))[2 * k + 1] = 8 * (d->offset[p + 1] - byte0);
+  }
+  memcpy(h + o_frames, P.frames.data(), 8 * (size_t)ns);
+  for (int64_t s = 0; s < ns; s++) ((int64_t *)(h + o_off))[s] = P.frames[(size_t)s] > 0 ? offset_out[s] : 0;
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemcpyAsync(dp, h, plan_bytes, hipMemcpyHostToDevice, s));
+  if (nbytes) HIP_TRY(c, hipMemcpyAsync(D.bytes.p, d->bytes + byte0, (size_t)nbytes, hipMemcpyHostToDevice, s));
+  const int lanes = D.lanes;
+  hipLaunchKernelGGL(k_unpack, dim3((unsigned)((nb + lanes - 1) / lanes)), dim3(64), (size_t)VAMD_POSIT * lanes * 4, s, (const Bound *)c->d_bound, D.U, lanes, (long)nb,
+                     (const uint32_t *)D.bytes.p, nwords,
+                     (const long long *)(dp + o_bits), (const int *)(dp + o_order), c->B.res_cap[0], c->B.res_cap[1], c->d_dbg ? c->d_dbg + 56 : nullptr,
+                     rows[0], rows[1], (unsigned char *)D.status.p);
+  HIP_TRY(c, hipGetLastError());
+  for (int W = 0; W < 2; W++)
+    if (src[W].nb > 0 && (r = launch_synth(c, W, src[W], (float *)D.synth[W].p))) return r;
+  if (P.max_frames > 0) {
+    LapP L;
+    L.ch = ch, L.bs0 = c->B.bs[0], L.bs1 = c->B.bs[1];
+    L.win0 = c->B.xf[0].win_short, L.win1 = c->B.xf[0].win_long;
+    L.order = (const int *)(dp + o_order), L.stream_start = (const long long *)(dp + o_start);
+    L.src0 = (const long long *)(dp + o_src0), L.src1 = (const long long *)(dp + o_src1);
+    L.synth0 = (const float *)D.synth[0].p, L.synth1 = (const float *)D.synth[1].p;
+    const long per_stream = (long)((P.max_frames + 1023) / 1024);  // (as vamd_synth_streams sizes it)
+    hipLaunchKernelGGL(k_lap, dim3((unsigned)(per_stream < 1024 ? per_stream : 1024), (unsigned)(ns < 1024 ? ns : 1024)), dim3(256), 0, s, L, (long)ns,
+                       (const long long *)(dp + o_frames), (const long long *)(dp + o_off), pcm);
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipMemcpyAsync(h + o_status, D.status.p, nb, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  for (int64_t st = 0; st < ns; st++)
+    for (int64_t k = P.lap_start[(size_t)st]; k < P.lap_start[(size_t)st + 1]; k++) status[st] |= h[o_status + (size_t)k];
+  return VAMD_OK;
+}

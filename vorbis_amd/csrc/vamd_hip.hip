@@ -1,7 +1,8 @@
 // vamd_hip.hip -- libvorbis_amd.so: the C ABI of include/vorbis_amd.h over the gfx950 kernels (vamd_kernels.h: thin
-// __global__ shells around the wave-level bodies in k_*.h).  One translation unit, six files: this root with the context's
+// __global__ shells around the wave-level bodies in k_*.h).  One translation unit, seven files: this root with the context's
 // life cycle and the small getters, the context (vamd_ctx.h), and the host side in three parts by topic -- the batch calls
-// and their launch sequence (vamd_batch.h), stream planning (vamd_plan.h), the host-pointer per-block calls (vamd_block.h).
+// and their launch sequence (vamd_batch.h), stream planning (vamd_plan.h), the host-pointer per-block calls (vamd_block.h) --
+// and the packet decoder (vamd_decode.h).
 // (Round 5 took the kernels and the context out of one file of 2 700 lines; round 10 the three parts out of 2 000.)
 //
 // Launch geometry: one 64-lane wavefront per workgroup, one workgroup per
@@ -40,6 +41,8 @@
 #include "k_lpc.h"
 #include "k_bitrate.h"
 #include "k_synth.h"
+#include "k_unpack.h"
+#include "vamd_decode_plan.h"
 
 using namespace vamd;
 
@@ -136,9 +139,12 @@ int vamd_create_abi(vamd_ctx **out, const void *setup_blob, size_t blob_bytes, i
   return VAMD_OK;
 }
 
+static void decode_release(vamd_ctx *c);  // vamd_decode.h
+
 void vamd_destroy(vamd_ctx *c) {
   DeviceGuard dev_guard(c);
   if (!c) return;
+  decode_release(c);
   for (int W = 0; W < 2; W++)
     for (int i = 0; i < vamd_ctx::WS_COUNT; i++)
       if (c->ws[W][i].p) (void)hipFree(c->ws[W][i].p);
@@ -287,6 +293,7 @@ int vamd_envelope_geometry(const vamd_ctx *c, int *winlength, int *searchstep) {
 }
 
 #include "vamd_batch.h"  // workspace planning, the launch sequence, the batch entry points
+#include "vamd_decode.h" // the packet decoder: plan on the host, k_unpack ahead of k_synth and k_lap
 #include "vamd_plan.h"   // the detector over streams, the walk, the plans
 #include "vamd_block.h"  // the host-pointer calls: a block, a look-ahead's blocks, a detector call
 

@@ -1694,3 +1694,36 @@ __global__ __launch_bounds__(256) void k_lap(LapP L, long nstreams, const long l
     }
   }
 }
+
+// ---- the decoder's front half (k_unpack.h) ----
+// One lane per packet, `lanes` <= 64 packets a wave (the other lanes idle: with fewer packets a wave there are more waves
+// to hide a lane's dependent loads behind): block k of order[] (W << 30 | index inside W's batch) is unpacked from bits
+// [bits[2k], bits[2k+1]) of words[] into its own rows of its size class; status[k] = 0 or VAMD_STATUS_*.
+//   dynamic LDS: VAMD_POSIT * lanes ints (the lanes' posts)
+//   ent_row0 / ent_row1 = the row lengths of res_entries (vamd_residue_capacity) per size class
+//   dbg = the phase stopwatch's slots (null = off), marks as unpack_packet names them
+struct UnpackRows {
+  int *post_valid;
+  ilog_t *ilogmask;
+  int *res_class;
+  unsigned short *res_entries;
+  int *res_count;
+};
+__global__ __launch_bounds__(64) void k_unpack(const Bound *B, UnpackP U, int lanes, long nblocks, const uint32_t *__restrict__ words, long long nwords,
+                                               const long long *__restrict__ bits, const int *__restrict__ order, int ent_row0, int ent_row1,
+                                               unsigned long long *dbg, UnpackRows r0, UnpackRows r1, unsigned char *__restrict__ status) {
+  int *fit = (int *)vamd_smem;
+  PhaseClock pc;
+  pc.start(dbg);
+  const long k = (long)blockIdx.x * lanes + LANE;
+  if (LANE < lanes && k < nblocks) {
+    const int o = order[k], W = (o >> 30) & 1;
+    const long u = o & 0x3fffffff;
+    const UnpackRows &r = W ? r1 : r0;
+    const int ch = B->channels, n2 = B->bs[W] >> 1, S = B->chmap[W].submaps;
+    status[k] = (unsigned char)unpack_packet(*B, U, words, nwords, bits[2 * k], bits[2 * k + 1], W, r.post_valid + u * ch, r.ilogmask + u * ch * n2,
+                                             r.res_class + u * (S * VAMD_RES_CLASS_STRIDE), r.res_entries + u * (long)(W ? ent_row1 : ent_row0),
+                                             r.res_count + u * S * 2, fit + LANE, lanes, pc);
+  }
+  pc.flush();
+}
