@@ -89,6 +89,18 @@ class BlockDecoder:
         pcm = C.cast(self.vb, C.POINTER(C.POINTER(_f32p)))[0]
         return np.stack([np.ctypeslib.as_array(pcm[c], (self.bs[W],)).copy() for c in range(self.channels)])
 
+    def synthesis(self, packet):
+        """(vorbis_synthesis()'s return value, vb->pcm) for ANY packet: the block's size is the one the packet's own head
+        names (two block sizes are two modes: bit 1 of the first byte); None for vb->pcm where the return value is nonzero"""
+        o = self._op(self.n, packet)
+        self.n += 1
+        r = self.L.vorbis_synthesis(self.vb, C.byref(o))
+        if r:
+            return r, None
+        W = (packet[0] >> 1) & 1 if self.bs[0] != self.bs[1] else 0
+        pcm = C.cast(self.vb, C.POINTER(C.POINTER(_f32p)))[0]
+        return 0, np.stack([np.ctypeslib.as_array(pcm[c], (self.bs[W],)).copy() for c in range(self.channels)])
+
     def close(self):
         self.L.vorbis_block_clear(self.vb)
         self.L.vorbis_dsp_clear(self.vd)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import ref
-from tests import ogg_host, synth_host
+from tests import decode_cases, ogg_host, synth_host, unpack_host
 from tests.test_feed_decoded import Q4, feed_of, same_bits, streams
 from tests.test_unpack_cpu import MANAGED_RATES
 
@@ -142,6 +142,148 @@ def test_a_live_feeds_packets():
     finally:
         an.close()
         feed.close()
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    return unpack_host.build(tmp_path_factory.mktemp("unpack_host"))
+
+
+MUTATED_CASES, CLEAN = 192, 6  # some 3800 packets, 60 waves of k_unpack; the clean streams among the cases
+_fresh = {}
+
+
+def decode_group(an, g):
+    """one decode_streams call over a decode_cases.Group -> per stream (status, pcm [ch][frames] on the host)"""
+    got, status = an.decode_streams(g.streams, g.ends, with_status=True)
+    assert len(got) == len(g.streams) and all(t.is_cuda and t.device.index == an.device for t in got)
+    return [(int(status[s]), got[s].cpu().numpy()) for s in range(len(got))]
+
+
+def fresh(key, g):
+    """the group through a context of its own, with the environment as the suite has it; once per key"""
+    import vorbis_amd
+    if key not in _fresh:
+        an = vorbis_amd.Analyzer(g.blob)
+        try:
+            _fresh[key] = decode_group(an, g)
+        finally:
+            an.close()
+    return _fresh[key]
+
+
+def assert_same_results(a, b):
+    assert len(a) == len(b)
+    for s, ((sa, pa), (sb, pb)) in enumerate(zip(a, b)):
+        assert sa == sb and same_bits(pa, pb), (s, sa, sb, pa.shape, pb.shape)
+
+
+def mutated_group(name, n=MUTATED_CASES, clean=CLEAN):
+    return decode_cases.with_clean(decode_cases.cases(name, n), clean)
+
+
+@pytest.mark.parametrize("name", list(synth_host.SETUPS))
+def test_mutated_streams(exe, tmp_path, name):
+    """tests/test_unpack_cpu.py::test_mutated_streams on the GPU, twice the cases and six clean streams among them in ONE
+    call, so that mutated and clean packets share waves: lanes that leave early with a status beside lanes that go on,
+    divergent serial decodes, the posts in LDS a wave's lanes apart.  Against the reference as on the host; and the
+    statuses are the host build's.  Seen: 0, STATUS_TRUNCATED and, in four setups once each, STATUS_NOTAUDIO; never
+    STATUS_BADCODE."""
+    g = mutated_group(name)
+    assert g.cls[-1] != "clean" and g.where[-1][1] == len(g.streams[-1]) - 1  # the group's final bytes are a mutated packet
+    got = fresh((name, MUTATED_CASES), g)
+    decode_cases.check(g, got)
+    host = unpack_host.host_decode_streams(exe, tmp_path, g.blob, g.streams, g.ends, g.channels)
+    assert [st for st, _ in got] == [st for st, _ in host]
+
+
+@pytest.mark.parametrize("lanes", [1, 5, 63])
+def test_packets_a_wave(lanes, monkeypatch):
+    """the test knob VAMD_UNPACK_LANES -- k_unpack's grid, its LDS and the stride of a lane's posts: the same statuses and
+    the same bits as with 64 packets a wave, which are the reference's"""
+    import vorbis_amd
+    for name in ("44k_stereo_q4", "44k_51_q3"):
+        g = mutated_group(name, 48, 2)
+        want = fresh((name, 48), g)  # (before the knob is set)
+        decode_cases.check(g, want)
+        with monkeypatch.context() as m:
+            m.setenv("VAMD_TEST_KNOBS", "1")
+            m.setenv("VAMD_UNPACK_LANES", str(lanes))
+            an = vorbis_amd.Analyzer(g.blob)
+            try:
+                assert "VAMD_UNPACK_LANES=%d" % lanes in an.config_string().split()
+                got = decode_group(an, g)
+            finally:
+                an.close()
+        assert_same_results(got, want)
+
+
+def test_end_granules():
+    """tests/test_unpack_cpu.py::test_end_granules on the GPU: thirty streams in one group, the counts that are no multiple
+    of four in the tail of k_lap's four-frames-a-thread loop"""
+    g = decode_cases.end_granules()
+    got = fresh("ends", g)
+    decode_cases.check(g, got)
+    assert tuple(pcm.shape[1] for _, pcm in got[:10]) == decode_cases.END_COUNTS_9000
+
+
+def test_many_streams():
+    """more streams than k_lap has rows (1024: it strides over the rest), through decode_run: every stream at its offset"""
+    import vorbis_amd
+    g = decode_cases.short_streams(1100)
+    ch = g.channels
+    an = vorbis_amd.Analyzer(g.blob)
+    try:
+        pcm, frames, off, status = an.decode_run(an.decode_prepare(g.streams, g.ends))
+        h = pcm.cpu().numpy()
+    finally:
+        an.close()
+    assert len(frames) == 1100 and not status.any()
+    assert [int(f) for f in frames[:8]] == list(synth_host.SHORT_LENGTHS)
+    for s in range(1100):
+        want = g.want(s)
+        got = h[int(off[s]):int(off[s]) + ch * int(frames[s])].reshape(ch, int(frames[s]))
+        assert same_bits(got, want), (s, got.shape, want.shape)
+
+
+def test_context_reuse():
+    """one context over a large group, a group of one 20-frame stream (its bytes go where the large group's lay: the
+    workspace is kept, and exactly the group's bytes are copied), the large group again: what contexts of their own give.
+    Then decode_run into a caller's tensor: the planned floats, nothing behind them, and no tensor too small."""
+    import torch
+    import vorbis_amd
+    big = mutated_group(Q4)
+    want_big = fresh((Q4, MUTATED_CASES), big)
+    decode_cases.check(big, want_big)
+    short = decode_cases.short_streams(8)
+    one = decode_cases.Group(Q4, short.blob, short.headers, short.channels)
+    one.streams, one.ends, one.cls, one.where = short.streams[1:2], short.ends[1:2], ["clean"], [None]
+    assert one.want(0).shape == (2, 20)
+    want_one = fresh("one", one)
+    decode_cases.check(one, want_one)
+    an = vorbis_amd.Analyzer(big.blob)
+    try:
+        first = decode_group(an, big)
+        small = decode_group(an, one)
+        again = decode_group(an, big)
+        assert_same_results(first, want_big)
+        assert_same_results(small, want_one)
+        assert_same_results(again, want_big)
+        prep = an.decode_prepare(big.streams, big.ends)
+        pcm, frames, off, status = an.decode_run(prep)
+        total = int(frames.sum()) * big.channels
+        assert total > 0 and pcm.numel() >= total
+        sentinel = -12345.678
+        t = torch.full((total + 64,), sentinel, dtype=torch.float32, device=pcm.device)
+        pcm2, frames2, off2, status2 = an.decode_run(prep, pcm=t)
+        assert pcm2.data_ptr() == t.data_ptr() and np.array_equal(frames, frames2) and np.array_equal(off, off2) and np.array_equal(status, status2)
+        h = t.cpu().numpy()
+        assert np.array_equal(h[:total].view(np.uint32), pcm[:total].cpu().numpy().view(np.uint32))
+        assert np.array_equal(h[total:], np.full(64, sentinel, np.float32))
+        with pytest.raises(ValueError):
+            an.decode_run(prep, pcm=torch.empty(total - 1, dtype=torch.float32, device=pcm.device))
+    finally:
+        an.close()
 
 
 def test_flagged_streams_and_bad_descriptors():

@@ -6,12 +6,14 @@ one-lane emulation's own tensors and the reference decoder, bit for bit (floats 
    and synth_block over them is vb->pcm of vorbis_synthesis() on the same packet;
 2. whole streams: plan from the packets' mode bits, unpack, synth, lap against the reference decoder's output;
 3. malformed input: every packet of a stream cut at every byte length, seeded bit flips, random bytes -- a status or rows
-   inside the bounds the synthesis walk relies on, under the sanitisers."""
+   inside the bounds the synthesis walk relies on, under the sanitisers;
+4. mutated streams and the end granule's edges (tests/decode_cases.py, the cases tests/test_decode_gpu.py runs on the GPU):
+   what a mutated packet decodes to where libvorbis decodes it in full, and the last block's cut, against the reference."""
 import numpy as np
 import pytest
 
 from oracle import ref
-from tests import ogg_host, synth_host, unpack_host
+from tests import decode_cases, ogg_host, synth_host, unpack_host
 from tests.synth_host import RES_CLASS_STRIDE
 
 pytestmark = pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built")
@@ -142,6 +144,29 @@ def test_managed_streams(exe, tmp_path):
     for s, (packets, granules) in enumerate(streams):
         if s not in flagged:
             assert same_bits(got[s][1], ogg_host.reference_decode(headers + packets, granules)), s
+
+
+MUTATED_CASES = 96
+
+
+@pytest.mark.parametrize("name", list(synth_host.SETUPS))
+def test_mutated_streams(exe, tmp_path, name):
+    """packets no encoder wrote (tests/decode_cases.py: one packet of a stream with a bit flipped or its tail replaced),
+    each classified by the reference alone, and what the decoder makes of them held against the reference: a packet
+    libvorbis decodes without reaching its end decodes to the same bits and is not flagged, a packet that is no audio packet
+    is flagged as one, a packet libvorbis ran out of is flagged and nothing is compared.  The statuses seen over the eight
+    setups: 0, STATUS_TRUNCATED, and STATUS_NOTAUDIO once (44k_stereo_q4); never STATUS_BADCODE -- the books are complete
+    trees, the phrase books have exactly nparts^dim entries."""
+    g = decode_cases.cases(name, MUTATED_CASES)
+    decode_cases.check(g, unpack_host.host_decode_streams(exe, tmp_path, g.blob, g.streams, g.ends, g.channels))
+
+
+def test_end_granules(exe, tmp_path):
+    """the plan's cut of the last block against vorbis_synthesis_blockin's, at its edges (tests/decode_cases.py)"""
+    g = decode_cases.end_granules()
+    got = unpack_host.host_decode_streams(exe, tmp_path, g.blob, g.streams, g.ends, g.channels)
+    decode_cases.check(g, got)
+    assert tuple(pcm.shape[1] for _, pcm in got[:10]) == decode_cases.END_COUNTS_9000
 
 
 @pytest.mark.parametrize("name", ["44k_stereo_q4", "44k_51_q3"])

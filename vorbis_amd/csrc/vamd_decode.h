@@ -51,10 +51,7 @@ static int decode_ready(vamd_ctx *c) {
     HIP_TRY(c, hipMemcpy(D.d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice));
     U.tab = D.d_tab;
     D.U = U;
-    // (a test knob, honoured beside VAMD_TEST_KNOBS=1 only as vamd_knobs.h's are: packets a wave, 1 .. 64; profiles/r22_decode.txt)
-    const char *t = getenv("VAMD_TEST_KNOBS"), *e = getenv("VAMD_UNPACK_LANES");
-    const int lanes = t && atoi(t) == 1 && e ? atoi(e) : 0;
-    if (lanes >= 1 && lanes <= 64) D.lanes = lanes;
+    D.lanes = c->K.unpack_lanes;  // (a test knob, vamd_knobs.h: 64 unless set)
     D.ready = true;
   }
   for (int W = 0; W < D.U.modes; W++) {

@@ -47,6 +47,7 @@ struct Knobs {
   long feed_slice = 2048;        // VAMD_FEED_SLICE: blocks per slice of a bitrate-managed vamd_feed group (small: many slices)
   long feed_out_bytes = 0;       // VAMD_FEED_OUT_BYTES: a vamd_feed lane's packet arena to start with (small: it has to grow; 0: the feed's own)
   long plan_window = 0;          // VAMD_PLAN_WINDOW: marks in the stream walk's LDS window (small: many refills; raised to the walk's minimum; 0: default)
+  int unpack_lanes = 64;         // VAMD_UNPACK_LANES: packets a wave of k_unpack (1..64, anything else: 64; profiles/r22_decode.txt)
 };
 
 inline Knobs read_knobs() {
@@ -89,6 +90,8 @@ inline Knobs read_knobs() {
       k.feed_slice = num("VAMD_FEED_SLICE", k.feed_slice);
       k.feed_out_bytes = num("VAMD_FEED_OUT_BYTES", 0);
       k.plan_window = num("VAMD_PLAN_WINDOW", 0);
+      const long lanes = num("VAMD_UNPACK_LANES", k.unpack_lanes);
+      if (lanes >= 1 && lanes <= 64) k.unpack_lanes = (int)lanes;
     }
     return k;
   }
@@ -103,11 +106,11 @@ inline void knobs_string(const Knobs &k, char *buf, size_t cap) {
              " VAMD_NO_OVERLAP=%d VAMD_COUPLE_BAND_LOG2=%s%d VAMD_XF_WAVES_CAP=%d VAMD_RES_TEAM_MAX=%ld VAMD_RES_IN_LDS=%d VAMD_PACK_PAIR_MAX=%ld VAMD_PACK_PER_PACKET=%d"
              " VAMD_FOLD_SEPARATE=%d VAMD_CHASE_WAVE_MAX=%ld VAMD_MASKS_SEPARATE=%d VAMD_NOISE_TEAMS=%d VAMD_NOISE_WAVES=%d VAMD_FLOOR_LDS_PAD=%ld"
              " VAMD_FLOOR_PAIR_MIN=%ld VAMD_FLOOR_PAIR_W=%d VAMD_STAGE_COPIES=%d VAMD_ENV_UNTILED=%d VAMD_XF_VARIANT=%d VAMD_FAIL_ENVELOPE_AFTER=%ld"
-             " VAMD_FAIL_ENCODE_AFTER=%ld VAMD_FEED_SLICE=%ld VAMD_FEED_OUT_BYTES=%ld VAMD_PLAN_WINDOW=%ld VAMD_CHASE_LDS_PAD=%ld",
+             " VAMD_FAIL_ENCODE_AFTER=%ld VAMD_FEED_SLICE=%ld VAMD_FEED_OUT_BYTES=%ld VAMD_PLAN_WINDOW=%ld VAMD_CHASE_LDS_PAD=%ld VAMD_UNPACK_LANES=%d",
              (int)k.no_overlap, k.couple_band_set ? "" : "unset:", k.couple_band_log2, k.xf_waves_cap, k.res_team_max, (int)k.res_in_lds,
              k.pack_pair_max, (int)k.pack_per_packet, (int)k.fold_separate, k.chase_wave_max, (int)k.masks_separate, k.noise_teams, k.noise_waves, k.floor_lds_pad,
              k.floor_pair_min, k.floor_pair_w, (int)k.stage_copies, (int)k.env_untiled, k.xf_variant, k.fail_envelope_after,
-             k.fail_encode_after, k.feed_slice, k.feed_out_bytes, k.plan_window, k.chase_lds_pad);
+             k.fail_encode_after, k.feed_slice, k.feed_out_bytes, k.plan_window, k.chase_lds_pad, k.unpack_lanes);
 }
 
 }  // namespace vamd
