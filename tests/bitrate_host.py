@@ -3,9 +3,10 @@ header itself, not a sibling of it, built -ffp-contract=off as the library is.  
 ctypes struct, and the packet the manager hands out rebuilt from a candidate."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from tests import hostbuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PACKETBLOBS = 15
@@ -100,14 +101,8 @@ def blocksizes(blob):
     return [int(x) for x in np.frombuffer(bytes(blob[24:32]), np.int32)]
 
 
-def build(outdir):
-    src = os.path.join(outdir, "walk_shim.cpp")
-    lib = os.path.join(outdir, "libwalk.so")
-    with open(src, "w") as f:
-        f.write(_SHIM)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"), src, "-o", lib])
-    return lib
+def build():
+    return hostbuild.shim("walk", _SHIM)
 
 
 class HostWalk:

@@ -11,12 +11,16 @@ import os
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SETUPS = {"44k_stereo_q4": (2, 44100, 0.4), "44k_stereo_q9": (2, 44100, 0.9), "44k_stereo_q1": (2, 44100, 0.1),
-          "44k_mono_q5": (1, 44100, 0.5)}
+# (channels, rate, quality, coupled): every setup the tests build a reference encoder for
+ENCODERS = {"44k_stereo_q4": (2, 44100, 0.4, True), "44k_stereo_q9": (2, 44100, 0.9, True), "44k_stereo_q1": (2, 44100, 0.1, True),
+            "44k_stereo_qm1": (2, 44100, -0.1, True), "44k_mono_q5": (1, 44100, 0.5, True), "44k_51_q3": (6, 44100, 0.3, True),
+            "8k_mono_q3": (1, 8000, 0.3, True), "44k_stereo_q4_uncoupled": (2, 44100, 0.4, False)}
+# (channels, rate, quality) of the setups Checker takes
+SETUPS = {k: ENCODERS[k][:3] for k in ("44k_stereo_q4", "44k_stereo_q9", "44k_stereo_q1", "44k_mono_q5")}
 
 # the 5.1 layout (two submaps, four coupling steps; q 0.3 keeps coupling and noise normalisation both live).
 # Kept apart from SETUPS (the fixture carries the decisions and the packet, not the float taps).
-SURROUND = {"44k_51_q3": (6, 44100, 0.3)}
+SURROUND = {k: ENCODERS[k][:3] for k in ("44k_51_q3",)}
 
 FLOAT_KEYS = ("mdct_raw", "logfft", "logmdct", "noise", "tone", "logmask", "mdct", "local_ampmax")
 INT_KEYS = ("post_valid", "ilogmask", "iwork", "nonzero")

@@ -9,7 +9,7 @@ packet replaced, the kind of mutation cycling over
   1  one bit flipped inside the first 12 bytes (the head and the floors),
   2  every byte from a random position >= 1 to the end replaced by random bytes
 (the mode bits are not spared; the last case mutates the last packet of its stream, so that a group's final bytes are a
-mutated packet).  The mutated packet's class, from vorbis_synthesis() on it alone (synth_host.BlockDecoder.synthesis):
+mutated packet).  The mutated packet's class, from vorbis_synthesis() on it alone (ref_host.BlockDecoder.synthesis):
   notaudio  it returns nonzero;
   complete  the packet alone and the packet followed by 16 more bytes -- of 0x00, of 0xff, and of the other fills of
             PADS -- give the same vb->pcm bits: the reference never needed a bit beyond the packet's end;
@@ -18,7 +18,10 @@ mutated packet).  The mutated packet's class, from vorbis_synthesis() on it alon
 Everything is deterministic in (setup, cases, seed) and computed once per process."""
 import numpy as np
 
-from tests import ogg_host, synth_host
+from tests import ref_host
+from tests.feed_cases import same_bits
+from tests.signals import gated_noise
+from tests.synth_host import SETUPS, SHORT_LENGTHS
 from tests.unpack_host import STATUS_BADCODE, STATUS_NOTAUDIO, STATUS_TRUNCATED
 
 KINDS = ("flip", "flip_head", "random_tail")
@@ -32,32 +35,27 @@ PADS = tuple(bytes([v]) * PAD for v in (0x00, 0xff, 0x55, 0xaa)) + tuple(
 _groups, _bases = {}, {}
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def base_frames(name, v):
     """some 20 packets: at 44.1 kHz 9000 + 100 v frames (19 or 20 packets of 256 / 2048, 11 of 512 / 4096), both block
     sizes among them; the 8 kHz setup has one block size, 512, and 5000 + 100 v frames are 21 packets of it"""
-    rate = synth_host.SETUPS[name][1]
+    rate = SETUPS[name][1]
     return (9000 if rate >= 44100 else 5000) + 100 * v
 
 
 def base_streams(name, seed):
     """-> (setup blob, headers, block sizes, [(packets, end granule)] x 4)"""
     if (name, seed) not in _bases:
-        enc = synth_host.encoder(name)
+        enc = ref_host.encoder(name)
         out, Ws = [], set()
         for v in range(4):
-            e = synth_host.encoder(name)
-            recs = e.encode_stream(synth_host.gated_noise(e.channels, e.rate, base_frames(name, v), 1000 * seed + v))
+            e = ref_host.encoder(name)
+            recs = e.encode_stream(gated_noise(e.channels, e.rate, base_frames(name, v), 1000 * seed + v))
             out.append(([r["packet"] for r in recs], recs[-1]["granulepos"]))
             Ws |= {r["W"] for r in recs}
             assert recs[-1]["granulepos"] == base_frames(name, v) and len(recs) >= 8
         bs = (enc.blocksize(0), enc.blocksize(1))
         assert bs[0] == bs[1] or Ws == {0, 1}, (name, Ws)  # a setup with two block sizes: both are in the base streams
-        _bases[name, seed] = (enc.pack_setup(), synth_host.encoder_headers(synth_host.encoder(name)), bs, out)
+        _bases[name, seed] = (enc.pack_setup(), ref_host.encoder_headers(ref_host.encoder(name)), bs, out)
     return _bases[name, seed]
 
 
@@ -101,7 +99,7 @@ class Group:
         another block size.  Once per distinct stream."""
         key = (tuple(self.streams[s]), self.ends[s])
         if key not in self._want:
-            w = ogg_host.reference_decode(self.headers + self.streams[s], [-1] * (len(self.streams[s]) - 1) + [self.ends[s]])
+            w = ref_host.reference_decode(self.headers + self.streams[s], [-1] * (len(self.streams[s]) - 1) + [self.ends[s]])
             w.setflags(write=False)
             self._want[key] = w
         return self._want[key]
@@ -115,9 +113,9 @@ def cases(name, n, seed=1):
     if (name, n, seed) in _groups:
         return _groups[name, n, seed]
     blob, headers, bs, base = base_streams(name, seed)
-    g = Group(name, blob, headers, synth_host.SETUPS[name][0])
+    g = Group(name, blob, headers, SETUPS[name][0])
     rng = np.random.default_rng(seed)
-    dec = synth_host.BlockDecoder(headers)
+    dec = ref_host.BlockDecoder(headers)
     for s in range(n):
         packets, end = base[s % 4]
         kind = KINDS[s % 3]
@@ -166,13 +164,13 @@ def end_granules(name="44k_stereo_q4"):
     on the last packet and -1 on the others; .F and .step per stream"""
     if ("ends", name) in _groups:
         return _groups["ends", name]
-    enc = synth_host.encoder(name)
+    enc = ref_host.encoder(name)
     bs = (enc.blocksize(0), enc.blocksize(1))
-    g = Group(name, enc.pack_setup(), synth_host.encoder_headers(synth_host.encoder(name)), enc.channels)
+    g = Group(name, enc.pack_setup(), ref_host.encoder_headers(ref_host.encoder(name)), enc.channels)
     g.F, g.step = [], []
     for frames in END_FRAMES:
-        e = synth_host.encoder(name)
-        recs = e.encode_stream(synth_host.gated_noise(e.channels, e.rate, frames, frames))
+        e = ref_host.encoder(name)
+        recs = e.encode_stream(gated_noise(e.channels, e.rate, frames, frames))
         packets, Ws = [r["packet"] for r in recs], [r["W"] for r in recs]
         assert recs[-1]["granulepos"] == frames and len(packets) >= 2
         F = sum(bs[a] // 4 + bs[b] // 4 for a, b in zip(Ws[:-1], Ws[1:]))
@@ -187,16 +185,16 @@ def end_granules(name="44k_stereo_q4"):
 
 
 def short_streams(count, name="44k_stereo_q4"):
-    """count streams: the eight of synth_host.SHORT_LENGTHS, a few packets each, again and again -> a Group (cls "clean";
+    """count streams: the eight of SHORT_LENGTHS, a few packets each, again and again -> a Group (cls "clean";
     the reference decodes each distinct one once)"""
     if ("short", name, count) in _groups:
         return _groups["short", name, count]
-    enc = synth_host.encoder(name)
-    g = Group(name, enc.pack_setup(), synth_host.encoder_headers(synth_host.encoder(name)), enc.channels)
+    enc = ref_host.encoder(name)
+    g = Group(name, enc.pack_setup(), ref_host.encoder_headers(ref_host.encoder(name)), enc.channels)
     eight = []
-    for frames in synth_host.SHORT_LENGTHS:
-        e = synth_host.encoder(name)
-        recs = e.encode_stream(synth_host.gated_noise(e.channels, e.rate, frames, frames))
+    for frames in SHORT_LENGTHS:
+        e = ref_host.encoder(name)
+        recs = e.encode_stream(gated_noise(e.channels, e.rate, frames, frames))
         eight.append(([r["packet"] for r in recs], recs[-1]["granulepos"]))
     for s in range(count):
         g.streams.append(eight[s % 8][0]), g.ends.append(eight[s % 8][1]), g.cls.append("clean"), g.where.append(None)

@@ -5,12 +5,11 @@
   over a host buffer, through the vector-load path or through element loads alone), and the host's range check.
 * The grid of source layouts both suites walk: where the streams of a group lie in one flat buffer, with which strides."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import hostbuild
+
 
 SRC_S16, SRC_F32, SRC_F16, SRC_BF16 = 0, 1, 2, 3
 ELEM_BYTES = {SRC_S16: 2, SRC_F32: 4, SRC_F16: 2, SRC_BF16: 2}
@@ -49,14 +48,8 @@ extern "C" int extent(int ch, long long frames, long long cstride, long long fst
 """
 
 
-def build(outdir):
-    src = os.path.join(outdir, "feed_source_shim.cpp")
-    lib = os.path.join(outdir, "libfeed_source_host.so")
-    with open(src, "w") as f:
-        f.write(_SHIM)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"), src, "-o", lib])
-    return lib
+def build():
+    return hostbuild.shim("feed_source", _SHIM)
 
 
 def aligned(n, dtype, align=64, offset=0):

@@ -3,12 +3,11 @@ stream (vamd_feed_host.h: live_piece, live_planned) compiled with the host compi
 themselves, built -ffp-contract=off as the library is.  With the host-compiled stream ends and detector of tests/emul it
 chains one stream's live sequence as run_group_live and vamd_live_plan do: the bookkeeping is the mirror's, not restated."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import hostbuild
+
 
 _SHIM = r"""
 #include <vector>
@@ -64,14 +63,8 @@ extern "C" int mirror_planned(void *m, int closed, long long shift, long retain)
 """
 
 
-def build(outdir):
-    src = os.path.join(outdir, "live_shim.cpp")
-    lib = os.path.join(outdir, "liblive.so")
-    with open(src, "w") as f:
-        f.write(_SHIM)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"), "-I" + os.path.join(ROOT, "tests", "emul"), src, "-o", lib])
-    return lib
+def build():
+    return hostbuild.shim("live", _SHIM)
 
 
 class LiveWalk:

@@ -3,12 +3,11 @@ with the host compiler, for the tests: the shipped header itself, as tests/live_
 VAMD_WINDOW_CHECK counts the reads that fall outside the window instead of aborting, and the window's buffer has a margin on
 both sides so that such a read stays inside the test's own memory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import hostbuild
+
 
 _SHIM = r"""
 #include <vector>
@@ -66,14 +65,8 @@ extern "C" void pw_walk_window(const unsigned char *f1, long split, const unsign
 """
 
 
-def build(outdir):
-    src = os.path.join(outdir, "plan_window_shim.cpp")
-    lib = os.path.join(outdir, "libplanwindow.so")
-    with open(src, "w") as f:
-        f.write(_SHIM)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"), "-I" + os.path.join(ROOT, "tests", "emul"), src, "-o", lib])
-    return lib
+def build():
+    return hostbuild.shim("plan_window", _SHIM)
 
 
 class Walk:

@@ -12,11 +12,9 @@ import numpy as np
 import pytest
 
 from tests import checker
+from tests.feed_cases import ABI, LIB
 
 ROOT = checker.ROOT
-LIB = os.path.join(ROOT, "vorbis_amd", "libvorbis_amd.so")
-# VAMD_ABI_VERSION of the header: what a caller compiled against it hands vamd_create() (the macro does it for C callers)
-ABI = int(re.search(r"#define VAMD_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "vorbis_amd.h")).read()).group(1))
 
 
 def declared_symbols():

@@ -14,8 +14,8 @@ pytestmark = pytest.mark.skipif(not ref.available(), reason="oracle/_ref not bui
 
 
 @pytest.fixture(scope="module")
-def walk_lib(tmp_path_factory):
-    return bh.build(str(tmp_path_factory.mktemp("walk")))
+def walk_lib():
+    return bh.build()
 
 
 def run_config(lib, ch, rates, kind, seconds=4.0, seed=7):

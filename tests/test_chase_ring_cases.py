@@ -14,27 +14,15 @@ program only.  It decides no step anywhere above -- the program fails if it does
 argues: with linesper <= ring the guard is unreachable, and the library is built WITHOUT it.  That the counter works is
 shown on windows of 16 lines over 8 slots, a pair the library never runs, where it must move.
 """
-import os
-import subprocess
-
 import pytest
 
-from tests import checker
-
-ROOT = checker.ROOT
+from tests import hostbuild
 
 
 @pytest.mark.parametrize("prefetch", [0, 1])
-def test_ring_of_8_and_16_against_the_plain_walk(tmp_path, prefetch):
+def test_ring_of_8_and_16_against_the_plain_walk(prefetch):
     """prefetch: VAMD_CHASE_PREFETCH, how the walk fetches its row (0 as shipped: everything; 1, the earlier form: the seeded rows)."""
-    exe = str(tmp_path / "chase_ring_cases")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-ffp-contract=off", "-Wno-unknown-pragmas", "-DVAMD_CHASE_PREFETCH=%d" % prefetch]
-                          + (["-DCHASE_CASES_SEEDED_ONLY"] if prefetch else [])
-                          + ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"),
-                           "-I" + os.path.join(ROOT, "tests", "emul"),
-                           os.path.join(ROOT, "tests", "c", "chase_ring_cases.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0 and r.stdout.rstrip().endswith(": ok"), r.stdout[-4000:] + r.stderr[-4000:]
-    assert "guard: decided 0 steps" in r.stdout
+    exe = hostbuild.program("chase_ring_cases.cpp", ["-DVAMD_CHASE_PREFETCH=%d" % prefetch] + (["-DCHASE_CASES_SEEDED_ONLY"] if prefetch else []))
+    stdout = hostbuild.run_ok(exe)
+    print(stdout)
+    assert "guard: decided 0 steps" in stdout

@@ -50,7 +50,7 @@ def references(tmp_path_factory):
     """The file with every shape's input and checker taps (one per distinct signal block), written once."""
     if "path" not in _ref_file:
         import vorbis_amd
-        from tests.test_floor_paths import chk_for
+        from tests.feed_cases import chk_for
         out = {}
         for name, W, nb in SHAPES:
             if (name, W) in out:

@@ -1,15 +1,15 @@
 """GPU: the packet decoder (vamd_decode_plan / vamd_decode_streams; Analyzer.decode_streams) -- audio packets in host
 memory to PCM on the device, k_unpack ahead of k_synth and k_lap -- against libvorbis' decoder over the same packets with
-their granule positions (tests/ogg_host.py), bit for bit.  The packets are the reference encoder's, a VBR decoded feed's, a
+their granule positions (tests/ref_host.py), bit for bit.  The packets are the reference encoder's, a VBR decoded feed's, a
 bitrate-managed feed's and a live feed's; the malformed cases are ones tests/test_unpack_cpu.py has taken through the same
 code on the host."""
 import numpy as np
 import pytest
 
 from oracle import ref
-from tests import decode_cases, ogg_host, synth_host, unpack_host
-from tests.test_feed_decoded import Q4, feed_of, same_bits, streams
-from tests.test_unpack_cpu import MANAGED_RATES
+from tests import decode_cases, ref_host, synth_host, unpack_host
+from tests.feed_cases import Q4, decoded_feed_of as feed_of, run_live, same_bits
+from tests.signals import MANAGED_RATES, gated_noise, gated_streams as streams
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built")]
 EINVAL = -131
@@ -17,14 +17,14 @@ EINVAL = -131
 
 def analyzer(name):
     import vorbis_amd
-    return vorbis_amd.Analyzer(synth_host.encoder(name).pack_setup())
+    return vorbis_amd.Analyzer(ref_host.encoder(name).pack_setup())
 
 
 def reference_streams(name, parts):
     """the reference encoder's packets of [frames, ch] streams -> per stream (packets, granules)"""
     out = []
     for p in parts:
-        recs = synth_host.encoder(name).encode_stream(np.ascontiguousarray(p.T))
+        recs = ref_host.encoder(name).encode_stream(np.ascontiguousarray(p.T))
         out.append(([r["packet"] for r in recs], [r["granulepos"] for r in recs]))
     return out
 
@@ -35,7 +35,7 @@ def check(an, headers, rows, got, status, skip=()):
         assert got[s].is_cuda and got[s].device.index == an.device
         if s in skip:
             continue
-        want = ogg_host.reference_decode(headers + packets, granules)
+        want = ref_host.reference_decode(headers + packets, granules)
         g = got[s].cpu().numpy()
         assert status[s] == 0 and same_bits(g, want), "stream %d: %s against %s, %d samples differ" % (
             s, g.shape, want.shape, int((g.view(np.uint32) != want.view(np.uint32)).sum()) if g.shape == want.shape else -1)
@@ -51,7 +51,7 @@ def test_decode_equals_the_reference_decoder(name):
     finally:
         an.close()
     assert [tuple(g.shape) for g in got] == [(p.shape[1], len(p)) for p in parts]
-    check(an, synth_host.encoder_headers(synth_host.encoder(name)), rows, got, status)
+    check(an, ref_host.encoder_headers(ref_host.encoder(name)), rows, got, status)
 
 
 def test_short_streams():
@@ -62,7 +62,7 @@ def test_short_streams():
     try:
         got, status = an.decode_streams([p for p, _ in rows], [g[-1] for _, g in rows], with_status=True)
         assert [tuple(g.shape) for g in got] == [(2, n) for n in synth_host.SHORT_LENGTHS]
-        check(an, synth_host.encoder_headers(synth_host.encoder(Q4)), rows, got, status)
+        check(an, ref_host.encoder_headers(ref_host.encoder(Q4)), rows, got, status)
         # no packets, one packet: no frames; without a granule position the last block is not cut
         none, st = an.decode_streams([[], rows[3][0][:1], rows[3][0]], with_status=True)
         assert [tuple(g.shape) for g in none[:2]] == [(2, 0), (2, 0)] and not st.any()
@@ -75,8 +75,8 @@ def test_module_level_decode():
     import vorbis_amd
     parts = streams(Q4, (0.2,), 31)
     rows = reference_streams(Q4, parts)
-    got = vorbis_amd.decode(synth_host.encoder(Q4).pack_setup(), [rows[0][0]], [rows[0][1][-1]])
-    want = ogg_host.reference_decode(synth_host.encoder_headers(synth_host.encoder(Q4)) + rows[0][0], rows[0][1])
+    got = vorbis_amd.decode(ref_host.encoder(Q4).pack_setup(), [rows[0][0]], [rows[0][1][-1]])
+    want = ref_host.reference_decode(ref_host.encoder_headers(ref_host.encoder(Q4)) + rows[0][0], rows[0][1])
     assert same_bits(got[0].cpu().numpy(), want)
 
 
@@ -118,7 +118,7 @@ def test_a_managed_feeds_packets():
         flagged = [s for s in range(len(parts)) if status[s]]
         assert all(status[s] == vorbis_amd.STATUS_TRUNCATED and got[s].shape == (2, 0) for s in flagged)
         assert 2 * len(flagged) <= len(parts), flagged
-        check(an, synth_host.encoder_headers(ref.RefEncoder(2, 44100, managed=MANAGED_RATES)), pairs, got, status, skip=flagged)
+        check(an, ref_host.encoder_headers(ref.RefEncoder(2, 44100, managed=MANAGED_RATES)), pairs, got, status, skip=flagged)
     finally:
         an.close()
         feed.close()
@@ -127,10 +127,9 @@ def test_a_managed_feeds_packets():
 def test_a_live_feeds_packets():
     """a live feed in pieces (for which the feed has no decoded signal either)"""
     import vorbis_amd
-    from tests.test_feed_live import run_live
     parts = streams(Q4, (0.3, 0.5), 41)
     cuts = [[5000, 0, len(parts[0]) - 5000], [1, 9000, len(parts[1]) - 9001]]
-    blob = synth_host.encoder(Q4).pack_setup()
+    blob = ref_host.encoder(Q4).pack_setup()
     feed = vorbis_amd.Feed(blob, lanes_per_device=1, max_streams=2, max_frames=32000, fmt=vorbis_amd.FEED_F32, write_frames=1024)
     an = vorbis_amd.Analyzer(blob)
     try:
@@ -138,15 +137,15 @@ def test_a_live_feeds_packets():
         pairs = [([p for p, _, _, _ in row], [g for _, g, _, _ in row]) for row in rows]
         got, status = an.decode_streams([p for p, _ in pairs], [g[-1] for _, g in pairs], with_status=True)
         assert [tuple(g.shape) for g in got] == [(2, len(p)) for p in parts]
-        check(an, synth_host.encoder_headers(synth_host.encoder(Q4)), pairs, got, status)
+        check(an, ref_host.encoder_headers(ref_host.encoder(Q4)), pairs, got, status)
     finally:
         an.close()
         feed.close()
 
 
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return unpack_host.build(tmp_path_factory.mktemp("unpack_host"))
+def exe():
+    return unpack_host.build()
 
 
 MUTATED_CASES, CLEAN = 192, 6  # some 3800 packets, 60 waves of k_unpack; the clean streams among the cases
@@ -290,12 +289,12 @@ def test_flagged_streams_and_bad_descriptors():
     """tests/test_unpack_cpu.py::test_flagged_streams on the GPU; then a descriptor whose offsets are not monotone: EINVAL,
     nothing launched, and the context decodes the next group as before"""
     import vorbis_amd
-    x = np.ascontiguousarray(synth_host.gated_noise(2, 44100, 20000, 3).T)
+    x = np.ascontiguousarray(gated_noise(2, 44100, 20000, 3).T)
     (packets, granules), = reference_streams(Q4, [x])
     assert len(packets) > 4 and len(packets[2]) > 5
     cut = packets[:2] + [packets[2][:5]] + packets[3:]
     typed = packets[:1] + [bytes([packets[1][0] ^ 1]) + packets[1][1:]] + packets[2:]
-    want = ogg_host.reference_decode(synth_host.encoder_headers(synth_host.encoder(Q4)) + packets, granules)
+    want = ref_host.reference_decode(ref_host.encoder_headers(ref_host.encoder(Q4)) + packets, granules)
     an = analyzer(Q4)
     try:
         got, status = an.decode_streams([packets, cut, typed, packets], [granules[-1]] * 4, with_status=True)

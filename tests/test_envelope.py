@@ -21,6 +21,8 @@ import vorbis_amd
 from vorbis_amd import EnvelopeState, envelope_marks
 from oracle import port, ref
 from tests import checker
+from tests.feed_cases import check_state
+from tests.signals import gated
 
 ROOT = checker.ROOT
 GOLDEN = ("44k_stereo_q4", "44k_mono_q5")
@@ -38,23 +40,6 @@ def golden(name):
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def gated(ch, frames, seed, period=5000, on=700):
-    rng = np.random.default_rng(seed)
-    t = np.arange(frames)
-    g = np.where((t % period) < on, 0.6, 0.004).astype(np.float32)
-    return ((rng.random((ch, frames), dtype=np.float32) - 0.5) * 2 * g).astype(np.float32)
-
-
-def check_state(st, want, ch):
-    """EnvelopeState (history form) against the reference's rings (already rolled oldest-first)."""
-    assert st.stretch == want["stretch"]
-    amp = np.array(st.amp_hist, np.float32).reshape(8, 16, 8)[:ch]
-    near = np.array(st.near_hist, np.float32).reshape(8, 30)[:ch]
-    # reference keeps 17 amplitudes / 15 near-DC terms; the histories keep 16 / 30
-    assert np.array_equal(bits(amp[:, :, :7].transpose(0, 2, 1)), bits(want["amp"][:, :, 1:]))
-    assert np.array_equal(bits(near[:, 15:]), bits(want["near"]))
 
 
 # ------------------------------------------------------------------------------------------

@@ -8,38 +8,10 @@ import numpy as np
 import pytest
 
 from tests import checker
+from tests.feed_cases import reference_packets, small_arena, spy_totals
+from tests.signals import s16_streams
 
 pytestmark = pytest.mark.gpu
-
-
-def s16_streams(rng, ch, frames, kinds):
-    out = []
-    t = np.arange(frames)
-    for kind in kinds:
-        if kind == "noise":
-            x = (rng.random((frames, ch)) - 0.5) * 0.8
-        elif kind == "gated":
-            gate = np.where((t % 9000) < 700, 0.5, 0.0005)[:, None]
-            x = (rng.random((frames, ch)) - 0.5) * 2 * gate
-        elif kind == "sine":
-            x = 0.6 * np.sin(2 * np.pi * 440.0 / 44100.0 * t)[:, None] * np.ones((1, ch)) + (rng.random((frames, ch)) - 0.5) * 1e-3
-        elif kind == "clicks":
-            x = (rng.random((frames, ch)) - 0.5) * 0.002
-            x[::4001] = 0.9
-        elif kind == "silence":
-            x = np.zeros((frames, ch))
-        else:
-            raise ValueError(kind)
-        out.append(np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16))
-    return np.stack(out)
-
-
-def reference_packets(setup, pcm_s16):
-    """The reference's application loop over one stream's samples [frames, ch] int16."""
-    from oracle import ref
-    ch, rate, q = checker.SETUPS[setup]
-    planar = np.ascontiguousarray((pcm_s16.astype(np.float32) / np.float32(32768.0)).T)
-    return ref.RefEncoder(ch, rate, q).encode_stream(planar)
 
 
 def compare(setup, pcm, got):
@@ -56,27 +28,6 @@ def compare(setup, pcm, got):
                     s, k, len(want), "equal" if data == w["packet"] else "DIFFER", gp, w["granulepos"], W, w["W"], eos, w["eos"]))
                 break
     return bad
-
-
-def small_arena(monkeypatch, arena):
-    """arena (a string, or None): VAMD_FEED_OUT_BYTES (a test knob) -- every lane's packet arena starts that small, so a
-    group whose packets take more has to grow it (the VBR retry, the growth between a managed group's slices, the Ogg
-    mirror's)."""
-    if arena:
-        monkeypatch.setenv("VAMD_TEST_KNOBS", "1")
-        monkeypatch.setenv("VAMD_FEED_OUT_BYTES", arena)
-
-
-def spy_totals(feed):
-    """-> a list that receives total_bytes of every group feed.packets() returns from now on"""
-    totals, packets = [], feed.packets
-
-    def spy(slot, copy=True):
-        r = packets(slot, copy)
-        totals.append(r["total_bytes"])
-        return r
-    feed.packets = spy
-    return totals
 
 
 @pytest.mark.parametrize("setup", ["44k_stereo_q4", "44k_stereo_q9", "44k_mono_q5"])

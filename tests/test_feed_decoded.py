@@ -1,29 +1,16 @@
 """GPU: the decoded feed (VAMD_FEED_DECODED, vamd_feed_decoded; include/vorbis_amd.h "the decoded feed") -- per stream the
 signal on the device against libvorbis' decoder run over the feed's own packets with their granule positions
-(tests/ogg_host.py: vorbis_synthesis + vorbis_synthesis_blockin + vorbis_synthesis_pcmout), bit for bit."""
+(tests/ref_host.py: vorbis_synthesis + vorbis_synthesis_blockin + vorbis_synthesis_pcmout), bit for bit."""
 import numpy as np
 import pytest
 
 from oracle import ref
-from tests import ogg_host, synth_host
+from tests import ref_host, synth_host
+from tests.feed_cases import Q4, decoded_feed_of as feed_of, same_bits, small_arena
+from tests.signals import gated_noise, gated_streams as streams
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (needs /root/reference)")]
 EINVAL, EIMPL = -131, -130
-Q4 = "44k_stereo_q4"
-
-
-def streams(name, seconds, seed):
-    """gated noise, one [frames, ch] float32 array per stream"""
-    ch, rate, _, _ = synth_host.SETUPS[name]
-    return [np.ascontiguousarray(synth_host.gated_noise(ch, rate, int(rate * sec) + 7 * i + 1, seed + i).T) for i, sec in enumerate(seconds)]
-
-
-def feed_of(name, parts, **kw):
-    import vorbis_amd
-    kw.setdefault("lanes_per_device", 1)
-    kw.setdefault("decoded", True)
-    return vorbis_amd.Feed(synth_host.encoder(name).pack_setup(), max_streams=len(parts), max_frames=max(len(p) for p in parts),
-                           fmt=vorbis_amd.FEED_F32, **kw)
 
 
 def wrote(feed, parts):
@@ -54,15 +41,11 @@ def group(feed, parts, ogg=False):
 
 
 def reference_decode_rows(headers, row):
-    return ogg_host.reference_decode(headers + [p for p, _, _, _ in row], [gp for _, gp, _, _ in row])
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+    return ref_host.reference_decode(headers + [p for p, _, _, _ in row], [gp for _, gp, _, _ in row])
 
 
 def check_against_decoder(name, parts, got, skip=()):
-    headers = synth_host.encoder_headers(synth_host.encoder(name))
+    headers = ref_host.encoder_headers(ref_host.encoder(name))
     for s, p in enumerate(parts):
         if s in skip:
             continue
@@ -81,11 +64,11 @@ def test_decoded_equals_the_reference_decoder(name):
         got = group(feed, parts)
     finally:
         feed.close()
-    enc = synth_host.encoder(name)
+    enc = ref_host.encoder(name)
     if enc.blocksize(0) != enc.blocksize(1):  # long/long, long/short, short/long, short/short
         assert set().union(*[synth_host.lap_cases([W for _, _, W, _ in row]) for row in got["rows"]]) == {(0, 0), (0, 1), (1, 0), (1, 1)}
     for s, p in enumerate(parts):  # the packets are the reference encoder's (as tests/test_feed.py checks)
-        want = synth_host.encoder(name).encode_stream(np.ascontiguousarray(p.T))
+        want = ref_host.encoder(name).encode_stream(np.ascontiguousarray(p.T))
         assert [(w["packet"], w["granulepos"], w["W"], w["eos"]) for w in want] == got["rows"][s], "stream %d's packets" % s
     check_against_decoder(name, parts, got)
 
@@ -106,10 +89,9 @@ def test_short_streams():
 def test_the_flag_changes_nothing_else(arena, monkeypatch):
     """the same group through a feed with and without the flag, and through an Ogg feed with and without it: packets,
     granule positions, info and files byte for byte; arena: the packet arena starts at 4096 bytes and has to grow"""
-    from tests.test_feed import small_arena
     small_arena(monkeypatch, arena)
     parts = streams(Q4, (0.4, 0.25, 0.6), 21)
-    headers = ogg_host.reference_headers(2, 44100, 0.4)
+    headers = ref_host.reference_headers(2, 44100, 0.4)
     res = {}
     for key, kw in (("plain", dict(decoded=False)), ("decoded", dict()), ("ogg", dict(decoded=False, ogg_headers=headers)),
                     ("ogg_decoded", dict(ogg_headers=headers))):
@@ -134,7 +116,7 @@ def test_device_fed_group():
     those of a host-fed float group of the same values, lie on the lane's device, and survive release and the next group"""
     import torch
     frames = 20000
-    x = np.stack([synth_host.gated_noise(2, 44100, 2 * frames, 40 + s) for s in range(3)])
+    x = np.stack([gated_noise(2, 44100, 2 * frames, 40 + s) for s in range(3)])
     wide = torch.from_numpy(x).cuda().to(torch.bfloat16)
     view = wide[:, :, ::2]
     assert not view.is_contiguous()
@@ -208,7 +190,7 @@ def test_errors():
     finally:
         feed.close()
     managed = ref.RefEncoder(2, 44100, managed=(-1, 128000, -1)).pack_setup()
-    for blob, kw, word in ((managed, dict(), "bitrate-managed"), (synth_host.encoder(Q4).pack_setup(), dict(write_frames=1024), "live")):
+    for blob, kw, word in ((managed, dict(), "bitrate-managed"), (ref_host.encoder(Q4).pack_setup(), dict(write_frames=1024), "live")):
         with pytest.raises(vorbis_amd.VamdError) as e:
             vorbis_amd.Feed(blob, lanes_per_device=1, max_streams=2, max_frames=4096, fmt=vorbis_amd.FEED_F32, decoded=True, **kw)
         assert e.value.code == EIMPL and word in str(e.value) and "VAMD_FEED_DECODED" in str(e.value), e.value

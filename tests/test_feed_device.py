@@ -10,14 +10,13 @@ import pytest
 from tests import bitrate_host as bh
 from tests import checker
 from tests import feed_source_host as fs
-from tests import ogg_host as oh
-from tests.test_feed import s16_streams
-from tests.test_feed_live import N_HEAD, diff, mixed_streams, random_cuts
+from tests import ref_host as rh
+from tests.feed_cases import Q4, diff
+from tests.signals import N_HEAD, mixed_streams, random_cuts, s16_streams
 
 pytestmark = pytest.mark.gpu
 
 EINVAL = -131
-Q4 = "44k_stereo_q4"
 
 
 def _ref():
@@ -173,7 +172,7 @@ def test_ragged_list_of_separate_allocations():
 
 # ---- 4. live ----
 def f16_streams(rng, ch):
-    """tests/test_feed_live.py's streams and cuts, their samples rounded to float16: -> (float16 [frames_s, ch] each, cuts)"""
+    """tests/signals.py's mixed streams and cuts, their samples rounded to float16: -> (float16 [frames_s, ch] each, cuts)"""
     streams, cuts = mixed_streams(rng, ch)
     return [(x.astype(np.float32) / np.float32(32768.0)).astype(np.float16) for x in streams], cuts
 
@@ -277,7 +276,7 @@ def test_ogg_files_equal_the_host_fed_groups():
     import torch
     import vorbis_amd
     _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(61)
     lengths = [30000, 2049, 12000, 1]
     parts = [s16_streams(rng, 2, n, [k])[0] for n, k in zip(lengths, ["gated", "noise", "sine", "clicks"])]
@@ -296,7 +295,7 @@ def test_ogg_files_equal_the_host_fed_groups():
 def test_live_ogg_pieces_with_random_flushes_equal_the_host_fed_feeds():
     import vorbis_amd
     _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(62)
     streams, cuts = mixed_streams(rng, 2)
     rounds = max(len(c) for c in cuts)

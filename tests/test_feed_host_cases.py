@@ -9,19 +9,8 @@ steps at block sizes 256 / 2048 and 777 frames per write (an absent stream, a 1-
 bound, the rebase's bounds, a stream reopened).  Every array is a heap block of exactly the size visited, so a read or
 write past either end is the sanitizer's to report.
 """
-import os
-import subprocess
-
-from tests import checker
-
-ROOT = checker.ROOT
+from tests import hostbuild
 
 
-def test_feed_host_arithmetic_on_crafted_cases(tmp_path):
-    exe = str(tmp_path / "feed_host_cases")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "c", "feed_host_cases.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.rstrip().endswith(": ok"), r.stdout[-4000:] + r.stderr[-4000:]
+def test_feed_host_arithmetic_on_crafted_cases():
+    hostbuild.run_ok(hostbuild.program("feed_host_cases.cpp", ["-Wall"]))

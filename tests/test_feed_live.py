@@ -7,82 +7,16 @@ import pytest
 
 from tests import bitrate_host as bh
 from tests import checker
-from tests.test_feed import s16_streams, small_arena, spy_totals
+from tests.feed_cases import diff, record_rows as reference, run_live, small_arena, spy_totals
+from tests.signals import mixed_streams, random_cuts, s16_streams
 
 pytestmark = pytest.mark.gpu
-
-N_HEAD = 3072  # (2048 / 1024 + 1) * 1024: where the example's cadence runs the backward extrapolation
-
 
 def _ref():
     from oracle import ref
     if not ref.available():
         pytest.skip("needs the reference build")
     return ref
-
-
-def planar(x):
-    return np.ascontiguousarray((x.astype(np.float32) / np.float32(32768.0)).T if x.dtype == np.int16 else x.T)
-
-
-def reference(enc, x, write_frames=1024):
-    return [(w["packet"], w["granulepos"], w["W"], w["eos"]) for w in enc.encode_stream(planar(x), write_frames=write_frames)]
-
-
-def diff(want, got, s=0):
-    if len(want) != len(got):
-        return ["stream %d: %d packets, the reference %d" % (s, len(got), len(want))]
-    for k, (w, g) in enumerate(zip(want, got)):
-        if w != g:
-            return ["stream %d packet %d/%d: bytes %s granulepos %d/%d W %d/%d eos %d/%d" % (
-                s, k, len(want), "equal" if w[0] == g[0] else "DIFFER", g[1], w[1], g[2], w[2], g[3], w[3])]
-    return []
-
-
-def run_live(feed, streams, cuts):
-    """Feed streams [frames_s, ch] to a one-lane live feed in rounds: in round r stream s gets cuts[s][r] frames and is closed
-    with its last piece (a stream whose cuts ran out gets nothing).  -> per stream its packets over all rounds."""
-    got = [[] for _ in streams]
-    pos = [0] * len(streams)
-    for r in range(max(len(c) for c in cuts)):
-        pieces, close = [], []
-        for s, x in enumerate(streams):
-            n = cuts[s][r] if r < len(cuts[s]) else 0
-            pieces.append(x[pos[s]:pos[s] + n])
-            pos[s] += n
-            close.append(r == len(cuts[s]) - 1)
-        for s, row in enumerate(feed.encode_live(pieces, close)):
-            got[s] += row
-    assert pos == [len(x) for x in streams]
-    return got
-
-
-def random_cuts(rng, frames, special=()):
-    """piece lengths summing to `frames`: random cut points (and those in `special`), a few empty pieces in between"""
-    points = set(int(p) for p in special if 0 < p < frames)
-    for _ in range(frames // 5000 + 3):
-        if frames > 1:
-            points.add(int(rng.integers(1, frames)))
-    edges = [0] + sorted(points) + [frames]
-    cuts = [b - a for a, b in zip(edges, edges[1:])]
-    for k in sorted(rng.choice(len(cuts), size=min(3, len(cuts)), replace=False))[::-1]:
-        cuts.insert(int(k), 0)
-    return cuts
-
-
-def mixed_streams(rng, ch):
-    """the cases of a live lane: long streams cut at random (one piece ending exactly at n_head, 1-frame pieces), a stream
-    shorter than n_head, a 1-frame stream, a stream opened and closed in one piece, a close on an empty piece"""
-    lengths = [31000, 24000, 2500, 1, 9000, 17000]
-    kinds = ["gated", "noise", "sine", "noise", "clicks", "gated"]
-    streams = [s16_streams(rng, ch, n, [k])[0] for n, k in zip(lengths, kinds)]
-    cuts = [random_cuts(rng, 31000, [N_HEAD, N_HEAD + 1]),
-            [1, 1, 1000, 1, 0] + random_cuts(rng, 22997, [N_HEAD - 1003]),
-            [100, 2400],
-            [1],
-            [0, 0, 9000],
-            random_cuts(rng, 17000) + [0]]
-    return streams, cuts
 
 
 @pytest.mark.parametrize("setup", ["44k_stereo_q4", "44k_stereo_q9", "44k_mono_q5"])

@@ -8,8 +8,8 @@ from tests import live_host
 
 
 @pytest.fixture(scope="module")
-def walker(tmp_path_factory):
-    return live_host.LiveWalk(live_host.build(str(tmp_path_factory.mktemp("live"))), (256, 2048))
+def walker():
+    return live_host.LiveWalk(live_host.build(), (256, 2048))
 
 
 def signal(kind, frames, seed):

@@ -1,21 +1,19 @@
 """GPU suite: the live Ogg feed (vamd_feed_ogg_headers_live, include/vorbis_amd.h "the live Ogg feed") -- continuing streams
 fed in pieces, per group and stream the next bytes of the stream's Ogg file back, paged on the device with the open page's
 packets carried between groups (vorbis_amd/csrc/k_ogg.h).  A stream's pieces laid end to end must be the file: the
-reference's headers and packets (tests/test_feed_ogg.py's check_file: spec demuxer, host mux byte for byte, policy,
+reference's headers and packets (tests/feed_cases.py's check_file: spec demuxer, host mux byte for byte, policy,
 reference decoder), the whole-stream Ogg feed's file for the same serial number, the same under every cut -- and every
 piece a whole number of pages on its own."""
-import tempfile
-
 import numpy as np
 import pytest
 
 from tests import bitrate_host as bh
 from tests import checker
+from tests import ogg_framing as fr
 from tests import ogg_host as oh
-from tests import ogg_live_host as olh
-from tests.test_feed import s16_streams, small_arena, spy_totals
-from tests.test_feed_live import mixed_streams, planar, random_cuts
-from tests.test_feed_ogg import check_file
+from tests import ref_host as rh
+from tests.feed_cases import check_file, records, rows_of, small_arena, spy_totals, whole_file
+from tests.signals import managed_s16_streams as managed_streams, mixed_streams, random_cuts, s16_streams
 
 pytestmark = pytest.mark.gpu
 
@@ -29,21 +27,16 @@ def _ref():
 
 @pytest.fixture(scope="module")
 def host():
-    return oh.HostOgg(oh.build(tempfile.mkdtemp(prefix="ogg")))
+    return oh.HostOgg()
 
 
 @pytest.fixture(scope="module")
 def live_host():
-    return olh.LiveOgg(olh.build(tempfile.mkdtemp(prefix="ogglive")))
-
-
-def records(enc, x):
-    """the reference's application loop over one stream, written 1024 frames at a time"""
-    return enc.encode_stream(planar(x), write_frames=1024)
+    return oh.HostOgg()
 
 
 def run_live_ogg(feed, streams, cuts, serials=None):
-    """Feed streams [frames_s, ch] to a one-lane live Ogg feed in rounds, as tests/test_feed_live.py's run_live does: in round
+    """Feed streams [frames_s, ch] to a one-lane live Ogg feed in rounds, as tests/feed_cases.py's run_live does: in round
     r stream s gets cuts[s][r] frames and is closed with its last piece.  serials: given to every round (they count where a
     stream begins).  -> per stream a list over the rounds of dict(bytes, npages, status, rows, close)."""
     got = [[] for _ in streams]
@@ -78,23 +71,12 @@ def run_live_ogg(feed, streams, cuts, serials=None):
     return got
 
 
-def whole_file(groups):
-    """a stream's pieces laid end to end; every piece a whole number of pages (their checksums verified), as many as npages says"""
-    for g in groups:
-        assert len(olh.pages_of(g["bytes"])) == g["npages"]
-    return b"".join(g["bytes"] for g in groups)
-
-
-def rows_of(groups):
-    return [r for g in groups for r in g["rows"]]
-
-
 @pytest.mark.parametrize("setup", ["44k_stereo_q4", "44k_stereo_q9", "44k_mono_q5"])
 def test_random_cuts_give_the_whole_stream_feeds_files(host, setup):
     import vorbis_amd
     ref = _ref()
     ch, rate, q = checker.SETUPS[setup]
-    headers = oh.reference_headers(ch, rate, q)
+    headers = rh.reference_headers(ch, rate, q)
     rng = np.random.default_rng(7 + ch)
     streams, cuts = mixed_streams(rng, ch)
     serials = [100 + s for s in range(len(streams))]
@@ -125,7 +107,7 @@ def test_pieces_of_700_frames(host):
     """Most groups complete no page: their ranges are empty and the carry grows."""
     import vorbis_amd
     ref = _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(70)
     x = s16_streams(rng, 2, 30000, ["gated"])[0]
     y = s16_streams(rng, 2, 9100, ["noise"])[0]
@@ -149,14 +131,14 @@ def test_the_255_segment_rule_and_a_continued_page_across_groups(host, live_host
     closing its stream and leave an open page whose first packet is continued, and some one that carries >= 200 packets."""
     import vorbis_amd
     ref = _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     S = 249968
     rng = np.random.default_rng(7)
     x = np.zeros((S + 12000, 2))
     x[S:] = (rng.random((12000, 2)) - 0.5) * 0.8
     x = np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)
     want = records(ref.RefEncoder(2, 44100, 0.4), x)
-    expect, _ = oh.demux(host.mux(headers, [w["packet"] for w in want], [w["granulepos"] for w in want], 0))
+    expect, _ = fr.demux(host.mux(headers, [w["packet"] for w in want], [w["granulepos"] for w in want], 0))
     assert (expect[2]["nseg"], expect[2]["body"], expect[2]["done"]) == (255, 727, 254) and expect[3]["flags"] == 5, \
         "the reference's packets no longer cut the first audio page inside a packet"
     cuts = []
@@ -184,10 +166,6 @@ def test_the_255_segment_rule_and_a_continued_page_across_groups(host, live_host
     assert continued > 0 and carried > 0, (continued, carried)
 
 
-def managed_streams(lengths, kind="music"):
-    return [np.clip(np.round(bh.signal(kind, 2, n, 40 + i).T * 32768.0), -32768, 32767).astype(np.int16) for i, n in enumerate(lengths)]
-
-
 def test_managed_and_its_slices(host, monkeypatch):
     """ABR 128 kb/s in random pieces, with the default slice and with slices of 5 blocks: the same bytes, the host mux of
     the reference's managed packets."""
@@ -195,7 +173,7 @@ def test_managed_and_its_slices(host, monkeypatch):
     ref = _ref()
     rates = (-1, 128000, -1)
     blob = bh.managed_blob(2, rates)
-    headers = oh.reference_headers(2, 44100, managed=rates)
+    headers = rh.reference_headers(2, 44100, managed=rates)
     streams = managed_streams([26000, 9000, 2000])
     rng = np.random.default_rng(3)
     cuts = [random_cuts(rng, len(x)) for x in streams]
@@ -225,13 +203,13 @@ def test_a_group_laid_out_twice_advances_its_streams_once(kind, monkeypatch):
     _ref()
     if kind == "vbr":
         blob = vorbis_amd.default_setup_blob("44k_stereo_q4")
-        headers = oh.reference_headers(2, 44100, 0.4)
+        headers = rh.reference_headers(2, 44100, 0.4)
         rng = np.random.default_rng(44)
         streams = [s16_streams(rng, 2, n, [k])[0] for n, k in [(40000, "noise"), (20000, "gated")]]
     else:
         rates = (-1, 128000, -1)
         blob = bh.managed_blob(2, rates)
-        headers = oh.reference_headers(2, 44100, managed=rates)
+        headers = rh.reference_headers(2, 44100, managed=rates)
         streams = managed_streams([90000, 60000, 2000])
     rng = np.random.default_rng(45)
     cuts = [random_cuts(rng, len(x)) for x in streams]
@@ -250,14 +228,14 @@ def test_a_group_laid_out_twice_advances_its_streams_once(kind, monkeypatch):
     assert max(totals) > 4096, totals
     for s in range(len(streams)):
         assert [g["bytes"] for g in b[s]] == [g["bytes"] for g in a[s]], "stream %d" % s
-        oh.demux(whole_file(b[s]))
+        fr.demux(whole_file(b[s]))
 
 
 def test_a_non_finite_sample_ends_its_streams_file_only(host, live_host):
     """The inputs of tests/test_feed_live.py's test_non_finite_sample_ends_its_stream_only."""
     import vorbis_amd
     ref = _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(5)
     streams = [s16_streams(rng, 2, 30000, [k])[0].astype(np.float32) / np.float32(32768.0) for k in ["gated", "noise", "sine"]]
     poisoned = streams[1].copy()
@@ -280,10 +258,10 @@ def test_a_non_finite_sample_ends_its_streams_file_only(host, live_host):
         assert g["status"] == 0
     for g in got[1][hit:]:
         assert g["bytes"] == b"" and g["npages"] == 0 and g["status"] == vorbis_amd.api.STATUS_NONFINITE
-    prefix = olh.pages_of(whole_file(got[1][:hit]))              # a valid Ogg prefix: whole pages, no end-of-stream page
+    prefix = fr.pages_of(whole_file(got[1][:hit]))              # a valid Ogg prefix: whole pages, no end-of-stream page
     assert len(prefix) >= 2 and [p["seq"] for p in prefix] == list(range(len(prefix))) and not any(p["flags"] & 4 for p in prefix)
     assert prefix[0]["flags"] == 2 and all(p["serial"] == 11 for p in prefix)
-    held = olh.packets_of(prefix)
+    held = fr.packets_of(prefix)
     assert held[:3] == list(headers)
     assert held[3:] == [w["packet"] for w in want[1][:len(held) - 3]]
     st = live_host.stream(headers, 11)                            # ... and group by group what the host mux in pieces hands out
@@ -293,7 +271,7 @@ def test_a_non_finite_sample_ends_its_streams_file_only(host, live_host):
     serials = set()
     for s in range(3):
         assert after[s][0]["status"] == 0
-        pages = check_file(host, headers, wl, after[s][0]["rows"], after[s][0]["bytes"], 8000, oh.demux(after[s][0]["bytes"])[0][0]["serial"],
+        pages = check_file(host, headers, wl, after[s][0]["rows"], after[s][0]["bytes"], 8000, fr.demux(after[s][0]["bytes"])[0][0]["serial"],
                            after[s][0]["npages"])
         serials.add(pages[0]["serial"])
     assert len(serials) == 3
@@ -304,7 +282,7 @@ def test_slot_reuse_and_serial_numbers(host):
     to a stream: a given one applies where the stream begins and is ignored for an open one; default ones are distinct."""
     import vorbis_amd
     ref = _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(99)
     a, b, c = (s16_streams(rng, 2, n, [k])[0] for n, k in [(9000, "gated"), (7000, "noise"), (15000, "sine")])
     feed = vorbis_amd.Feed(vorbis_amd.default_setup_blob("44k_stereo_q4"), lanes_per_device=1, max_streams=2, max_frames=6000,
@@ -325,14 +303,14 @@ def test_slot_reuse_and_serial_numbers(host):
         feed.close()
     seen = {}
     for name, x in (("a", a), ("b", b), ("c", c)):
-        pages, got = oh.demux(files[name])
+        pages, got = fr.demux(files[name])
         assert got[:3] == list(headers)
         assert got[3:] == [w["packet"] for w in records(ref.RefEncoder(2, 44100, 0.4), x)]
         assert pages[0]["flags"] == 2 and [p["seq"] for p in pages] == list(range(len(pages))) and pages[-1]["flags"] & 4
         assert len({p["serial"] for p in pages}) == 1
         seen[name] = pages[0]["serial"]
     assert seen["a"] == 11 and seen["c"] == 22
-    dp, _ = oh.demux(d)
+    dp, _ = fr.demux(d)
     assert dp[0]["flags"] == 2 and dp[0]["seq"] == 0
     assert len({seen["a"], seen["b"], seen["c"], dp[0]["serial"]}) == 4 and dp[0]["serial"] == seen["b"] + 1
     assert d[:58] != files["a"][:58] and d[58:] != b""
@@ -342,7 +320,7 @@ def test_packets_of_a_live_ogg_feed_equal_a_plain_live_feeds():
     import vorbis_amd
     _ref()
     blob = vorbis_amd.default_setup_blob("44k_stereo_q4")
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(12)
     parts = [s16_streams(rng, 2, n, [k])[0] for n, k in [(20000, "gated"), (5000, "noise"), (12345, "clicks")]]
     cuts = [[7000, 6000, 7000], [5000], [1, 0, 12344]]
@@ -375,8 +353,8 @@ def test_errors():
     _ref()
     EINVAL = vorbis_amd.api.VAMD_EINVAL
     blob = vorbis_amd.default_setup_blob("44k_stereo_q4")
-    headers = oh.reference_headers(2, 44100, 0.4)
-    mono = oh.reference_headers(1, 44100, 0.5)
+    headers = rh.reference_headers(2, 44100, 0.4)
+    mono = rh.reference_headers(1, 44100, 0.5)
     whole = vorbis_amd.Feed(blob, lanes_per_device=1, max_streams=2, max_frames=4096)
     try:
         with pytest.raises(vorbis_amd.VamdError) as e:

@@ -1,21 +1,19 @@
 """GPU suite: the live Ogg feed's flush per write (vamd_feed_ogg_flush, include/vorbis_amd.h "a flush per write") -- a group
 names the streams whose open page leaves with it.  The device's bytes are held, group by group, against the shipped host
-mux in pieces with the same flush points (tests/ogg_flush_host.py); behind every flushing group the pieces so far hold
+mux in pieces with the same flush points (tests/ogg_host.py); behind every flushing group the pieces so far hold
 exactly the packets vamd_feed_packets has reported; the whole file holds the reference encoder's packets and decodes to
 the samples the unflushed file decodes to; and a feed that flushes nothing returns what it returned before the call
 existed.  Shapes and inputs are tests/test_feed_live_ogg.py's."""
-import tempfile
-
 import numpy as np
 import pytest
 
 from tests import bitrate_host as bh
 from tests import checker
-from tests import ogg_flush_host as ofh
+from tests import ogg_framing as fr
 from tests import ogg_host as oh
-from tests.test_feed import s16_streams, small_arena, spy_totals
-from tests.test_feed_live import mixed_streams, random_cuts
-from tests.test_feed_live_ogg import managed_streams, records, rows_of, whole_file
+from tests import ref_host as rh
+from tests.feed_cases import records, rows_of, small_arena, spy_totals, whole_file
+from tests.signals import managed_s16_streams as managed_streams, mixed_streams, random_cuts, s16_streams
 
 pytestmark = pytest.mark.gpu
 
@@ -29,12 +27,12 @@ def _ref():
 
 @pytest.fixture(scope="module")
 def host():
-    return oh.HostOgg(oh.build(tempfile.mkdtemp(prefix="ogg")))
+    return oh.HostOgg()
 
 
 @pytest.fixture(scope="module")
 def flush_host():
-    return ofh.FlushOgg(ofh.build(tempfile.mkdtemp(prefix="oggflush")))
+    return oh.HostOgg()
 
 
 def run_flushed(feed, streams, cuts, serials, flush_of, comments=None):
@@ -93,7 +91,7 @@ def hold_against_the_host_mux(flush_host, headers, serial, groups):
     group of the open stream the pieces so far hold exactly the packets reported so far, whole, and nothing is open.
     -> the pages of all groups, the flushed ones marked"""
     st = flush_host.stream(headers, serial)
-    got, pages, given, begun = ofh.Reassembler(), [], [], False
+    got, pages, given, begun = fr.Reassembler(), [], [], False
     for r, g in enumerate(groups):
         if not begun and not g["frames"]:                              # not yet begun, or behind its end: untouched, flushed or not
             assert g["bytes"] == b"" and g["npages"] == 0 and not g["rows"]
@@ -103,7 +101,7 @@ def hold_against_the_host_mux(flush_host, headers, serial, groups):
         want = st.piece([w[0] for w in g["rows"]], [w[1] for w in g["rows"]], g["close"], g["flush"])
         assert g["bytes"] == want, "round %d: the device's bytes are not the host mux's with the same flush" % r
         begun = not g["close"]
-        mine = ofh.pages_of(g["bytes"])
+        mine = fr.pages_of(g["bytes"])
         assert len(mine) == g["npages"]
         for p in mine:
             p["flushed"] = False
@@ -124,7 +122,7 @@ def check_flushed_file(host, headers, want, groups, pages, frames, serial):
     the reference decoder gives what it gives for the unflushed file of the same packets."""
     f = whole_file(groups)
     rows = rows_of(groups)
-    fp, got = oh.demux(f)                                             # (every CRC bit-serially, the continued flags)
+    fp, got = fr.demux(f)                                             # (every CRC bit-serially, the continued flags)
     assert got[:3] == list(headers)
     assert got[3:] == [w["packet"] for w in want] and got[3:] == [r[0] for r in rows]
     assert [r[1] for r in rows] == [w["granulepos"] for w in want]
@@ -133,15 +131,15 @@ def check_flushed_file(host, headers, want, groups, pages, frames, serial):
     assert fp[-1]["flags"] & 4 and fp[-1]["granule"] == frames and sum(bool(p["flags"] & 4) for p in fp) == 1
     first_audio = next(i for i, p in enumerate(fp) if sum(q["done"] for q in fp[:i + 1]) == 3) + 1
     for i, p in enumerate(fp[first_audio:-1], first_audio):           # the policy, or a flush
-        assert (p["body"] > oh.FILL and p["done"] >= oh.MIN_PACKETS) or p["nseg"] == 255 or pages[i]["flushed"], (i, p)
+        assert (p["body"] > fr.FILL and p["done"] >= fr.MIN_PACKETS) or p["nseg"] == 255 or pages[i]["flushed"], (i, p)
         if pages[i]["flushed"]:
             assert pages[i]["lacing"][-1] < 255 and p["granule"] != -1 and not p["flags"] & 4
     plain = host.mux(headers, [r[0] for r in rows], [r[1] for r in rows], serial)
-    pp, _ = oh.demux(plain)
+    pp, _ = fr.demux(plain)
     nflushed = sum(p["flushed"] for p in pages)
     assert len(f) - len(plain) == 27 * (len(fp) - len(pp)) and (nflushed > 0 or f == plain)
-    a = oh.reference_decode(got, oh.page_granules(fp, len(want)))
-    b = oh.reference_decode(got, oh.page_granules(pp, len(want)))
+    a = rh.reference_decode(got, fr.page_granules(fp, len(want)))
+    b = rh.reference_decode(got, fr.page_granules(pp, len(want)))
     assert a.shape[1] == frames and np.array_equal(a, b), "the flushed file does not decode to the unflushed file's samples"
     return fp
 
@@ -151,7 +149,7 @@ def test_random_flushes(host, flush_host, setup):
     import vorbis_amd
     ref = _ref()
     ch, rate, q = checker.SETUPS[setup]
-    headers = oh.reference_headers(ch, rate, q)
+    headers = rh.reference_headers(ch, rate, q)
     rng = np.random.default_rng(7 + ch)
     streams, cuts = mixed_streams(rng, ch)
     serials = [100 + s for s in range(len(streams))]
@@ -178,7 +176,7 @@ def test_no_flush_is_the_feed_as_it_was(flush_host):
     slot's next group."""
     import vorbis_amd
     _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(21)
     streams = [s16_streams(rng, 2, n, [k])[0] for n, k in [(21000, "noise"), (16000, "gated")]]
     cuts = [[6000, 5000, 0, 6000, 4000], [8000, 4000, 4000]]
@@ -207,7 +205,7 @@ def test_pieces_of_700_frames(host, flush_host):
     one returns nothing."""
     import vorbis_amd
     ref = _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(70)
     x = s16_streams(rng, 2, 14600, ["gated"])[0]
     y = s16_streams(rng, 2, 9100, ["noise"])[0]
@@ -221,9 +219,9 @@ def test_pieces_of_700_frames(host, flush_host):
         feed.close()
     assert sum(g["bytes"] == b"" for g in got[0][1:10]) >= 5 and sum(len(g["rows"]) for g in got[0][:10]) > 0
     assert got[0][10]["npages"] == 1 and not got[0][10]["rows"], "a flushed piece without frames returns the carried packets' page"
-    page = ofh.pages_of(got[0][10]["bytes"])[0]
+    page = fr.pages_of(got[0][10]["bytes"])[0]
     held = [r[0] for g in got[0][:10] for r in g["rows"]]
-    done = sum(p["done"] for g in got[0][:10] for p in ofh.pages_of(g["bytes"])) - 3
+    done = sum(p["done"] for g in got[0][:10] for p in fr.pages_of(g["bytes"])) - 3
     assert page["done"] == len(held) - done > 0 and page["granule"] == [r[1] for g in got[0][:10] for r in g["rows"]][-1]
     assert got[0][11]["npages"] == 0 and got[0][11]["bytes"] == b"", "a second flush finds the open page empty"
     for s, z in enumerate((x, y)):
@@ -240,7 +238,7 @@ def test_the_255_segment_stream_flushed_where_the_open_page_is_continued_or_full
     find).  The bytes are the host mux's; some flushed page has flag 0x01, some holds at least 200 packets."""
     import vorbis_amd
     ref = _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     S = 249968
     rng = np.random.default_rng(7)
     x = np.zeros((S + 12000, 2))
@@ -280,7 +278,7 @@ def test_the_255_segment_stream_flushed_where_the_open_page_is_continued_or_full
         if s < 2:
             check_flushed_file(host, headers, want, got[s], pages, x.shape[0], 8 + s)
         else:
-            assert oh.demux(whole_file(got[s]))[1] == list(headers) + [w["packet"] for w in want]
+            assert fr.demux(whole_file(got[s]))[1] == list(headers) + [w["packet"] for w in want]
     assert flagged > 0 and many > 0, (flagged, many, where)
 
 
@@ -291,7 +289,7 @@ def test_managed_and_its_slices(flush_host, monkeypatch):
     _ref()
     rates = (-1, 128000, -1)
     blob = bh.managed_blob(2, rates)
-    headers = oh.reference_headers(2, 44100, managed=rates)
+    headers = rh.reference_headers(2, 44100, managed=rates)
     streams = managed_streams([26000, 9000, 2000])
     rng = np.random.default_rng(3)
     cuts = [random_cuts(rng, len(x)) for x in streams]
@@ -311,7 +309,7 @@ def test_managed_and_its_slices(flush_host, monkeypatch):
     for s in range(3):
         assert [g["bytes"] for g in b[s]] == [g["bytes"] for g in a[s]], "stream %d: the slice size changes the bytes" % s
         nflushed += sum(p["flushed"] for p in hold_against_the_host_mux(flush_host, headers, 7 + s, a[s]))
-        assert oh.demux(whole_file(a[s]))[0][-1]["flags"] & 4
+        assert fr.demux(whole_file(a[s]))[0][-1]["flags"] & 4
     assert nflushed > 0
 
 
@@ -321,7 +319,7 @@ def test_a_vbr_group_laid_out_twice_is_flushed_once(flush_host, monkeypatch):
     import vorbis_amd
     _ref()
     blob = vorbis_amd.default_setup_blob("44k_stereo_q4")
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(44)
     streams = [s16_streams(rng, 2, n, [k])[0] for n, k in [(40000, "noise"), (20000, "gated")]]
     rng = np.random.default_rng(45)
@@ -343,7 +341,7 @@ def test_a_vbr_group_laid_out_twice_is_flushed_once(flush_host, monkeypatch):
     for s in range(2):
         assert [g["bytes"] for g in b[s]] == [g["bytes"] for g in a[s]], "stream %d" % s
         nflushed += sum(p["flushed"] for p in hold_against_the_host_mux(flush_host, headers, 1 + s, b[s]))
-        oh.demux(whole_file(b[s]))
+        fr.demux(whole_file(b[s]))
     assert nflushed > 0
 
 
@@ -352,7 +350,7 @@ def test_a_flushed_stream_with_a_non_finite_sample(flush_host):
     and keeps its status; its neighbours' flushed bytes are the host mux's."""
     import vorbis_amd
     _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(5)
     streams = [s16_streams(rng, 2, 30000, [k])[0].astype(np.float32) / np.float32(32768.0) for k in ["gated", "noise", "sine"]]
     poisoned = streams[1].copy()
@@ -381,7 +379,7 @@ def test_streams_that_begin_with_a_flushed_group(flush_host):
     flushed page in one range.  One that begins with a piece too short for any packet: its header pages alone."""
     import vorbis_amd
     _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     own = vorbis_amd.comment_packet([("TITLE", "flushed"), ("COMMENT", "x" * 700)], "vorbis_amd tests")
     rng = np.random.default_rng(31)
     a = s16_streams(rng, 2, 24000, ["noise"])[0]
@@ -392,13 +390,13 @@ def test_streams_that_begin_with_a_flushed_group(flush_host):
         got = run_flushed(feed, [a, b], [[20000, 4000], [100, 5900]], [41, 42], lambda r: True, comments=[own, None])
     finally:
         feed.close()
-    first = ofh.pages_of(got[0][0]["bytes"])
+    first = fr.pages_of(got[0][0]["bytes"])
     assert len(got[0][0]["rows"]) > 4 and first[0]["flags"] == 2 and first[-1]["lacing"][-1] < 255 and first[-1]["granule"] == got[0][0]["rows"][-1][1]
     pages = hold_against_the_host_mux(flush_host, [headers[0], own, headers[2]], 41, got[0])
-    assert pages[len(first) - 1]["flushed"] and ofh.packets_of(first)[:3] == [headers[0], own, headers[2]]
+    assert pages[len(first) - 1]["flushed"] and fr.packets_of(first)[:3] == [headers[0], own, headers[2]]
     assert not got[1][0]["rows"], "100 frames gave a packet: the case needs a shorter piece"
-    only = ofh.pages_of(got[1][0]["bytes"])
-    assert got[1][0]["npages"] == len(only) and ofh.packets_of(only) == list(headers) and [p["granule"] for p in only] == [0] * len(only)
+    only = fr.pages_of(got[1][0]["bytes"])
+    assert got[1][0]["npages"] == len(only) and fr.packets_of(only) == list(headers) and [p["granule"] for p in only] == [0] * len(only)
     assert not any(p["flushed"] for p in hold_against_the_host_mux(flush_host, headers, 42, got[1])[:len(only)])
 
 
@@ -407,7 +405,7 @@ def test_errors():
     _ref()
     EINVAL = vorbis_amd.api.VAMD_EINVAL
     blob = vorbis_amd.default_setup_blob("44k_stereo_q4")
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     y = s16_streams(np.random.default_rng(8), 2, 8192, ["noise"])[0]
     x = y[:4096]
 
@@ -449,11 +447,11 @@ def test_errors():
         live.wrote_live(slot, [8192], [0])
         refused(live, slot, [1], 1, "between vamd_feed_buffer and vamd_feed_wrote_live")     # after wrote
         o = live.ogg(slot)
-        assert ofh.packets_of(ofh.pages_of(bytes(o["bytes"][:int(o["total_bytes"])])))[:3] == list(headers)
+        assert fr.packets_of(fr.pages_of(bytes(o["bytes"][:int(o["total_bytes"])])))[:3] == list(headers)
         refused(live, slot, [1], 1, "between vamd_feed_buffer and vamd_feed_wrote_live")
         live.release(slot)
         out = live.encode_live_ogg([x[:0]], [0], flush=True)              # the feed is usable: the open page, flushed
-        assert len(ofh.pages_of(out[0])) == 1 and not ofh.pages_of(out[0])[0]["flags"] & 4
+        assert len(fr.pages_of(out[0])) == 1 and not fr.pages_of(out[0])[0]["flags"] & 4
         assert live.encode_live_ogg([x[:2000]], [1])[0][-1:] != b""
     finally:
         live.close()

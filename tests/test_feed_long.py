@@ -5,7 +5,6 @@ of thousands of frames: packets, plans and managed groups must be what the defau
 application loop emits.  Without any knob, an 11 M-frame stream -- past the 10.48 M frames the walk's LDS used to hold --
 goes through a whole-stream Ogg feed and comes back as the reference's packets in the host mux's file."""
 import functools
-import tempfile
 
 import numpy as np
 import pytest
@@ -14,7 +13,9 @@ from tests import bitrate_host as bh
 from tests import checker
 from tests import ogg_host as oh
 from tests import plan_window_host as pwh
-from tests.test_feed import s16_streams
+from tests import ref_host as rh
+from tests.feed_cases import diff, planar, record_rows as records
+from tests.signals import s16_streams
 
 pytestmark = pytest.mark.gpu
 
@@ -33,31 +34,13 @@ def _ref():
 @functools.lru_cache(maxsize=None)
 def minimum():
     """plan_window_min of the shipped setups' block sizes, from the shipped header"""
-    return pwh.PlanWindow(pwh.build(tempfile.mkdtemp(prefix="planwindow")), (256, 2048)).minimum
+    return pwh.PlanWindow(pwh.build(), (256, 2048)).minimum
 
 
 def window_of(which):
     lo = minimum()
     assert lo + 200 < PRIME < lo + 400
     return {"minimum": lo, "prime": PRIME}[which]
-
-
-def planar(x):
-    return np.ascontiguousarray((x.astype(np.float32) / np.float32(32768.0)).T if x.dtype == np.int16 else x.T)
-
-
-def records(enc, x):
-    return [(w["packet"], w["granulepos"], w["W"], w["eos"]) for w in enc.encode_stream(planar(x), write_frames=1024)]
-
-
-def diff(want, got, s=0):
-    if len(want) != len(got):
-        return ["stream %d: %d packets, the reference %d" % (s, len(got), len(want))]
-    for k, (w, g) in enumerate(zip(want, got)):
-        if w != tuple(g):
-            return ["stream %d packet %d/%d: bytes %s granulepos %d/%d W %d/%d eos %d/%d" % (
-                s, k, len(want), "equal" if w[0] == g[0] else "DIFFER", g[1], w[1], g[2], w[2], g[3], w[3])]
-    return []
 
 
 @functools.lru_cache(maxsize=None)
@@ -173,7 +156,7 @@ def test_past_the_old_cap_ogg_file():
     x = np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)[:, None]
     del t
     ch, rate, q = checker.SETUPS["44k_mono_q5"]
-    headers = oh.reference_headers(ch, rate, q)
+    headers = rh.reference_headers(ch, rate, q)
     feed = vorbis_amd.Feed(vorbis_amd.default_setup_blob("44k_mono_q5"), lanes_per_device=1, max_streams=1, max_frames=frames,
                            ogg_headers=headers)
     try:
@@ -192,5 +175,5 @@ def test_past_the_old_cap_ogg_file():
     bad = diff(want, rows)
     assert not bad, "\n".join(bad)
     assert len(rows) > 10_000 and rows[-1][3] == 1 and rows[-1][1] == frames
-    host = oh.HostOgg(oh.build(tempfile.mkdtemp(prefix="ogg")))
+    host = oh.HostOgg()
     assert f == host.mux(headers, [r[0] for r in rows], [r[1] for r in rows], serial), "the file is not the host mux's of these packets"

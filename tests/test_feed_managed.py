@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import bitrate_host as bh
+from tests.feed_cases import planar
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +30,6 @@ def streams(kind, ch, lengths, seed, fmt):
         else:
             out.append(np.ascontiguousarray(x, dtype=np.float32))
     return out
-
-
-def planar(x):
-    return np.ascontiguousarray((x.astype(np.float32) / np.float32(32768.0)).T if x.dtype == np.int16 else x.T)
 
 
 def compare(ref, ch, rates, pcm, got):
@@ -84,7 +81,7 @@ def test_info_carries_the_walks_choice(name, ch, rates, kind):
     same blocks (and bits = what the manager handed out)."""
     import vorbis_amd
     ref = _ref()
-    lib = bh.build(_tmp())
+    lib = bh.build()
     blob = bh.managed_blob(ch, rates)
     hw = bh.HostWalk(lib, blob)
     x = streams(kind, ch, [88200], 5, "s16")[0]
@@ -105,11 +102,6 @@ def test_info_carries_the_walks_choice(name, ch, rates, kind):
     assert np.array_equal(r["choice"], choice), (r["choice"], choice)
     assert np.array_equal((r["bits"] + 7) // 8, fin)
     assert len(set(choice.tolist())) > 1
-
-
-def _tmp():
-    import tempfile
-    return tempfile.mkdtemp(prefix="walk")
 
 
 @pytest.mark.parametrize("arena", [None, "4096"])
@@ -167,7 +159,7 @@ def test_walk_on_the_device_equals_the_host_walk():
     import torch
     import vorbis_amd
     ref = _ref()
-    lib = bh.build(_tmp())
+    lib = bh.build()
     blob = bh.managed_blob(2, (160000, 96000, 64000))
     hw = bh.HostWalk(lib, blob)
     an = vorbis_amd.Analyzer(blob, device=0)

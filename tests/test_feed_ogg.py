@@ -1,18 +1,19 @@
 """GPU suite: the Ogg feed (vamd_feed_ogg_headers / vamd_feed_ogg, include/vorbis_amd.h) -- whole streams in from host
 memory, one complete Ogg Vorbis I file per stream back, framed on the device (vorbis_amd/csrc/k_ogg.h).  Every file is
-taken apart by a demuxer written from doc/framing.html alone (tests/ogg_host.py; it checks every page's CRC with a
+taken apart by a demuxer written from doc/framing.html alone (tests/ogg_framing.py; it checks every page's CRC with a
 bit-serial routine) and must hold the reference's own header packets and packets, which must also be the packets the
 same group's vamd_feed_packets reports; it must equal, byte for byte, what the shipped host mux makes of those packets
 (one policy, two implementations); and the reference decoder must get exactly the stream's frame count out of it."""
-import tempfile
-
 import numpy as np
 import pytest
 
 from tests import bitrate_host as bh
 from tests import checker
+from tests import ogg_framing as fr
 from tests import ogg_host as oh
-from tests.test_feed import s16_streams, small_arena, spy_totals
+from tests import ref_host as rh
+from tests.feed_cases import check_file, reference_records, small_arena, spy_totals
+from tests.signals import s16_streams
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +27,7 @@ def _ref():
 
 @pytest.fixture(scope="module")
 def host():
-    return oh.HostOgg(oh.build(tempfile.mkdtemp(prefix="ogg")))
+    return oh.HostOgg()
 
 
 def run_group(feed, parts, serials=None):
@@ -54,29 +55,6 @@ def run_group(feed, parts, serials=None):
     return files, feed._rows(r, len(parts)), o
 
 
-def check_file(host, headers, want, rows, f, frames, serial, npages):
-    """want: the reference's records of the stream; rows: the feed's packet records of it; f: its file"""
-    pages, got = oh.demux(f)                                 # (asserts every CRC, bit-serially, and the continued flags)
-    assert got[:3] == list(headers)
-    assert got[3:] == [w["packet"] for w in want], "the file's packets are not the reference's"
-    assert got[3:] == [r[0] for r in rows], "the file's packets are not the ones vamd_feed_packets reports"
-    assert [r[1] for r in rows] == [w["granulepos"] for w in want]
-    assert f == host.mux(headers, [r[0] for r in rows], [r[1] for r in rows], serial), "the device's pages are not the host mux's"
-    assert len(pages) == npages
-    assert pages[0]["bytes"] == 58 and pages[0]["flags"] == 2 and pages[0]["granule"] == 0
-    assert all(p["serial"] == serial for p in pages)
-    oh.check_policy(pages, next(i for i, p in enumerate(pages) if sum(q["done"] for q in pages[:i + 1]) == 3) + 1)
-    assert pages[-1]["flags"] & 4 and pages[-1]["granule"] == frames
-    dec = oh.reference_decode(got, oh.page_granules(pages, len(want)))
-    assert dec.shape[1] == frames, "the reference decoder returns %d frames of %d" % (dec.shape[1], frames)
-    return pages
-
-
-def reference_records(ref, ch, q, x, managed=None):
-    planar = np.ascontiguousarray((x.astype(np.float32) / np.float32(32768.0)).T if x.dtype == np.int16 else x.T)
-    return ref.RefEncoder(ch, 44100, q, managed=managed).encode_stream(planar)
-
-
 def check_group(host, ref, setup, headers, parts, files, rows, o, serials):
     ch, _, q = checker.SETUPS[setup]
     out = []
@@ -96,7 +74,7 @@ def test_files_of_whole_streams(host, setup, arena, monkeypatch):
     ref = _ref()
     small_arena(monkeypatch, arena)
     ch, rate, q = checker.SETUPS[setup]
-    headers = oh.reference_headers(ch, rate, q)
+    headers = rh.reference_headers(ch, rate, q)
     rng = np.random.default_rng(2026)
     frames = 30000
     pcm = s16_streams(rng, ch, frames, ["noise", "gated", "sine", "clicks", "silence", "gated"])
@@ -117,7 +95,7 @@ def test_short_streams(host, frames):
     import vorbis_amd
     ref = _ref()
     setup = "44k_stereo_q4"
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(frames)
     pcm = s16_streams(rng, 2, frames, ["noise", "gated", "sine"])
     feed = vorbis_amd.Feed(vorbis_amd.default_setup_blob(setup), lanes_per_device=1, max_streams=4, max_frames=8192, ogg_headers=headers)
@@ -133,7 +111,7 @@ def test_unequal_streams_and_their_place_in_the_group(host):
     import vorbis_amd
     ref = _ref()
     setup = "44k_stereo_q4"
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(31)
     lengths = [40000, 1, 33, 2049, 17000, 3072, 39999, 700, 25000, 4097, 12345]
     kinds = ["gated", "noise", "sine", "clicks", "noise", "gated", "sine", "gated", "clicks", "noise", "gated"]
@@ -155,7 +133,7 @@ def test_the_255_segment_rule(host):
     import vorbis_amd
     ref = _ref()
     setup = "44k_stereo_q4"
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     x = np.zeros((400000, 2), np.int16)
     feed = vorbis_amd.Feed(vorbis_amd.default_setup_blob(setup), lanes_per_device=1, max_streams=1, max_frames=400000, ogg_headers=headers)
     try:
@@ -174,7 +152,7 @@ def test_a_continued_page(host):
     import vorbis_amd
     ref = _ref()
     setup = "44k_stereo_q4"
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     parts = []
     for S in (249968, 241776):
         rng = np.random.default_rng(7)
@@ -183,7 +161,7 @@ def test_a_continued_page(host):
         parts.append(np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16))
     for s, x in enumerate(parts):
         want = reference_records(ref, 2, 0.4, x)
-        expect, _ = oh.demux(host.mux(headers, [w["packet"] for w in want], [w["granulepos"] for w in want], s))
+        expect, _ = fr.demux(host.mux(headers, [w["packet"] for w in want], [w["granulepos"] for w in want], s))
         assert any(p["flags"] & 1 for p in expect), "the reference's packets of stream %d no longer give a continued page" % s
         assert expect[2]["nseg"] == 255 and expect[3]["flags"] & 1, "... nor cut their first audio page inside a packet"
         if s == 0:
@@ -207,7 +185,7 @@ def test_managed_and_its_slices(host, arena, monkeypatch):
     ref = _ref()
     rates = (-1, 128000, -1)
     blob = bh.managed_blob(2, rates)
-    headers = oh.reference_headers(2, 44100, managed=rates)
+    headers = rh.reference_headers(2, 44100, managed=rates)
     parts = []
     for s, n in enumerate([66150, 20000, 700]):
         x = bh.signal("music", 2, n, 50 + s).T
@@ -241,7 +219,7 @@ def test_serial_numbers(host):
     import vorbis_amd
     setup = "44k_stereo_q4"
     _ref()
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(4)
     pcm = s16_streams(rng, 2, 9000, ["noise", "gated", "sine"])
     feed = vorbis_amd.Feed(vorbis_amd.default_setup_blob(setup), lanes_per_device=2, max_streams=4, max_frames=9000, ogg_headers=headers)
@@ -254,11 +232,11 @@ def test_serial_numbers(host):
     seen = []
     for files in (a, b):
         for f in files:
-            pages, _ = oh.demux(f)
+            pages, _ = fr.demux(f)
             assert len({p["serial"] for p in pages}) == 1
             seen.append(pages[0]["serial"])
     assert len(set(seen)) == 6
-    given = [{p["serial"] for p in oh.demux(f)[0]} for f in c]
+    given = [{p["serial"] for p in fr.demux(f)[0]} for f in c]
     assert given[0] == {0xdeadbeef} and given[1] == {5} and len(given[2]) == 1 and not given[2] & set(seen)
 
 
@@ -266,7 +244,7 @@ def test_a_stream_with_a_nan_gets_no_file(host):
     import vorbis_amd
     ref = _ref()
     setup = "44k_stereo_q4"
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(8)
     pcm = (s16_streams(rng, 2, 20000, ["noise", "gated", "sine"]).astype(np.float32) / np.float32(32768.0))
     pcm[1, 10000, 0] = np.nan
@@ -288,8 +266,8 @@ def test_errors():
     import vorbis_amd
     _ref()
     blob = vorbis_amd.default_setup_blob("44k_stereo_q4")
-    headers = oh.reference_headers(2, 44100, 0.4)
-    mono = oh.reference_headers(1, 44100, 0.5)
+    headers = rh.reference_headers(2, 44100, 0.4)
+    mono = rh.reference_headers(1, 44100, 0.5)
     for bad in ((mono[0], headers[1], headers[2]), (headers[0][:29], headers[1], headers[2]), (headers[0], headers[2], headers[1])):
         with pytest.raises(vorbis_amd.VamdError) as e:
             vorbis_amd.Feed(blob, lanes_per_device=1, max_streams=2, max_frames=4096, ogg_headers=bad)
@@ -321,7 +299,7 @@ def test_packets_of_an_ogg_feed_equal_a_plain_feeds():
     _ref()
     setup = "44k_stereo_q4"
     blob = vorbis_amd.default_setup_blob(setup)
-    headers = oh.reference_headers(2, 44100, 0.4)
+    headers = rh.reference_headers(2, 44100, 0.4)
     rng = np.random.default_rng(12)
     parts = [s16_streams(rng, 2, n, [k])[0] for n, k in [(20000, "gated"), (5000, "noise"), (12345, "clicks")]]
     res = []

@@ -1,26 +1,24 @@
 """GPU suite: a comment header of its own per stream of an Ogg feed (vamd_feed_ogg_comments, include/vorbis_amd.h) -- the
 comment goes to the device with its group and is paged there (vorbis_amd/csrc/k_ogg.h).  The oracle for every file is the
 shipped host mux given that stream's own three headers; every file is also taken apart by the independent demuxer
-(tests/ogg_host.py), which must return the stream's comment as packet 1 and the reference encoder's packets behind the
+(tests/ogg_framing.py), which must return the stream's comment as packet 1 and the reference encoder's packets behind the
 headers, decoded by the reference, and its three headers read by the reference's vorbis_synthesis_headerin, whose
 vorbis_comment_query must hand the tags back."""
-import tempfile
-
 import numpy as np
 import pytest
 
+from tests import ogg_framing as fr
 from tests import ogg_host as oh
-from tests import ogg_live_host as olh
-from tests import ogg_tags_host as oth
-from tests.test_feed import s16_streams, small_arena, spy_totals
-from tests.test_feed_ogg import check_file, reference_records
+from tests import ref_host as rh
+from tests.feed_cases import check_file, planar, reference_records, small_arena, spy_totals
+from tests.signals import s16_streams, sized_comment
 
 pytestmark = pytest.mark.gpu
 
 SETUP = "44k_stereo_q4"
 KINDS = ["noise", "gated", "sine", "clicks", "silence", "gated", "noise"]
 FRAMES = [2049, 7777, 3000, 4097, 5555, 6001, 2500]
-SHARED_TAGS = [("ENCODER", "vorbis_amd feed")]          # (tests/ogg_host.py, reference_headers' default)
+SHARED_TAGS = [("ENCODER", "vorbis_amd feed")]          # (tests/ref_host.py, reference_headers' default)
 
 
 def _ref():
@@ -32,7 +30,7 @@ def _ref():
 
 @pytest.fixture(scope="module")
 def host():
-    return oh.HostOgg(oh.build(tempfile.mkdtemp(prefix="oggtags")))
+    return oh.HostOgg()
 
 
 class World:
@@ -44,7 +42,7 @@ class World:
     def __init__(self, ref):
         import vorbis_amd
         self.ref = ref
-        self.headers = oh.reference_headers(2, 44100, 0.4)
+        self.headers = rh.reference_headers(2, 44100, 0.4)
         self.vendor = vorbis_amd.comment_fields(self.headers[1])[0]
         rng = np.random.default_rng(1311)
         self.streams = [s16_streams(rng, 2, n, [k])[0] for n, k in zip(FRAMES, KINDS)]
@@ -57,7 +55,7 @@ class World:
                                                  enumerate((255, self.fill, self.fill + 255, 65026, 200000))]
 
     def sized(self, nbytes, title):
-        packet, tags = oth.sized_comment(nbytes, title, self.vendor)
+        packet, tags = sized_comment(nbytes, title, self.vendor)
         return packet, self.vendor, tags
 
     @staticmethod
@@ -70,7 +68,7 @@ class World:
         headers = [self.headers[0], packet, self.headers[2]]
         assert status == 0
         pages = check_file(host, headers, self.want[s] if want is None else want, rows, f, self.streams[s].shape[0], self.serials[s], npages)
-        got_vendor, count, values = oth.reference_tags(oh.demux(f)[1][:3], sorted({k for k, _ in tags}))
+        got_vendor, count, values = rh.reference_tags(fr.demux(f)[1][:3], sorted({k for k, _ in tags}))
         assert got_vendor == vendor.encode() and count == len(tags)
         for k in values:
             assert values[k] == [v.encode() for kk, v in tags if kk == k], "stream %d: vorbis_comment_query(%s)" % (s, k)
@@ -220,7 +218,7 @@ def test_live(host, world):
             assert o["nstreams"] == 3 and off[-1] == o["total_bytes"]
             for t in range(3):
                 piece = bytes(o["bytes"][int(off[t]):int(off[t + 1])])
-                assert len(olh.pages_of(piece)) == int(o["npages"][t]) and o["status"][t] == 0
+                assert len(fr.pages_of(piece)) == int(o["npages"][t]) and o["status"][t] == 0
                 if who[t] is None:
                     assert piece == b"" and not rows[t]
                 else:
@@ -237,13 +235,13 @@ def test_live(host, world):
         whole.close()
     for i, (slot, r0, s, c) in enumerate(plan):
         f = b"".join(got[i]["bytes"])
-        want = ref.RefEncoder(2, 44100, 0.4).encode_stream(oh.planar(world.streams[s]), write_frames=1024)
+        want = ref.RefEncoder(2, 44100, 0.4).encode_stream(planar(world.streams[s]), write_frames=1024)
         pages = world.check(host, s, c, f, got[i]["rows"], 0, got[i]["npages"], want=want)
         assert f == files[i], "stream %d: the pieces are not the whole-stream Ogg feed's file" % s
         if s == 2:                                                   # the 65 026-byte comment: continued onto a second page
             assert (pages[1]["nseg"], pages[1]["done"]) == (255, 0) and pages[2]["flags"] == 1
         # all header pages leave with the group that begins the stream
-        first = olh.pages_of(got[i]["bytes"][0])
+        first = fr.pages_of(got[i]["bytes"][0])
         assert sum(p["done"] for p in first) >= 3 and first[0]["flags"] == 2
 
 

@@ -2,7 +2,6 @@
 (tests/feed_source_host.py): the conversion of every 16-bit pattern against numpy, the ingest body over a host buffer for
 every layout and misalignment the GPU suite walks (the vector-load path and the element path against each other and
 against a numpy gather), and the host's range check."""
-import tempfile
 
 import numpy as np
 import pytest
@@ -14,7 +13,7 @@ HEAD, PAD = 1024, 3 * 2048  # the stereo q4 setup's room in front of and behind 
 
 @pytest.fixture(scope="module")
 def host():
-    return fs.HostSource(fs.build(tempfile.mkdtemp(prefix="feedsrc")))
+    return fs.HostSource(fs.build())
 
 
 def test_conversion_of_every_16_bit_pattern(host):

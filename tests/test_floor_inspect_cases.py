@@ -11,23 +11,11 @@ is the sanitizer's to report.
 This pins the logic of the walk that ends at the first failing chunk (VAMD_FL_INSPECT_STOP) and of the walk it
 replaces; a chunk is one point in this build.  The 64-lane and the half-wave forms are tests/test_floor_split_gpu.py's.
 """
-import os
-import subprocess
-
 import pytest
 
-from tests import checker
-
-ROOT = checker.ROOT
+from tests import hostbuild
 
 
 @pytest.mark.parametrize("stop", [1, 0])
-def test_inspect_error_wave_against_the_serial_walk(tmp_path, stop):
-    exe = str(tmp_path / "floor_inspect_cases")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-ffp-contract=off", "-Wno-unknown-pragmas", "-DVAMD_FL_INSPECT_STOP=%d" % stop,
-                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"),
-                           "-I" + os.path.join(ROOT, "tests", "emul"),
-                           os.path.join(ROOT, "tests", "c", "floor_inspect_cases.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.rstrip().endswith(": ok"), r.stdout[-4000:] + r.stderr[-4000:]
+def test_inspect_error_wave_against_the_serial_walk(stop):
+    hostbuild.run_ok(hostbuild.program("floor_inspect_cases.cpp", ["-DVAMD_FL_INSPECT_STOP=%d" % stop]))

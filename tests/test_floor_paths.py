@@ -14,45 +14,16 @@ few, more than a CU's resident waves of one SIMD, more than 256 channel-blocks).
 silent block (the fit returns NULL: post_valid == 0); a lone spike; a full-scale two-tone block (many splits: the greedy
 loop, fit_line_pair and the post tables at work) -- the special ones in the first, second, last-but-one and last places.
 """
-import os
-
 import numpy as np
 import pytest
 
 from tests import checker
+from tests.feed_cases import FLOOR_KEYS as KEYS, FLOOR_WANT as WANT, channels, chk_for
 
 pytestmark = pytest.mark.gpu
-KEYS = ("mdct", "logmask", "post_valid", "nonzero", "iwork")  # (+ posts: compare_block takes them when both sides have them)
-WANT = KEYS + ("posts",)
 SHAPES = ((1, 1), (0, 1), (1, 0), (0, 0))  # (lW, nW) of a long block
 SETUPS = ("44k_stereo_q4", "44k_stereo_q9", "44k_mono_q5", "44k_51_q3")
-_checkers, _refs = {}, {}
-
-
-class SurroundChecker:
-    """checker.Checker for the setups it has no entry for (checker.SURROUND): the reference where it is built, else the port."""
-
-    def __init__(self, name):
-        from oracle import port, ref
-        ch, rate, q = checker.SURROUND[name]
-        if ref.available():
-            self.enc, self.kind = ref.RefEncoder(ch, rate, q), "reference"
-        else:
-            blob = np.fromfile(os.path.join(checker.ROOT, "vorbis_amd", "data", "setup_%s.bin" % name), dtype=np.uint8)
-            self.enc, self.kind = port.PortEncoder(blob), "port"
-
-    def tap_block(self, pcm, lW=1, W=1, nW=1, blocktype=1, ampmax_in=-9999.0):
-        return self.enc.tap_block(pcm, lW, W, nW, blocktype, ampmax_in)
-
-
-def chk_for(name):
-    if name not in _checkers:
-        _checkers[name] = checker.Checker(name) if name in checker.SETUPS else SurroundChecker(name)
-    return _checkers[name]
-
-
-def channels(name):
-    return (checker.SETUPS.get(name) or checker.SURROUND[name])[0]
+_refs = {}
 
 
 def make_blocks(nb, ch, n, seed):

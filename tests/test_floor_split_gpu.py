@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 from tests import checker, floor_split_signals
-from tests.test_floor_paths import KEYS, WANT, chk_for
+from tests.feed_cases import FLOOR_KEYS as KEYS, FLOOR_WANT as WANT, chk_for
 
 pytestmark = pytest.mark.gpu
 _refs = {}
@@ -82,7 +82,7 @@ def test_managed_blocks():
     import torch
     import vorbis_amd
     from oracle import ref
-    from tests.test_managed import KEYS as M_KEYS, same
+    from tests.feed_cases import MANAGED_KEYS as M_KEYS, managed_same as same
     if not ref.available():
         pytest.skip("oracle/_ref not built: the managed setup is packed by the reference build")
     e = ref.RefEncoder(2, 44100, managed=(-1, 128000, -1))

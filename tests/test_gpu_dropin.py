@@ -15,22 +15,11 @@ import numpy as np
 import pytest
 
 from oracle import ref
+from tests.signals import dropin_stream as _stream
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not (ref.available() and ref.hybrid_available()),
                                  reason="oracle/_ref libraries not built (needs /root/reference at build time)")]
-
-
-def _stream(ch, seconds, kind, seed):
-    rng = np.random.default_rng(seed)
-    frames = int(44100 * seconds)
-    x = (rng.random((ch, frames), dtype=np.float32) - 0.5)
-    if kind == "gated":   # transients -> short blocks, transitions (SURVEY.md 8d "C5")
-        t = np.arange(frames)
-        x *= 2 * np.where((t % 11025) < 1102, 0.5, 0.0005).astype(np.float32)
-    elif kind == "s16":   # encoder_example.c:197-202: s16 samples / 32768
-        x = np.round(x * 32767).astype(np.int16).astype(np.float32) / 32768.0
-    return np.ascontiguousarray(x, dtype=np.float32)
 
 
 @pytest.mark.parametrize("ch,q,kind", [(2, 0.4, "s16"), (2, 0.9, "gated"), (2, 0.1, "gated"), (1, 0.5, "gated")])
@@ -151,7 +140,7 @@ import sys, threading, time, json
 sys.path.insert(0, @ROOT@)
 import numpy as np
 from oracle import ref
-from tests.test_gpu_dropin import _stream
+from tests.signals import dropin_stream as _stream
 N, q = int(sys.argv[1]), float(sys.argv[2])
 streams = [_stream(2, 1.5, "gated" if k % 2 else "s16", seed=100 + k) for k in range(N)]
 want = [ref.RefEncoder(2, 44100, q).encode_stream(x) for x in streams]

@@ -14,9 +14,9 @@ import pytest
 
 import vorbis_amd
 from oracle import port, ref
+from tests.feed_cases import MANAGED_KEYS as KEYS, managed_same as same
 
 pytestmark = pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (needs /root/reference)")
-KEYS = ("m_post_valid", "m_iwork", "m_nonzero", "m_posts")
 
 
 def blocks(e, seed):
@@ -27,16 +27,6 @@ def blocks(e, seed):
         if amp == 1.0 and e.channels == 2:
             pcm[1] = pcm[0] * 0.6   # correlated channels: lossless coupling
         yield pcm, W
-
-
-def same(a, b):
-    for k in KEYS:
-        x, y = a[k], b[k]
-        if k == "m_posts":  # reference rows are 65 wide, ours 32; only `posts` entries are meaningful
-            x, y = x[:, :, :29], y[:, :, :29]
-        if not np.array_equal(x, y):
-            return k
-    return None
 
 
 # (max, nominal, min) bitrates; 64 kb/s puts noise normalisation and the sliding lowpass inside the block

@@ -1,17 +1,19 @@
 """CPU suite: the Ogg feed's paging walk, CRC and host mux (vorbis_amd/csrc/k_ogg.h compiled with the host compiler,
 tests/ogg_host.py) against a bit-serial CRC and a demuxer written from doc/framing.html alone -- and, with the reference
 build, against the reference's own header packets, packets and decoder."""
-import tempfile
-
 import numpy as np
 import pytest
 
+from tests import ogg_framing as fr
 from tests import ogg_host as oh
+from tests import ref_host as rh
+from tests.feed_cases import planar
+from tests.signals import WHOLE_SIZE_LISTS as SIZE_LISTS, s16_streams
 
 
 @pytest.fixture(scope="module")
 def host():
-    return oh.HostOgg(oh.build(tempfile.mkdtemp(prefix="ogg")))
+    return oh.HostOgg()
 
 
 def test_chunked_crc_equals_the_bit_serial_one(host):
@@ -25,7 +27,7 @@ def test_chunked_crc_equals_the_bit_serial_one(host):
 
     def want(n):
         if n not in serial:
-            serial[n] = oh.crc_bitserial(data[:n])
+            serial[n] = fr.crc_bitserial(data[:n])
         return serial[n]
     for n in range(601):
         assert host.crc_shipped(data[:n]) == want(n), n
@@ -49,29 +51,11 @@ def test_chunked_crc_equals_the_bit_serial_one(host):
                 r = ((r << 1) ^ 0x04c11db7) & 0xffffffff if r & 0x80000000 else (r << 1) & 0xffffffff
         at = n
         table[n] = r
-    assert table[lengths[3]] == oh.crc_bitserial(data[:lengths[3]])
+    assert table[lengths[3]] == fr.crc_bitserial(data[:lengths[3]])
     for n in lengths:
         assert host.crc_shipped(data[:n]) == table[n], n
         assert host.crc_chunked(data[:n], chunk, 64) == table[n], n
         assert host.crc_chunked(data[:n], 1, 16) == table[n], n
-
-
-SIZE_LISTS = {
-    "empty_packets": [0, 0, 0],
-    "one": [1],
-    "254": [254],
-    "255": [255],
-    "256": [256],
-    "510": [510],
-    "65025": [65025],
-    "70000": [70000],
-    "70000_then_small": [70000, 10, 20, 5000, 30, 40, 50],
-    "300_one_byte": [1] * 300,
-    "254_one_byte_then_300": [1] * 254 + [300],
-    "fill_rule": [1500, 1500, 1500, 1500, 1500, 10, 10, 10, 10, 5000, 10],
-    "three_big": [3000, 3000, 3000],
-    "mixed": [0, 255, 1, 510, 0, 4097, 2, 2, 2, 2, 2, 765, 0],
-}
 
 
 @pytest.mark.parametrize("name", list(SIZE_LISTS))
@@ -86,10 +70,10 @@ def test_walk_on_synthetic_sizes(host, name):
     packets = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in sizes]
     granules = [1000 * (i + 1) for i in range(len(sizes))]
     f = host.mux(None, packets, granules, 0xfeedface)
-    pages, got = oh.demux(f)
+    pages, got = fr.demux(f)
     assert got == packets
     assert [len(p) for p in got] == sizes
-    oh.check_policy(pages, 0)
+    fr.check_policy(pages, 0)
     planned, file_bytes = host.plan(sizes, granules)
     assert file_bytes == len(f) and len(planned) == len(pages)
     done = 0
@@ -134,9 +118,9 @@ def test_walks_agree_on_random_lists(host):
         assert fa == fb and a == b, trial
         if trial % 4 == 0 and sum(sizes) < 3_000_000:
             packets = [rng.integers(0, 256, v, dtype=np.uint8).tobytes() for v in sizes]
-            pages, got = oh.demux(host.mux(None, packets, granules, trial))
+            pages, got = fr.demux(host.mux(None, packets, granules, trial))
             assert got == packets
-            oh.check_policy(pages, 0)
+            fr.check_policy(pages, 0)
             assert [(p["nseg"], p["body"], p["granule"], p["flags"]) for p in pages] == [(q["nseg"], q["body"], q["granule"], q["flags"]) for q in a]
 
 
@@ -148,14 +132,14 @@ def test_header_runs(host):
         headers = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in hb]
         packets = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (100, 200, 300)]
         f = host.mux(headers, packets, [64, 1088, 2000], 7)
-        pages, got = oh.demux(f)
+        pages, got = fr.demux(f)
         assert got == headers + packets
         assert (pages[0]["flags"], pages[0]["granule"], pages[0]["seq"], pages[0]["bytes"], pages[0]["done"]) == (2, 0, 0, 58, 1)
         nh = next(i for i, p in enumerate(pages) if sum(q["done"] for q in pages[:i + 1]) == 3) + 1
         for p in pages[1:nh]:
             assert p["granule"] == (0 if p["done"] else -1) and not p["flags"] & 6
         assert all(p["nseg"] == 255 for p in pages[1:nh - 1])
-        oh.check_policy(pages, nh)
+        fr.check_policy(pages, nh)
         assert (pages[nh]["flags"] & 1) == 0 and pages[-1]["granule"] == 2000
         assert nh <= host.slots(hb, 0, 0)
 
@@ -190,24 +174,24 @@ def test_reference_packets_through_the_host_mux(host, kind):
         pytest.skip("needs the reference build")
     rng = np.random.default_rng(11)
     frames = 30000
-    pcm = oh.s16_streams(rng, 2, frames, [kind])[0]
-    headers = oh.reference_headers(2, 44100, 0.4)
+    pcm = s16_streams(rng, 2, frames, [kind])[0]
+    headers = rh.reference_headers(2, 44100, 0.4)
     assert [len(h) for h in headers][0] == 30
-    recs = ref.RefEncoder(2, 44100, 0.4).encode_stream(oh.planar(pcm))
+    recs = ref.RefEncoder(2, 44100, 0.4).encode_stream(planar(pcm))
     packets, granules = [r["packet"] for r in recs], [r["granulepos"] for r in recs]
     f = host.mux(headers, packets, granules, 0x1234)
-    pages, got = oh.demux(f)
+    pages, got = fr.demux(f)
     assert got == headers + packets
     assert pages[0]["bytes"] == 58 and pages[0]["flags"] == 2 and pages[1]["done"] == 2
-    oh.check_policy(pages, 2)
+    fr.check_policy(pages, 2)
     assert all(p["serial"] == 0x1234 for p in pages)
     assert pages[-1]["flags"] & 4 and pages[-1]["granule"] == frames
-    dec = oh.reference_decode(got, oh.page_granules(pages, len(packets)))
+    dec = rh.reference_decode(got, fr.page_granules(pages, len(packets)))
     assert dec.shape == (2, frames)
     if kind == "sine":
         # it is the stream that went in, in place, not merely as long: a lossy coder keeps a -4 dB tone, far above any
         # masking threshold, with its error at least 20 dB below it -- a correlation of 1 / sqrt(1 + 0.01) > 0.99
-        x = oh.planar(pcm)
+        x = planar(pcm)
         assert np.corrcoef(dec[0, 2000:20000], x[0, 2000:20000])[0, 1] > 0.99
 
 
@@ -216,16 +200,16 @@ def test_reference_headers_and_short_streams(host):
     if not ref.available():
         pytest.skip("needs the reference build")
     import numpy as np
-    a = oh.reference_headers(2, 44100, 0.4)
+    a = rh.reference_headers(2, 44100, 0.4)
     b, _, _ = ref.matrix_case(2, 44100, 0.4, np.zeros(4096, np.float32))
     assert a[0] == b[0] and a[2] == b[2] and a[0][:7] == b"\x01vorbis" and a[1][:7] == b"\x03vorbis" and a[2][:7] == b"\x05vorbis"
-    m = oh.reference_headers(2, 44100, managed=(-1, 128000, -1))
+    m = rh.reference_headers(2, 44100, managed=(-1, 128000, -1))
     assert m[0] != a[0] and m[2] == a[2]
     rng = np.random.default_rng(2)
     for frames in (1, 3000):
-        pcm = oh.s16_streams(rng, 2, frames, ["noise"])[0]
-        recs = ref.RefEncoder(2, 44100, 0.4).encode_stream(oh.planar(pcm))
+        pcm = s16_streams(rng, 2, frames, ["noise"])[0]
+        recs = ref.RefEncoder(2, 44100, 0.4).encode_stream(planar(pcm))
         packets, granules = [r["packet"] for r in recs], [r["granulepos"] for r in recs]
-        pages, got = oh.demux(host.mux(a, packets, granules, 1))
+        pages, got = fr.demux(host.mux(a, packets, granules, 1))
         assert got == a + packets and pages[-1]["granule"] == frames
-        assert oh.reference_decode(got, oh.page_granules(pages, len(packets))).shape == (2, frames)
+        assert rh.reference_decode(got, fr.page_granules(pages, len(packets))).shape == (2, frames)

@@ -1,50 +1,20 @@
 """CPU suite: an Ogg file in pieces -- the resumed paging walk, the carry and the mux in pieces of vorbis_amd/csrc/k_ogg.h
-(compiled with the host compiler, tests/ogg_live_host.py), which the live Ogg feed's device path is held against.  Whatever
+(compiled with the host compiler, tests/ogg_host.py), which the live Ogg feed's device path is held against.  Whatever
 the cut into groups, the pieces laid end to end are the file the whole-stream mux (ogg_mux) makes of the same packets;
 every piece is a whole number of pages with correct checksums; the carry and the two bounds a live group is sized by
 hold."""
-import tempfile
-
 import numpy as np
 import pytest
 
+from tests import ogg_framing as fr
 from tests import ogg_host as oh
-from tests import ogg_live_host as olh
-
-HB = [30, 89, 4140]
+from tests.signals import HB, LIVE_SIZE_LISTS as SIZE_LISTS, cuts_of
 
 
 @pytest.fixture(scope="module")
 def hosts():
-    d = tempfile.mkdtemp(prefix="ogglive")
-    return oh.HostOgg(oh.build(d)), olh.LiveOgg(olh.build(d))
-
-
-def size_lists():
-    rng = np.random.default_rng(17)
-    return {
-        "random": [int(v) for v in rng.integers(0, 1201, 70)] + [5000, 3, 4100, 2],
-        "400_one_byte": [1] * 400,
-        "multiples_of_255": [int(v) for v in rng.choice([0, 255, 510, 765, 1020], 60)],
-        "70000_among_small": [10, 20, 70000, 30, 5000, 40, 50, 60],
-        "254_one_byte_then_2000": [1] * 254 + [2000] * 6,
-    }
-
-
-SIZE_LISTS = size_lists()
-
-
-def cuts_of(name, n, rng):
-    """-> lists of group sizes (packets per group; the last group closes the stream)"""
-    out = [[i, n - i] for i in range(n + 1)]                       # after every packet index in turn
-    out.append([1] * n)                                             # single packets
-    for _ in range(6):                                              # random cuts with empty groups, a close on an empty group
-        points = sorted(int(v) for v in rng.integers(0, n + 1, int(rng.integers(1, 9))))
-        edges = [0] + points + [n]
-        groups = [b - a for a, b in zip(edges, edges[1:])]
-        groups.insert(int(rng.integers(0, len(groups) + 1)), 0)
-        out.append(groups + [0])
-    return out
+    host = oh.HostOgg()
+    return host, host
 
 
 def run_cut(live, headers, packets, granules, groups, serial, cap, seen):
@@ -60,8 +30,8 @@ def run_cut(live, headers, packets, granules, groups, serial, cap, seen):
         assert 0 <= st.ncarry <= 255 and st.carried <= live.carry_body and st.carried_rounded <= live.carry_bytes - 18
         assert st.ncarry == (0 if close else st.open_page["npackets"])
         assert st.carried == (0 if close else st.open_page["body"])
-        assert st.npages <= live.slots([len(h) for h in headers], n, cap), (g, st.npages)
-        assert len(piece) <= live.file_bound(sum((v + 3) // 4 * 4 for v in new), n, 1, [len(h) for h in headers]), (g, len(piece))
+        assert st.npages <= live.live_slots([len(h) for h in headers], n, cap), (g, st.npages)
+        assert len(piece) <= live.live_file_bound(sum((v + 3) // 4 * 4 for v in new), n, 1, [len(h) for h in headers]), (g, len(piece))
         if not close:
             seen["continued"] += st.open_page["byte0"] > 0
             seen["carried"] += st.open_page["npackets"] >= 200
@@ -80,7 +50,7 @@ def test_pieces_equal_the_whole_mux(hosts, name):
     granules = [int(v) for v in np.cumsum(rng.integers(1, 2049, len(sizes)))]
     serial = 0xfeed0000 + len(sizes)
     want = whole.mux(headers, packets, granules, serial)
-    want_pages, got = oh.demux(want)
+    want_pages, got = fr.demux(want)
     assert got == headers + packets
     seen = {"continued": 0, "carried": 0}
     for groups in cuts_of(name, len(sizes), rng):
@@ -88,14 +58,14 @@ def test_pieces_equal_the_whole_mux(hosts, name):
         assert b"".join(p for p, _ in pieces) == want, groups
         seq = 0
         for piece, npages in pieces:
-            pages = olh.pages_of(piece)                              # a whole number of pages, every checksum
+            pages = fr.pages_of(piece)                              # a whole number of pages, every checksum
             assert len(pages) == npages
             for p in pages:
                 assert p["seq"] == seq and p["serial"] == serial
                 seq += 1
         assert seq == len(want_pages)
         # a page is handed out once it is closed, never before: no group but the closing one ends with the stream's last page
-        assert all(not olh.pages_of(p)[-1]["flags"] & 4 for p, n in pieces[:-1] if n)
+        assert all(not fr.pages_of(p)[-1]["flags"] & 4 for p, n in pieces[:-1] if n)
     # the coverage guard: these inputs leave, at some boundary, an open page that began inside a packet (byte0 > 0) and one
     # that carries at least 200 packets -- so neither case can go uncovered silently
     if name == "254_one_byte_then_2000":
@@ -117,4 +87,4 @@ def test_a_bare_run_and_a_second_stream_in_the_same_state(hosts):
         granules = list(range(100, 100 + len(sizes)))
         got = st.piece(packets[:13], granules[:13], False) + st.piece([], [], False) + st.piece(packets[13:], granules[13:], True)
         assert got == whole.mux(None, packets, granules, 5)
-        assert olh.pages_of(got)[0]["seq"] == 0
+        assert fr.pages_of(got)[0]["seq"] == 0

@@ -3,17 +3,14 @@ reader of comment headers against the reference's vorbis_commentheader_out, the 
 (ogg_comment_check, compiled with the host compiler) against the reference's vorbis_synthesis_headerin, and the bounds a
 group with comments of its own is sized by: page slots from its longest comment, the file arena from their sum."""
 import struct
-import tempfile
 
 import numpy as np
 import pytest
 
 import vorbis_amd
 from tests import ogg_host as oh
-from tests import ogg_live_host as olh
-from tests import ogg_tags_host as oth
-from tests.test_ogg_cpu import SIZE_LISTS
-from tests.test_ogg_live_cpu import SIZE_LISTS as LIVE_SIZE_LISTS
+from tests import ref_host as rh
+from tests.signals import LIVE_SIZE_LISTS, WHOLE_SIZE_LISTS as SIZE_LISTS
 
 TAG_SETS = {
     "none": [],
@@ -34,8 +31,8 @@ def _ref():
 
 @pytest.fixture(scope="module")
 def hosts():
-    d = tempfile.mkdtemp(prefix="oggtags")
-    return oh.HostOgg(oh.build(d)), olh.LiveOgg(olh.build(d)), oth.TagsOgg(oth.build(d))
+    host = oh.HostOgg()
+    return host, host, host
 
 
 @pytest.fixture(scope="module")
@@ -44,7 +41,7 @@ def reference_packets():
     _ref()
     out = {}
     for name, tags in TAG_SETS.items():
-        h = oh.reference_headers(2, 44100, 0.4, tags=tags)
+        h = rh.reference_headers(2, 44100, 0.4, tags=tags)
         out[name] = h[1]
         out["ident"] = h[0]
     return out
@@ -115,7 +112,7 @@ def test_validator_agrees_with_the_reference(hosts, reference_packets):
     for what, candidate, accepted in validator_cases(reference_packets):
         code = tags.check(candidate)
         assert (code == 0) == accepted, "%s: ogg_comment_check = %d (%s)" % (what, code, tags.why(code))
-        r = oth.reference_headerin(reference_packets["ident"], candidate)
+        r = rh.reference_headerin(reference_packets["ident"], candidate)
         assert (r == 0) == (code == 0), "%s: vorbis_synthesis_headerin = %d, ogg_comment_check = %d" % (what, r, code)
 
 
@@ -177,7 +174,7 @@ def test_live_slots_and_file_bound_of_a_group_with_comments(hosts):
                     new = sum((v + 3) // 4 * 4 for v in sizes[k:k + m])
                     k += m
                     for longest in (c, max(COMMENT_LENGTHS)):
-                        assert st.npages <= live.slots([30, longest, setup], m, cap), (name, c, g, st.npages)
+                        assert st.npages <= live.live_slots([30, longest, setup], m, cap), (name, c, g, st.npages)
                     assert len(piece) <= tags.live_file_bound_v(new, m, 1, hb, c), (name, c, g, len(piece))
                     got += piece
                 assert got == want, (name, c, groups)

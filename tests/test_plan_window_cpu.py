@@ -21,8 +21,8 @@ IDS = ["256_2048", "512_4096", "64_8192"]
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    return pwh.build(str(tmp_path_factory.mktemp("planwindow")))
+def lib():
+    return pwh.build()
 
 
 def golden_flags(name):

@@ -9,7 +9,8 @@ import tempfile
 import numpy as np
 import pytest
 
-from tests.test_abi_and_host import ABI, LIB, ROOT
+from tests.checker import ROOT
+from tests.feed_cases import ABI, LIB
 
 
 def _offsets():

@@ -117,7 +117,8 @@ def test_kernel_bodies_match_reference_managed(rates):
 def test_detector_kernel_bodies_match_reference():
     """The block-switching detector ORs its triggers over all six channels (lib/envelope.c:234-239)."""
     from tests.emul.emul import Emul
-    from tests.test_envelope import gated, check_state
+    from tests.feed_cases import check_state
+    from tests.signals import gated
     from vorbis_amd import EnvelopeState, envelope_marks
     x = gated(6, 40000, 66)
     x[2] = np.roll(x[2], 2500)        # the centre channel's bursts fall between the others'
@@ -136,7 +137,8 @@ def test_detector_kernel_bodies_match_reference():
 @pytest.mark.gpu
 @needs_ref
 def test_gpu_detector_matches_reference():
-    from tests.test_envelope import gated, check_state
+    from tests.feed_cases import check_state
+    from tests.signals import gated
     from vorbis_amd import envelope_marks
     x = gated(6, 60000, 67)
     x[4] = np.roll(x[4], 1700)

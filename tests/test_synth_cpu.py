@@ -11,19 +11,16 @@ import numpy as np
 import pytest
 
 from oracle import ref
-from tests import ogg_host, synth_host
+from tests import ref_host, synth_host
+from tests.feed_cases import same_bits
+from tests.signals import gated_noise
 
 pytestmark = pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (needs /root/reference)")
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return synth_host.build(tmp_path_factory.mktemp("synth_host"))
+def exe():
+    return synth_host.build()
 
 
 @pytest.mark.parametrize("n", [256, 512, 1024, 2048, 4096])
@@ -35,7 +32,7 @@ def test_mdct_backward(exe, tmp_path, n):
     spectra.append(spectra[0] * (rng.random(n // 2) < 0.1))
     spectra.append(np.full(n // 2, 1e-41, np.float32))  # fp32 subnormals are kept
     for k, x in enumerate(spectra):
-        want, trig = synth_host.reference_mdct_backward(n, x)
+        want, trig = ref_host.reference_mdct_backward(n, x)
         got = synth_host.host_mdct_backward(exe, tmp_path, n, trig, x)
         assert same_bits(got, want), "n=%d spectrum %d: %d of %d values differ" % (n, k, int((got.view(np.uint32) != want.view(np.uint32)).sum()), n)
     assert np.signbit(want).any()  # (the last one asked for signed zeros / subnormals; the zero spectrum gives -0)
@@ -44,10 +41,10 @@ def test_mdct_backward(exe, tmp_path, n):
 @pytest.mark.parametrize("name", list(synth_host.SETUPS))
 def test_single_blocks(exe, tmp_path, name):
     from tests.emul.emul import Emul
-    enc = synth_host.encoder(name)
+    enc = ref_host.encoder(name)
     blob = enc.pack_setup()
     em = Emul(blob)
-    dec = synth_host.BlockDecoder(synth_host.encoder_headers(synth_host.encoder(name)))
+    dec = ref_host.BlockDecoder(ref_host.encoder_headers(ref_host.encoder(name)))
     bs = (enc.blocksize(0), enc.blocksize(1))
     assert dec.bs == bs and dec.channels == enc.channels
     blocks, want, what = [], [], []
@@ -71,11 +68,11 @@ def test_single_blocks(exe, tmp_path, name):
 
 def _stream(name, frames, seed):
     """-> (blocks [(W, vb->pcm)], headers, packets, granules) of the reference encoder over gated noise"""
-    enc = synth_host.encoder(name)
-    x = synth_host.gated_noise(enc.channels, enc.rate, frames, seed)
+    enc = ref_host.encoder(name)
+    x = gated_noise(enc.channels, enc.rate, frames, seed)
     recs = enc.encode_stream(x)
-    headers = synth_host.encoder_headers(synth_host.encoder(name))
-    dec = synth_host.BlockDecoder(headers)
+    headers = ref_host.encoder_headers(ref_host.encoder(name))
+    dec = ref_host.BlockDecoder(headers)
     blocks = [(r["W"], dec.block(r["packet"], r["W"])) for r in recs]
     dec.close()
     return blocks, headers, [r["packet"] for r in recs], [r["granulepos"] for r in recs]
@@ -86,11 +83,11 @@ def test_lap(exe, tmp_path, name, seconds):
     ch, rate, _, _ = synth_host.SETUPS[name]
     frames = int(rate * seconds) + 13
     blocks, headers, packets, granules = _stream(name, frames, 5)
-    enc = synth_host.encoder(name)
+    enc = ref_host.encoder(name)
     bs = (enc.blocksize(0), enc.blocksize(1))
     if bs[0] != bs[1]:  # long/long, long/short, short/long, short/short
         assert synth_host.lap_cases([W for W, _ in blocks]) == {(0, 0), (0, 1), (1, 0), (1, 1)}
-    want = ogg_host.reference_decode(headers + packets, granules)
+    want = ref_host.reference_decode(headers + packets, granules)
     assert want.shape == (ch, frames)
     got = synth_host.host_lap(exe, tmp_path, bs, synth_host.windows(enc.pack_setup(), bs), blocks, frames)
     assert same_bits(got, want), int((got.view(np.uint32) != want.view(np.uint32)).sum())
@@ -99,9 +96,9 @@ def test_lap(exe, tmp_path, name, seconds):
 @pytest.mark.parametrize("frames", synth_host.SHORT_LENGTHS)
 def test_lap_short_streams(exe, tmp_path, frames):
     blocks, headers, packets, granules = _stream("44k_stereo_q4", frames, frames)
-    enc = synth_host.encoder("44k_stereo_q4")
+    enc = ref_host.encoder("44k_stereo_q4")
     bs = (enc.blocksize(0), enc.blocksize(1))
-    want = ogg_host.reference_decode(headers + packets, granules)
+    want = ref_host.reference_decode(headers + packets, granules)
     assert want.shape == (2, frames)
     got = synth_host.host_lap(exe, tmp_path, bs, synth_host.windows(enc.pack_setup(), bs), blocks, frames)
     assert same_bits(got, want)

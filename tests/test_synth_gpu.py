@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import ref
-from tests import synth_host
+from tests import ref_host, synth_host
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (needs /root/reference)")]
 
@@ -17,9 +17,9 @@ WANT = ("mdct", "logmask", "posts", "post_valid", "iwork", "nonzero", "ampmax_ou
 def test_blocks_against_the_reference_decoder(name):
     import torch
     import vorbis_amd
-    enc = synth_host.encoder(name)
+    enc = ref_host.encoder(name)
     an = vorbis_amd.Analyzer(enc.pack_setup(), 0)
-    dec = synth_host.BlockDecoder(synth_host.encoder_headers(synth_host.encoder(name)))
+    dec = ref_host.BlockDecoder(ref_host.encoder_headers(ref_host.encoder(name)))
     bs = (enc.blocksize(0), enc.blocksize(1))
     bad = []
     for W in ((1, 0) if bs[0] != bs[1] else (0,)):
@@ -48,9 +48,9 @@ def test_synth_without_any_other_output():
     """synth alone: the residue search runs although nobody takes its outputs"""
     import torch
     import vorbis_amd
-    enc = synth_host.encoder("44k_stereo_q4")
+    enc = ref_host.encoder("44k_stereo_q4")
     an = vorbis_amd.Analyzer(enc.pack_setup(), 0)
-    dec = synth_host.BlockDecoder(synth_host.encoder_headers(synth_host.encoder("44k_stereo_q4")))
+    dec = ref_host.BlockDecoder(ref_host.encoder_headers(ref_host.encoder("44k_stereo_q4")))
     kinds = synth_host.block_set(2, enc.blocksize(1), 8)
     pcm = torch.from_numpy(np.stack(list(kinds.values()))).cuda()
     synth = an.analyze(pcm, W=1, want=("synth",))["synth"].cpu().numpy()

@@ -14,7 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import checker, tone_fold_signals
+from tests import checker, hostbuild, tone_fold_signals
 from tests.emul.emul import Emul
 
 ROOT = checker.ROOT
@@ -22,11 +22,8 @@ ALL_SETUPS = tuple(checker.SETUPS) + tuple(checker.SURROUND)
 KEYS = ("tone", "logmask", "mdct", "post_valid", "nonzero", "iwork")  # (+ posts: compare_block takes them itself)
 
 
-def test_group_tables_follow_the_reference_walk(tmp_path):
-    exe = str(tmp_path / "tone_fold_groups")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "c", "tone_fold_groups.cpp"), "-o", exe])
+def test_group_tables_follow_the_reference_walk():
+    exe = hostbuild.program("tone_fold_groups.cpp")
     blobs = sorted(glob.glob(os.path.join(ROOT, "vorbis_amd", "data", "setup_*.bin")))
     assert len(blobs) == 5
     r = subprocess.run([exe] + blobs, capture_output=True, text=True)
@@ -36,7 +33,7 @@ def test_group_tables_follow_the_reference_walk(tmp_path):
 def _checker(name):
     if name in checker.SETUPS:
         return checker.Checker(name)
-    from tests.test_floor_paths import SurroundChecker
+    from tests.feed_cases import SurroundChecker
     return SurroundChecker(name)
 
 

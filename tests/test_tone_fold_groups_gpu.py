@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from tests import checker, tone_fold_signals
-from tests.test_floor_paths import channels, chk_for
+from tests.feed_cases import channels, chk_for
 
 pytestmark = pytest.mark.gpu
 SETUPS = ("44k_stereo_q4", "44k_stereo_q9", "44k_mono_q5", "44k_51_q3")

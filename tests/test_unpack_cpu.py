@@ -13,29 +13,26 @@ import numpy as np
 import pytest
 
 from oracle import ref
-from tests import decode_cases, ogg_host, synth_host, unpack_host
+from tests import decode_cases, ref_host, synth_host, unpack_host
+from tests.feed_cases import same_bits
+from tests.signals import gated_noise, managed_streams
 from tests.synth_host import RES_CLASS_STRIDE
 
 pytestmark = pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built")
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 @pytest.fixture(scope="module")
-def exe(tmp_path_factory):
-    return unpack_host.build(tmp_path_factory.mktemp("unpack_host"))
+def exe():
+    return unpack_host.build()
 
 
 @pytest.mark.parametrize("name", list(synth_host.SETUPS))
 def test_single_blocks(exe, tmp_path, name):
     from tests.emul.emul import Emul
-    enc = synth_host.encoder(name)
+    enc = ref_host.encoder(name)
     blob = enc.pack_setup()
     em = Emul(blob)
-    dec = synth_host.BlockDecoder(synth_host.encoder_headers(synth_host.encoder(name)))
+    dec = ref_host.BlockDecoder(ref_host.encoder_headers(ref_host.encoder(name)))
     bs, ch = (enc.blocksize(0), enc.blocksize(1)), enc.channels
     rows, want, what = [], [], []
     for W in ((1, 0) if bs[0] != bs[1] else (0,)):
@@ -70,9 +67,9 @@ def test_single_blocks(exe, tmp_path, name):
 
 
 def _stream(name, frames, seed):
-    enc = synth_host.encoder(name)
-    recs = enc.encode_stream(synth_host.gated_noise(enc.channels, enc.rate, frames, seed))
-    headers = synth_host.encoder_headers(synth_host.encoder(name))
+    enc = ref_host.encoder(name)
+    recs = enc.encode_stream(gated_noise(enc.channels, enc.rate, frames, seed))
+    headers = ref_host.encoder_headers(ref_host.encoder(name))
     return enc, headers, [r["packet"] for r in recs], [r["granulepos"] for r in recs], [r["W"] for r in recs]
 
 
@@ -83,7 +80,7 @@ def test_streams(exe, tmp_path, name, seconds):
     enc, headers, packets, granules, Ws = _stream(name, frames, 5)
     if enc.blocksize(0) != enc.blocksize(1):  # long/long, long/short, short/long, short/short
         assert synth_host.lap_cases(Ws) == {(0, 0), (0, 1), (1, 0), (1, 1)}
-    want = ogg_host.reference_decode(headers + packets, granules)
+    want = ref_host.reference_decode(headers + packets, granules)
     assert want.shape == (ch, frames)
     (status, got), = unpack_host.host_decode_streams(exe, tmp_path, enc.pack_setup(), [packets], [granules[-1]], ch)
     assert status == 0
@@ -97,7 +94,7 @@ def test_short_streams(exe, tmp_path):
         enc, headers, packets, granules, _ = _stream("44k_stereo_q4", frames, frames)
         streams.append(packets)
         ends.append(granules[-1])
-        want.append(ogg_host.reference_decode(headers + packets, granules))
+        want.append(ref_host.reference_decode(headers + packets, granules))
         assert want[-1].shape == (2, frames)
     got = unpack_host.host_decode_streams(exe, tmp_path, enc.pack_setup(), streams, ends, 2)
     for frames, (status, pcm), w in zip(synth_host.SHORT_LENGTHS, got, want):
@@ -111,26 +108,11 @@ def test_flagged_streams(exe, tmp_path):
     assert len(packets) > 4 and len(packets[2]) > 5
     cut = packets[:2] + [packets[2][:5]] + packets[3:]
     typed = packets[:1] + [bytes([packets[1][0] ^ 1]) + packets[1][1:]] + packets[2:]
-    want = ogg_host.reference_decode(headers + packets, granules)
+    want = ref_host.reference_decode(headers + packets, granules)
     got = unpack_host.host_decode_streams(exe, tmp_path, enc.pack_setup(), [packets, cut, typed, packets], [granules[-1]] * 4, 2)
     assert [s for s, _ in got] == [0, unpack_host.STATUS_TRUNCATED, unpack_host.STATUS_NOTAUDIO, 0]
     assert got[1][1].shape == (2, 0) and got[2][1].shape == (2, 0)
     assert same_bits(got[0][1], want) and same_bits(got[3][1], want)
-
-
-MANAGED_RATES = (-1, 128000, -1)  # the setup tests/test_feed_decoded.py::test_errors builds: ABR 128 kb/s
-
-
-def managed_streams(seconds=(0.3, 0.7, 1.1, 1.5), seed=11):
-    """-> (setup blob, headers, per stream (packets, granules)) of the reference's managed encoder over the gated-noise
-    streams of tests/test_feed_decoded.py"""
-    out = []
-    for i, sec in enumerate(seconds):
-        enc = ref.RefEncoder(2, 44100, managed=MANAGED_RATES)
-        recs = enc.encode_stream(synth_host.gated_noise(2, 44100, int(44100 * sec) + 7 * i + 1, seed + i))
-        out.append(([r["packet"] for r in recs], [r["granulepos"] for r in recs]))
-    enc = ref.RefEncoder(2, 44100, managed=MANAGED_RATES)
-    return enc.pack_setup(), synth_host.encoder_headers(ref.RefEncoder(2, 44100, managed=MANAGED_RATES)), out
 
 
 def test_managed_streams(exe, tmp_path):
@@ -143,7 +125,7 @@ def test_managed_streams(exe, tmp_path):
     assert all(got[s][0] == unpack_host.STATUS_TRUNCATED for s in flagged) and 2 * len(flagged) <= len(streams), flagged
     for s, (packets, granules) in enumerate(streams):
         if s not in flagged:
-            assert same_bits(got[s][1], ogg_host.reference_decode(headers + packets, granules)), s
+            assert same_bits(got[s][1], ref_host.reference_decode(headers + packets, granules)), s
 
 
 MUTATED_CASES = 96

@@ -6,25 +6,14 @@ import subprocess
 
 import numpy as np
 
-from tests.synth_host import RES_CLASS_STRIDE, ROOT
+from tests import hostbuild
+from tests.synth_host import RES_CLASS_STRIDE
 
 STATUS_NOTAUDIO, STATUS_BADCODE, STATUS_TRUNCATED = 4, 8, 16  # include/vorbis_amd.h
 
 
-_built = []
-
-
-def build(outdir):
-    """once per process: the modules that use the program share it"""
-    if _built and os.path.exists(_built[0]):
-        return _built[0]
-    exe = os.path.join(str(outdir), "unpack_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-ffp-contract=off", "-fno-fast-math", "-Wno-unknown-pragmas", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"), "-I" + os.path.join(ROOT, "tests", "emul"),
-                           os.path.join(ROOT, "tests", "c", "unpack_host.cpp"), "-o", exe])
-    _built[:] = [exe]
-    return exe
+def build():
+    return hostbuild.program("unpack_host.cpp")
 
 
 def _run(exe, args):

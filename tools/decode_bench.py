@@ -9,7 +9,7 @@ is one JSON line, and the steps hand the packets on in a file in --work.
              decoder's for the first streams
     phases   k_unpack's in-kernel stopwatch (vamd_debug_cycles): head / floors / residues
     trace    rocprofv3 --kernel-trace --stats over `time`: k_unpack, k_synth, k_lap in us per launch
-    cpu      ogg_host.reference_decode over the same packets, a process per stream on --cpus CPUs
+    cpu      ref_host.reference_decode over the same packets, a process per stream on --cpus CPUs
 
     python tools/decode_bench.py --streams 64 --seconds 20 --reps 5 [--steps encode,time,phases,trace,cpu]
 """
@@ -68,15 +68,15 @@ def step_encode(a):
 
 
 def _reference(args):
-    from tests import ogg_host
+    from tests import ref_host
     headers, packets, granules = args
-    return ogg_host.reference_decode(headers + packets, granules)
+    return ref_host.reference_decode(headers + packets, granules)
 
 
 def step_time(a):
     import torch
     import vorbis_amd
-    from tests import ogg_host
+    from tests import ref_host
     rows = load_rows(a.packets)
     an = vorbis_amd.Analyzer(vorbis_amd.default_setup_blob(SETUP), 0)
     prep = an.decode_prepare([p for p, _ in rows], [g[-1] for _, g in rows])
@@ -87,7 +87,7 @@ def step_time(a):
         t0 = time.perf_counter()
         an.decode_run(prep, pcm)  # (returns when the statuses are back: the stream is idle)
         ms.append((time.perf_counter() - t0) * 1e3)
-    headers = ogg_host.reference_headers(2, 44100, 0.4)
+    headers = ref_host.reference_headers(2, 44100, 0.4)
     same = 0
     for s in range(min(2, len(rows))):
         want = _reference((headers, rows[s][0], rows[s][1]))
@@ -149,9 +149,9 @@ def step_trace(a):
 
 def step_cpu(a):
     from multiprocessing import Pool
-    from tests import ogg_host
+    from tests import ref_host
     rows = load_rows(a.packets)
-    headers = ogg_host.reference_headers(2, 44100, 0.4)
+    headers = ref_host.reference_headers(2, 44100, 0.4)
     t0 = time.perf_counter()
     with Pool(a.cpus) as pool:
         frames = sum(x.shape[1] for x in pool.imap_unordered(_reference, [(headers, p, g) for p, g in rows]))

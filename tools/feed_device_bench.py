@@ -180,8 +180,8 @@ def main():
     blob = vorbis_amd.default_setup_blob("44k_stereo_q4")
     headers = None
     if a.only != "ingest":
-        from tests import ogg_host
-        headers = ogg_host.reference_headers(2, 44100, 0.4)  # (needs the reference build, oracle/_ref)
+        from tests import ref_host
+        headers = ref_host.reference_headers(2, 44100, 0.4)  # (needs the reference build, oracle/_ref)
     if a.only == "host":
         return whole(a, vorbis_amd, blob, pcm, ["host"], "_s16", headers)
     everything = ["host", "dev_s16", "dev_f32", "dev_f16", "dev_bf16"]

@@ -71,8 +71,8 @@ def main():
     for k in names:
         kw = {}
         if k == "ogg":
-            from tests import ogg_host
-            kw["ogg_headers"] = ogg_host.reference_headers(2, 44100, 0.4)  # (needs the reference build, oracle/_ref)
+            from tests import ref_host
+            kw["ogg_headers"] = ref_host.reference_headers(2, 44100, 0.4)  # (needs the reference build, oracle/_ref)
         feeds[k] = vorbis_amd.Feed(blob, lanes_per_device=a.lanes, max_streams=a.streams, max_frames=frames, **kw)
     best = {k: None for k in names}
     walls = {k: [] for k in names}
@@ -116,8 +116,8 @@ def live(a, vorbis_amd, blob, pcm, names):
     for k in names:
         kw = {}
         if k == "ogg":
-            from tests import ogg_host
-            kw["ogg_headers"] = ogg_host.reference_headers(2, 44100, 0.4)  # (needs the reference build, oracle/_ref)
+            from tests import ref_host
+            kw["ogg_headers"] = ref_host.reference_headers(2, 44100, 0.4)  # (needs the reference build, oracle/_ref)
         feeds[k] = vorbis_amd.Feed(blob, lanes_per_device=1, max_streams=a.streams, max_frames=piece, write_frames=1024, **kw)
     best = {k: None for k in names}
     walls = {k: [] for k in names}

@@ -12,7 +12,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 from oracle import ref  # noqa: E402
-from tests.test_gpu_dropin import _stream  # noqa: E402
+from tests.signals import dropin_stream as _stream  # noqa: E402
 
 secs = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 q = float(sys.argv[2]) if len(sys.argv) > 2 else 0.4
