@@ -205,7 +205,9 @@ int vamd_device_count(void);
 /* The environment knobs in force for a context, as "NAME=value" words (read once, at vamd_create; vorbis_amd/csrc/vamd_knobs.h).  The
  * operating knobs (VAMD_VERBOSE, VAMD_BATCH_LANES / _EAGER / _JOIN / _SPIN_BELOW) are always honoured; the test knobs --
  * kernel choices turned the other way, widened margins, occupancy caps, injected failures -- only beside
- * VAMD_TEST_KNOBS=1, so that an inherited environment cannot change what a drop-in library does. */
+ * VAMD_TEST_KNOBS=1, so that an inherited environment cannot change what a drop-in library does.  The last word is not a
+ * knob: chase_walk=<short>,<long> names the stack walk a large batch of either size class takes ("regs" or "ring"), which
+ * the build and the setup decide. */
 const char *vamd_config_string(const vamd_ctx *ctx);
 
 /* ---- Input domain ---------------------------------------------------------------------------------

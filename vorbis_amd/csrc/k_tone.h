@@ -8,10 +8,14 @@
 //    scatter the chosen tone curve into seed[] with an LDS float max (max is
 //    order-free, so the result equals the reference's sequential update).
 //  * seed_chase is NOT a sliding-window max (SURVEY.md 0.8 iv).  Its first half
-//    (the stack discipline) is restated literally and walked by one lane, with
-//    the two top-of-stack entries held in registers so the common path never
-//    waits on LDS; its second half (painting each surviving entry over its span)
-//    is a prefix-max over the entries' end positions and is done by all lanes.
+//    (the stack discipline) is restated literally and walked by one lane.  A step
+//    can pop or look at only the lines within linesper of it, so where linesper is 8
+//    (every libvorbisenc setup) the walk's state is a mask of which of the last seven
+//    lines are still stacked plus their values, all in registers (tone_chase_regs,
+//    chase_chunk_regs); longer windows keep a ring in LDS with the two top-of-stack
+//    entries in registers (tone_chase_ring).  Its second half (painting each surviving
+//    entry over its span) is a prefix-max over the entries' end positions and is done
+//    by all lanes.
 //  * max_seeds' pointer walk over (octave line, bin) is static too: the lines each
 //    of its outer-loop iterations ("group") scans and the bins that take the outcome
 //    are precomputed; lanes fold runs of lines into their groups' minima, every bin then
@@ -21,7 +25,7 @@
 // wave owned a single block -- can instead run with one *lane* per channel-block
 // (64 walks per wave instruction):
 //   tone_seed_block   wave per block   : scatter -> seed[] to HBM
-//   tone_chase_thread thread per block : stack walk -> list of surviving lines
+//   tone_chase_regs / tone_chase_ring  thread per block : stack walk -> list of surviving lines
 //   tone_fold_block   wave per block   : paint + max_seeds fold -> tone curve
 // tonemask_block() composes the same three pieces for one block (test build).
 #pragma once
@@ -411,6 +415,84 @@ VAMD_DEV ChaseChunk chase_chunk_regs(const float *seeds, int n, int s, int e, in
     }
   }
   return out;
+}
+
+// ---- round 24: the whole-block walk on the same state (profiles/r24_chase_regs.txt) --------------------------------------
+// tone_chase_ring's job -- one lane walks a block's row from line 0 and writes the survivor list -- with chase_chunk_regs'
+// state: no ring, no LDS.  What the ring walk waited for were its trips to LDS inside the dependent chain (two reads that
+// end every pop, a read-back before an index's first write, two stores per push), taken by 64 lanes at the pace of the
+// one with the most pops; here a pop and a push are LP-2 register moves each.  The walk starts at line 0 and therefore
+// in the true state (m = 0: no warm-up, no signatures to compare), and finality is the mask's top: the bit a push shifts
+// out of the window stands for line i-(LP-1), which no later line can pop or look at, so if it is set that line goes to
+// the survivor list -- lines leave the window in ascending order, which is the list's.  At the end the bits still in the
+// mask go out oldest first.  Rows are read, and survivors stored, exactly as tone_chase_ring does (whole 128-byte lines,
+// 32 lines a trip, eight positions per 16-byte store, the last one to seven singly): list and count are byte for byte
+// the ring walk's (tests/c/chase_regs_cases.cpp).
+//   VAMD_CHASE_REGS (1; 0 = the ring walk, as before): the walk of the lane-per-block kernel where linesper is 8
+#ifndef VAMD_CHASE_REGS
+#define VAMD_CHASE_REGS 1
+#endif
+template <int LP>
+VAMD_DEV int tone_chase_regs(const float *__restrict__ seeds, int n, unsigned short *__restrict__ surv) {
+  constexpr int WN = LP - 1;
+  constexpr uint32_t WMASK = (1u << WN) - 1u;
+  static_assert(LP >= 3 && LP <= 32, "the window's mask is one register, the pop test looks at two values");
+  unsigned long long wlo = 0, whi = 0;  // the last eight survivors, oldest in the low bits of wlo
+  int nw = 0;
+  auto emit = [&](int pos) {
+    wlo = (wlo >> 16) | (whi << 48);
+    whi = (whi >> 16) | ((unsigned long long)(unsigned)pos << 48);
+    nw++;
+    if ((nw & 7) == 0) {
+      unsigned long long *dst = (unsigned long long *)(surv + nw - 8);
+      dst[0] = wlo;
+      dst[1] = whi;
+    }
+  };
+  uint32_t m = 0;  // bit k: line i-1-k is on the stack
+  float st[WN];    // their values, newest first
+#pragma unroll
+  for (int j = 0; j < WN; j++) st[j] = 0.f;
+  const F4 *q = (const F4 *)seeds;
+  const int nblk = (n + 31) >> 5;
+  for (int b = 0; b < nblk; b++) {
+    F4 w[8];
+    float blk[32];
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = q[8 * b + k];
+#pragma unroll
+    for (int k = 0; k < 8; k++) blk[4 * k] = w[k].x, blk[4 * k + 1] = w[k].y, blk[4 * k + 2] = w[k].z, blk[4 * k + 3] = w[k].w;
+#pragma unroll
+    for (int j = 0; j < 32; j++) {
+      const int i = (b << 5) + j;
+      if (i < n) {
+        const float s = blk[j];
+        // two entries within reach, the line not below the top, the top not above the one under it (lib/psy.c:470-474)
+        while ((m & (m - 1)) != 0 && !(s < st[0]) && st[0] <= st[1]) {
+          m &= m - 1;
+#pragma unroll
+          for (int k = 0; k + 1 < WN; k++) st[k] = st[k + 1];
+        }
+        if (m >> (WN - 1)) emit(i - WN);  // leaves the window still stacked: final
+        m = ((m << 1) | 1u) & WMASK;
+#pragma unroll
+        for (int k = WN - 1; k > 0; k--) st[k] = st[k - 1];
+        st[0] = s;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = WN - 1; k >= 0; k--)
+    if ((m >> k) & 1u) emit(n - 1 - k);
+  for (int k = nw & ~7; k < nw; k++) {  // the last one to seven
+    const int sh = 16 * (8 - (nw & 7) + (k & 7));
+    surv[k] = (unsigned short)(sh < 64 ? wlo >> sh : whi >> (sh - 64));
+  }
+  return nw;
+}
+// does the lane-per-block kernel take it, for a size class whose two block types have these parameters?  (host)
+inline bool chase_walk_regs(const PsyP &P0, const PsyP &P1) {
+  return VAMD_CHASE_REGS && P0.eighth_octave_lines == 8 && P1.eighth_octave_lines == 8;
 }
 
 #define VAMD_CHASE_CHUNKS 64  // chunks per block = lanes of the wave

@@ -444,6 +444,14 @@ static long noise_teams_per_cu(const vamd_ctx *c, int n2, size_t lds, bool overl
     // 8 fit.  Noise mask + visible tone tail per 131 072 stereo blocks: the parent, five teams, 2.78 + 0.01 ms; the new
     // walk with five 2.79 + 0.01, with six 2.51 + 0.19, with seven 2.37 + 0.54.  What is left of the tail is k_tone_seed,
     // 8 of whose waves fit beside six teams for 12 beside five.  C5: 10.12 ms against 10.17, 10.51 with 28 waves.)
+    // (round 24, profiles/r24_chase_regs.txt: six stays.  The walk now keeps its window in registers (k_tone.h:
+    // tone_chase_regs) and takes no LDS at all, so what a CU holds of it beside the teams is decided by wave slots and
+    // registers alone: 62 VGPRs, two waves a SIMD in the 128 that six teams leave, 8 a CU as before -- but each is done in
+    // 123 k wave cycles where the ring walk took 213 k, and beside six teams the chain now ends before the noise mask
+    // does.  Noise mask + visible tone tail per 131 072 stereo blocks: the parent, six teams, 2.53 + 0.19 ms; the new
+    // walk with five 2.80 + 0.01, with six 2.52 + 0.01, with seven 2.36 + 0.41.  The LDS the walk gave back does not buy
+    // the seventh team: beside seven, 4 wave slots a CU are left and k_tone_seed alone takes 2.9 ms in them, longer
+    // than the noise mask itself.  C5: 24 waves against 28 in the record.)
     // (a run of smaller blocks alone was not measured again: as before)
     const int beside = c->K.noise_waves > 0 ? c->K.noise_waves : (alone && n2 < 1024 ? 20 : 24);
     const long cap = (fold_later ? beside : 16) / nw;
@@ -527,7 +535,10 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
     hipLaunchKernelGGL(k_tone_chase<RING>, dim3((gcb + VAMD_CHASE_LANES - 1) / VAMD_CHASE_LANES), dim3(VAMD_CHASE_LANES),      \
                        (size_t)RING * VAMD_CHASE_LANES * 8 + chase_pad, s, P0.eighth_octave_lines, nl, nlp, (long)gcb, d, p.seed, \
                        p.surv, p.nsurv)
-      if (ring_slots == VAMD_RING) {
+      if (!by_wave && chase_walk_regs(P0, P1)) {  // the window in registers, no ring (k_tone.h: tone_chase_regs)
+        hipLaunchKernelGGL(k_tone_chase_regs<8>, dim3((gcb + VAMD_CHASE_LANES - 1) / VAMD_CHASE_LANES), dim3(VAMD_CHASE_LANES), chase_pad, s,
+                           nl, nlp, (long)gcb, d, p.seed, p.surv, p.nsurv);
+      } else if (ring_slots == VAMD_RING) {
         VAMD_GO(VAMD_RING);
       } else {
         VAMD_GO(VAMD_CHASE_RING);

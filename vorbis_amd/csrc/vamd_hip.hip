@@ -126,6 +126,11 @@ int vamd_create_abi(vamd_ctx **out, const void *setup_blob, size_t blob_bytes, i
   }
   c->image_bytes = image.size();
   bind_params(image, doff, derived, c->d_image, &c->B);
+  {  // ... and which stack walk a large batch of either size class takes (not a knob: the build and the setup decide)
+    const size_t n = strlen(c->config);
+    snprintf(c->config + n, sizeof(c->config) - n, " chase_walk=%s,%s", chase_walk_regs(c->B.psy[0], c->B.psy[1]) ? "regs" : "ring",
+             chase_walk_regs(c->B.psy[2], c->B.psy[3]) ? "regs" : "ring");
+  }
   const size_t bound_bytes = (sizeof(Bound) + 15) & ~(size_t)15;
   if (hipMalloc((void **)&c->d_bound, bound_bytes + 16) != hipSuccess ||
       hipMemset(c->d_bound, 0, bound_bytes + 16) != hipSuccess ||

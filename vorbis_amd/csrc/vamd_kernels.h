@@ -596,14 +596,14 @@ __global__ __launch_bounds__(64 * NoiseGeom<LOGN2>::NW) void k_noise_tone(PsyP P
 // round 2: half-filled waves -- twice as many waves for the SIMDs to interleave -- are slower, 1.01 against 0.82 ms per
 // 131 072 stereo blocks; a walk whose stack is a register bit mask fed through coalesced LDS tiles executes three
 // times the instructions once 64 divergent walks share them, 2.96 ms.  docs/history/DESIGN_r01-r05.md has the round's account.)
+// (That form staged the lines through LDS tiles.  k_tone_chase_regs below keeps the mask and reads its row as the ring walk
+// does: the ring walk's vector instructions per wave, no LDS, 0.58 of its wave cycles -- round 24, profiles/r24_chase_regs.txt.)
 // RING: the slots of a lane's ring, chase_ring_slots(linesper) (chosen by the launch)
 #define VAMD_CHASE_LANES 64
-template <int RING>
-__global__ __launch_bounds__(64) void k_tone_chase(int linesper, int nl, int nlp, long ncb, DescP d,
-                                                   const float *__restrict__ seed_g,
-                                                   unsigned short *__restrict__ surv, int *__restrict__ nsurv) {
-  float *ring_amp = (float *)vamd_smem;
-  int *ring_pos = (int *)(ring_amp + RING * VAMD_CHASE_LANES);
+// the shell both forms of the kernel share: the lane's walk between the clock probe's two readings
+//   walk(cb) -> the block's survivor count
+template <class Walk>
+__device__ __forceinline__ void tone_chase_lanes(const DescP &d, long ncb, int *__restrict__ nsurv, Walk walk) {
   const long cb = (long)blockIdx.x * VAMD_CHASE_LANES + threadIdx.x;
   PhaseClock pc;
   pc.start(d.dbg ? d.dbg + 32 : nullptr);
@@ -616,8 +616,7 @@ __global__ __launch_bounds__(64) void k_tone_chase(int linesper, int nl, int nlp
   unsigned long long w0 = 0;
   long long t0 = 0;
   if (probe) w0 = wall_clock64(), t0 = clock64();
-  if (cb < ncb)
-    nsurv[cb] = tone_chase_ring<RING>(seed_g + cb * nlp, linesper, nl, ring_amp, ring_pos, VAMD_CHASE_LANES, threadIdx.x, surv + cb * nlp);
+  if (cb < ncb) nsurv[cb] = walk(cb);
   if (probe) {
     atomicAdd(d.clk, (unsigned long long)(clock64() - t0));
     atomicAdd(d.clk + 1, wall_clock64() - w0);
@@ -625,6 +624,23 @@ __global__ __launch_bounds__(64) void k_tone_chase(int linesper, int nl, int nlp
   }
   pc.mark(2);
   pc.flush();
+}
+template <int RING>
+__global__ __launch_bounds__(64) void k_tone_chase(int linesper, int nl, int nlp, long ncb, DescP d,
+                                                   const float *__restrict__ seed_g,
+                                                   unsigned short *__restrict__ surv, int *__restrict__ nsurv) {
+  float *ring_amp = (float *)vamd_smem;
+  int *ring_pos = (int *)(ring_amp + RING * VAMD_CHASE_LANES);
+  tone_chase_lanes(d, ncb, nsurv, [&](long cb) {
+    return tone_chase_ring<RING>(seed_g + cb * nlp, linesper, nl, ring_amp, ring_pos, VAMD_CHASE_LANES, threadIdx.x, surv + cb * nlp);
+  });
+}
+// ... with the walk's window in registers (tone_chase_regs, k_tone.h): no LDS.  (What the launch still passes as dynamic
+// LDS is the occupancy experiment's padding, VAMD_CHASE_LDS_PAD; the kernel never looks at it.)
+template <int LP>
+__global__ __launch_bounds__(64) void k_tone_chase_regs(int nl, int nlp, long ncb, DescP d, const float *__restrict__ seed_g,
+                                                        unsigned short *__restrict__ surv, int *__restrict__ nsurv) {
+  tone_chase_lanes(d, ncb, nsurv, [&](long cb) { return tone_chase_regs<LP>(seed_g + cb * nlp, nl, surv + cb * nlp); });
 }
 
 // the same for a small batch: one WAVE per channel-block, the walk cut into one chunk per lane (chase_chunk, k_tone.h)
