@@ -108,6 +108,16 @@ int vamd_debug_cycles(vamd_ctx *ctx, int enable, unsigned long long *out80);
 int vamd_debug_survivors(vamd_ctx *ctx, int W, long channel_blocks, float *seed, uint16_t *surv, int32_t *nsurv,
                          int32_t *row_lines, int32_t *lines);
 
+/* Test aid (no libvorbis counterpart): which kernels the context's last batch call (vamd_analyze_batch and its stream,
+ * mixed-stream, synthesis and bitrate-managed forms) launched for size class W, as words in launch order, one per launch
+ * of the stages behind the transform: the kernel's name, and "/threads" where the launch code chooses the workgroup's size
+ * ("k_noise k_tone_seed k_tone_chase_regs k_floor k_couple/64 k_residue_chunks k_pack_waves"; "k_residue:team/N" is
+ * k_residue searching runs of eight values a thread, "k_tone_chase/N" the walk on a ring of N slots).  The launch code
+ * picks kernels by batch size, so a test of a batch kernel asks here whether its batch took it.  The string belongs to
+ * the context and is rewritten by its next batch call; "" before the first, and for a size class the call had no blocks
+ * of. */
+const char *vamd_launch_record(const vamd_ctx *ctx, int W);
+
 /* Measurement aid (no libvorbis counterpart): the shader clock while the chip is busy.  While `acc3` (device memory,
  * three 64-bit words zeroed by the caller) is set, every batch of more than a few thousand blocks at the masking level
  * or above has the first wave of its tone stack walk -- which runs beside the noise mask, the path's longest stage --

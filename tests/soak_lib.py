@@ -83,6 +83,21 @@ def signals(rng, nb, ch, n):
 NKINDS = 14
 
 
+def draw_flags(rng, nb, W, managed=False):
+    """What run() draws for `nb` blocks of size class W behind their signals: (lW, nW, blocktype, ampmax_in) per block; for
+    bitrate-managed blocks, whose block type follows the size class and whose chain starts fresh, (lW, nW) only."""
+    lW = rng.integers(0, 2, nb).astype(np.int32) * W
+    nW = rng.integers(0, 2, nb).astype(np.int32) * W
+    if managed:
+        return lW, nW
+    bt = (rng.integers(0, 2, nb)).astype(np.int32)
+    amp_in = np.where(rng.random(nb) < 0.5, -9999.0, rng.uniform(-60, 0, nb)).astype(np.float32)
+    return lW, nW, bt, amp_in
+
+
+MANAGED = ((2, (-1, 128000, -1)), (2, (-1, 64000, -1)), (6, (-1, 256000, -1)), (1, (64000, 48000, 32000)))
+HOSTILE_CONFIGS = ((2, 44100, 0.4), (2, 44100, 0.1), (6, 44100, 0.3), (1, 22050, 0.5))
+
 
 def run(NB=300, managed=True, log=print):
     """Returns (blocks compared, mismatching blocks)."""
@@ -97,10 +112,7 @@ def run(NB=300, managed=True, log=print):
             n = e.blocksize(W)
             nb = NB if W else NB // 3
             x = signals(rng, nb, ch, n)
-            lW = rng.integers(0, 2, nb).astype(np.int32) * W
-            nW = rng.integers(0, 2, nb).astype(np.int32) * W
-            bt = (rng.integers(0, 2, nb)).astype(np.int32)
-            amp_in = np.where(rng.random(nb) < 0.5, -9999.0, rng.uniform(-60, 0, nb)).astype(np.float32)
+            lW, nW, bt, amp_in = draw_flags(rng, nb, W)
             o = an.analyze(torch.from_numpy(x).cuda(), W=W, lW=lW, nW=nW, blocktype=bt, ampmax_in=amp_in,
                            want=("ampmax_out", "packets", "packet_bits", "status"))
             torch.cuda.synchronize()
@@ -139,7 +151,7 @@ def run(NB=300, managed=True, log=print):
     if not managed:
         return total, bad
     # bitrate-managed: all fifteen candidate packets of every block
-    for ch, rates in ((2, (-1, 128000, -1)), (2, (-1, 64000, -1)), (6, (-1, 256000, -1)), (1, (64000, 48000, 32000))):
+    for ch, rates in MANAGED:
         e = ref.RefEncoder(ch, 44100, managed=rates)
         an = vorbis_amd.Analyzer(e.pack_setup(), 0)
         rng = np.random.default_rng(ch * 7 + rates[1] // 1000)
@@ -147,8 +159,7 @@ def run(NB=300, managed=True, log=print):
             n = e.blocksize(W)
             nb = max(8, NB // 10) if W else max(8, NB // 30)
             x = signals(rng, nb, ch, n)
-            lW = rng.integers(0, 2, nb).astype(np.int32) * W
-            nW = rng.integers(0, 2, nb).astype(np.int32) * W
+            lW, nW = draw_flags(rng, nb, W, managed=True)
             o = an.analyze_managed(torch.from_numpy(x).cuda(), W=W, lW=lW, nW=nW, blocktype=1 if W else 0, packets=True,
                                    want=("status",))
             torch.cuda.synchronize()
@@ -228,7 +239,7 @@ def run_hostile(nb=48, log=print):
     every other block of their batch bit-exact.  Returns (checks made, failures)."""
     from vorbis_amd import VamdError
     checks = bad = 0
-    for ch, rate, q in ((2, 44100, 0.4), (2, 44100, 0.1), (6, 44100, 0.3), (1, 22050, 0.5)):
+    for ch, rate, q in HOSTILE_CONFIGS:
         e = ref.RefEncoder(ch, rate, q)
         an = vorbis_amd.Analyzer(e.pack_setup(), 0)
         rng = np.random.default_rng(ch * 1000 + int(q * 10))

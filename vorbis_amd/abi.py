@@ -116,6 +116,7 @@ PROTOTYPES = {
     "vamd_analyze_block": (_int, _block + [_vp, _vp, _vp, _vp, _vp, _vp, _pfloat]),
     "vamd_debug_cycles": (_int, [_vp, _int, _vp]),
     "vamd_debug_survivors": (_int, [_vp, _int, _long, _vp, _vp, _vp, _pi32, _pi32]),
+    "vamd_launch_record": (C.c_char_p, [_vp, _int]),
     "vamd_calib_copy": (_int, [_vp, _vp, _vp, _size]),
     "vamd_analyze_stream_mixed": (_int, [_vp, _pDesc, _pIO, _pDesc, _pIO, _vp, _long, _pfloat]),
     "vamd_analyze_streams_mixed": (_int, [_vp, _pDesc, _pIO, _pDesc, _pIO, _vp, _vp, _long, _long, _vp]),

@@ -172,6 +172,11 @@ class Analyzer:
                                                 _vp(nsurv.ctypes.data), None, None))
         return seed, surv, nsurv, nl.value
 
+    def launch_record(self, W):
+        """vamd_launch_record(): the kernels the last batch call launched for size class W, a list of words in launch order
+        ("k_couple/64": the kernel, and the workgroup's threads where the launch code chooses them)."""
+        return self.L.vamd_launch_record(self.h, W).decode().split()
+
     def calib_copy(self, dst, src):
         """vamd_calib_copy(): src -> dst (device tensors of equal byte size) with the library's named copy kernel."""
         nbytes = src.numel() * src.element_size()

@@ -91,6 +91,9 @@ int vamd_debug_survivors(vamd_ctx *c, int W, long ncb, float *seed, uint16_t *su
   return VAMD_OK;
 }
 
+// (test aid) the kernels the last batch call launched for size class W, as words in launch order
+const char *vamd_launch_record(const vamd_ctx *c, int W) { return c && (W == 0 || W == 1) ? c->roads[W] : ""; }
+
 // from a run-time size to a template argument: the call site defines VAMD_GO(arg) as its launch
 #define VAMD_SWITCH_LOGN(logn)   \
   switch (logn) {                \
@@ -320,6 +323,7 @@ static void launch_residue_pack(vamd_ctx *c, BatchRun *R, hipStream_t s, int nbl
                            ? Rs.partvals * (Rs.tab_grouping >> 3) : 0;
     if (chunks > 0 && units <= res_team_max && chunks <= 64 * VAMD_RES_WAVES) {
       // a handful of units: a workgroup a unit, a thread a run (residue_team_chunks) -- a lone block's search in half the time
+      road(c, W, "k_residue:team", (chunks + 63) & ~63);
       hipLaunchKernelGGL(k_residue, dim3((unsigned)units), dim3((chunks + 63) & ~63),
                          (size_t)(Rs.lds_ints - Rs.bundle * n2 + Rs.fast_ints) * 4, s, Rs, cm, sm,
                          c->B.res_cap[W], nblobs, R->d, ch, n2, iwork, nonzero, rb.cls, rb.entries, rb.count, packets ? rb.books : nullptr, 1);
@@ -329,13 +333,16 @@ static void launch_residue_pack(vamd_ctx *c, BatchRun *R, hipStream_t s, int nbl
       const size_t per_wave = (size_t)((Rs.partvals + Rs.nstages * Rs.partvals + 1 + 3) & ~3);
       const size_t lds = ((size_t)Rs.fast_ints + VAMD_RESC_WAVES * per_wave) * 4;
       const unsigned grid = persistent_grid(c, (const void *)k_residue_chunks, 64 * VAMD_RESC_WAVES, lds, (units + VAMD_RESC_WAVES - 1) / VAMD_RESC_WAVES);
+      road(c, W, "k_residue_chunks");
       hipLaunchKernelGGL(k_residue_chunks, dim3(grid), dim3(64 * VAMD_RESC_WAVES), lds, s, Rs, cm, sm, c->B.res_cap[W], nblobs, R->d, ch,
                          n2, units, iwork, nonzero, rb.cls, rb.entries, rb.count, packets ? rb.books : nullptr);
       continue;
     }
     // a stereo bundle's search keeps two waves busy, the five-channel bundle of the 5.1 layout four; a handful of units
     // takes four either way (nothing else wants the CU, and a lone unit's latency is the caller's)
-    hipLaunchKernelGGL(k_residue, dim3((unsigned)units), dim3(64 * (c->B.res[W][sm].bundle * n2 > 4096 || units <= res_team_max ? VAMD_RES_WAVES : 2)),
+    const int res_threads = 64 * (c->B.res[W][sm].bundle * n2 > 4096 || units <= res_team_max ? VAMD_RES_WAVES : 2);
+    road(c, W, "k_residue", res_threads);
+    hipLaunchKernelGGL(k_residue, dim3((unsigned)units), dim3(res_threads),
                        (size_t)c->B.res[W][sm].lds_ints * 4, s, c->B.res[W][sm], cm, sm,
                        c->B.res_cap[W], nblobs, R->d, ch, n2, iwork, nonzero, rb.cls, rb.entries, rb.count, packets ? rb.books : nullptr, 0);
   }
@@ -346,12 +353,13 @@ static void launch_residue_pack(vamd_ctx *c, BatchRun *R, hipStream_t s, int nbl
     const long pair_max = c->K.pack_pair_max;
     // a handful of packets: two waves each -- where the rows hold any packet (the residue part is assembled past the
     // longest possible head and then moved down: in a shorter row the end of a cut-off packet would be lost on the way)
-    if (units <= pair_max && packet_stride >= c->B.pack[W].capacity)
+    if (units <= pair_max && packet_stride >= c->B.pack[W].capacity) {
+      road(c, W, "k_pack_pair");
       hipLaunchKernelGGL(k_pack_pair, dim3((unsigned)units), dim3(128), lds + ((size_t)VAMD_PK_RING + 4 + c->B.res[W][0].fast_ints) * 4, s, c->B.pack[W],
                          c->B.floor[W][0], c->B.floor[W][1], c->B.res[W][0], c->B.res[W][1], cm, c->B.res_cap[W], c->B.res_off_ints[W],
                          R->d, ch, W, nblobs, posts, wrapped, post_valid, rb.cls, rb.entries, rb.books, rb.count, (unsigned *)packets,
                          (int)(packet_stride / 4), packet_bits);
-    else if (cm.submaps == 1 && units >= 4 * (long)c->num_cus && !c->K.pack_per_packet) {
+    } else if (cm.submaps == 1 && units >= 4 * (long)c->num_cus && !c->K.pack_per_packet) {
       // a batch of a one-submap mode: persistent waves over the packets, the tables staged once per workgroup (k_pack_waves)
       const ResP &R0 = c->B.res[W][0];
       const int per_wave_ints = (R0.slots + 2 * R0.nstages * R0.slots + 1 + 3) & ~3;
@@ -359,13 +367,16 @@ static void launch_residue_pack(vamd_ctx *c, BatchRun *R, hipStream_t s, int nbl
                            (size_t)VAMD_PKW_WAVES * ((size_t)VAMD_PK_RING + VAMD_POSTS_STRIDE + per_wave_ints)) * 4;
       // (persistent -- registers, not LDS, set how many workgroups are resident here)
       const unsigned grid = persistent_grid(c, (const void *)k_pack_waves, 64 * VAMD_PKW_WAVES, ldsw, (units + VAMD_PKW_WAVES - 1) / VAMD_PKW_WAVES);
+      road(c, W, "k_pack_waves");
       hipLaunchKernelGGL(k_pack_waves, dim3(grid), dim3(64 * VAMD_PKW_WAVES), ldsw, s, c->B.pack[W],
                          c->B.floor[W][0], R0, cm, c->B.res_cap[W], per_wave_ints, R->d, ch, W, nblobs, units, posts, wrapped, post_valid,
                          rb.cls, rb.entries, rb.books, rb.count, (unsigned *)packets, (int)(packet_stride / 4), packet_bits);
-    } else
-    hipLaunchKernelGGL(k_pack, dim3((unsigned)units), dim3(64), lds, s, c->B.pack[W], c->B.floor[W][0], c->B.floor[W][1],
-                       c->B.res[W][0], c->B.res[W][1], cm, c->B.res_cap[W], c->B.res_off_ints[W], R->d, ch, W, nblobs, posts,
-                       wrapped, post_valid, rb.cls, rb.entries, rb.books, rb.count, (unsigned *)packets, (int)(packet_stride / 4), packet_bits);
+    } else {
+      road(c, W, "k_pack");
+      hipLaunchKernelGGL(k_pack, dim3((unsigned)units), dim3(64), lds, s, c->B.pack[W], c->B.floor[W][0], c->B.floor[W][1],
+                         c->B.res[W][0], c->B.res[W][1], cm, c->B.res_cap[W], c->B.res_off_ints[W], R->d, ch, W, nblobs, posts,
+                         wrapped, post_valid, rb.cls, rb.entries, rb.books, rb.count, (unsigned *)packets, (int)(packet_stride / 4), packet_bits);
+    }
     prof_mark(c, VAMD_ST_PACK);
   }
 }
@@ -378,6 +389,7 @@ static void launch_couple(vamd_ctx *c, BatchRun *R, hipStream_t s, int blob_base
   const int n2 = c->B.xf[W].n / 2;
   const long units = R->units;
   if (needs_general_couple(c, W)) {
+    road(c, W, "k_couple_general");
     hipLaunchKernelGGL(k_couple_general, dim3((unsigned)units), dim3(64), (size_t)n2 * 12 + 1024, s, P0, P1, c->B.couple_all[W],
                        blob_base, nblobs, R->d, mdct, ilogmask, iwork, nonzero, R->couple_state);
     return;
@@ -385,12 +397,16 @@ static void launch_couple(vamd_ctx *c, BatchRun *R, hipStream_t s, int blob_base
   // the LDS arrays serve noise normalisation's sort only (lib/psy.c:941-1010); without it the
   // stage is register-only and the CU holds twice as many of its waves
   const bool norm0 = P0.normal_p && P0.normal_start < n2, norm1 = P1.normal_p && P1.normal_start < n2;
-  if (norm0 || norm1)
+  if (norm0 || norm1) {
+    road(c, W, "k_couple_norm");
     hipLaunchKernelGGL(k_couple_norm, dim3((unsigned)units), dim3(64), (size_t)n2 * 12 + 1024, s, P0, P1, c->B.couple_all[W], blob_base,
                        nblobs, R->d, mdct, ilogmask, iwork, nonzero, c->couple_band);
-  else  // (a handful of blocks: four waves each)
-    hipLaunchKernelGGL(k_couple, dim3((unsigned)units), dim3(units <= 2048 && n2 >= 512 ? 256 : 64), 0, s, P0, P1, c->B.couple_all[W],
+  } else {  // (a handful of blocks: four waves each)
+    const int couple_threads = units <= 2048 && n2 >= 512 ? 256 : 64;
+    road(c, W, "k_couple", couple_threads);
+    hipLaunchKernelGGL(k_couple, dim3((unsigned)units), dim3(couple_threads), 0, s, P0, P1, c->B.couple_all[W],
                        blob_base, nblobs, R->d, mdct, ilogmask, iwork, nonzero, c->couple_band);
+  }
 }
 
 // ---- stages 2..5 (masking, floor, couple) and what follows them, in two steps; R->d.ampmax_in / p.ampglob must be final.
@@ -493,6 +509,7 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
   const bool merged = merge_env && !overlap && by_wave && lp8;
   if (merged) {
     const size_t nlds = (size_t)5 * VAMD_NZ_STRIDE(n2) * 4, tlds = seed_lds + (size_t)chase_ring_slots(8) * 8;
+    road(c, W, "k_noise_tone");
 #define VAMD_GO(L)                                                                                                          \
   hipLaunchKernelGGL((k_noise_tone<L, 8>), dim3(2 * gcb), dim3(64 * NoiseGeom<L>::NW), nlds > tlds ? nlds : tlds, s, P0, P1, d, ch, \
                      (long)gcb, p.mdct_raw, p.noise, nlp, run_peaks_stride(P0), p.peaks, p.local, p.ampglob,                  \
@@ -504,6 +521,7 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
     const size_t lds = (size_t)5 * VAMD_NZ_STRIDE(n2) * 4;
     const long per_cu = noise_teams_per_cu(c, n2, lds, overlap, alone, fold_later);
     const unsigned grid = (unsigned)((long)gcb < per_cu * c->num_cus ? (long)gcb : per_cu * c->num_cus);
+    road(c, W, "k_noise");
 #define VAMD_GO(L)                                                                                                    \
   hipLaunchKernelGGL(k_noise<L>, dim3(grid), dim3(64 * NoiseGeom<L>::NW), lds, s, P0, P1, d, ch, (long)gcb, p.mdct_raw, \
                      p.noise)
@@ -516,10 +534,12 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
     if (merged) {
       // (launched with the noise stage)
     } else if (by_wave && lp8) {  // ... and seed + chase in one launch (k_tone_seed_chase)
+      road(c, W, "k_tone_seed_chase");
       hipLaunchKernelGGL(k_tone_seed_chase<8>, dim3(gcb), dim3(64), seed_lds + (size_t)chase_ring_slots(8) * 8, s, P0, P1, d, ch, nlp,
                          run_peaks_stride(P0), p.peaks, p.local, p.ampglob, R->make_ampmax ? p.ampglob : nullptr, p.seed, p.surv,
                          p.nsurv);
     } else {
+      road(c, W, lp8 ? "k_tone_seed" : "k_tone_seed<0>");
       if (lp8)
         hipLaunchKernelGGL(k_tone_seed<8>, dim3(gcb), dim3(64), seed_lds, s, P0, P1, d, ch, nlp, run_peaks_stride(P0), p.peaks, p.local,
                            p.ampglob, R->make_ampmax ? p.ampglob : nullptr, p.seed);
@@ -536,18 +556,23 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
                        (size_t)RING * VAMD_CHASE_LANES * 8 + chase_pad, s, P0.eighth_octave_lines, nl, nlp, (long)gcb, d, p.seed, \
                        p.surv, p.nsurv)
       if (!by_wave && chase_walk_regs(P0, P1)) {  // the window in registers, no ring (k_tone.h: tone_chase_regs)
+        road(c, W, "k_tone_chase_regs");
         hipLaunchKernelGGL(k_tone_chase_regs<8>, dim3((gcb + VAMD_CHASE_LANES - 1) / VAMD_CHASE_LANES), dim3(VAMD_CHASE_LANES), chase_pad, s,
                            nl, nlp, (long)gcb, d, p.seed, p.surv, p.nsurv);
       } else if (ring_slots == VAMD_RING) {
+        road(c, W, by_wave ? "k_tone_chase_wave" : "k_tone_chase", (int)VAMD_RING);  // (the number: the ring's slots)
         VAMD_GO(VAMD_RING);
       } else {
+        road(c, W, by_wave ? "k_tone_chase_wave" : "k_tone_chase", (int)VAMD_CHASE_RING);
         VAMD_GO(VAMD_CHASE_RING);
       }
 #undef VAMD_GO
     }
-    if (!fold_later)
+    if (!fold_later) {
+      road(c, W, "k_tone_fold");
       hipLaunchKernelGGL(k_tone_fold, dim3(gcb), dim3(64), fold_lds_bytes(nlp, P0, P1), s, P0, P1, d, ch, nlp, p.seed, p.surv,
                          p.nsurv, p.local, p.tone);
+    }
   }
   if (overlap) (void)hipEventRecord(join_event(c, R), c->side);
 }
@@ -573,6 +598,7 @@ static void launch_floor_on(vamd_ctx *c, BatchRun *R, int level) {
   if (level >= VAMD_LEVEL_FULL && M) {
     // bitrate-managed: fifteen candidate packets per block
     const size_t flds = (size_t)((n2 + 15) & ~15) * 2 + sizeof(FloorScratch);
+    road(c, W, "k_floor_managed");
     hipLaunchKernelGGL(k_floor_managed, dim3(gcb), dim3(64), flds, s, P0, P1, c->B.floor[W][0], c->B.floor[W][1], c->B.chmap[W], d, ch, p.noise, p.tone,
                        p.mdct_raw, p.mdct, R->io->logmask, M->posts, M->post_valid, R->m_ilogmask, M->nonzero);
     prof_mark(c, VAMD_ST_FLOOR);
@@ -592,6 +618,7 @@ static void launch_floor_on(vamd_ctx *c, BatchRun *R, int level) {
     const bool paired = ch == 2 && c->B.chmap[W].sub[0] == c->B.chmap[W].sub[1] && F0.posts <= 32 && (long)gcb >= pair_min && pair_min >= 0 &&
                         ((c->K.floor_pair_w >> W) & 1) &&
                         n2 <= 32 * 4 * 8 && 2 * floor_lds <= c->lds_per_block;
+    road(c, W, paired ? "k_floor_pair" : "k_floor");
     if (paired)
       hipLaunchKernelGGL(k_floor_pair, dim3(gb), dim3(64), 2 * floor_lds, s,
                          (const Bound *)c->d_bound, W, d, (int)floor_lds, p.noise, fold_here ? R->io->tone : p.tone, fold_here ? p.seed : nullptr, p.surv, p.nsurv, p.local,
@@ -602,8 +629,10 @@ static void launch_floor_on(vamd_ctx *c, BatchRun *R, int level) {
                        (const Bound *)c->d_bound, W, d, ch, p.noise, fold_here ? R->io->tone : p.tone, fold_here ? p.seed : nullptr, p.surv, p.nsurv, p.local,
                        nlp_all, p.mdct_raw, p.mdct,
                        R->io->logmask, p.posts, p.post_valid, p.ilogmask, p.nonzero, p.wrapped);
-    if (R->io->ilogmask)  // (a tap: tests and callers with their own quantiser)
+    if (R->io->ilogmask) {  // (a tap: tests and callers with their own quantiser)
+      road(c, W, "k_widen_ilog");
       hipLaunchKernelGGL(k_widen_ilog, dim3(1024), dim3(256), 0, s, (long)gcb * n2, (const ilog_t *)p.ilogmask, R->io->ilogmask);
+    }
     prof_mark(c, VAMD_ST_FLOOR);
     launch_couple(c, R, s, VAMD_PACKETBLOBS / 2, 1, p.mdct, p.ilogmask, p.iwork, p.nonzero);
     prof_mark(c, VAMD_ST_COUPLE);
@@ -622,6 +651,7 @@ static int launch_synth(vamd_ctx *c, int W, const vamd_ctx::SynthSrc &y, float *
 static int run_batch(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io, int level, bool stream_mode,
                      float *ampmax_state, const vamd_managed_io *M = nullptr, float *synth = nullptr) {
   BatchRun R;
+  c->roads[0][0] = c->roads[1][0] = 0;  // (the record of what this call launches: vamd_launch_record)
   int r = prepare_run(c, desc, io, level, &R, M, synth != nullptr);
   if (r) return r;
   if (R.nb == 0) return VAMD_OK;
@@ -794,6 +824,7 @@ static int run_streams_mixed(vamd_ctx *c, const vamd_batch_desc *desc_short, con
   if (desc_short->nblocks && (r = check_desc(c, desc_short, io_short))) return r;
   if (desc_long->nblocks && (r = check_desc(c, desc_long, io_long))) return r;
   if (nblocks_total == 0) return VAMD_OK;
+  c->roads[0][0] = c->roads[1][0] = 0;  // (the record of what this call launches: vamd_launch_record)
   BatchRun R[2];
   if ((r = prepare_run(c, desc_short, io_short, VAMD_LEVEL_FULL, &R[0], M0))) return r;
   if ((r = prepare_run(c, desc_long, io_long, VAMD_LEVEL_FULL, &R[1], M1))) return r;

@@ -33,6 +33,9 @@ struct vamd_ctx {
   std::string err;
   Knobs K;           // the environment knobs, read once at vamd_create (vamd_knobs.h)
   char config[1024]; // ... and as text (vamd_config_string)
+  // (test aid) the kernels the last batch call launched for each size class, as words in launch order: the name, and the
+  // workgroup's threads where the launch code chooses them ("k_couple/64"); vamd_launch_record
+  char roads[2][320] = {{0}, {0}};
   // workspace, grown on demand (vamd_reserve to pre-size)
   enum { WS_MDCT_RAW, WS_LOGMDCT, WS_LOGFFT, WS_NOISE, WS_TONE, WS_MDCT, WS_ILOGMASK, WS_IWORK, WS_POSTS, WS_POSTVALID,
          WS_NONZERO, WS_LOCAL, WS_AMPIN, WS_AMPGLOB, WS_PCM, WS_SEED, WS_SURV, WS_NSURV, WS_MISC,
@@ -87,6 +90,18 @@ static void prof_mark(vamd_ctx *c, int stage) {
   (void)hipEventRecord(c->ev_pool[c->ev_used], c->stream);
   if (c->ev_stage.size() <= c->ev_used) c->ev_stage.resize(c->ev_used + 1);
   c->ev_stage[c->ev_used++] = stage;
+}
+
+// a launch of the batch sequence joins its size class's record (vamd_ctx::roads); a word that does not fit whole is
+// left out: the record never ends inside a kernel's name
+static void road(vamd_ctx *c, int W, const char *kernel, int threads = 0) {
+  char word[64];
+  const int len = threads ? snprintf(word, sizeof(word), " %s/%d", kernel, threads) : snprintf(word, sizeof(word), " %s", kernel);
+  if (len < 0 || len >= (int)sizeof(word)) return;
+  char *t = c->roads[W];
+  const size_t at = strlen(t);
+  const char *w = at ? word : word + 1;  // (no blank in front of the first word)
+  if (at + strlen(w) < sizeof(c->roads[W])) memcpy(t + at, w, strlen(w) + 1);
 }
 
 // waves per persistent transform workgroup: as many as fit beside the staged tables
