@@ -601,8 +601,8 @@ int vamd_synth_streams(vamd_ctx *ctx, const vamd_stream_plan *plan, long nstream
  * vamd_residue_capacity + 8 S bytes of rows, 4 ch n of vb->pcm and 29 of plan (ch channels, n the block's size, S its
  * submaps), and the packets themselves.
  *
- * Out of scope: header packets and setups other than the context's; Ogg demultiplexing; packets in device memory; streams
- * that begin at a nonzero granule (the first page's trim); eopbreak semantics (above). */
+ * Out of scope: header packets and setups other than the context's; packets in device memory; streams that begin at a
+ * nonzero granule (the first page's trim); eopbreak semantics (above).  Ogg files: vamd_decode_ogg, below. */
 #define VAMD_STATUS_NOTAUDIO  4
 #define VAMD_STATUS_BADCODE   8
 #define VAMD_STATUS_TRUNCATED 16
@@ -616,6 +616,53 @@ typedef struct vamd_decode_desc {
 int vamd_decode_plan(vamd_ctx *ctx, const vamd_decode_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
 int vamd_decode_streams(vamd_ctx *ctx, const vamd_decode_desc *desc, const int64_t *offset_out /* host [nstreams] */,
                         float *pcm /* device */, uint8_t *status /* host [nstreams] */);
+
+/* ---- Ogg Vorbis files in, PCM out (still ABI 9: additions only).  The packet decoder above with a FILE per stream: what
+ * vamd_feed_ogg writes, and libvorbis' files of the same setup, decode without a host loop over their bytes.  The contract
+ * is vamd_decode_plan's / vamd_decode_streams': frames, offset_out, the layout of pcm, "a flagged stream has no frames", one
+ * stream synchronisation per call, VAMD_EINVAL with a reason and nothing launched for a bad descriptor (null pointers; file
+ * offsets that are negative, not monotone or beyond 2^40), VAMD_EIMPL as there, the workspace in the context.
+ *
+ * File s is bytes[file_offset[s] .. file_offset[s+1]) in HOST memory: ONE logical Ogg bitstream (RFC 3533, doc/framing.html)
+ * that holds the three Vorbis header packets and then audio packets of the context's setup.  Its pages may be cut wherever
+ * the container allows -- packets across pages, pages that complete no packet, pages without a segment, the setup header
+ * and audio packets on one page -- not only as "the Ogg feed" below cuts them.  The stream's end granule is the granule
+ * position of the page that completes its last audio packet (it feeds the last block's cut, as end_granule does above); a
+ * missing end-of-stream flag is no error.
+ *
+ * Who does what.  The host walks each file's page headers and lacing tables -- serial in pages, about one byte in a
+ * hundred -- reads the three header packets and each audio packet's first byte (its mode bits: the block plan), and never
+ * reads outside the file's range, whatever the file claims.  The files go up in one copy as they lie.  On the device
+ * k_ogg_depage, a wave per page, recomputes the page's checksum over header + lacing + body and moves the page's audio
+ * bytes into a packed arena; from there on it is k_unpack, k_synth and k_lap as above.
+ *
+ * status[s]: the packet decoder's bits, or-ed with
+ *   VAMD_STATUS_BADPAGE    the container is broken: a capture pattern or version is wrong; the file ends inside a page
+ *                          header, a lacing table, a body or a packet (its last lacing value is 255); the serial number
+ *                          changes; the page sequence numbers are not 0, 1, 2 ...; a continued flag disagrees with "a packet
+ *                          is open"; a begin-of-stream flag anywhere but on page 0; a page's checksum does not match
+ *   VAMD_STATUS_BADHEADER  there are fewer than three packets; packet 0 is not an identification header of version 0 whose
+ *                          channels, rate and two block sizes are the blob's; packet 1 is no well-formed comment header
+ *                          (type 3, "vorbis", the lengths inside the packet, the framing bit); packet 2 is not type 5 +
+ *                          "vorbis", or differs from setup_header where one is given
+ * The header packets are not parsed beyond that: the context's blob stays the setup.  A flagged stream costs only itself.
+ *
+ * DELIBERATE DEVIATIONS: libogg resynchronises behind a damaged page and reports a hole, and libvorbis decodes on out of
+ * lap; here the stream is flagged.  A chained or multiplexed file is flagged BADPAGE at its second serial number, not
+ * decoded.  Out of scope, as above: setups other than the context's (the setup header is compared, not parsed), streams
+ * that begin at a nonzero granule, files that start in device memory, seeking. */
+#define VAMD_STATUS_BADPAGE   32
+#define VAMD_STATUS_BADHEADER 64
+typedef struct vamd_decode_ogg_desc {
+  int64_t nstreams;
+  const uint8_t *bytes;          /* HOST: the files, back to back */
+  const int64_t *file_offset;    /* host [nstreams + 1]: file s = bytes[file_offset[s] .. file_offset[s+1]) */
+  const uint8_t *setup_header;   /* or NULL: the setup header packet every file's third packet must equal */
+  int64_t setup_header_bytes;
+} vamd_decode_ogg_desc;
+int vamd_decode_ogg_plan(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
+int vamd_decode_ogg(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, const int64_t *offset_out /* host [nstreams] */,
+                    float *pcm /* device */, uint8_t *status /* host [nstreams] */);
 
 /* ---- the host shim for encoders that submit ONE block at a time from many threads.
  * libvorbis' unit of work is one block of one stream (mapping0_forward, reference lib/mapping0.c:233-687); a

@@ -13,6 +13,7 @@ ABI_VERSION = 9             # VAMD_ABI_VERSION of the header this mirror was wri
 QUANT_LIMIT_SQUARE, QUANT_LIMIT_INT = 46340, 0x7fffff80
 STATUS_RANGE, STATUS_NONFINITE = 1, 2   # bits of the `status` output (vorbis_amd.h, "Input domain")
 STATUS_NOTAUDIO, STATUS_BADCODE, STATUS_TRUNCATED = 4, 8, 16  # a decoded stream's status (vorbis_amd.h, "the packet decoder")
+STATUS_BADPAGE, STATUS_BADHEADER = 32, 64  # ... of a decoded file on top (vorbis_amd.h, "Ogg Vorbis files in")
 LEVEL_TRANSFORM, LEVEL_PSY, LEVEL_FULL = 1, 2, 3
 POSTS_STRIDE = 32
 BLOCKTYPE_IMPULSE, BLOCKTYPE_PADDING, BLOCKTYPE_TRANSITION, BLOCKTYPE_LONG = 0, 1, 0, 1
@@ -57,6 +58,10 @@ class _DecodeDesc(C.Structure):  # vamd_decode_desc
     _fields_ = [("nstreams", C.c_int64), ("npackets", C.c_int64), ("bytes", _vp), ("offset", _vp), ("stream_start", _vp), ("end_granule", _vp)]
 
 
+class _DecodeOggDesc(C.Structure):  # vamd_decode_ogg_desc
+    _fields_ = [("nstreams", C.c_int64), ("bytes", _vp), ("file_offset", _vp), ("setup_header", _vp), ("setup_header_bytes", C.c_int64)]
+
+
 class _Desc(C.Structure):
     _fields_ = [("W", C.c_int), ("nblocks", C.c_long), ("lW", _vp), ("nW", _vp), ("blocktype", _vp),
                 ("ampmax_in", _vp), ("uniform_lW", C.c_int), ("uniform_nW", C.c_int),
@@ -92,6 +97,7 @@ class VamdError(RuntimeError):
 _int, _long, _size, _float = C.c_int, C.c_long, C.c_size_t, C.c_float
 _pvp, _pint, _plong, _pfloat, _pi32 = C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_float), C.POINTER(C.c_int32)
 _pDesc, _pIO, _pMIO, _pPlan, _pDecode = C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO), C.POINTER(_Plan), C.POINTER(_DecodeDesc)
+_pDecodeOgg = C.POINTER(_DecodeOggDesc)
 _vp2 = _vp * 2
 _block = [_vp, _pvp, _int, _int, _int, _int, _float]   # (ctx, pcm[ch], lW, W, nW, blocktype, ampmax_in): how every per-block call begins
 
@@ -131,6 +137,8 @@ PROTOTYPES = {
     "vamd_synth_streams": (_int, [_vp, _pPlan, _long, _long, _vp, _vp, _vp, _vp, _vp]),
     "vamd_decode_plan": (_int, [_vp, _pDecode, _vp, _vp]),
     "vamd_decode_streams": (_int, [_vp, _pDecode, _vp, _vp, _vp]),
+    "vamd_decode_ogg_plan": (_int, [_vp, _pDecodeOgg, _vp, _vp]),
+    "vamd_decode_ogg": (_int, [_vp, _pDecodeOgg, _vp, _vp, _vp]),
     "vamd_analyze_block_managed": (_int, _block + [_vp] * 9),
     "vamd_plan_streams": (_int, [_vp, _vp, _long, _long, _long, _long, _vp, _pPlan]),
     "vamd_gather_blocks": (_int, [_vp, _pPlan, _int, _vp, _long, _vp]),

@@ -1,12 +1,12 @@
 """vamd_ctx in Python: the Analyzer -- batches, streams, plans, the bitrate manager's candidates, the detector, the packet
-decoder -- and decode() for a caller who holds packets and no context."""
+decoder for packets and for Ogg files -- and decode() / decode_ogg() for a caller who holds packets or files and no context."""
 import ctypes as C
 
 import numpy as np
 
 from .abi import (ABI_VERSION, BLOCKTYPE_LONG, LEVEL_FULL, LEVEL_PSY, LEVEL_TRANSFORM, PACKETBLOBS, POSTS_STRIDE, QUANT_LIMIT_INT,
                   QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_RANGE, VAMD_EDOMAIN, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
-                  _DecodeDesc, _Desc, _IO, _MIO, _Plan, _vp, load_library)
+                  _DecodeDesc, _DecodeOggDesc, _Desc, _IO, _MIO, _Plan, _vp, load_library)
 from .packets import packet_bytes
 
 
@@ -651,10 +651,14 @@ class Analyzer:
         """vamd_decode_plan + vamd_decode_streams over decode_prepare()'s descriptor.  pcm: a float32 tensor on the context's
         device to decode into (at least the planned frames x channels floats), or None: one is made.
         -> (pcm, frames, offset, status): stream s, channel c, frame k at pcm[offset[s] + c * frames[s] + k]"""
+        return self._decode_run(self.L.vamd_decode_plan, self.L.vamd_decode_streams, prep, pcm)
+
+    def _decode_run(self, plan, run, prep, pcm):
+        """the plan call, the output tensor, the decode call: of the packet entry and of the Ogg entry alike"""
         t = self.torch
         ns, d = prep["nstreams"], prep["desc"]
         frames, nblocks = np.zeros(max(ns, 1), np.int64), np.zeros(2, np.int64)
-        self._check(self.L.vamd_decode_plan(self.h, C.byref(d), _vp(frames.ctypes.data), _vp(nblocks.ctypes.data)))
+        self._check(plan(self.h, C.byref(d), _vp(frames.ctypes.data), _vp(nblocks.ctypes.data)))
         out_off = np.zeros(max(ns, 1), np.int64)
         if ns > 1:
             out_off[1:ns] = np.cumsum(frames[:ns - 1] * self.channels)
@@ -665,8 +669,15 @@ class Analyzer:
         self._need(pcm.numel() >= total, "pcm must hold %d floats" % total)
         status = np.zeros(max(ns, 1), np.uint8)
         self._bind_stream()
-        self._check(self.L.vamd_decode_streams(self.h, C.byref(d), _vp(out_off.ctypes.data), _vp(pcm.data_ptr()), _vp(status.ctypes.data)))
+        self._check(run(self.h, C.byref(d), _vp(out_off.ctypes.data), _vp(pcm.data_ptr()), _vp(status.ctypes.data)))
         return pcm, frames[:ns], out_off[:ns], status[:ns]
+
+    def _decoded_tensors(self, n, pcm, frames, out_off, status, with_status):
+        out = []
+        for s in range(n):
+            f = 0 if status[s] else int(frames[s])
+            out.append(pcm[int(out_off[s]):int(out_off[s]) + self.channels * f].view(self.channels, f))
+        return (out, status.copy()) if with_status else out
 
     def decode_streams(self, streams, granules=None, with_status=False, offset=None, stream_start=None):
         """vamd_decode_plan + vamd_decode_streams: audio packets of this context's setup in, PCM out -- k_unpack, k_synth and
@@ -675,12 +686,36 @@ class Analyzer:
         none), which cuts the last block's frames.  offset / stream_start: test hooks, the descriptor's arrays as given
         instead of as derived.  -> a list of float32 tensors [ch, frames] on the context's device; with_status, also the
         streams' status bytes (numpy uint8): a flagged stream -- STATUS_NOTAUDIO / _BADCODE / _TRUNCATED -- has no frames."""
-        pcm, frames, out_off, status = self.decode_run(self.decode_prepare(streams, granules, offset, stream_start))
-        out = []
-        for s in range(len(streams)):
-            f = 0 if status[s] else int(frames[s])
-            out.append(pcm[int(out_off[s]):int(out_off[s]) + self.channels * f].view(self.channels, f))
-        return (out, status.copy()) if with_status else out
+        return self._decoded_tensors(len(streams), *self.decode_run(self.decode_prepare(streams, granules, offset, stream_start)), with_status)
+
+    def decode_ogg_prepare(self, files, setup_header=None, file_offset=None):
+        """The descriptor of decode_ogg()'s group (vamd_decode_ogg_desc) with the host arrays it points into."""
+        for f in files:
+            self._need(isinstance(f, (bytes, bytearray, memoryview)), "decode_ogg: a file must be bytes")
+        ns = len(files)
+        data = np.frombuffer(b"".join(bytes(f) for f in files) + b"\0" * 8, np.uint8)
+        off = np.zeros(ns + 1, np.int64)
+        np.cumsum(np.array([len(f) for f in files], np.int64), out=off[1:])
+        if file_offset is not None:
+            off = np.ascontiguousarray(file_offset, np.int64)
+            self._need(off.size == ns + 1, "decode_ogg: file_offset must hold nstreams + 1 values")
+        hdr = np.frombuffer(bytes(setup_header), np.uint8) if setup_header is not None else None
+        d = _DecodeOggDesc(ns, _vp(data.ctypes.data), _vp(off.ctypes.data), _vp(hdr.ctypes.data) if hdr is not None and hdr.size else None,
+                           hdr.size if hdr is not None else 0)
+        return dict(desc=d, keep=(data, off, hdr), nstreams=ns)
+
+    def decode_ogg_run(self, prep, pcm=None):
+        """vamd_decode_ogg_plan + vamd_decode_ogg over decode_ogg_prepare()'s descriptor; pcm and the result as decode_run's"""
+        return self._decode_run(self.L.vamd_decode_ogg_plan, self.L.vamd_decode_ogg, prep, pcm)
+
+    def decode_ogg(self, files, setup_header=None, with_status=False, file_offset=None):
+        """vamd_decode_ogg_plan + vamd_decode_ogg: whole Ogg Vorbis files of this context's setup in, PCM out -- the page
+        walk on the host, checksums and unpaging (k_ogg_depage), k_unpack, k_synth and the lap on the GPU.  files: a list of
+        `bytes`, one file per stream (a Feed's Ogg output plugs in as it is); setup_header: the setup header packet every
+        file's third packet must equal, or None: only its type is looked at.  file_offset: a test hook, the descriptor's
+        array as given.  -> as decode_streams(); a flagged stream -- STATUS_BADPAGE / _BADHEADER or the packet decoder's
+        bits -- has no frames."""
+        return self._decoded_tensors(len(files), *self.decode_ogg_run(self.decode_ogg_prepare(files, setup_header, file_offset)), with_status)
 
     def analyze_block(self, pcm, lW=1, W=1, nW=1, blocktype=BLOCKTYPE_LONG, ampmax_in=-9999.0):
         """vamd_analyze_block: host numpy pcm[ch][n] in, host numpy results out (the per-block
@@ -842,5 +877,15 @@ def decode(setup_blob, streams, granules=None, with_status=False, device=None):
     a = Analyzer(setup_blob, device)
     try:
         return a.decode_streams(streams, granules, with_status)
+    finally:
+        a.close()
+
+
+def decode_ogg(setup_blob, files, setup_header=None, with_status=False, device=None):
+    """Analyzer(setup_blob).decode_ogg(...) for a caller who holds files and no context: the files must come from an
+    encoder of that setup."""
+    a = Analyzer(setup_blob, device)
+    try:
+        return a.decode_ogg(files, setup_header, with_status)
     finally:
         a.close()

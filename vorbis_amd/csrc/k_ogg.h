@@ -1,5 +1,5 @@
 // k_ogg.h -- Ogg pages around the feed's packets (doc/framing.html: page layout, lacing, CRC; doc/a1-encapsulation-ogg.tex:
-// how Vorbis I sits in Ogg).  Three parts:
+// how Vorbis I sits in Ogg).  Three parts, and the way back:
 //   * the CRC: table-driven per byte, and the algebra that lets a page be summed in chunks -- the register after a message
 //     M (initial value 0, no final XOR, MSb first) is M(x) x^32 mod P, so crc(A || B) = crc(A) x^(8 |B|) + crc(B): every
 //     lane sums a contiguous chunk, and a log-step tree joins neighbours with one multiply mod P each;
@@ -9,7 +9,9 @@
 //   * the kernels: k_ogg_plan (a wave per stream runs the walk, sizes scanned into LDS 64 at a time) and k_ogg_pages (a
 //     wave per page: header, lacing table, body gathered from the packets, CRC, written with aligned dword stores) -- and,
 //     for a live feed, whose files arrive in pieces, k_ogg_carry: what lies on the page still open stays on the device,
-//     unless the group flushes the stream (vamd_feed_ogg_flush): then the open page leaves with the group.
+//     unless the group flushes the stream (vamd_feed_ogg_flush): then the open page leaves with the group;
+//   * files back to packets, for the decoder (vamd_decode_ogg), is k_demux.h: k_ogg_depage, a wave per page of a table the
+//     host walked (vamd_demux.h) -- this file's chunked CRC held against the stored field, the audio bytes into a packed arena.
 // The CRC functions and the walk are ONE body: the library compiles them for gfx950, the CPU suite compiles this very
 // file with the host compiler (tests/ogg_host.py) together with the host-only mux at the end, which lays the same
 // pages out byte by byte -- the second implementation of the policy that the GPU's files are held against.
@@ -358,7 +360,9 @@ VAMD_OGG_FN int64_t ogg_live_file_bound_v(int64_t packet_bytes, int64_t npackets
          nstreams * (OGG_HEADER + OGG_MAX_SEGS);
 }
 
-#if defined(__HIPCC__)
+// (VAMD_OGG_NO_FEED_KERNELS: a translation unit that wants the functions above and not the feed's kernels -- they are
+// vamd_feed.hip's, and a second copy of their names would not link)
+#if defined(__HIPCC__) && !defined(VAMD_OGG_NO_FEED_KERNELS)
 // ---- the kernels ----
 // What the pager reads: the device mirror of the group's packets (bytes at the offsets of the output arena, each packet at
 // a multiple of 4, and their records), the three header packets, the streams' serial numbers, and, where the group names
@@ -778,7 +782,7 @@ __global__ __launch_bounds__(64) void k_ogg_carry(OggIn I, long nstreams, OggLiv
     if (bad) o->dead = 0x80;
   }
 }
-#endif  // __HIPCC__
+#endif  // __HIPCC__ && !VAMD_OGG_NO_FEED_KERNELS
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 // ---- host only: the chunked CRC as k_ogg_pages computes it, and the mux (the CPU suite; the GPU's files are held

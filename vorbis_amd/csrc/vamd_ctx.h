@@ -65,13 +65,14 @@ struct vamd_ctx {
     const int32_t *res_count = nullptr;
   } synth_src[2];
   // the packet decoder (vamd_decode.h): the codebooks' decode tables, built at first use, and its workspace, grown on
-  // demand -- the packets and the plan as they go up, per size class the rows k_unpack writes and k_synth's output
+  // demand -- the packets and the plan as they go up, per size class the rows k_unpack writes and k_synth's output; the
+  // Ogg entry's files as they go up (k_ogg_depage fills `bytes` from them)
   struct Decode {
     bool ready = false;
     int lanes = VAMD_UNPACK_LANES;  // packets a wave of k_unpack
     unsigned char *d_tab = nullptr;
     UnpackP U = {};
-    DevBuf bytes, plan, status;
+    DevBuf bytes, plan, status, files;
     DevBuf post_valid[2], ilogmask[2], res_class[2], res_entries[2], res_count[2], synth[2];
     HostBuf h_plan;
   } dec;

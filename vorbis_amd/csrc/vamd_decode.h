@@ -4,15 +4,22 @@
 // the context's stream: the packets and the plan go up, one copy each; k_unpack turns every packet into its block's rows
 // (k_unpack.h); k_synth runs per size class on those rows (k_synth.h, the launch the encoder's tensors take); k_lap
 // gathers the streams' samples; the statuses come back.
+// The Ogg entry (vamd_decode_ogg_plan, vamd_decode_ogg) takes whole files instead: the host walks their page headers and
+// lacing tables (vamd_demux.h), the files go up in one copy as they lie, and k_ogg_depage (k_demux.h) checks every page's
+// checksum and moves the audio bytes into the same packed arena -- from k_unpack on the two entries are one function.
 //
 // Workspace per block, in the context, grown on demand and released with it (ch channels, n the block's size, S submaps):
 //   rows     4 ch (post_valid) + ch n/2 (the integer curves) + S * 2048 (res_class) + 2 * vamd_residue_capacity
 //            (res_entries) + 8 S (res_count)
 //   k_synth  4 ch n (vb->pcm)
 //   plan     4 (order) + 8 (src) + 16 (the packet's bits) + 1 (status), and the packet itself
+//   files    (the Ogg entry) the files' bytes once more, and per page 32 (its row) + 1 (status)
 // -- for a stereo block of 2048 some 29 KiB, of which vb->pcm is 16.
 #pragma once
 #include "vamd_decode_plan.h"
+#include "vamd_demux.h"
+
+static_assert(OGG_DEPAGE_BADCRC == VAMD_STATUS_BADPAGE, "k_ogg_depage's status byte is the stream's");
 
 static int dev_need(vamd_ctx *c, DevBuf &b, size_t bytes) {
   if (b.bytes < bytes) {
@@ -28,7 +35,7 @@ static int dev_need(vamd_ctx *c, DevBuf &b, size_t bytes) {
 
 static void decode_release(vamd_ctx *c) {
   vamd_ctx::Decode &D = c->dec;
-  DevBuf *all[] = {&D.bytes, &D.plan, &D.status, &D.post_valid[0], &D.post_valid[1], &D.ilogmask[0], &D.ilogmask[1], &D.res_class[0], &D.res_class[1],
+  DevBuf *all[] = {&D.bytes, &D.plan, &D.status, &D.files, &D.post_valid[0], &D.post_valid[1], &D.ilogmask[0], &D.ilogmask[1], &D.res_class[0], &D.res_class[1],
                    &D.res_entries[0], &D.res_entries[1], &D.res_count[0], &D.res_count[1], &D.synth[0], &D.synth[1]};
   for (DevBuf *b : all)
     if (b->p) (void)hipFree(b->p);
@@ -84,28 +91,32 @@ int vamd_decode_plan(vamd_ctx *c, const vamd_decode_desc *d, int64_t *frames, in
   return VAMD_OK;
 }
 
-int vamd_decode_streams(vamd_ctx *c, const vamd_decode_desc *d, const int64_t *offset_out, float *pcm, uint8_t *status) {
-  DeviceGuard dev_guard(c);
-  if (!c) return VAMD_EINVAL;
-  DecodePlan P;
-  int r = decode_plan(c, d, &P);
-  if (r) return r;
-  const int64_t ns = d->nstreams;
-  if (ns && !status) return fail(c, VAMD_EINVAL, "decode: null status");
-  if (P.max_frames > 0 && (!offset_out || !pcm)) return fail(c, VAMD_EINVAL, "decode: null offset_out / pcm");
-  for (int64_t s = 0; s < ns; s++) {
-    if (P.frames[(size_t)s] > 0 && offset_out[s] < 0) return fail(c, VAMD_EINVAL, "decode: negative offset_out");
-    status[s] = P.status[(size_t)s];
-  }
-  const size_t nb = P.order.size();
-  if (!nb) return VAMD_OK;
+// What the two entries hand the shared tail: the packed arena's packet table, and where its bytes come from -- the
+// caller's host memory as they are (the packet entry), or the files' pages by way of k_ogg_depage (the Ogg entry).
+struct DecodeInput {
+  const int64_t *offset = nullptr;   // [npackets + 1] bytes; the arena is [byte0, byte0 + nbytes) of this numbering
+  int64_t byte0 = 0, nbytes = 0;
+  const uint8_t *packets = nullptr;  // the packet entry: the arena in host memory, from byte0 on
+  const DemuxScan *scan = nullptr;   // the Ogg entry: the page table, the pages' streams ...
+  const uint8_t *files = nullptr;    // ... and the group's files in host memory, one copy as they lie
+  int64_t files_bytes = 0;
+};
+
+// The tail both entries share, behind a plan that holds and statuses the host has already set: workspace, the plan's
+// upload, the arena (uploaded, or unpaged on the device), k_unpack, k_synth, k_lap, and the statuses back in one copy --
+// the blocks' and, behind them, the pages' -- folded into their streams.
+static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const DecodeInput &in, const int64_t *offset_out, float *pcm, uint8_t *status) {
+  int r;
+  const size_t nb = P.order.size(), npg = in.scan ? in.scan->pages.size() : 0;
+  if (!nb && !npg) return VAMD_OK;
   vamd_ctx::Decode &D = c->dec;
   const int ch = c->B.channels;
   // the workspace
-  const int64_t byte0 = d->offset[0], nbytes = d->offset[d->npackets] - byte0;
+  const int64_t byte0 = in.byte0, nbytes = in.nbytes;
   const long long nwords = (long long)((nbytes + 3) / 4);
   if ((r = dev_need(c, D.bytes, (size_t)nwords * 4 + 16))) return r;
-  if ((r = dev_need(c, D.status, nb + 16))) return r;
+  if ((r = dev_need(c, D.status, nb + npg + 16))) return r;
+  if (npg && (r = dev_need(c, D.files, (((size_t)in.files_bytes + 3) & ~(size_t)3) + 16))) return r;
   UnpackRows rows[2];
   vamd_ctx::SynthSrc src[2];
   for (int W = 0; W < 2; W++) {
@@ -121,34 +132,45 @@ int vamd_decode_streams(vamd_ctx *c, const vamd_decode_desc *d, const int64_t *o
     src[W].nb = (long)n, src[W].post_valid = rows[W].post_valid, src[W].ilogmask = rows[W].ilogmask, src[W].res_class = rows[W].res_class;
     src[W].res_entries = rows[W].res_entries, src[W].res_count = rows[W].res_count;
   }
-  // the plan, one piece: order | stream_start | src per size class | the packets' bits | frames | offset_out
+  // the plan, one piece: order | stream_start | src per size class | the packets' bits | frames | offset_out | the page table
   Arena a;
   const size_t o_order = a.take(4 * nb), o_start = a.take(8 * ((size_t)ns + 1)), o_src0 = a.take(8 * P.src[0].size() + 8),
-               o_src1 = a.take(8 * P.src[1].size() + 8), o_bits = a.take(16 * nb), o_frames = a.take(8 * (size_t)ns), o_off = a.take(8 * (size_t)ns);
-  const size_t plan_bytes = a.at, o_status = a.take(nb);
+               o_src1 = a.take(8 * P.src[1].size() + 8), o_bits = a.take(16 * nb), o_frames = a.take(8 * (size_t)ns), o_off = a.take(8 * (size_t)ns),
+               o_pages = a.take(sizeof(OggDepage) * npg);
+  const size_t plan_bytes = a.at, o_status = a.take(nb + npg);
   if ((r = pinned_get(c, D.h_plan, a.at, true))) return r;
   if ((r = dev_need(c, D.plan, plan_bytes))) return r;
   unsigned char *h = (unsigned char *)D.h_plan.p, *dp = (unsigned char *)D.plan.p;
-  memcpy(h + o_order, P.order.data(), 4 * nb);
+  if (nb) memcpy(h + o_order, P.order.data(), 4 * nb);
   memcpy(h + o_start, P.lap_start.data(), 8 * ((size_t)ns + 1));
   if (!P.src[0].empty()) memcpy(h + o_src0, P.src[0].data(), 8 * P.src[0].size());
   if (!P.src[1].empty()) memcpy(h + o_src1, P.src[1].data(), 8 * P.src[1].size());
   for (size_t k = 0; k < nb; k++) {
     const int64_t p = P.packet[k];
-    ((int64_t *)(h + o_bits))[2 * k] = 8 * (d->offset[p] - byte0);
-    ((int64_t *)(h + o_bits))[2 * k + 1] = 8 * (d->offset[p + 1] - byte0);
+    ((int64_t *)(h + o_bits))[2 * k] = 8 * (in.offset[p] - byte0);
+    ((int64_t *)(h + o_bits))[2 * k + 1] = 8 * (in.offset[p + 1] - byte0);
   }
   memcpy(h + o_frames, P.frames.data(), 8 * (size_t)ns);
   for (int64_t s = 0; s < ns; s++) ((int64_t *)(h + o_off))[s] = P.frames[(size_t)s] > 0 ? offset_out[s] : 0;
+  if (npg) memcpy(h + o_pages, in.scan->pages.data(), sizeof(OggDepage) * npg);
   hipStream_t s = c->stream;
   HIP_TRY(c, hipMemcpyAsync(dp, h, plan_bytes, hipMemcpyHostToDevice, s));
-  if (nbytes) HIP_TRY(c, hipMemcpyAsync(D.bytes.p, d->bytes + byte0, (size_t)nbytes, hipMemcpyHostToDevice, s));
+  if (npg) {
+    HIP_TRY(c, hipMemcpyAsync(D.files.p, in.files, (size_t)in.files_bytes, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ogg_depage, dim3((unsigned)npg), dim3(64), 0, s, (const uint8_t *)D.files.p, in.files_bytes, (const OggDepage *)(dp + o_pages),
+                       (uint8_t *)D.bytes.p, nbytes, (uint8_t *)D.status.p + nb);
+    HIP_TRY(c, hipGetLastError());
+  } else if (nbytes) {
+    HIP_TRY(c, hipMemcpyAsync(D.bytes.p, in.packets, (size_t)nbytes, hipMemcpyHostToDevice, s));
+  }
   const int lanes = D.lanes;
-  hipLaunchKernelGGL(k_unpack, dim3((unsigned)((nb + lanes - 1) / lanes)), dim3(64), (size_t)VAMD_POSIT * lanes * 4, s, (const Bound *)c->d_bound, D.U, lanes, (long)nb,
-                     (const uint32_t *)D.bytes.p, nwords,
-                     (const long long *)(dp + o_bits), (const int *)(dp + o_order), c->B.res_cap[0], c->B.res_cap[1], c->d_dbg ? c->d_dbg + 56 : nullptr,
-                     rows[0], rows[1], (unsigned char *)D.status.p);
-  HIP_TRY(c, hipGetLastError());
+  if (nb) {
+    hipLaunchKernelGGL(k_unpack, dim3((unsigned)((nb + lanes - 1) / lanes)), dim3(64), (size_t)VAMD_POSIT * lanes * 4, s, (const Bound *)c->d_bound, D.U, lanes, (long)nb,
+                       (const uint32_t *)D.bytes.p, nwords,
+                       (const long long *)(dp + o_bits), (const int *)(dp + o_order), c->B.res_cap[0], c->B.res_cap[1], c->d_dbg ? c->d_dbg + 56 : nullptr,
+                       rows[0], rows[1], (unsigned char *)D.status.p);
+    HIP_TRY(c, hipGetLastError());
+  }
   for (int W = 0; W < 2; W++)
     if (src[W].nb > 0 && (r = launch_synth(c, W, src[W], (float *)D.synth[W].p))) return r;
   if (P.max_frames > 0) {
@@ -163,9 +185,80 @@ int vamd_decode_streams(vamd_ctx *c, const vamd_decode_desc *d, const int64_t *o
                        (const long long *)(dp + o_frames), (const long long *)(dp + o_off), pcm);
     HIP_TRY(c, hipGetLastError());
   }
-  HIP_TRY(c, hipMemcpyAsync(h + o_status, D.status.p, nb, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(h + o_status, D.status.p, nb + npg, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   for (int64_t st = 0; st < ns; st++)
     for (int64_t k = P.lap_start[(size_t)st]; k < P.lap_start[(size_t)st + 1]; k++) status[st] |= h[o_status + (size_t)k];
+  for (size_t k = 0; k < npg; k++) status[in.scan->pages[k].stream] |= h[o_status + nb + k];
   return VAMD_OK;
+}
+
+// what both entries ask of their outputs, once the plan holds; then the host's statuses go out
+static int decode_outputs(vamd_ctx *c, const DecodePlan &P, int64_t ns, const int64_t *offset_out, const float *pcm, uint8_t *status) {
+  if (ns && !status) return fail(c, VAMD_EINVAL, "decode: null status");
+  if (P.max_frames > 0 && (!offset_out || !pcm)) return fail(c, VAMD_EINVAL, "decode: null offset_out / pcm");
+  for (int64_t s = 0; s < ns; s++) {
+    if (P.frames[(size_t)s] > 0 && offset_out[s] < 0) return fail(c, VAMD_EINVAL, "decode: negative offset_out");
+    status[s] = P.status[(size_t)s];
+  }
+  return VAMD_OK;
+}
+
+int vamd_decode_streams(vamd_ctx *c, const vamd_decode_desc *d, const int64_t *offset_out, float *pcm, uint8_t *status) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  DecodePlan P;
+  int r = decode_plan(c, d, &P);
+  if (r) return r;
+  if ((r = decode_outputs(c, P, d->nstreams, offset_out, pcm, status))) return r;
+  if (P.order.empty()) return VAMD_OK;
+  DecodeInput in;
+  in.offset = d->offset, in.byte0 = d->offset[0], in.nbytes = d->offset[d->npackets] - d->offset[0];
+  in.packets = d->bytes + in.byte0;
+  return decode_run(c, P, d->nstreams, in, offset_out, pcm, status);
+}
+
+// ---- files in: vamd_decode_ogg_plan, vamd_decode_ogg ----
+// The host's walk (vamd_demux.h), then the block plan over its packet table with the first bytes it read in place.
+static int decode_ogg_plan(vamd_ctx *c, const vamd_decode_ogg_desc *d, DemuxScan *X, DecodePlan *P) {
+  if (!d) return fail(c, VAMD_EINVAL, "decode_ogg: null descriptor");
+  int r = decode_ready(c);
+  if (r) return r;
+  DemuxSetup S;
+  S.channels = c->B.channels, S.rate = c->B.rate, S.bs[0] = c->B.bs[0], S.bs[1] = c->B.bs[1];
+  S.setup_header = d->setup_header, S.setup_header_bytes = d->setup_header_bytes;
+  std::string err;
+  if (!demux_scan(d->nstreams, d->bytes, d->file_offset, S, X, &err)) return fail(c, VAMD_EINVAL, err.c_str());
+  if (X->pages.size() > 0x7fffffffu) return fail(c, VAMD_EINVAL, "decode_ogg: more than 2^31 pages");
+  if (!decode_plan_build(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->nstreams, (int64_t)X->first.size(), nullptr, X->offset.data(),
+                         X->stream_start.data(), X->end_granule.data(), P, &err, X->first.data()))
+    return fail(c, VAMD_EINVAL, err.c_str());
+  for (int64_t s = 0; s < d->nstreams; s++) P->status[(size_t)s] |= X->status[(size_t)s];
+  return VAMD_OK;
+}
+
+int vamd_decode_ogg_plan(vamd_ctx *c, const vamd_decode_ogg_desc *d, int64_t *frames, int64_t *nblocks) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  DemuxScan X;
+  DecodePlan P;
+  int r = decode_ogg_plan(c, d, &X, &P);
+  if (r) return r;
+  for (int64_t s = 0; frames && s < d->nstreams; s++) frames[s] = P.frames[(size_t)s];
+  if (nblocks) nblocks[0] = P.nblocks[0], nblocks[1] = P.nblocks[1];
+  return VAMD_OK;
+}
+
+int vamd_decode_ogg(vamd_ctx *c, const vamd_decode_ogg_desc *d, const int64_t *offset_out, float *pcm, uint8_t *status) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  DemuxScan X;
+  DecodePlan P;
+  int r = decode_ogg_plan(c, d, &X, &P);
+  if (r) return r;
+  if ((r = decode_outputs(c, P, d->nstreams, offset_out, pcm, status))) return r;
+  DecodeInput in;
+  in.offset = X.offset.data(), in.byte0 = 0, in.nbytes = X.offset.back();
+  in.scan = &X, in.files = d->bytes + d->file_offset[0], in.files_bytes = d->file_offset[d->nstreams] - d->file_offset[0];
+  return decode_run(c, P, d->nstreams, in, offset_out, pcm, status);
 }

@@ -153,9 +153,12 @@ inline int decode_packet_class(const uint8_t *p, int64_t len, int modes, int mod
 
 // -> false with a reason for a bad descriptor.  end_granule: NULL, or per stream the last packet's granule position
 // (-1: none): the frames the stream's last block adds are cut to it, as vorbis_synthesis_blockin does for a stream that
-// began at granule 0 (lib/block.c:906-935; never by more than that block adds).
+// began at granule 0 (lib/block.c:906-935; never by more than that block adds).  first: NULL, or per packet its first byte --
+// a caller whose packets are not yet together anywhere (vamd_demux.h: they lie in pages, and the packed arena exists on
+// the device alone) hands the mode bits over this way, and `bytes` is not read.
 inline bool decode_plan_build(const int bs[2], int modes, int modebits, int64_t nstreams, int64_t npackets, const uint8_t *bytes,
-                              const int64_t *offset, const int64_t *stream_start, const int64_t *end_granule, DecodePlan *P, std::string *err) {
+                              const int64_t *offset, const int64_t *stream_start, const int64_t *end_granule, DecodePlan *P, std::string *err,
+                              const uint8_t *first = nullptr) {
   *P = DecodePlan();
   if (nstreams < 0 || npackets < 0) return *err = "decode: negative stream or packet count", false;
   if (!offset || !stream_start) return *err = "decode: null offset / stream_start", false;
@@ -163,7 +166,7 @@ inline bool decode_plan_build(const int bs[2], int modes, int modebits, int64_t 
   for (int64_t p = 0; p < npackets; p++)
     if (offset[p + 1] < offset[p]) return *err = "decode: packet offsets are not monotone", false;
   if (offset[npackets] > ((int64_t)1 << 40)) return *err = "decode: more than 2^40 bytes of packets", false;
-  if (offset[npackets] > 0 && !bytes) return *err = "decode: null bytes", false;
+  if (offset[npackets] > 0 && !bytes && !first) return *err = "decode: null bytes", false;
   if (stream_start[0] < 0 || stream_start[nstreams] > npackets) return *err = "decode: stream_start outside the packets", false;
   for (int64_t s = 0; s < nstreams; s++) {
     if (stream_start[s + 1] < stream_start[s]) return *err = "decode: stream_start is not monotone", false;
@@ -178,7 +181,7 @@ inline bool decode_plan_build(const int bs[2], int modes, int modebits, int64_t 
     cls.clear();
     uint8_t st = 0;
     for (int64_t p = p0; p < p1; p++) {
-      const int W = decode_packet_class(bytes + offset[p], offset[p + 1] - offset[p], modes, modebits);
+      const int W = decode_packet_class(first ? first + p : bytes + offset[p], offset[p + 1] - offset[p], modes, modebits);
       if (W < 0) st |= (uint8_t)-W;
       cls.push_back(W);
     }

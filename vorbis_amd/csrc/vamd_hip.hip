@@ -43,6 +43,8 @@
 #include "k_synth.h"
 #include "k_unpack.h"
 #include "vamd_decode_plan.h"
+#define VAMD_OGG_NO_FEED_KERNELS  // (k_ogg.h: k_ogg_plan / _pages / _carry are vamd_feed.hip's)
+#include "vamd_demux.h"
 
 using namespace vamd;
 
