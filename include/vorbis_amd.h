@@ -602,7 +602,8 @@ int vamd_synth_streams(vamd_ctx *ctx, const vamd_stream_plan *plan, long nstream
  * submaps), and the packets themselves.
  *
  * Out of scope: header packets and setups other than the context's; packets in device memory; streams that begin at a
- * nonzero granule (the first page's trim); eopbreak semantics (above).  Ogg files: vamd_decode_ogg, below. */
+ * nonzero granule (the first page's trim); eopbreak semantics (above).  Ogg files: vamd_decode_ogg, below.  A stream that
+ * is still being made, its packets in pieces: vamd_decode_live, below. */
 #define VAMD_STATUS_NOTAUDIO  4
 #define VAMD_STATUS_BADCODE   8
 #define VAMD_STATUS_TRUNCATED 16
@@ -616,6 +617,64 @@ typedef struct vamd_decode_desc {
 int vamd_decode_plan(vamd_ctx *ctx, const vamd_decode_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
 int vamd_decode_streams(vamd_ctx *ctx, const vamd_decode_desc *desc, const int64_t *offset_out /* host [nstreams] */,
                         float *pcm /* device */, uint8_t *status /* host [nstreams] */);
+
+/* ---- the live decoder: continuing streams decoded in pieces (still ABI 9: additions only).  The counterpart of a live
+ * feed (vamd_feed_create_live): a caller who receives a stream's packets while the stream is still being made -- a live
+ * feed's consumer, a receiver -- hands over the next piece of up to max_streams streams per call and gets that piece's
+ * samples.  A stream's pieces laid end to end are, bit for bit, what vamd_decode_streams gives for the whole stream, at ANY
+ * cut of its packet list into pieces, empty pieces and pieces of one packet included (tests/test_decode_live_cpu.py,
+ * tests/test_decode_live_gpu.py).  What is carried between a stream's pieces is its last block's second half, on the
+ * device (k_decode_carry_out writes it behind k_synth, k_decode_carry_in stands it in front of the next piece's blocks
+ * ahead of k_lap), and that block's size class and a frame count on the host; the rest of a call is the packet decoder
+ * above, on the context's stream and in the context's workspace.
+ *
+ * Slots, as a live feed has them: stream s of a call is the stream of slot[s] (distinct, 0 .. max_streams-1) -- the same
+ * stream until a piece closes it.  A slot is free until its first piece, which opens a stream at granule 0; a piece with
+ * close[s] != 0 ends the stream behind its blocks, and the slot's next piece opens a fresh one.  Slots a call does not
+ * name keep their state.  The pieces are packets as vamd_decode_desc lays them, in HOST memory.
+ *
+ *   vamd_decode_live_plan   host only, changes nothing: frames[s] of this piece and nblocks[2], the packets per size
+ *     class.  The frames of a piece: the stream's blocks of this piece, with the block carried from its last piece (if
+ *     any) in front, its centre at 0 -- the span of those centres, bs[lW]/4 + bs[W]/4 apart.  So a first piece of one packet
+ *     gives 0 frames (and leaves a carry), an empty piece gives 0 and leaves the slot as it stood, a carried block and m >= 1
+ *     packets give the sum of the m steps.  end_granule[s] is read for a closing piece that holds at least one packet:
+ *     frames -= min(total - end_granule, step) where it lies below total, the frames handed out since the stream opened
+ *     (this piece's included) and step what the last block adds -- vamd_decode_plan's cut.  An EMPTY closing piece only
+ *     frees the slot: its samples have already left, and its end_granule is not applied.
+ *   vamd_decode_live_wrote  plans again, runs -- the packets and the plan up, k_unpack, k_synth, the two carry kernels,
+ *     k_lap into pcm (DEVICE; stream s, channel c, frame k at pcm[offset_out[s] + c * frames[s] + k]), status[s] (host)
+ *     back: one stream synchronisation -- and commits the slots' state only when the call has succeeded.
+ *
+ * status[s] is 0 or the VAMD_STATUS_* bits of the stream's flagged packets.  From the piece that holds a flagged packet
+ * on the stream is dead: that piece and every later one have no frames (a packet flagged on the device leaves the piece's
+ * planned frames in the layout of pcm; they are not its signal) and carry the status, until a piece closes the stream.
+ * What earlier pieces handed out stands; other streams and the slot's next stream are untouched -- what a live feed does
+ * with a block outside the input domain.
+ *
+ * VAMD_EINVAL with the reason in vamd_last_error(ctx), nothing enqueued and no state changed: null pointers; counts,
+ * offsets or stream_start not monotone or out of range; a slot out of range or named twice; nstreams > max_streams; a
+ * granule position below -1.  VAMD_EIMPL as vamd_decode_plan gives it (at create already).  Every index the kernels use
+ * -- the slots, the carried rows, the last blocks' rows -- is computed and range-checked on the host before the first launch.
+ *
+ * Destroy a live decoder before its context.  Calls on one context are not concurrent, as everywhere.
+ * Out of scope: Ogg pages in pieces (a packet can span the pages of two pieces: the host walk would carry partial
+ * packets -- the next step, on top of this one); streams that begin at a nonzero granule; packets in device memory; the
+ * feed itself is unchanged (VAMD_FEED_DECODED on a live feed is still refused: decode its packets here). */
+typedef struct vamd_decode_live vamd_decode_live;
+int vamd_decode_live_create(vamd_ctx *ctx, int64_t max_streams, vamd_decode_live **out);
+void vamd_decode_live_destroy(vamd_decode_live *d);
+typedef struct vamd_decode_live_desc {
+  int64_t nstreams, npackets;
+  const int64_t *slot;           /* host [nstreams]: distinct, 0 .. max_streams-1 */
+  const uint8_t *bytes;          /* HOST: this call's audio packets, back to back */
+  const int64_t *offset;         /* host [npackets + 1], bytes */
+  const int64_t *stream_start;   /* host [nstreams + 1], into packets */
+  const uint8_t *close;          /* host [nstreams] or NULL: != 0 ends the stream after this piece */
+  const int64_t *end_granule;    /* host [nstreams] or NULL: read for closing streams only, -1 = none */
+} vamd_decode_live_desc;
+int vamd_decode_live_plan(vamd_decode_live *d, const vamd_decode_live_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
+int vamd_decode_live_wrote(vamd_decode_live *d, const vamd_decode_live_desc *desc, const int64_t *offset_out /* host [nstreams] */,
+                           float *pcm /* device */, uint8_t *status /* host [nstreams] */);
 
 /* ---- Ogg Vorbis files in, PCM out (still ABI 9: additions only).  The packet decoder above with a FILE per stream: what
  * vamd_feed_ogg writes, and libvorbis' files of the same setup, decode without a host loop over their bytes.  The contract

@@ -58,6 +58,11 @@ class _DecodeDesc(C.Structure):  # vamd_decode_desc
     _fields_ = [("nstreams", C.c_int64), ("npackets", C.c_int64), ("bytes", _vp), ("offset", _vp), ("stream_start", _vp), ("end_granule", _vp)]
 
 
+class _DecodeLiveDesc(C.Structure):  # vamd_decode_live_desc
+    _fields_ = [("nstreams", C.c_int64), ("npackets", C.c_int64), ("slot", _vp), ("bytes", _vp), ("offset", _vp), ("stream_start", _vp),
+                ("close", _vp), ("end_granule", _vp)]
+
+
 class _DecodeOggDesc(C.Structure):  # vamd_decode_ogg_desc
     _fields_ = [("nstreams", C.c_int64), ("bytes", _vp), ("file_offset", _vp), ("setup_header", _vp), ("setup_header_bytes", C.c_int64)]
 
@@ -97,7 +102,7 @@ class VamdError(RuntimeError):
 _int, _long, _size, _float = C.c_int, C.c_long, C.c_size_t, C.c_float
 _pvp, _pint, _plong, _pfloat, _pi32 = C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_float), C.POINTER(C.c_int32)
 _pDesc, _pIO, _pMIO, _pPlan, _pDecode = C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO), C.POINTER(_Plan), C.POINTER(_DecodeDesc)
-_pDecodeOgg = C.POINTER(_DecodeOggDesc)
+_pDecodeOgg, _pDecodeLive = C.POINTER(_DecodeOggDesc), C.POINTER(_DecodeLiveDesc)
 _vp2 = _vp * 2
 _block = [_vp, _pvp, _int, _int, _int, _int, _float]   # (ctx, pcm[ch], lW, W, nW, blocktype, ampmax_in): how every per-block call begins
 
@@ -137,6 +142,10 @@ PROTOTYPES = {
     "vamd_synth_streams": (_int, [_vp, _pPlan, _long, _long, _vp, _vp, _vp, _vp, _vp]),
     "vamd_decode_plan": (_int, [_vp, _pDecode, _vp, _vp]),
     "vamd_decode_streams": (_int, [_vp, _pDecode, _vp, _vp, _vp]),
+    "vamd_decode_live_create": (_int, [_vp, C.c_int64, _pvp]),
+    "vamd_decode_live_destroy": (None, [_vp]),
+    "vamd_decode_live_plan": (_int, [_vp, _pDecodeLive, _vp, _vp]),
+    "vamd_decode_live_wrote": (_int, [_vp, _pDecodeLive, _vp, _vp, _vp]),
     "vamd_decode_ogg_plan": (_int, [_vp, _pDecodeOgg, _vp, _vp]),
     "vamd_decode_ogg": (_int, [_vp, _pDecodeOgg, _vp, _vp, _vp]),
     "vamd_analyze_block_managed": (_int, _block + [_vp] * 9),

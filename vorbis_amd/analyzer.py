@@ -1,12 +1,13 @@
 """vamd_ctx in Python: the Analyzer -- batches, streams, plans, the bitrate manager's candidates, the detector, the packet
-decoder for packets and for Ogg files -- and decode() / decode_ogg() for a caller who holds packets or files and no context."""
+decoder for packets and for Ogg files, the LiveDecoder for continuing streams in pieces -- and decode() / decode_ogg() for
+a caller who holds packets or files and no context."""
 import ctypes as C
 
 import numpy as np
 
 from .abi import (ABI_VERSION, BLOCKTYPE_LONG, LEVEL_FULL, LEVEL_PSY, LEVEL_TRANSFORM, PACKETBLOBS, POSTS_STRIDE, QUANT_LIMIT_INT,
                   QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_RANGE, VAMD_EDOMAIN, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
-                  _DecodeDesc, _DecodeOggDesc, _Desc, _IO, _MIO, _Plan, _vp, load_library)
+                  _DecodeDesc, _DecodeLiveDesc, _DecodeOggDesc, _Desc, _IO, _MIO, _Plan, _vp, load_library)
 from .packets import packet_bytes
 
 
@@ -68,6 +69,8 @@ class Analyzer:
 
     def close(self):
         if getattr(self, "h", None):
+            for d in list(getattr(self, "_live", ())):  # (a live decoder does not outlive its context)
+                d.close()
             self.L.vamd_destroy(self.h)
             self.h = None
 
@@ -688,6 +691,15 @@ class Analyzer:
         streams' status bytes (numpy uint8): a flagged stream -- STATUS_NOTAUDIO / _BADCODE / _TRUNCATED -- has no frames."""
         return self._decoded_tensors(len(streams), *self.decode_run(self.decode_prepare(streams, granules, offset, stream_start)), with_status)
 
+    def live_decoder(self, max_streams):
+        """vamd_decode_live_create: a LiveDecoder for up to max_streams continuing streams on this context.  Closing the
+        Analyzer closes it."""
+        if not hasattr(self, "_live"):
+            self._live = []
+        d = LiveDecoder(self, max_streams)
+        self._live.append(d)
+        return d
+
     def decode_ogg_prepare(self, files, setup_header=None, file_offset=None):
         """The descriptor of decode_ogg()'s group (vamd_decode_ogg_desc) with the host arrays it points into."""
         for f in files:
@@ -869,6 +881,75 @@ class Analyzer:
         self._check(self.L.vamd_envelope_search_batch(self.h, _vp(pcm.data_ptr()), ch * ln, ln, ns, nsteps,
                                                       _vp(states.data_ptr()), _vp(ret.data_ptr())))
         return ret, states
+
+
+class LiveDecoder:
+    """vamd_decode_live: continuing streams decoded in pieces, a stream per slot (Analyzer.live_decoder).  A stream's
+    pieces laid end to end are what Analyzer.decode_streams gives for the whole stream, at any cut of its packet list."""
+
+    def __init__(self, analyzer, max_streams):
+        self.an, self.max_streams = analyzer, int(max_streams)
+        h = _vp()
+        analyzer._check(analyzer.L.vamd_decode_live_create(analyzer.h, self.max_streams, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.an.L.vamd_decode_live_destroy(self.h)
+            self.h = None
+            if self in self.an._live:
+                self.an._live.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def prepare(self, slots, pieces, close=(), end_granules=None):
+        """The descriptor of a call (vamd_decode_live_desc) with the host arrays it points into.  slots: the slots this call
+        names; pieces[i]: the list of packets (bytes) of slot slots[i], in order -- it may be empty; close: the slots whose
+        stream ends with this piece; end_granules: {slot: the granule position of the stream's last packet} for closing
+        slots (a live feed's closing group carries it), a sequence with one value per slot of the call (None or -1: none),
+        or None."""
+        an = self.an
+        an._need(self.h is not None, "live decoder: closed")
+        an._need(len(slots) == len(pieces), "live decoder: one piece per slot")
+        for row in pieces:
+            for p in row:
+                an._need(isinstance(p, (bytes, bytearray, memoryview)), "live decoder: a packet must be bytes")
+        ns = len(slots)
+        flat = [bytes(p) for row in pieces for p in row]
+        data = np.frombuffer(b"".join(flat) + b"\0" * 8, np.uint8)
+        off = np.zeros(len(flat) + 1, np.int64)
+        np.cumsum([len(p) for p in flat], out=off[1:])
+        start = np.zeros(ns + 1, np.int64)
+        np.cumsum([len(row) for row in pieces], out=start[1:])
+        slot = np.array([int(s) for s in slots] + [0], np.int64)  # (never an empty array: its pointer is read as non-null)
+        closing = set(int(s) for s in close)
+        an._need(closing <= set(int(s) for s in slots), "live decoder: a closing slot that this call does not name")
+        cl = np.array([int(s) in closing for s in slots] + [0], np.uint8)
+        if end_granules is not None and not isinstance(end_granules, dict):  # (a sequence: one per slot of the call)
+            an._need(len(end_granules) == ns, "live decoder: one end granule per slot of the call")
+            end_granules = {int(s): g for s, g in zip(slots, end_granules)}
+        end_granules = end_granules or {}
+        gran = np.array([-1 if end_granules.get(int(s)) is None else int(end_granules[int(s)]) for s in slots] + [-1], np.int64)
+        d = _DecodeLiveDesc(ns, len(flat), _vp(slot.ctypes.data), _vp(data.ctypes.data), _vp(off.ctypes.data), _vp(start.ctypes.data),
+                            _vp(cl.ctypes.data), _vp(gran.ctypes.data))
+        return dict(desc=d, keep=(data, off, start, slot, cl, gran), nstreams=ns, npackets=len(flat))
+
+    def run(self, prep, pcm=None):
+        """vamd_decode_live_plan + vamd_decode_live_wrote over prepare()'s descriptor; pcm and the result as
+        Analyzer.decode_run's: (pcm, frames, offset, status)"""
+        an, h = self.an, self.h
+        an._need(h is not None, "live decoder: closed")
+        return an._decode_run(lambda _, *a: an.L.vamd_decode_live_plan(h, *a), lambda _, *a: an.L.vamd_decode_live_wrote(h, *a), prep, pcm)
+
+    def write(self, slots, pieces, close=(), end_granules=None, with_status=False):
+        """The next piece of each named slot's stream -> a list of float32 tensors [ch, frames] on the context's device, one
+        per slot of the call; a dead stream -- one that has held a flagged packet -- gives [ch, 0] until a piece closes it.
+        with_status, also the status bytes (numpy uint8).  See prepare() for the arguments."""
+        return self.an._decoded_tensors(len(slots), *self.run(self.prepare(slots, pieces, close, end_granules)), with_status)
 
 
 def decode(setup_blob, streams, granules=None, with_status=False, device=None):

@@ -429,4 +429,35 @@ VAMD_DEV float lap_sample(const LapP &L, long long k, long long at, int c) {
   return B[d + i];
 }
 
+// ---- the lap across pieces: a continuing stream's last block, carried between calls (vamd_decode_live.h) --------------------
+// lap_sample reads, of the block in front, its second half and its size class.  A live decoder keeps that half per slot
+// in `carry` ([slots][ch][bs1/2]; a short block's half fills the front of its row) and, in the next call, stands it in an
+// extra row of its size class behind the rows k_synth wrote, so that the lap above runs on the call's plan as on any other.
+struct CarryRow {
+  int slot, W, row;  // the slot's row of `carry`; the size class; the block's row in that class's synth buffer
+};
+struct CarryP {
+  int ch, bs0, bs1;
+  float *carry;
+  float *synth0, *synth1;  // [rows of the class][ch][bs]
+};
+VAMD_DEV float *carry_slot_half(const CarryP &P, const CarryRow &r, int c) { return P.carry + ((size_t)r.slot * P.ch + c) * (size_t)(P.bs1 >> 1); }
+VAMD_DEV float *carry_block_half(const CarryP &P, const CarryRow &r, int c) {
+  const int n = r.W ? P.bs1 : P.bs0;
+  return (r.W ? P.synth1 : P.synth0) + ((size_t)r.row * P.ch + c) * (size_t)n + (n >> 1);
+}
+// channel c of a continuing stream: the slot's carried half into the second half of the stream's extra row.  The row's
+// first half is never read (lap_sample reads A from na/2 on, and an extra row is only ever an A) and is left as it is.
+VAMD_DEV void decode_carry_in(const CarryP &P, const CarryRow &r, int c) {
+  const F4 *src = (const F4 *)carry_slot_half(P, r, c);
+  F4 *dst = (F4 *)carry_block_half(P, r, c);
+  TEAM_FOR(i, (r.W ? P.bs1 : P.bs0) >> 3) dst[i] = src[i];
+}
+// channel c of a stream that goes on: the second half of its last block's row into the slot's carry
+VAMD_DEV void decode_carry_out(const CarryP &P, const CarryRow &r, int c) {
+  const F4 *src = (const F4 *)carry_block_half(P, r, c);
+  F4 *dst = (F4 *)carry_slot_half(P, r, c);
+  TEAM_FOR(i, (r.W ? P.bs1 : P.bs0) >> 3) dst[i] = src[i];
+}
+
 }  // namespace vamd

@@ -7,6 +7,8 @@
 // The Ogg entry (vamd_decode_ogg_plan, vamd_decode_ogg) takes whole files instead: the host walks their page headers and
 // lacing tables (vamd_demux.h), the files go up in one copy as they lie, and k_ogg_depage (k_demux.h) checks every page's
 // checksum and moves the audio bytes into the same packed arena -- from k_unpack on the two entries are one function.
+// The live decoder (vamd_decode_live.h) takes the next pieces of continuing streams through the same function, with the
+// blocks carried between pieces standing in the plan and two carry kernels between k_synth and k_lap (DecodeCarry).
 //
 // Workspace per block, in the context, grown on demand and released with it (ch channels, n the block's size, S submaps):
 //   rows     4 ch (post_valid) + ch n/2 (the integer curves) + S * 2048 (res_class) + 2 * vamd_residue_capacity
@@ -17,6 +19,7 @@
 // -- for a stereo block of 2048 some 29 KiB, of which vb->pcm is 16.
 #pragma once
 #include "vamd_decode_plan.h"
+#include "vamd_decode_live_plan.h"
 #include "vamd_demux.h"
 
 static_assert(OGG_DEPAGE_BADCRC == VAMD_STATUS_BADPAGE, "k_ogg_depage's status byte is the stream's");
@@ -102,12 +105,25 @@ struct DecodeInput {
   int64_t files_bytes = 0;
 };
 
-// The tail both entries share, behind a plan that holds and statuses the host has already set: workspace, the plan's
+// What a live decoder's call adds (vamd_decode_live.h): the plan's lists of the blocks that have a packet, the carry
+// kernels' tables, and the slots' carries on the device.
+struct DecodeCarry {
+  const DecodeLivePlan *plan = nullptr;
+  float *carry = nullptr;
+};
+
+// The tail all entries share, behind a plan that holds and statuses the host has already set: workspace, the plan's
 // upload, the arena (uploaded, or unpaged on the device), k_unpack, k_synth, k_lap, and the statuses back in one copy --
-// the blocks' and, behind them, the pages' -- folded into their streams.
-static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const DecodeInput &in, const int64_t *offset_out, float *pcm, uint8_t *status) {
+// the blocks' and, behind them, the pages' -- folded into their streams.  With `live`, P is live->plan->P: order[] holds
+// carried blocks that have no packet, k_unpack takes the plan's own list, and the carries move between k_synth and k_lap;
+// without, nothing is enqueued or uploaded that was not before.
+static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const DecodeInput &in, const int64_t *offset_out, float *pcm, uint8_t *status,
+                      const DecodeCarry *live = nullptr) {
   int r;
-  const size_t nb = P.order.size(), npg = in.scan ? in.scan->pages.size() : 0;
+  const std::vector<int32_t> &unpack = live ? live->plan->unpack : P.order;
+  const std::vector<int64_t> &unpack_start = live ? live->plan->unpack_start : P.lap_start;
+  const size_t nb = unpack.size(), nlap = P.order.size(), npg = in.scan ? in.scan->pages.size() : 0;
+  const size_t nin = live ? live->plan->in.size() : 0, nout = live ? live->plan->out.size() : 0;
   if (!nb && !npg) return VAMD_OK;
   vamd_ctx::Decode &D = c->dec;
   const int ch = c->B.channels;
@@ -126,22 +142,27 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
     if ((r = dev_need(c, D.res_class[W], n * S * VAMD_RES_CLASS_STRIDE * 4 + 16))) return r;
     if ((r = dev_need(c, D.res_entries[W], n * (size_t)c->B.res_cap[W] * 2 + 16))) return r;
     if ((r = dev_need(c, D.res_count[W], n * S * 8 + 16))) return r;
-    if ((r = dev_need(c, D.synth[W], n * ch * n2 * 8 + 16))) return r;
+    if ((r = dev_need(c, D.synth[W], (n + (size_t)P.extra[W]) * ch * n2 * 8 + 16))) return r;
     rows[W].post_valid = (int *)D.post_valid[W].p, rows[W].ilogmask = (ilog_t *)D.ilogmask[W].p, rows[W].res_class = (int *)D.res_class[W].p;
     rows[W].res_entries = (unsigned short *)D.res_entries[W].p, rows[W].res_count = (int *)D.res_count[W].p;
     src[W].nb = (long)n, src[W].post_valid = rows[W].post_valid, src[W].ilogmask = rows[W].ilogmask, src[W].res_class = rows[W].res_class;
     src[W].res_entries = rows[W].res_entries, src[W].res_count = rows[W].res_count;
   }
   // the plan, one piece: order | stream_start | src per size class | the packets' bits | frames | offset_out | the page table
+  // | a live call's list for k_unpack and its two carry tables
   Arena a;
-  const size_t o_order = a.take(4 * nb), o_start = a.take(8 * ((size_t)ns + 1)), o_src0 = a.take(8 * P.src[0].size() + 8),
+  const size_t o_order = a.take(4 * nlap), o_start = a.take(8 * ((size_t)ns + 1)), o_src0 = a.take(8 * P.src[0].size() + 8),
                o_src1 = a.take(8 * P.src[1].size() + 8), o_bits = a.take(16 * nb), o_frames = a.take(8 * (size_t)ns), o_off = a.take(8 * (size_t)ns),
-               o_pages = a.take(sizeof(OggDepage) * npg);
+               o_pages = a.take(sizeof(OggDepage) * npg), o_unpack = live ? a.take(4 * nb) : o_order, o_in = a.take(sizeof(CarryRow) * nin),
+               o_out = a.take(sizeof(CarryRow) * nout);
   const size_t plan_bytes = a.at, o_status = a.take(nb + npg);
   if ((r = pinned_get(c, D.h_plan, a.at, true))) return r;
   if ((r = dev_need(c, D.plan, plan_bytes))) return r;
   unsigned char *h = (unsigned char *)D.h_plan.p, *dp = (unsigned char *)D.plan.p;
-  if (nb) memcpy(h + o_order, P.order.data(), 4 * nb);
+  if (nlap) memcpy(h + o_order, P.order.data(), 4 * nlap);
+  if (live && nb) memcpy(h + o_unpack, unpack.data(), 4 * nb);
+  if (nin) memcpy(h + o_in, live->plan->in.data(), sizeof(CarryRow) * nin);
+  if (nout) memcpy(h + o_out, live->plan->out.data(), sizeof(CarryRow) * nout);
   memcpy(h + o_start, P.lap_start.data(), 8 * ((size_t)ns + 1));
   if (!P.src[0].empty()) memcpy(h + o_src0, P.src[0].data(), 8 * P.src[0].size());
   if (!P.src[1].empty()) memcpy(h + o_src1, P.src[1].data(), 8 * P.src[1].size());
@@ -167,12 +188,20 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
   if (nb) {
     hipLaunchKernelGGL(k_unpack, dim3((unsigned)((nb + lanes - 1) / lanes)), dim3(64), (size_t)VAMD_POSIT * lanes * 4, s, (const Bound *)c->d_bound, D.U, lanes, (long)nb,
                        (const uint32_t *)D.bytes.p, nwords,
-                       (const long long *)(dp + o_bits), (const int *)(dp + o_order), c->B.res_cap[0], c->B.res_cap[1], c->d_dbg ? c->d_dbg + 56 : nullptr,
+                       (const long long *)(dp + o_bits), (const int *)(dp + o_unpack), c->B.res_cap[0], c->B.res_cap[1], c->d_dbg ? c->d_dbg + 56 : nullptr,
                        rows[0], rows[1], (unsigned char *)D.status.p);
     HIP_TRY(c, hipGetLastError());
   }
   for (int W = 0; W < 2; W++)
     if (src[W].nb > 0 && (r = launch_synth(c, W, src[W], (float *)D.synth[W].p))) return r;
+  if (nin || nout) {
+    CarryP C;
+    C.ch = ch, C.bs0 = c->B.bs[0], C.bs1 = c->B.bs[1];
+    C.carry = live->carry, C.synth0 = (float *)D.synth[0].p, C.synth1 = (float *)D.synth[1].p;
+    if (nin) hipLaunchKernelGGL(k_decode_carry_in, dim3((unsigned)std::min<size_t>(nin * ch, 256)), dim3(64), 0, s, C, (const CarryRow *)(dp + o_in), (long)nin);
+    if (nout) hipLaunchKernelGGL(k_decode_carry_out, dim3((unsigned)std::min<size_t>(nout * ch, 256)), dim3(64), 0, s, C, (const CarryRow *)(dp + o_out), (long)nout);
+    HIP_TRY(c, hipGetLastError());
+  }
   if (P.max_frames > 0) {
     LapP L;
     L.ch = ch, L.bs0 = c->B.bs[0], L.bs1 = c->B.bs[1];
@@ -188,7 +217,7 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
   HIP_TRY(c, hipMemcpyAsync(h + o_status, D.status.p, nb + npg, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   for (int64_t st = 0; st < ns; st++)
-    for (int64_t k = P.lap_start[(size_t)st]; k < P.lap_start[(size_t)st + 1]; k++) status[st] |= h[o_status + (size_t)k];
+    for (int64_t k = unpack_start[(size_t)st]; k < unpack_start[(size_t)st + 1]; k++) status[st] |= h[o_status + (size_t)k];
   for (size_t k = 0; k < npg; k++) status[in.scan->pages[k].stream] |= h[o_status + nb + k];
   return VAMD_OK;
 }

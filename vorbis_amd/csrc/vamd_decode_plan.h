@@ -136,6 +136,9 @@ struct DecodePlan {
   std::vector<int64_t> lap_start;  // [nstreams + 1] into order[]
   std::vector<int64_t> src[2];     // [nblocks[W]] the block's first sample; a stream's first centre is 0
   std::vector<int64_t> packet;     // [blocks] the packet of each block of order[]
+  // (a live decoder's plan, vamd_decode_live_plan.h, also holds carried blocks in order[], lap_start and src[W] -- extra[W]
+  // rows behind the nblocks[W] unpacked ones -- and names the blocks that have a packet in lists of their own)
+  int64_t extra[2] = {0, 0};
   std::vector<int64_t> frames;     // [nstreams]
   std::vector<uint8_t> status;     // [nstreams] what the packets' heads already tell: such a stream has no blocks
   int64_t max_frames = 0;
@@ -151,15 +154,12 @@ inline int decode_packet_class(const uint8_t *p, int64_t len, int modes, int mod
   return modes > 1 ? mode : 0;
 }
 
-// -> false with a reason for a bad descriptor.  end_granule: NULL, or per stream the last packet's granule position
-// (-1: none): the frames the stream's last block adds are cut to it, as vorbis_synthesis_blockin does for a stream that
-// began at granule 0 (lib/block.c:906-935; never by more than that block adds).  first: NULL, or per packet its first byte --
-// a caller whose packets are not yet together anywhere (vamd_demux.h: they lie in pages, and the packed arena exists on
-// the device alone) hands the mode bits over this way, and `bytes` is not read.
-inline bool decode_plan_build(const int bs[2], int modes, int modebits, int64_t nstreams, int64_t npackets, const uint8_t *bytes,
-                              const int64_t *offset, const int64_t *stream_start, const int64_t *end_granule, DecodePlan *P, std::string *err,
-                              const uint8_t *first = nullptr) {
-  *P = DecodePlan();
+// the frames between the centres of two neighbouring blocks of size classes lW and W (lib/block.c:840-842)
+inline int64_t decode_step(const int bs[2], int lW, int W) { return bs[lW] / 4 + bs[W] / 4; }
+
+// what every packet descriptor must hold (vamd_decode_desc, vamd_decode_live_desc) -> false with a reason
+inline bool decode_desc_check(int64_t nstreams, int64_t npackets, const uint8_t *bytes, const int64_t *offset, const int64_t *stream_start,
+                              const int64_t *end_granule, const uint8_t *first, std::string *err) {
   if (nstreams < 0 || npackets < 0) return *err = "decode: negative stream or packet count", false;
   if (!offset || !stream_start) return *err = "decode: null offset / stream_start", false;
   if (offset[0] < 0) return *err = "decode: negative packet offset", false;
@@ -172,6 +172,19 @@ inline bool decode_plan_build(const int bs[2], int modes, int modebits, int64_t 
     if (stream_start[s + 1] < stream_start[s]) return *err = "decode: stream_start is not monotone", false;
     if (end_granule && end_granule[s] < -1) return *err = "decode: a granule position below -1", false;
   }
+  return true;
+}
+
+// -> false with a reason for a bad descriptor.  end_granule: NULL, or per stream the last packet's granule position
+// (-1: none): the frames the stream's last block adds are cut to it, as vorbis_synthesis_blockin does for a stream that
+// began at granule 0 (lib/block.c:906-935; never by more than that block adds).  first: NULL, or per packet its first byte --
+// a caller whose packets are not yet together anywhere (vamd_demux.h: they lie in pages, and the packed arena exists on
+// the device alone) hands the mode bits over this way, and `bytes` is not read.
+inline bool decode_plan_build(const int bs[2], int modes, int modebits, int64_t nstreams, int64_t npackets, const uint8_t *bytes,
+                              const int64_t *offset, const int64_t *stream_start, const int64_t *end_granule, DecodePlan *P, std::string *err,
+                              const uint8_t *first = nullptr) {
+  *P = DecodePlan();
+  if (!decode_desc_check(nstreams, npackets, bytes, offset, stream_start, end_granule, first, err)) return false;
   P->frames.assign((size_t)nstreams, 0);
   P->status.assign((size_t)nstreams, 0);
   P->lap_start.assign((size_t)nstreams + 1, 0);
@@ -190,7 +203,7 @@ inline bool decode_plan_build(const int bs[2], int modes, int modebits, int64_t 
       int64_t at = 0, step = 0;
       for (int64_t p = p0; p < p1; p++) {
         const int W = cls[(size_t)(p - p0)];
-        step = p > p0 ? bs[cls[(size_t)(p - p0 - 1)]] / 4 + bs[W] / 4 : 0;  // lib/block.c:840-842
+        step = p > p0 ? decode_step(bs, cls[(size_t)(p - p0 - 1)], W) : 0;
         at += step;
         if (P->nblocks[W] >= (1 << 30)) return *err = "decode: more than 2^30 blocks of a size class", false;
         P->order.push_back((int32_t)(W << 30) | (int32_t)P->nblocks[W]++);

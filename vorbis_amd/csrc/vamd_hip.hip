@@ -43,6 +43,7 @@
 #include "k_synth.h"
 #include "k_unpack.h"
 #include "vamd_decode_plan.h"
+#include "vamd_decode_live_plan.h"
 #define VAMD_OGG_NO_FEED_KERNELS  // (k_ogg.h: k_ogg_plan / _pages / _carry are vamd_feed.hip's)
 #include "vamd_demux.h"
 
@@ -301,6 +302,7 @@ int vamd_envelope_geometry(const vamd_ctx *c, int *winlength, int *searchstep) {
 
 #include "vamd_batch.h"  // workspace planning, the launch sequence, the batch entry points
 #include "vamd_decode.h" // the packet decoder: plan on the host, k_unpack ahead of k_synth and k_lap
+#include "vamd_decode_live.h"  // ... and continuing streams in pieces: the lap carried between calls
 #include "vamd_plan.h"   // the detector over streams, the walk, the plans
 #include "vamd_block.h"  // the host-pointer calls: a block, a look-ahead's blocks, a detector call
 

@@ -1711,6 +1711,16 @@ __global__ __launch_bounds__(256) void k_lap(LapP L, long nstreams, const long l
   }
 }
 
+// The live decoder's carries (k_synth.h, "the lap across pieces"): a workgroup per (row of the table, channel), striding
+// over the pairs; a wave's lanes move 16 bytes each.  k_decode_carry_in before k_lap, k_decode_carry_out behind k_synth,
+// in-before-out on one stream: a slot may be read and written in one call.
+__global__ __launch_bounds__(64) void k_decode_carry_in(CarryP P, const CarryRow *__restrict__ rows, long nrows) {
+  for (long p = blockIdx.x; p < nrows * P.ch; p += gridDim.x) decode_carry_in(P, rows[p / P.ch], (int)(p % P.ch));
+}
+__global__ __launch_bounds__(64) void k_decode_carry_out(CarryP P, const CarryRow *__restrict__ rows, long nrows) {
+  for (long p = blockIdx.x; p < nrows * P.ch; p += gridDim.x) decode_carry_out(P, rows[p / P.ch], (int)(p % P.ch));
+}
+
 // ---- the decoder's front half (k_unpack.h) ----
 // One lane per packet, `lanes` <= 64 packets a wave (the other lanes idle: with fewer packets a wave there are more waves
 // to hide a lane's dependent loads behind): block k of order[] (W << 30 | index inside W's batch) is unpacked from bits
