@@ -4,8 +4,8 @@ The floor stage (k_floor, k_floor_pair: k_floor.inc) takes the tone fold, the ma
 floor1_encode in one wave per channel-block.  What it leaves -- mdct (scaled in place), logmask, posts, post_valid,
 nonzero -- and what the next stage makes of its curve (iwork) are compared with tests.checker's tap_block for all the
 blocks of the batch: the stage's tables are fetched once per channel-block and handed from the fit to the quantiser to
-the curve (VAMD_FL_TABLES_ONCE), and its table and tensor accesses go through one 32-bit offset per quad
-(VAMD_FL_GLOBAL_ADDR), so a wrong table, offset or hand-over shows in whichever block it hits.
+the curve (PostTables), and its table and tensor accesses go through one 32-bit offset per quad
+(dm_load / dm_store), so a wrong table, offset or hand-over shows in whichever block it hits.
 
 Setups: the bench's (44k_stereo_q4), one whose short blocks have 19 posts and pair their channels in a wave (q9,
 k_floor_pair from VAMD_FLOOR_PAIR_MIN channel-blocks), an odd channel count (mono) and two submaps with a floor each

@@ -3,7 +3,7 @@ by, every output of the floor stage against the CPU checker, bit for bit, for EV
 
 Beside tests/test_floor_paths.py (seeded noise, a silent block, a spike, two tones).  inspect_error_wave ends its walk
 with the first chunk of 64 points (32 on the pair path) that holds a failing point (VAMD_FL_INSPECT_STOP), and
-fit_line_pair forms a side's two quotients in two lanes (VAMD_FL_FIT_LANES); the signals of tests/floor_split_signals.py
+fit_line_pair forms the two sides' fits in two groups of lanes; the signals of tests/floor_split_signals.py
 say which exit each is there for: the failure in the first chunk (noise), in the LAST chunk of the whole range and of the
 right-hand ranges (band_top), walks that run to their end (faint, band_low's left-hand ranges), no loop at all (silent),
 many splits with short ranges and sides without a fit (tones, six_sines), and stereo blocks whose channels differ, so

@@ -1,9 +1,9 @@
 """GPU suite (-m gpu): the 2048-sample transform against the CPU checker, with logfft tapped and untapped.
 
 Where logfft itself is not tapped, k_transform<11> may form it inside the FFT's last trip and keep only its run peaks
-and local_ampmax (VAMD_XF_TAIL_LOGFFT); a tapped logfft always takes the hand-over through LDS.  That is the only thing
-in which the two runs can differ, so their bit-for-bit equality checks that one switch.  Every other choice of the
-kernel's build (VAMD_XF_OUT_REGS, VAMD_XF_P123_REGS, VAMD_XF_HEAD_REGS) is taken in both runs alike and is checked by
+and local_ampmax (xf_tail_fused, k_transform.h); a tapped logfft always takes the hand-over through LDS.  That is the only
+thing in which the two runs can differ, so their bit-for-bit equality checks that one choice.  Everything else of the size's
+path (the spectrum out of registers, FFT passes 1 + 2 -> 3 and the MDCT's head in registers) is taken in both runs alike and is checked by
 the CPU checker alone, which shares no code with the kernels; so is vamd_mdct_forward_batch at 2048.
 
 A persistent wave takes channel-blocks a stride apart (workgroups x waves: 2048 channel-blocks = 1024 stereo blocks

@@ -6,7 +6,9 @@ export VAMD_TEST_KNOBS=1  # the knobs below are test knobs: ignored without this
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 python -c "import bench; print('# source_hash', bench.source_hash())"
-run() { echo "== $*"; env "$@" timeout 900 python -m pytest tests -m gpu -q -x 2>&1 | tail -2; }
+# (each run under its own time limit; a run that fails or is cut off ends the script: nothing is started on the GPU after it)
+set -o pipefail
+run() { echo "== $*"; env "$@" timeout -k 10 900 python -m pytest tests -m gpu -q -x 2>&1 | tail -2 || exit 1; }
 run VAMD_MASKS_SEPARATE=1 VAMD_PACK_PAIR_MAX=0 VAMD_RES_TEAM_MAX=0
 run VAMD_CHASE_WAVE_MAX=0 VAMD_NO_OVERLAP=1
 run VAMD_STAGE_COPIES=1 VAMD_FOLD_SEPARATE=1

@@ -7,7 +7,7 @@ them (-Rpass-analysis=kernel-resource-usage), one line per kernel whose demangle
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pat = re.compile(sys.argv[1] if len(sys.argv) > 1 else ".")
-extra = [x for x in sys.argv[2:] if not x.startswith("--unit=")]   # further compiler flags, e.g. -DVAMD_NOISE_NO_PREFETCH
+extra = [x for x in sys.argv[2:] if not x.startswith("--unit=")]   # further compiler flags, e.g. -DVAMD_CHASE_PREFETCH=1
 unit = ([x[7:] for x in sys.argv[2:] if x.startswith("--unit=")] or ["vamd_hip"])[0]   # --unit=vamd_feed: the feed's kernels (k_ogg.h)
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vorbis_amd", "csrc"),

@@ -25,46 +25,23 @@ namespace vamd {
 
 #define VAMD_MAXPOSTS 32
 
-// ---- round 12: what a wave used to redo for every channel-block although it depends on the setup alone ----------------
-// (profiles/r12_floor_phases.txt; each switch can be turned the other way with -D...=0 for an A/B of its own)
-//   * VAMD_FL_TABLES_ONCE: one set of post tables per channel-block (PostTables), handed from the fit to the quantiser
-//     to the curve; every stage used to fetch its own.
-//   * VAMD_FL_GLOBAL_ADDR (vamd_wave.h): the tables behind PsyP / FloorP addressed as device memory.
-//   * VAMD_FL_SEG_ROLLED: the fit's work-list loop rolled (floor_fit_posts): no value spilt to scratch round it.
-//   * VAMD_FL_OFFSET_AHEAD: fold_and_mix_wave asks for a quad's noise offsets together with its noise and spectrum.
-// Same arithmetic on the same operands; only where an operand comes from changes.
-#ifndef VAMD_FL_TABLES_ONCE
-#define VAMD_FL_TABLES_ONCE 1
-#endif
-#ifndef VAMD_FL_OFFSET_AHEAD
-#define VAMD_FL_OFFSET_AHEAD 1
-#endif
-#ifndef VAMD_FL_SEG_ROLLED
-#define VAMD_FL_SEG_ROLLED 1
-#endif
-#if !VAMD_GPU
-#define VAMD_FL_SEG_LOOP
-#elif VAMD_FL_SEG_ROLLED
+// What depends on the setup alone is not redone per channel-block (profiles/r12_floor_phases.txt; DESIGN.md "Decided
+// variants"): one set of post tables per channel-block (PostTables), handed from the fit to the quantiser to the curve; the
+// tables behind PsyP / FloorP addressed as device memory (vamd_wave.h); the fit's work-list loop rolled (floor_fit_posts), so
+// that no value is spilt to scratch round it; and fold_and_mix_wave asks for a quad's noise offsets together with its noise and
+// spectrum.
+#if VAMD_GPU
 #define VAMD_FL_SEG_LOOP _Pragma("unroll 1")
 #else
-#define VAMD_FL_SEG_LOOP _Pragma("unroll 4")
+#define VAMD_FL_SEG_LOOP
 #endif
-// ---- round 19: the greedy split loop of floor1_fit (profiles/r19_floor_split.txt; -D...=0 restores the earlier code) ---
-//   * VAMD_FL_INSPECT_STOP: inspect_error_wave asks after every chunk of NLANES points whether a point of it failed the
-//     over / under test and returns 1 there, as the reference's inspect_error does at the point itself
-//     (lib/floor1.c:537-538); it used to walk the whole range and ask once.  A call without a failing point runs every
-//     trip and reaches the count thresholds and the mse sum as before.
-//   * VAMD_FL_FIT_LANES (off): fit_line_pair's two fp64 quotients of a side, aa and bb, formed side by side in two lanes --
-//     one division expansion a call where every lane of a group evaluates both -- and handed over with one DPP shift per
-//     word before rint(aa + bb * x).  The same IEEE divisions on the same operands, and the same results on the GPU; the
-//     stage gained 0.018 ms with it alone, inside three spreads of the parent, and nothing beside the early stop, so it
-//     stays at 0 with its figures in the profile file.
-// Which lane evaluates an expression and how many trips run after the outcome is settled: no expression changes.
+// VAMD_FL_INSPECT_STOP (profiles/r19_floor_split.txt; -D...=0 restores the earlier code, which tests/test_floor_inspect_cases.py
+// holds beside this one): inspect_error_wave asks after every chunk of NLANES points whether a point of it failed the over /
+// under test and returns 1 there, as the reference's inspect_error does at the point itself (lib/floor1.c:537-538); it used to
+// walk the whole range and ask once.  A call without a failing point runs every trip and reaches the count thresholds and the
+// mse sum as before.  How many trips run after the outcome is settled: no expression changes.
 #ifndef VAMD_FL_INSPECT_STOP
 #define VAMD_FL_INSPECT_STOP 1
-#endif
-#ifndef VAMD_FL_FIT_LANES
-#define VAMD_FL_FIT_LANES 0
 #endif
 // scratch builds for the phase profile (tools/fl_phases_pmc.sh): -DVAMD_COUNT_CALLS turns the stopwatch's slots into event
 // counters, summed over the waves -- slot 0 inspect_error_wave calls, slot 1 fit_line_pair calls of the split loop (= calls

@@ -98,13 +98,9 @@ VAMD_DEV void fold_and_mix_wave(const PsyP &P, float att, const float *seed, con
     const unsigned int qo = (unsigned)q << 4;  // the quad's byte offset in every float stream
     f4_get(dm_load_f4(noise, qo), nz);
     f4_get(dm_load_f4(mdct_io_src, qo), md);
-#if VAMD_FL_OFFSET_AHEAD
     // (asked for here, with the quad's other streams: behind the fold and the tap's store it was waited for on the spot)
     const F4 no4 = dm_load_f4(P.noiseoffset1, qo);
     const F4 *no_ahead = &no4;
-#else
-    const F4 *no_ahead = nullptr;
-#endif
     tone_fold_quad(P, att, seed, gmin, q, tn);
     if (tone_out) dm_store_f4(tone_out, qo, f4_make(tn));
     keep[kq] = offset_and_mix_quad(P, q, nz, tn, md, mk, twofitatten, no_ahead);
@@ -385,7 +381,7 @@ struct PostSteps {
 };
 
 // The look's tables that the fit, the quantiser and the curve of a channel-block share, one post per lane.  They depend on
-// the setup alone: fetched once per channel-block (VAMD_FL_TABLES_ONCE, k_floor.h) and handed from stage to stage -- the
+// the setup alone: fetched once per channel-block and handed from stage to stage -- the
 // list when the fit begins, the rest when its split loop is through (the loop holds a dozen lane arrays of its own) --
 // where each stage used to fetch its own copy.
 VAMD_DEV void load_post_table(LaneInts &t, const int *p, int shift, int count) {  // LaneInts::load_shifted out of the image
@@ -437,44 +433,6 @@ VAMD_DEV void fit_line_pair(const double *term, double *sums, int firstL, int fi
     sums[grp * 8 + q] = acc;
   }
   WAVE_SYNC();
-#if VAMD_FL_FIT_LANES
-  // The two quotients of a side in two lanes: the odd lanes of a group form aa = (yb*x2b - xyb*xb) / denom, the even lanes
-  // bb = (bn*xyb - xb*yb) / denom -- each picks its four operands out of the side's row by index, so the wave issues ONE
-  // division expansion -- and lane 1 (9) takes bb over from lane 0 (8) with a DPP shift per word.  The sides' results are
-  // then lane 1's and lane 9's.
-  const double *row = sums + grp * 8;
-  const bool odd = (LANE & 1) != 0;
-  const double xb = row[0], x2b = row[2], bn = row[4];
-  const double p = row[odd ? 1 : 4], q2 = row[odd ? 2 : 3], r2 = row[odd ? 3 : 0], s2 = row[odd ? 0 : 1];
-  const int x0 = grp ? x0R : x0L, x1 = grp ? x1R : x1L;
-  const double denom = (bn * x2b - xb * xb);
-  double quot = 0.;
-  if (denom > 0.) quot = (p * q2 - r2 * s2) / denom;
-  long long qbits;
-  memcpy(&qbits, &quot, 8);
-  const unsigned int blo = (unsigned int)wave_shift_up1((int)(unsigned int)qbits, 0);
-  const unsigned int bhi = (unsigned int)wave_shift_up1((int)(unsigned int)((unsigned long long)qbits >> 32), 0);
-  const long long bbits = (long long)(((unsigned long long)bhi << 32) | blo);
-  int r = 1, y0 = 0, y1 = 0;
-  if (denom > 0.) {
-    const double aa = quot;  // (an odd lane's)
-    double bb;               // (the even lane's below it)
-    memcpy(&bb, &bbits, 8);
-    y0 = (int)rint(aa + bb * x0);
-    y1 = (int)rint(aa + bb * x1);
-    if (y0 > 1023) y0 = 1023;
-    if (y1 > 1023) y1 = 1023;
-    if (y0 < 0) y0 = 0;
-    if (y1 < 0) y1 = 0;
-    r = 0;
-  }
-  *ret0 = wave_read(r, 1);
-  *ly0 = wave_read(y0, 1);
-  *ly1 = wave_read(y1, 1);
-  *ret1 = wave_read(r, 9);
-  *hy0 = wave_read(y0, 9);
-  *hy1 = wave_read(y1, 9);
-#else
   const double xb = sums[grp * 8], yb = sums[grp * 8 + 1], x2b = sums[grp * 8 + 2], xyb = sums[grp * 8 + 3],
                bn = sums[grp * 8 + 4];
   const int x0 = grp ? x0R : x0L, x1 = grp ? x1R : x1L;
@@ -497,7 +455,6 @@ VAMD_DEV void fit_line_pair(const double *term, double *sums, int firstL, int fi
   *ret1 = wave_read(r, 8);
   *hy0 = wave_read(y0, 8);
   *hy1 = wave_read(y1, 8);
-#endif
   WAVE_SYNC();  // sums[] is rewritten by the next split
 }
 
@@ -819,15 +776,10 @@ VAMD_DEV int floor_fit_render_block(const FloorP &F, int n2, const unsigned shor
                                     int *__restrict__ posts_out, int *__restrict__ post_valid,
                                     ilog_t *__restrict__ ilogmask, PhaseClock &pc, int *__restrict__ wrapped_out = nullptr) {
   LaneInts outp;
-#if VAMD_FL_TABLES_ONCE
   PostTables tb;
   tb.load_list(F);
   const int valid = floor_fit_posts(F, qc, sc, outp, pc, &tb);  // (a fit that returns 0 leaves the rest unloaded: nobody reads it)
   return floor_encode_render(F, n2, outp, valid, sc, posts_out, post_valid, ilogmask, pc, wrapped_out, &tb);
-#else
-  const int valid = floor_fit_posts(F, qc, sc, outp, pc);
-  return floor_encode_render(F, n2, outp, valid, sc, posts_out, post_valid, ilogmask, pc, wrapped_out);
-#endif
 }
 
 // floor1_interpolate_fit, lib/floor1.c:731-750, one post per lane

@@ -96,21 +96,8 @@ VAMD_DEV void seed_curve_scatter(float *seed, const float *__restrict__ band_row
 //             hands over a copy of the unpainted lines instead.
 //   posstack  the survivor list (HBM);  head  its first two chunks as fetched ahead by surv_head_load (optional)
 //
-// ---- round 17: max_seeds' fold by groups (profiles/r17_tone_fold_groups.txt; each switch can be turned the other way
-// with -D...=0 / =1 for an A/B of its own, the tables are derived in both forms) ------------------------------------------
-//   * VAMD_TF_MIN_RUNS (on): the groups' minima from runs of VAMD_TF_RUN_LINES (4 or 8) consecutive lines per lane, one
-//     LDS float min per group a run touches, instead of one per line.
-//   * VAMD_TF_GROUP_FOLD (off): max_seeds' start value, cap and compares once per group; a bin looks its group's value up.
-// Same compares and selects on the same operands; a min is order-free.
-#ifndef VAMD_TF_MIN_RUNS
-#define VAMD_TF_MIN_RUNS 1
-#endif
-#ifndef VAMD_TF_RUN_LINES
-#define VAMD_TF_RUN_LINES 8
-#endif
-#ifndef VAMD_TF_GROUP_FOLD
-#define VAMD_TF_GROUP_FOLD 0  // measured slower than the per-bin form it replaces (a phase more, behind a table fetch): off
-#endif
+// max_seeds' fold by groups: the consecutive lines a lane folds into its groups' minima (tone_group_minima; 4 or 8)
+constexpr int TONE_RUN_LINES = 8;
 // the smaller of two real seed values (> VAMD_NEGINF, +inf allowed, no NaN): the median of the two and a value below
 // both, one instruction -- fminf() quiets signalling NaNs first (three), a compare and a select are two
 #if VAMD_GPU
@@ -131,18 +118,17 @@ VAMD_DEV float tone_min(float a, float b) { return b < a ? b : a; }
 //   seeds   this block's seed[] (HBM, read 32 lines -- a cache line -- at a time)
 //   surv    out: surviving line indices, ascending (uint16), returns their count
 //
-// ---- round 21: the walk's share of a CU beside the noise mask (profiles/r21_chase_ring.txt) ------------------------------
-// k_tone_chase runs beside k_noise's persistent teams and its speed there follows the waves it has resident.  Two switches
-// decide how many fit, each with the parent's form at its other setting:
-//   * VAMD_CHASE_RING (8; 16 as before): slots of the ring where linesper <= 8 -- every libvorbisenc setup; longer windows
-//     always have VAMD_RING = 16, which is also what a caller that does not know linesper sizes a ring for.  Eight slots of
-//     (amplitude, position) are 4 KB a wave of 64 walks where sixteen are 8.
+// k_tone_chase runs beside k_noise's persistent teams and its speed there follows the waves it has resident
+// (profiles/r21_chase_ring.txt; DESIGN.md "Decided variants"):
+//   * VAMD_CHASE_RING: slots of the ring where linesper <= 8 -- every libvorbisenc setup; longer windows always have
+//     VAMD_RING = 16, which is also what a caller that does not know linesper sizes a ring for.  Eight slots of (amplitude,
+//     position) are 4 KB a wave of 64 walks where sixteen are 8.
 //   * VAMD_CHASE_PREFETCH (0; 1 as before): a row's next 32 lines in flight while 32 are walked.  That is 64 registers of row
 //     data and a kernel of 94 VGPRs -- one wave a SIMD in the 128 that six noise teams leave; without it the kernel has 62
 //     and two fit.  A lane still asks for whole 128-byte lines, once each; what the prefetch hid is now hidden by the other
-//     resident waves (215 k wave cycles alone against 205 k).
+//     resident waves.
 // Beside six teams (8 wave slots, 40 KB, 128 VGPRs a SIMD) that makes 8 walk waves a CU where there were 4, and six teams
-// are then ahead of five (vamd_batch.h: noise_teams_per_cu).  Either switch alone loses.
+// are then ahead of five (vamd_batch.h: noise_teams_per_cu).
 //
 // Why RING = linesper slots are enough, although the slot of index k is written again by index k + RING while entry k may
 // still be on the stack.  Positions on the stack are distinct and ascending, so when index k + RING is written, at line L,
@@ -157,16 +143,13 @@ VAMD_DEV float tone_min(float a, float b) { return b < a ? b : a; }
 // chase_chunk's window() from reaching a reused slot: it walks down from the top and stops at entry k+1, which is out of
 // its window.
 #define VAMD_RING 16
-#ifndef VAMD_CHASE_RING
 #define VAMD_CHASE_RING 8
-#endif
 #ifndef VAMD_CHASE_GUARD
 #define VAMD_CHASE_GUARD 0
 #endif
 #ifndef VAMD_CHASE_PREFETCH
 #define VAMD_CHASE_PREFETCH 0
 #endif
-static_assert(VAMD_CHASE_RING == 8 || VAMD_CHASE_RING == VAMD_RING, "VAMD_CHASE_RING is 8 or 16");
 // slots of the ring for windows of `linesper` lines
 constexpr int chase_ring_slots(int linesper) { return linesper <= 8 ? VAMD_CHASE_RING : VAMD_RING; }
 template <int RING>
@@ -417,7 +400,7 @@ VAMD_DEV ChaseChunk chase_chunk_regs(const float *seeds, int n, int s, int e, in
   return out;
 }
 
-// ---- round 24: the whole-block walk on the same state (profiles/r24_chase_regs.txt) --------------------------------------
+// ---- the whole-block walk on the same state (profiles/r24_chase_regs.txt): the lane-per-block kernel's where linesper is 8
 // tone_chase_ring's job -- one lane walks a block's row from line 0 and writes the survivor list -- with chase_chunk_regs'
 // state: no ring, no LDS.  What the ring walk waited for were its trips to LDS inside the dependent chain (two reads that
 // end every pop, a read-back before an index's first write, two stores per push), taken by 64 lanes at the pace of the
@@ -428,10 +411,6 @@ VAMD_DEV ChaseChunk chase_chunk_regs(const float *seeds, int n, int s, int e, in
 // mask go out oldest first.  Rows are read, and survivors stored, exactly as tone_chase_ring does (whole 128-byte lines,
 // 32 lines a trip, eight positions per 16-byte store, the last one to seven singly): list and count are byte for byte
 // the ring walk's (tests/c/chase_regs_cases.cpp).
-//   VAMD_CHASE_REGS (1; 0 = the ring walk, as before): the walk of the lane-per-block kernel where linesper is 8
-#ifndef VAMD_CHASE_REGS
-#define VAMD_CHASE_REGS 1
-#endif
 template <int LP>
 VAMD_DEV int tone_chase_regs(const float *__restrict__ seeds, int n, unsigned short *__restrict__ surv) {
   constexpr int WN = LP - 1;
@@ -492,14 +471,12 @@ VAMD_DEV int tone_chase_regs(const float *__restrict__ seeds, int n, unsigned sh
 }
 // does the lane-per-block kernel take it, for a size class whose two block types have these parameters?  (host)
 inline bool chase_walk_regs(const PsyP &P0, const PsyP &P1) {
-  return VAMD_CHASE_REGS && P0.eighth_octave_lines == 8 && P1.eighth_octave_lines == 8;
+  return P0.eighth_octave_lines == 8 && P1.eighth_octave_lines == 8;
 }
 
 #define VAMD_CHASE_CHUNKS 64  // chunks per block = lanes of the wave
-#ifndef VAMD_CHASE_WARM
 #define VAMD_CHASE_WARM 2    // cold start this many windows (linesper) before a chunk: one needs a repair round every time,
                              // two in one block out of thirty, three or four never (measured on the host; 16 + 20 lines walked)
-#endif
 // What the chunks of one block add up to: accepted iff every chunk entered in its predecessor's exit state
 // (k_tone_chase_wave runs chase_chunk one per lane and combines with wave operations; tests/emul/emul.cpp walks the same
 // chunks one after the other and compares with the serial walk).

@@ -62,22 +62,16 @@ VAMD_DEV void seed_chase_paint(float *seeds, const float *src, int linesper, int
 // order-free -- and every bin the iteration covers takes that value.  Static tables (vamd_derive.h):
 //   line_slot[line]  the group whose scan covers the line (`ngroups` where none does), as a byte offset into gmin[]
 //   bin_fold[bin]    p0 | group << 16 (bins below tail_linpos; the bins of the tail loop, :539-543, take seed[nlines - 1])
-//   group_p0[g]      the line group g starts from; g = ngroups stands for the bins of the tail loop
-//   bin_group[bin]   a bin's group, 16 bits
+// (group_p0, bin_group and line_group, which the setup image also holds, are read by no kernel.)
 // gmin[ngroups + 1] (LDS): the groups' scanned minima; slot `ngroups` takes the lines that no group scans.
-//  * VAMD_TF_MIN_RUNS (on): a lane takes VAMD_TF_RUN_LINES consecutive lines, reduces them in registers and sends one LDS
-//    float min per group its run touches (a group's lines are one run, so a change of group ends a segment).  Before,
-//    a lane sent one line: in the low octaves a group spans up to 101 lines, all 64 lanes of an instruction hit one or
-//    two addresses and the LDS unit took them one after the other.  No test for a line without a group: its slot is
-//    nobody's.
-//  * VAMD_TF_GROUP_FOLD (off: fewer instructions, measured slower): start value, cap and the three compares once per
-//    group (315 at 1024 bins) instead of once per bin, stored over gmin[g]; tone_fold_quad is then group_p0 / bin_group
-//    look-ups -- a table load, the ATH quad, four LDS reads, add, max -- and does not read seed[].
-// With a switch at 0 that piece is the per-line / per-bin form it replaces (profiles/r17_tone_fold_groups.txt).
-#if VAMD_TF_MIN_RUNS
-static_assert(VAMD_TF_RUN_LINES == 4 || VAMD_TF_RUN_LINES == 8, "a run is one or two 16-byte LDS reads");
+// A lane takes TONE_RUN_LINES consecutive lines, reduces them in registers and sends one LDS float min per group its run
+// touches (a group's lines are one run, so a change of group ends a segment).  With one line a lane, a group of the low
+// octaves -- up to 101 lines -- has all 64 lanes of an instruction hit one or two addresses, which the LDS unit takes one
+// after the other.  No test for a line without a group: its slot is nobody's.  (profiles/r17_tone_fold_groups.txt; DESIGN.md
+// "Decided variants" for the forms this one was measured against.)
 VAMD_DEV void tone_group_minima(const PsyP &P, const float *seed, float *gmin) {
-  constexpr int R = VAMD_TF_RUN_LINES;
+  constexpr int R = TONE_RUN_LINES;
+  static_assert(R == 4 || R == 8, "a run is one or two 16-byte LDS reads");
   const float inf = f_from_bits(0x7f800000u);
   const int nruns = (P.total_octave_lines + R - 1) / R;  // (seed[] and line_slot[] are padded to whole runs)
   // (two trips of the loop at 777 lines: not unrolled, eight ends of a segment are code enough)
@@ -104,7 +98,6 @@ VAMD_DEV void tone_group_minima(const PsyP &P, const float *seed, float *gmin) {
     }
   }
 }
-#endif
 VAMD_DEV void tone_fold_prepare(const PsyP &P, float *seed, const float *seed_src,
                                 const unsigned short *__restrict__ surv, int nsurv, float *gmin /* LDS [ngroups + 1] */,
                                 PhaseClock &pc, int slot = 3, const SurvHead *head = nullptr) {
@@ -117,51 +110,14 @@ VAMD_DEV void tone_fold_prepare(const PsyP &P, float *seed, const float *seed_sr
   // single lanes
   WAVE_FOR(g, P.ngroups + 1) gmin[g] = f_from_bits(0x7f800000u);  // +inf = "no real value scanned"
   WAVE_SYNC();
-#if VAMD_TF_MIN_RUNS
   tone_group_minima(P, seed, gmin);
-#else
-  WAVE_FOR(p, nlines) {
-    const int g = dm_load<unsigned short>(P.line_group, 2u * (unsigned)p);
-    const float s = seed[p];
-    if (g != 0xffff && s > VAMD_NEGINF) lds_atomic_min(gmin + g, s);
-  }
-#endif
   WAVE_SYNC();
   pc.mark(slot + 1);
-#if VAMD_TF_GROUP_FOLD
-  // what the bins of group g get (a lane reads and writes its own groups' slots only)
-  WAVE_FOR(g, P.ngroups + 1) {
-    float minV = seed[dm_load<int>(P.group_p0, 4u * (unsigned)g)];
-    if (g < P.ngroups) {
-      if (minV > P.tone_abs_limit) minV = P.tone_abs_limit;
-      const float rest = gmin[g];
-      if (rest < f_from_bits(0x7f800000u)) {
-        if (minV == VAMD_NEGINF || rest < minV) minV = rest;
-      }
-    }
-    gmin[g] = minV;
-  }
-  WAVE_SYNC();
-#endif
 }
 VAMD_DEV float tone_ath_att(const PsyP &P, float local_ampmax) {
   float att = local_ampmax + P.ath_adjatt;
   return att < P.ath_maxatt ? P.ath_maxatt : att;
 }
-#if VAMD_TF_GROUP_FOLD
-VAMD_DEV void tone_fold_quad(const PsyP &P, float att, const float *, const float *gmin, int q, float *o) {
-  const unsigned long long gq = dm_load<unsigned long long>(P.bin_group, (unsigned)q << 3);  // the quad's four groups
-  float av[4];
-  f4_get(dm_load_f4(P.ath, (unsigned)q << 4), av);
-#pragma unroll
-  for (int c = 0; c < 4; c++) {
-    const float minV = gmin[(int)(gq >> (16 * c)) & 0xffff];
-    float v = av[c] + att;
-    if (v < minV) v = minV;
-    o[c] = v;
-  }
-}
-#else
 VAMD_DEV void tone_fold_quad(const PsyP &P, float att, const float *seed, const float *gmin, int q, float *o) {
   const int nlines = P.total_octave_lines;
   const I4 bf = dm_load_i4(P.bin_fold, (unsigned)q << 4);
@@ -187,4 +143,3 @@ VAMD_DEV void tone_fold_quad(const PsyP &P, float att, const float *seed, const 
     o[c] = v;
   }
 }
-#endif

@@ -25,12 +25,6 @@
 
 namespace vamd {
 
-// the fold of the size-specialised transform reads whole quads, one trip in flight (mdct_forward_wave); GPU only: the
-// one-lane test build keeps the plain loop
-#ifndef VAMD_XF_FOLD_QUADS
-#define VAMD_XF_FOLD_QUADS 0  // measured round 5 on this build: 1.513 against 1.482 ms (profiles/r05_xf_variants.txt); kept as a variant
-#endif
-
 #define VAMD_XF_A_FLOATS(n) (((n) + ((n) >> 5) + 4 + 3) & ~3)
 #define VAMD_XF_B_FLOATS(n) (((n) + ((n) >> 4) + 4 + 3) & ~3)
 
@@ -237,9 +231,9 @@ VAMD_DEV void fold_fetch(FoldOps<LOGN> &o, const float *in) {
 // its 13 us there, and the kernel sat at the bytes its sixteen waves per CU keep in flight: 3.8 TB/s); the three regimes
 // change at the pairs n/16 and 3n/16, multiples of a wave's stride of 64 for n >= 1024, so which quarters a trip folds is
 // known when it is compiled.  (Round 5: the form used to be taken for n = 512 too, where the regimes change in the
-// middle of a trip -- found by the whole-quad variant below failing the 22 kHz short blocks; no shipped path reached
+// middle of a trip -- found by a whole-quad variant of the fold failing the 22 kHz short blocks; no shipped path reached
 // k_mdct_only at 512, and tests/test_gpu_parity.py::test_mdct_forward_every_size now does.)
-// ---- round 6: the head of the 2048-sample transform without LDS ------------------------------
+// ---- the head of the 2048-sample transform without LDS (head_regs below) -------------------------------------------
 // The stage is bound by the CU's LDS pipe; of the MDCT's six trips through it, two move data that never needs to leave
 // the wave's registers:
 //   * fold -> first butterfly trip.  The fold's item p = LANE + 64 k produces the pair (w2[2p], w2[2p+1]); the trip that
@@ -255,30 +249,18 @@ VAMD_DEV void fold_fetch(FoldOps<LOGN> &o, const float *in) {
 // Same butterflies on the same operands in the same order (the expression trees are the reference's, lib/mdct.c:216-336);
 // only who holds a pair changes.  The second trip stores to LDS as before: the 32-point groups want sixteen consecutive
 // pairs in one lane, a transpose inside rows of sixteen lanes, which the DPP can only do a bit at a time.
-#ifndef VAMD_XF_HEAD_REGS
-#define VAMD_XF_HEAD_REGS 1
-#endif
-// ---- round 11: three more trips of the 2048-sample transform that never needed LDS ------------------------------
-//   * VAMD_XF_OUT_REGS: the bit-reverse item u = LANE + 64 k holds out[u], out[n2-1-u], out[n4-1-u] and out[n2-n4+u] when it
+// ---- three more trips of the 2048-sample transform that never needed LDS (profiles/r11_xf_trips.txt) -----------------
+//   * OUT_REGS: the bit-reverse item u = LANE + 64 k holds out[u], out[n2-1-u], out[n4-1-u] and out[n2-n4+u] when it
 //     has rotated them: four runs of 64 consecutive floats per instruction, two ascending and two descending, each a
 //     whole aligned 256 bytes.  They go to HBM (and, where logmdct is wanted, through todB_345 first) from the registers
 //     that hold them, instead of four 4-byte LDS stores, a sync and the quad reads that fed the 16-byte HBM stores.
-//   * VAMD_XF_TAIL_LOGFFT: the fused last radix-4 + radix-2 pass (fft_tail42_wave) ends in exactly the (Re_k, Im_k) pairs
+//   * the tail's logfft: the fused last radix-4 + radix-2 pass (fft_tail42_wave) ends in exactly the (Re_k, Im_k) pairs
 //     that transform_logfft reloads.  Where nobody taps logfft -- only its run peaks and local_ampmax are wanted, both
 //     maxima -- the tail forms each bin's dB value from its registers and folds it into the run's slot and the lane's
 //     maximum there: no store of the spectrum, no sync, no reload.  A tapped logfft keeps the old hand-over.
-//   * VAMD_XF_P123_REGS: FFT passes 1 + 2 -> 3 through v_permlane32_swap (fft_pass123_wave2048 below).
-//   * VAMD_MD_OUT_REGS: the first of these in k_mdct_only (the HBM-bound kernel: off until a C2 A/B of its own says otherwise).
-// Same arithmetic on the same operands; only where a value is when it is used changes.
-#ifndef VAMD_XF_OUT_REGS
-#define VAMD_XF_OUT_REGS 1
-#endif
-#ifndef VAMD_XF_TAIL_LOGFFT
-#define VAMD_XF_TAIL_LOGFFT 1
-#endif
-#ifndef VAMD_MD_OUT_REGS
-#define VAMD_MD_OUT_REGS 0
-#endif
+//   * FFT passes 1 + 2 -> 3 through v_permlane32_swap (fft_pass123_wave2048 below).
+// Same arithmetic on the same operands; only where a value is when it is used changes.  (k_mdct_only, the HBM-bound kernel,
+// takes none of them: DESIGN.md "Decided variants".)
 template <int LOGN, class Team>
 constexpr bool xf_size_path() {  // the size-specialised 2048-sample path, one wave per channel-block, on the GPU
   return VAMD_GPU && LOGN == 11 && std::is_same<Team, WaveTeam>::value;
@@ -301,7 +283,7 @@ VAMD_DEV void swap_rows16(float &a, float &b) {  // a's odd rows of sixteen lane
 // detector, k_env_spectrum: its steps overlap by half, so transform t's samples start in_stride = 64 floats after its
 // predecessor's and a windowed copy of every step would be twice the LDS).  x * win[i] is rounded as the separate
 // windowing pass rounds it; the sums the fold takes of such products are the same sums.
-// OUT_REGS (VAMD_XF_OUT_REGS above): the spectrum goes from the bit-reverse items' registers to hbm_out [n/2] and its dB twin
+// OUT_REGS (above): the spectrum goes from the bit-reverse items' registers to hbm_out [n/2] and its dB twin
 // to hbm_log [n/2] (each may be null); out0 is not written.
 template <int LOGS = 0, int LOGN = 0, class Team = WaveTeam, bool PACKED = false, bool FOLD_AHEAD = false, bool WIN = false,
           bool OUT_REGS = false>
@@ -310,7 +292,7 @@ VAMD_DEV void mdct_forward_wave(const XformP &P, const float *in0, float *w0, fl
                                 FoldOps<LOGN> *ahead = nullptr, const float *in_next = nullptr, const float *win = nullptr,
                                 float *__restrict__ hbm_out = nullptr, float *__restrict__ hbm_log = nullptr) {
   static_assert(!OUT_REGS || LOGS == 0, "the spectrum out of registers: one transform per wave");
-  static_assert(!WIN || (!FOLD_AHEAD && !(VAMD_XF_FOLD_QUADS && LOGN >= 10 && LOGS == 0)), "the window in the fold: the generic fold only");
+  static_assert(!WIN || !FOLD_AHEAD, "the window in the fold: the generic fold only");
   const int n = LOGN ? (1 << LOGN) : P.n, n2 = n >> 1, n4 = n >> 2, n8 = n >> 3;
   const int log2n = LOGN ? LOGN : P.log2n;
   const float *__restrict__ trig = P.trig;
@@ -337,7 +319,7 @@ VAMD_DEV void mdct_forward_wave(const XformP &P, const float *in0, float *w0, fl
   };
   int s = 0;
 #if VAMD_GPU
-  constexpr bool head_regs = VAMD_XF_HEAD_REGS && LOGN == 11 && LOGS == 0 && std::is_same<Team, WaveTeam>::value;
+  constexpr bool head_regs = LOGN == 11 && LOGS == 0 && std::is_same<Team, WaveTeam>::value;
 #else
   constexpr bool head_regs = false;
 #endif
@@ -465,43 +447,6 @@ VAMD_DEV void mdct_forward_wave(const XformP &P, const float *in0, float *w0, fl
       *(F2 *)(w2 + VAMD_PW(2 * p)) = o;
     }
     if (in_next) fold_fetch<LOGN>(*ahead, in_next);
-  } else if constexpr (VAMD_XF_FOLD_QUADS && LOGN >= 10 && LOGS == 0) {  // (n = 512: the regimes change inside a wave's trip)
-    // The same fold out of LDS with WHOLE quads (round 5; measured round 4, profiles/r04_xf_phases.txt): a pair needs two
-    // words of each of its two quads, and the compiler narrows such a read to ds_read2_b32 -- lanes 16 bytes apart on a
-    // 4-byte access are a four-way bank conflict (two thirds of the fold's LDS cycles).  All four words through an
-    // opaque use make it a ds_read_b128, which the LDS serves 16 lanes at a time from all banks; one trip in flight
-    // (four would want 32 registers the kernel does not have: 7 spills, +2 %), the regimes known per trip as in the
-    // FOLD_AHEAD form.  Conflicts 30.6 -> 23.1 % of the kernel's LDS cycles; time 1.482 -> 1.513 ms (round 5) -- not the default.
-    constexpr int NT = (1 << LOGN) / 4 / 64;
-    float *w2 = w0 + n2;
-#pragma unroll 1
-    for (int k = 0; k < NT; k++) {
-      const int p = LANE + 64 * k;
-      const F2 T = *(const F2 *)(trig + n2 - 2 * (p + 1));
-      const float *q0, *q1;
-      const int regime = 2 * (64 * k) < n8 ? 0 : (2 * (64 * k) < n2 - n8 ? 1 : 2);  // (wave-uniform: n8 is a multiple of 128 for n >= 1024)
-      if (regime == 0) {
-        q0 = in0 + n2 + n4 - 4 * (p + 1), q1 = in0 + n2 + n4 + 4 * p;
-      } else if (regime == 1) {
-        q0 = in0 + n2 + n4 - 4 * (p + 1), q1 = in0 + 4 * (p - n8 / 2);
-      } else {
-        q0 = in0 + n - 4 * (p - (n2 - n8) / 2 + 1), q1 = in0 + 4 * (p - n8 / 2);
-      }
-      F4 x0 = *(const F4 *)q0, x1 = *(const F4 *)q1;
-      asm volatile("" : "+v"(x0.x), "+v"(x0.y), "+v"(x0.z), "+v"(x0.w), "+v"(x1.x), "+v"(x1.y), "+v"(x1.z), "+v"(x1.w));
-      float r0, r1;
-      if (regime == 0) {
-        r0 = x0.z + x1.y, r1 = x0.x + x1.w;
-      } else if (regime == 1) {
-        r0 = x0.z - x1.y, r1 = x0.x - x1.w;
-      } else {
-        r0 = -x0.z - x1.y, r1 = -x0.x - x1.w;
-      }
-      F2 o;
-      o.x = r1 * T.y + r0 * T.x;
-      o.y = r1 * T.x - r0 * T.y;
-      *(F2 *)(w2 + VAMD_PW(2 * p)) = o;
-    }
   } else
   TEAM_EACH(pp, n4 << LOGS, tm) {
     VAMD_MDCT_SPLIT(pp, log2n - 2)
@@ -978,7 +923,7 @@ VAMD_DEV void fft_pass3_wave(const float *__restrict__ cc, float *__restrict__ c
   }
 }
 
-// ---- passes 1 + 2 -> 3 of the 2048-sample FFT without LDS (VAMD_XF_P123_REGS, round 11) ------------------------------------
+// ---- passes 1 + 2 -> 3 of the 2048-sample FFT without LDS (profiles/r11_xf_trips.txt) ---------------------------------------
 // Pass 3's group k3 (< 32) consumes the sixteen outputs of each of the four pass-1+2 units k3 + 32 q, q = 0..3 -- element e
 // of unit k3 + 32 q is its cc[16 k3 + e + (n/4) q].  With the units dealt k = LANE + 64 kk those four are the two units of
 // lane k3 (q = 0, 2) and the two of lane k3 + 32 (q = 1, 3): the exchange crosses lane bit 5 only, v_permlane32_swap, as the
@@ -988,9 +933,6 @@ VAMD_DEV void fft_pass3_wave(const float *__restrict__ cc, float *__restrict__ c
 // fft_pass3_wave states them, and its stores: lanes of a half-wave hold 32 different k3 at 66 floats' distance.
 // c and ch may be the same block (they are: pass 3 writes where passes 1 + 2 read) -- every load is consumed before the
 // exchange, every store issued after it.
-#ifndef VAMD_XF_P123_REGS
-#define VAMD_XF_P123_REGS 1
-#endif
 #if VAMD_GPU
 VAMD_DEV void fft_pass123_wave2048(const float *c, float *ch, const float *wa) {
   constexpr int n = 2048, u = n / 16;
@@ -1114,7 +1056,7 @@ VAMD_DEV void radf2_wave(int ido, int l1, const float *__restrict__ cc, float *_
 // and 4ido-i of those two blocks -- so a thread runs both, then the four radix-2 butterflies on what it holds.
 // Unit 0 takes the two k-only columns of both blocks (values at 0, ido-1, ido, ... 4ido-1) and the radix-2 work
 // they feed (its i = 0 column and the butterflies at ido, 2ido, 3ido).  src, dst: offset layout, plain.
-// SINK (VAMD_XF_TAIL_LOGFFT): nothing is stored.  A pair stored at t is bin t/2's (Re, Im); each is turned into its logfft
+// SINK: nothing is stored.  A pair stored at t is bin t/2's (Re, Im); each is turned into its logfft
 // value (lib/mapping0.c:255-346, as transform_logfft forms it) where it is, and folded into its run's slot of
 // sink.peaks_lds and into sink.amp.  Item g holds the bins tail_bin(g, 0..7).
 template <int LOGN>
@@ -1281,7 +1223,7 @@ VAMD_DEV void fft_tail42_wave(const float *__restrict__ cc, float *__restrict__ 
 // LOGN > 0: n = 2^LOGN, whose FFTPACK factorisation is radix 4 throughout with one radix-2 pass at the end
 // when LOGN is odd (drfti1 tries 4 first and moves a leftover 2 to the front of ifac[], which drftf1
 // walks backwards: lib/smallft.c:35-70,572-631); vamd_create() checks the blob's factors against that.
-// sink (VAMD_XF_TAIL_LOGFFT, the sizes with the fused tail): the last trip's bins go into it instead of a buffer -- its
+// sink (the sizes with the fused tail): the last trip's bins go into it instead of a buffer -- its
 // peaks_lds is set up here, in the buffer that trip would have written -- and the return value points at nothing.
 template <int LOGN = 0, class Team = WaveTeam>
 VAMD_DEV const float *drft_forward_wave(const XformP &P, float *c, float *ch, const Team &tm = Team(), TailSink *sink = nullptr,
@@ -1295,7 +1237,7 @@ VAMD_DEV const float *drft_forward_wave(const XformP &P, float *c, float *ch, co
     // iw = n - 3 after the first pass, n - 15 for the second, n - 63 for the third
     bool done = false;
 #if VAMD_GPU
-    if constexpr (VAMD_XF_P123_REGS && xf_size_path<LOGN, Team>()) {
+    if constexpr (xf_size_path<LOGN, Team>()) {
       fft_pass123_wave2048(c, bufc, wa);  // (one trip, the hand-over in registers)
       done = true;
     }
@@ -1341,7 +1283,7 @@ VAMD_DEV const float *drft_forward_wave(const XformP &P, float *c, float *ch, co
   }
   if (TAIL42) {
     na = 1 - na;
-    if constexpr (VAMD_XF_TAIL_LOGFFT && TAIL42 && xf_size_path<LOGN, Team>()) {
+    if constexpr (TAIL42 && xf_size_path<LOGN, Team>()) {
       if (sink) {
         float *peaks = na ? c : ch;  // the destination: its last reader was the pass before the one that has just synced
         TEAM_EACH(r, nruns, tm) peaks[r] = f_from_bits(0xff800000u);  // -inf: every run has a bin, and every bin a finite value
@@ -1382,8 +1324,8 @@ VAMD_DEV const float *transform_spectra(const XformP &P, float *A, float *B, flo
                                         TailSink *sink = nullptr, int nruns = 0) {
   const int n = LOGN ? (1 << LOGN) : P.n, n2 = n >> 1;
   // MDCT: spectrum lands in B[0..n2) (LDS), then goes out with its dB twin, 16 bytes per thread and tensor
-  // (the 2048-sample path: straight out of the MDCT's last items, VAMD_XF_OUT_REGS)
-  constexpr bool OUT_REGS = VAMD_XF_OUT_REGS && xf_size_path<LOGN, Team>();
+  // (the 2048-sample path: straight out of the MDCT's last items)
+  constexpr bool OUT_REGS = xf_size_path<LOGN, Team>();
   mdct_forward_wave<0, LOGN, Team, LOGN != 0, false, false, OUT_REGS>(P, A, B, B, pc, 0, 0, 0, tm, nullptr, nullptr, nullptr, mdct_out,
                                                                       logmdct_out);
   if constexpr (!OUT_REGS) {
@@ -1440,7 +1382,7 @@ VAMD_DEV float transform_logfft(const XformP &P, const float *spec, float *__res
 #if VAMD_GPU
   // (the ids opaque once per block, as in fft_tail42_wave: the sixteen slot addresses are not to be held across the block loop)
   I2 rid_now[VAMD_XF_QPS(LOGN)];
-  if constexpr (VAMD_XF_TAIL_LOGFFT && xf_size_path<LOGN, Team>()) {  // (k_transform: rid is its register array, whatever it holds)
+  if constexpr (xf_size_path<LOGN, Team>()) {  // (k_transform: rid is its register array, whatever it holds)
 #pragma unroll
     for (int k = 0; k < VAMD_XF_QPS(LOGN); k++) {
       rid_now[k] = rid[k];
@@ -1488,10 +1430,10 @@ VAMD_DEV float transform_logfft(const XformP &P, const float *spec, float *__res
   return amp;
 }
 
-// whether a block's logfft comes out of the FFT's tail (VAMD_XF_TAIL_LOGFFT): then `rid` holds xf_tail_run_ids', not xf_run_ids'
+// whether a block's logfft comes out of the FFT's tail: then `rid` holds xf_tail_run_ids', not xf_run_ids'
 template <int LOGN, class Team>
 VAMD_DEV bool xf_tail_fused(const float *logfft_out, const float *peaks_out) {
-  return VAMD_XF_TAIL_LOGFFT && xf_size_path<LOGN, Team>() && !logfft_out && peaks_out;
+  return xf_size_path<LOGN, Team>() && !logfft_out && peaks_out;
 }
 
 template <int LOGN = 0, class Team = WaveTeam>
@@ -1500,7 +1442,7 @@ VAMD_DEV float transform_block(const XformP &P, float *A, float *B, float *__res
                                const Team &tm = Team(), float *raw_max = nullptr, const I2 *rid = nullptr,
                                const unsigned short *__restrict__ run_of_bin = nullptr, int nruns = 0,
                                float *__restrict__ peaks_out = nullptr) {
-  if constexpr (VAMD_XF_TAIL_LOGFFT && xf_size_path<LOGN, Team>()) {
+  if constexpr (xf_size_path<LOGN, Team>()) {
     if (xf_tail_fused<LOGN, Team>(logfft_out, peaks_out)) {  // logfft is wanted as run peaks and local_ampmax only: out of the FFT's tail
       TailSink sink;
       sink.rid = rid;  // (xf_tail_run_ids')

@@ -436,9 +436,8 @@ static long noise_teams_per_cu(const vamd_ctx *c, int n2, size_t lds, bool overl
   // persistent teams.  A CU's LDS and 32 wave slots hold 8 of them at 1024 bins (both exactly full) -- but then the
   // tone chain on the side stream finds no room until they retire and runs behind them.  Six teams (three quarters of
   // the wave slots) keep the vector units as busy -- the stage is issue-bound -- and leave eight slots and 40 KB in
-  // which the tone kernels, which wait on LDS atomics and memory, run BESIDE them: per 131 072 stereo blocks
-  // noise + tone tail 2.24 + 1.16 ms with eight teams, 2.42 + 0.82 with seven, 2.62 + 0.50 with six, 2.89 + 0.29
-  // with five, 3.30 + 0.01 with four.
+  // which the tone kernels, which wait on LDS atomics and memory, run BESIDE them.  (The figures behind every number
+  // here, round by round: DESIGN.md, "Decided variants".)
   const int nw = n2 >= 256 ? 4 : (n2 >= 64 ? n2 / 64 : 1);
   long per_cu = (long)(c->lds_per_block / lds);
   if (per_cu > 32 / nw) per_cu = 32 / nw;
@@ -447,28 +446,11 @@ static long noise_teams_per_cu(const vamd_ctx *c, int n2, size_t lds, bool overl
     if (per_cu > noise_cap) per_cu = noise_cap;
   } else if (overlap) {
     // ... and where the tone chain carries its own last step (the fold as a launch of its own: the masks-only level,
-    // bitrate-managed blocks) it needs half the CU to finish beside the noise mask: four teams.  65 536 stereo blocks
-    // at the masks-only level: noise + visible tone tail 1.17 + 0.80 ms with seven teams, 1.25 + 0.64 with six,
-    // 1.38 + 0.60 with five, 1.63 + 0.08 with four.
-    // (round 6, with round 5's faster seeding: a run of ONE size class does better with five teams -- noise mask +
-    // visible tone tail per 131 072 stereo blocks 2.77 + 0.01 ms against 2.51 + 0.32 with six, 2.34 + 0.54 with seven,
-    // 2.16 + 0.93 with eight; a mixed run, whose chains also have the other class's masks and floor fits to run
-    // beside, keeps six: C5 11.25 ms against 11.34 with five.  profiles/r06_noise_teams.txt)
-    // (round 21, profiles/r21_chase_ring.txt: six for both.  What stood against the sixth team in a run of one size class
-    // was k_tone_chase: 94 VGPRs and 8 KB of ring a wave, so beside six teams -- 8 wave slots, 40 KB and 128 VGPRs a SIMD
-    // left -- 4 of its waves fit a CU.  With 62 VGPRs and a ring of 4 KB (k_tone.h: VAMD_CHASE_PREFETCH, VAMD_CHASE_RING)
-    // 8 fit.  Noise mask + visible tone tail per 131 072 stereo blocks: the parent, five teams, 2.78 + 0.01 ms; the new
-    // walk with five 2.79 + 0.01, with six 2.51 + 0.19, with seven 2.37 + 0.54.  What is left of the tail is k_tone_seed,
-    // 8 of whose waves fit beside six teams for 12 beside five.  C5: 10.12 ms against 10.17, 10.51 with 28 waves.)
-    // (round 24, profiles/r24_chase_regs.txt: six stays.  The walk now keeps its window in registers (k_tone.h:
-    // tone_chase_regs) and takes no LDS at all, so what a CU holds of it beside the teams is decided by wave slots and
-    // registers alone: 62 VGPRs, two waves a SIMD in the 128 that six teams leave, 8 a CU as before -- but each is done in
-    // 123 k wave cycles where the ring walk took 213 k, and beside six teams the chain now ends before the noise mask
-    // does.  Noise mask + visible tone tail per 131 072 stereo blocks: the parent, six teams, 2.53 + 0.19 ms; the new
-    // walk with five 2.80 + 0.01, with six 2.52 + 0.01, with seven 2.36 + 0.41.  The LDS the walk gave back does not buy
-    // the seventh team: beside seven, 4 wave slots a CU are left and k_tone_seed alone takes 2.9 ms in them, longer
-    // than the noise mask itself.  C5: 24 waves against 28 in the record.)
-    // (a run of smaller blocks alone was not measured again: as before)
+    // bitrate-managed blocks) it needs half the CU to finish beside the noise mask: four teams (16 waves).  Otherwise
+    // six teams (24 waves): the walk (k_tone.h: tone_chase_regs) takes no LDS and 62 VGPRs, two waves a SIMD in the 128
+    // that six teams leave, and beside six the chain ends before the noise mask does; the seventh team is kept out by
+    // k_tone_seed, which alone takes longer than the noise mask in the 4 wave slots seven leave.  A run of smaller
+    // blocks alone keeps the five teams (20 waves) it was measured with.
     const int beside = c->K.noise_waves > 0 ? c->K.noise_waves : (alone && n2 < 1024 ? 20 : 24);
     const long cap = (fold_later ? beside : 16) / nw;
     if (per_cu > cap) per_cu = cap > 0 ? cap : 1;
@@ -502,7 +484,7 @@ static void launch_masks(vamd_ctx *c, BatchRun *R, int level, bool forked, bool 
   const bool by_wave = (long)gcb <= wave_max_cb && P0.eighth_octave_lines <= 16 && nl <= 2048;
   const bool lp8 = P0.eighth_octave_lines == 8 && P1.eighth_octave_lines == 8;
   // the stack walk's ring: VAMD_CHASE_RING slots where no window is longer than 8 lines, 16 otherwise (k_tone.h)
-  const bool ring8 = P0.eighth_octave_lines <= 8 && P1.eighth_octave_lines <= 8 && VAMD_CHASE_RING < VAMD_RING;
+  const bool ring8 = P0.eighth_octave_lines <= 8 && P1.eighth_octave_lines <= 8;
   const size_t ring_slots = ring8 ? VAMD_CHASE_RING : VAMD_RING;
   // a handful of blocks, no second stream: both masks in one launch, side by side (k_noise_tone)
   const bool merge_env = !c->K.masks_separate;

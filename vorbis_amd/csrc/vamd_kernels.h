@@ -38,12 +38,8 @@ __device__ __forceinline__ void flag_range(const DescP &d, long i) {
 // occupancy (1.96 -> 2.42 ms at best: 12 % fewer vector instructions per channel-block, but 9.6 KB of LDS per wave
 // hold the CU to sixteen waves, and the half-uniform reads of the ordered sections go through the LDS pipe where
 // v_readlane did not: 64 % of the issue slots used against 100 %) -- never.
-#ifndef VAMD_FLOOR_PAIR_MIN_LONG
 #define VAMD_FLOOR_PAIR_MIN_LONG 0x7fffffffL
-#endif
-#ifndef VAMD_FLOOR_PAIR_MIN_SHORT
 #define VAMD_FLOOR_PAIR_MIN_SHORT 16384L
-#endif
 
 struct XformLds {
   XformP P;       // table pointers rebound to the LDS copies
@@ -123,26 +119,16 @@ __global__ __launch_bounds__(64 * VAMD_MD_WAVES) void k_mdct_only(XformP G, int 
   PhaseClock pc;
   pc.start(nullptr);
   for (long f = (long)blockIdx.x * nw + (threadIdx.x >> 6); f < nframes; f += (long)gridDim.x * nw) {
-    constexpr bool OUT_REGS = VAMD_MD_OUT_REGS && xf_size_path<LOGN, WaveTeam>();  // (k_transform.h, round 11)
-    mdct_forward_wave<0, LOGN, WaveTeam, LOGN != 0, true, false, OUT_REGS>(P, in + f * n, B, B, pc, 0, 0, 0, WaveTeam(), nullptr, nullptr,
-                                                                           nullptr, out + f * n2, nullptr);
-    if constexpr (!OUT_REGS) {
-      WAVE_FOR(q, n2 >> 2)((F4 *)(out + f * n2))[q] = ((const F4 *)B)[q];
-      WAVE_SYNC();
-    }
+    mdct_forward_wave<0, LOGN, WaveTeam, LOGN != 0, true>(P, in + f * n, B, B, pc);
+    WAVE_FOR(q, n2 >> 2)((F4 *)(out + f * n2))[q] = ((const F4 *)B)[q];
+    WAVE_SYNC();
   }
 }
 
 // stage 1: window + MDCT + FFT + logs, one wave per channel-block.  Instantiated per block size (LOGN =
 // log2 n; 0 = any size, read from the parameters).
-#ifndef VAMD_XF_VGPRS
-#define VAMD_XF_VGPRS 256
-#endif
 template <int LOGN>
-#ifndef VAMD_XF_BOUND_WAVES  // (scratch builds: the register budget of a workgroup of this many waves, whatever is launched)
-#define VAMD_XF_BOUND_WAVES VAMD_XF_WAVES
-#endif
-__global__ __launch_bounds__(64 * VAMD_XF_BOUND_WAVES) __attribute__((amdgpu_num_vgpr(VAMD_XF_VGPRS))) void k_transform(XformP G, int W, DescP d, int ch, long ncb,
+__global__ __launch_bounds__(64 * VAMD_XF_WAVES) __attribute__((amdgpu_num_vgpr(256))) void k_transform(XformP G, int W, DescP d, int ch, long ncb,
                                                                  const float *__restrict__ pcm,
                                                                  float *__restrict__ mdct_raw,
                                                                  float *__restrict__ logmdct,
@@ -166,7 +152,7 @@ __global__ __launch_bounds__(64 * VAMD_XF_BOUND_WAVES) __attribute__((amdgpu_num
   // previous block's spectra included.
   int lW = 0, nW = 0;
   I2 rid[VAMD_XF_QPS(LOGN)] = {};  // which run of bins each of this lane's bins belongs to: the same for every block
-  if constexpr (VAMD_XF_TAIL_LOGFFT && xf_size_path<LOGN, WaveTeam>()) {  // (the same registers either way: logfft is tapped or not for the whole launch)
+  if constexpr (xf_size_path<LOGN, WaveTeam>()) {  // (the same registers either way: logfft is tapped or not for the whole launch)
     if (xf_tail_fused<LOGN, WaveTeam>(logfft, peaks))
       xf_tail_run_ids<LOGN>(run_of_bin, rid, tm);
     else if (peaks)
@@ -184,21 +170,12 @@ __global__ __launch_bounds__(64 * VAMD_XF_BOUND_WAVES) __attribute__((amdgpu_num
     pcm_fetch(tile, samples(cb, blk), n, tm);
   }
   for (; cb < ncb; cb += cstride) {
-#ifdef VAMD_XF_NO_PREFETCH  // (scratch builds, profiles/r05_xf_variants.txt: what the next block's samples in registers are worth)
-    {
-      const long blk0 = (long)((unsigned)cb / (unsigned)ch);
-      lW = d_lW(d, blk0), nW = d_nW(d, blk0);
-      pcm_fetch(tile, samples(cb, blk0), n, tm);
-    }
-#endif
     transform_window(P, W, lW, nW, tile, L.A, pc, tm);
-#ifndef VAMD_XF_NO_PREFETCH
     if (cb + cstride < ncb) {  // next block, one ahead
       const long blk = (long)((unsigned)(cb + cstride) / (unsigned)ch);
       lW = d_lW(d, blk), nW = d_nW(d, blk);
       pcm_fetch(tile, samples(cb + cstride, blk), n, tm);
     }
-#endif
     float raw;
     // (logfft goes out as what the tone stage reads of it -- its peak over each run of bins of one octave line, nrp
     // floats per channel-block -- and in full only where a caller taps it)
@@ -597,7 +574,7 @@ __global__ __launch_bounds__(64 * NoiseGeom<LOGN2>::NW) void k_noise_tone(PsyP P
 // 131 072 stereo blocks; a walk whose stack is a register bit mask fed through coalesced LDS tiles executes three
 // times the instructions once 64 divergent walks share them, 2.96 ms.  docs/history/DESIGN_r01-r05.md has the round's account.)
 // (That form staged the lines through LDS tiles.  k_tone_chase_regs below keeps the mask and reads its row as the ring walk
-// does: the ring walk's vector instructions per wave, no LDS, 0.58 of its wave cycles -- round 24, profiles/r24_chase_regs.txt.)
+// does: the ring walk's vector instructions per wave, no LDS, 0.58 of its wave cycles -- profiles/r24_chase_regs.txt.)
 // RING: the slots of a lane's ring, chase_ring_slots(linesper) (chosen by the launch)
 #define VAMD_CHASE_LANES 64
 // the shell both forms of the kernel share: the lane's walk between the clock probe's two readings
@@ -773,9 +750,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 // the level loops -- serves both channels, and a short block's 128 bins fill a half where they left half a wave idle.
 // Launched for stereo setups whose two channels share a floor (launch_rest); everything per block (psy look, floor,
 // sizes) is wave-uniform as before, everything per channel lives in the half's lanes.  LDS: `half_bytes` per half.
-#ifndef VAMD_FLOOR_PAIR_WAVES
 #define VAMD_FLOOR_PAIR_WAVES 6  // waves per SIMD: 77 registers, nothing spilt (4 / 5 / 6 / 8 measured)
-#endif
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(VAMD_FLOOR_PAIR_WAVES, VAMD_FLOOR_PAIR_WAVES))) void k_floor_pair(const Bound *__restrict__ Bd, int W, DescP d, int half_bytes,
                                                    const float *__restrict__ noise, float *__restrict__ tone,
                                                    const float *__restrict__ seed_g, const unsigned short *__restrict__ surv,

@@ -292,12 +292,8 @@ VAMD_DEV int div_small(int num, int den, float rcp) {
 // pointer to the compiler: flat loads, and a 64-bit address formed per lane on the vector unit for each of them.  Every
 // such pointer points into the setup's image in device memory, and so do a batch's tensors.  dm_*: the access goes
 // through a pointer that says so -- a global load or store off the scalar base with an unsigned 32-bit lane offset in
-// bytes, so that one offset (16 q for quad q) serves every stream of a quad (VAMD_FL_GLOBAL_ADDR, k_floor.h).  Plain
-// pointer arithmetic on the one-lane test build.
-#ifndef VAMD_FL_GLOBAL_ADDR
-#define VAMD_FL_GLOBAL_ADDR 1
-#endif
-#if VAMD_GPU && VAMD_FL_GLOBAL_ADDR
+// bytes, so that one offset (16 q for quad q) serves every stream of a quad.  Plain pointer arithmetic on the one-lane test build.
+#if VAMD_GPU
 #define VAMD_DEVMEM __attribute__((address_space(1)))
 typedef float dm_f4_t __attribute__((ext_vector_type(4)));
 typedef int dm_i4_t __attribute__((ext_vector_type(4)));

@@ -82,21 +82,9 @@ VAMD_DEV int wave_shift_up1(int v, int fill) {  // lane l of a half gets lane l-
   return (threadIdx.x & 31) == 0 ? fill : r;
 }
 // a value of lane `lane` of this lane's half; the index is the same for the lanes of a half, not for the wave.
-// Two forms: through the LDS pipe (ds_bpermute: one instruction, a round trip of ~100 cycles on the ordered chain), or on
-// the vector unit alone -- the two halves' indices to scalar registers, two v_readlane, one select: five instructions,
-// no trip (VAMD_PAIR_READLANE; which one is measured in profiles/r05_floor_pair.txt)
-#ifndef VAMD_PAIR_READLANE
-#define VAMD_PAIR_READLANE 0
-#endif
-VAMD_DEV int half_read(int v, int lane) {
-#if VAMD_PAIR_READLANE
-  const int i0 = __builtin_amdgcn_readlane(lane, 0) & 31, i1 = __builtin_amdgcn_readlane(lane, 32) & 31;
-  const int a = __builtin_amdgcn_readlane(v, i0), b = __builtin_amdgcn_readlane(v, 32 + i1);
-  return VAMD_PAIR_HALF ? b : a;
-#else
-  return __shfl(v, VAMD_PAIR_BASE + lane, 64);
-#endif
-}
+// Through the LDS pipe (ds_bpermute: one instruction, a round trip of ~100 cycles on the ordered chain); the form on the
+// vector unit alone was measured against it in profiles/r05_floor_pair.txt (DESIGN.md "Decided variants").
+VAMD_DEV int half_read(int v, int lane) { return __shfl(v, VAMD_PAIR_BASE + lane, 64); }
 VAMD_DEV int wave_read(int v, int lane) { return half_read(v, lane); }
 VAMD_DEV int wave_gather(int v, int lane) { return __shfl(v, VAMD_PAIR_BASE + lane, 64); }
 VAMD_DEV unsigned int load_uniform_u32(const unsigned int *p, int i) { return p[i]; }  // (half-uniform index: a vector load)
