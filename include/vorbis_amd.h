@@ -657,9 +657,9 @@ int vamd_decode_streams(vamd_ctx *ctx, const vamd_decode_desc *desc, const int64
  * -- the slots, the carried rows, the last blocks' rows -- is computed and range-checked on the host before the first launch.
  *
  * Destroy a live decoder before its context.  Calls on one context are not concurrent, as everywhere.
- * Out of scope: Ogg pages in pieces (a packet can span the pages of two pieces: the host walk would carry partial
- * packets -- the next step, on top of this one); streams that begin at a nonzero granule; packets in device memory; the
- * feed itself is unchanged (VAMD_FEED_DECODED on a live feed is still refused: decode its packets here). */
+ * Out of scope: streams that begin at a nonzero granule; packets in device memory; the feed itself is unchanged
+ * (VAMD_FEED_DECODED on a live feed is still refused: decode its packets here).  Ogg pages in pieces:
+ * vamd_decode_ogg_live, below. */
 typedef struct vamd_decode_live vamd_decode_live;
 int vamd_decode_live_create(vamd_ctx *ctx, int64_t max_streams, vamd_decode_live **out);
 void vamd_decode_live_destroy(vamd_decode_live *d);
@@ -722,6 +722,81 @@ typedef struct vamd_decode_ogg_desc {
 int vamd_decode_ogg_plan(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
 int vamd_decode_ogg(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, const int64_t *offset_out /* host [nstreams] */,
                     float *pcm /* device */, uint8_t *status /* host [nstreams] */);
+
+/* ---- the live Ogg decoder: continuing Ogg Vorbis streams decoded in pieces of BYTES (still ABI 9: additions only).  The
+ * counterpart of a live Ogg feed (vamd_feed_ogg_headers_live / vamd_feed_ogg, with or without vamd_feed_ogg_flush), of a
+ * receiver on a socket: per slot and per call the caller hands over the next bytes of the stream's Ogg bitstream, in HOST
+ * memory, cut at ANY byte -- inside a page header, a lacing table, a body, a header packet, an audio packet that spans
+ * pages -- and gets PCM on the device for the audio packets those bytes complete.  For a clean stream whose last page
+ * carries the end-of-stream flag (every file vamd_feed_ogg and libvorbis write) the pieces' samples laid end to end are,
+ * bit for bit, what vamd_decode_ogg gives for the whole file, at any cut list, empty pieces and pieces of one byte
+ * included (tests/test_demux_live_cpu.py, tests/test_decode_ogg_live_gpu.py).
+ *
+ * frames, offset_out, the layout of pcm, status, "a flagged stream has no frames", one stream synchronisation per call
+ * and "slots are committed only when the call has succeeded" are vamd_decode_live_wrote's; VAMD_EINVAL comes with a reason
+ * and nothing enqueued (null pointers; piece offsets negative, not monotone or beyond 2^40; a slot out of range or named
+ * twice; nstreams > max_streams); vamd_decode_ogg_live_plan is host only and changes nothing.
+ *
+ * Options (NULL: all defaults): setup_header as in vamd_decode_ogg_desc (copied at create); max_packet_bytes, 0 = the
+ * larger of vamd_packet_capacity(ctx, 0) and (ctx, 1); max_header_bytes, 0 = 1 MiB.
+ *
+ * Slots.  A slot is free until its first byte arrives; it then holds ONE logical bitstream until a piece with close[s] != 0
+ * closes it.  A slot the call does not name keeps its state.
+ * Headers.  Nothing decodes until the three header packets are complete; the host collects their bytes and holds them to
+ * vamd_decode_ogg's checks when the third completes.  A failure is VAMD_STATUS_BADHEADER and a dead stream; so are more
+ * than max_header_bytes of header bytes (a hostile stream cannot grow host memory without end).
+ * A page the cut divides stays on the HOST until it is whole (at most 65 306 bytes per slot) and goes up with the piece
+ * that completes it: only whole pages reach the device, gathered with the call's other whole pages into one upload.
+ * A packet that whole pages leave open stays on the DEVICE, in a byte carry [max_streams][max_packet_bytes, rounded up to
+ * 4]; the host keeps its length so far and its first byte (the mode bits of the block plan).  k_ogg_packet_carry_in puts
+ * it in front of the stream's next pages in the call's arena, k_ogg_depage unpages those behind it,
+ * k_ogg_packet_carry_out takes what is still open back.  A DELIBERATE DEVIATION from vamd_decode_ogg, which has no such
+ * bound: an OPEN audio packet longer than max_packet_bytes is VAMD_STATUS_BADPAGE, flagged on the host before any launch
+ * (a packet that completes inside the call that began it is not held to the bound).
+ * The end granule is the granule position of the page that completed the stream's last audio packet.  It cuts the last
+ * block's share, by vamd_decode_live_plan's rule, in the call that decodes that packet -- if that page carries the
+ * end-of-stream flag (so closing later, with an empty piece, gives the same samples), or if the piece closes the stream.
+ * A stream closed without the flag gets the cut only if the closing piece holds its last packet.  (The flag counts on the
+ * page that COMPLETES the last audio packet, where every encoder puts it; an end-of-stream page that completes no packet
+ * ends the stream without a cut, its samples having left with the packet.)
+ * An ended stream.  A slot that has seen its end-of-stream page is ended: any further page before the close is
+ * VAMD_STATUS_BADPAGE (A DELIBERATE DEVIATION: the whole-file walk ignores the flag).  The caller still closes to free it.
+ * Closing.  A closing piece with a divided page still held, or a packet still open, is VAMD_STATUS_BADPAGE (the file "ends
+ * inside a page / a packet"); one whose three headers are not complete -- an empty closing piece on a free slot included
+ * -- is VAMD_STATUS_BADHEADER (vamd_decode_ogg's answer for a file of no bytes).  Either way the slot is free afterwards.
+ * Container checks -- capture pattern, version, serial, sequence numbers, the continued flag, begin-of-stream on page 0
+ * alone -- are vamd_decode_ogg's, the walk's state carried per slot; a page's checksum is k_ogg_depage's and arrives with
+ * the call's statuses.  From the piece that is flagged on the stream is dead: no frames, and the status on every later
+ * piece until one closes it.  What earlier pieces handed out stands; the neighbours and the slot's next stream are
+ * untouched.
+ * Memory safety.  No byte outside [piece_offset[s], piece_offset[s+1]) is read, whatever the stream claims.  Every index a
+ * kernel uses -- the pages' runs of the upload and of the arena, the carry rows' slots and runs, the packets' places, and
+ * the live decoder's rows -- is computed and range-checked on the host before the first launch; the kernels trust a row no
+ * further than the buffers reach.
+ *
+ * Destroy a live Ogg decoder before its context.  Out of scope: resynchronisation behind a damaged page; chained or
+ * multiplexed streams; streams that begin at a nonzero granule; bytes that start in device memory; seeking; setups other
+ * than the context's. */
+typedef struct vamd_decode_ogg_live vamd_decode_ogg_live;
+typedef struct vamd_decode_ogg_live_opts {
+  const uint8_t *setup_header;   /* or NULL: the setup header packet every stream's third packet must equal */
+  int64_t setup_header_bytes;
+  int64_t max_packet_bytes;      /* 0: the larger vamd_packet_capacity */
+  int64_t max_header_bytes;      /* 0: 1 MiB */
+} vamd_decode_ogg_live_opts;
+typedef struct vamd_decode_ogg_live_desc {
+  int64_t nstreams;
+  const int64_t *slot;           /* host [nstreams]: distinct, 0 .. max_streams-1 */
+  const uint8_t *bytes;          /* HOST: this call's pieces, back to back */
+  const int64_t *piece_offset;   /* host [nstreams + 1]: piece s = bytes[piece_offset[s] .. piece_offset[s+1]) */
+  const uint8_t *close;          /* host [nstreams] or NULL: != 0 ends the stream after this piece */
+} vamd_decode_ogg_live_desc;
+int vamd_decode_ogg_live_create(vamd_ctx *ctx, int64_t max_streams, const vamd_decode_ogg_live_opts *opts, vamd_decode_ogg_live **out);
+void vamd_decode_ogg_live_destroy(vamd_decode_ogg_live *d);
+int vamd_decode_ogg_live_plan(vamd_decode_ogg_live *d, const vamd_decode_ogg_live_desc *desc, int64_t *frames /* host [nstreams] */,
+                              int64_t *nblocks /* [2] */);
+int vamd_decode_ogg_live_wrote(vamd_decode_ogg_live *d, const vamd_decode_ogg_live_desc *desc, const int64_t *offset_out /* host [nstreams] */,
+                               float *pcm /* device */, uint8_t *status /* host [nstreams] */);
 
 /* ---- the host shim for encoders that submit ONE block at a time from many threads.
  * libvorbis' unit of work is one block of one stream (mapping0_forward, reference lib/mapping0.c:233-687); a

@@ -67,6 +67,14 @@ class _DecodeOggDesc(C.Structure):  # vamd_decode_ogg_desc
     _fields_ = [("nstreams", C.c_int64), ("bytes", _vp), ("file_offset", _vp), ("setup_header", _vp), ("setup_header_bytes", C.c_int64)]
 
 
+class _DecodeOggLiveOpts(C.Structure):  # vamd_decode_ogg_live_opts
+    _fields_ = [("setup_header", _vp), ("setup_header_bytes", C.c_int64), ("max_packet_bytes", C.c_int64), ("max_header_bytes", C.c_int64)]
+
+
+class _DecodeOggLiveDesc(C.Structure):  # vamd_decode_ogg_live_desc
+    _fields_ = [("nstreams", C.c_int64), ("slot", _vp), ("bytes", _vp), ("piece_offset", _vp), ("close", _vp)]
+
+
 class _Desc(C.Structure):
     _fields_ = [("W", C.c_int), ("nblocks", C.c_long), ("lW", _vp), ("nW", _vp), ("blocktype", _vp),
                 ("ampmax_in", _vp), ("uniform_lW", C.c_int), ("uniform_nW", C.c_int),
@@ -103,6 +111,7 @@ _int, _long, _size, _float = C.c_int, C.c_long, C.c_size_t, C.c_float
 _pvp, _pint, _plong, _pfloat, _pi32 = C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_float), C.POINTER(C.c_int32)
 _pDesc, _pIO, _pMIO, _pPlan, _pDecode = C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO), C.POINTER(_Plan), C.POINTER(_DecodeDesc)
 _pDecodeOgg, _pDecodeLive = C.POINTER(_DecodeOggDesc), C.POINTER(_DecodeLiveDesc)
+_pDecodeOggLive, _pDecodeOggLiveOpts = C.POINTER(_DecodeOggLiveDesc), C.POINTER(_DecodeOggLiveOpts)
 _vp2 = _vp * 2
 _block = [_vp, _pvp, _int, _int, _int, _int, _float]   # (ctx, pcm[ch], lW, W, nW, blocktype, ampmax_in): how every per-block call begins
 
@@ -148,6 +157,10 @@ PROTOTYPES = {
     "vamd_decode_live_wrote": (_int, [_vp, _pDecodeLive, _vp, _vp, _vp]),
     "vamd_decode_ogg_plan": (_int, [_vp, _pDecodeOgg, _vp, _vp]),
     "vamd_decode_ogg": (_int, [_vp, _pDecodeOgg, _vp, _vp, _vp]),
+    "vamd_decode_ogg_live_create": (_int, [_vp, C.c_int64, _pDecodeOggLiveOpts, _pvp]),
+    "vamd_decode_ogg_live_destroy": (None, [_vp]),
+    "vamd_decode_ogg_live_plan": (_int, [_vp, _pDecodeOggLive, _vp, _vp]),
+    "vamd_decode_ogg_live_wrote": (_int, [_vp, _pDecodeOggLive, _vp, _vp, _vp]),
     "vamd_analyze_block_managed": (_int, _block + [_vp] * 9),
     "vamd_plan_streams": (_int, [_vp, _vp, _long, _long, _long, _long, _vp, _pPlan]),
     "vamd_gather_blocks": (_int, [_vp, _pPlan, _int, _vp, _long, _vp]),

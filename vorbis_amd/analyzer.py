@@ -1,5 +1,6 @@
 """vamd_ctx in Python: the Analyzer -- batches, streams, plans, the bitrate manager's candidates, the detector, the packet
-decoder for packets and for Ogg files, the LiveDecoder for continuing streams in pieces -- and decode() / decode_ogg() for
+decoder for packets and for Ogg files, the LiveDecoder and the LiveOggDecoder for continuing streams in pieces of packets and
+of Ogg bytes -- and decode() / decode_ogg() for
 a caller who holds packets or files and no context."""
 import ctypes as C
 
@@ -7,7 +8,7 @@ import numpy as np
 
 from .abi import (ABI_VERSION, BLOCKTYPE_LONG, LEVEL_FULL, LEVEL_PSY, LEVEL_TRANSFORM, PACKETBLOBS, POSTS_STRIDE, QUANT_LIMIT_INT,
                   QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_RANGE, VAMD_EDOMAIN, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
-                  _DecodeDesc, _DecodeLiveDesc, _DecodeOggDesc, _Desc, _IO, _MIO, _Plan, _vp, load_library)
+                  _DecodeDesc, _DecodeLiveDesc, _DecodeOggDesc, _DecodeOggLiveDesc, _DecodeOggLiveOpts, _Desc, _IO, _MIO, _Plan, _vp, load_library)
 from .packets import packet_bytes
 
 
@@ -700,6 +701,17 @@ class Analyzer:
         self._live.append(d)
         return d
 
+    def live_ogg_decoder(self, max_streams, setup_header=None, max_packet_bytes=0, max_header_bytes=0):
+        """vamd_decode_ogg_live_create: a LiveOggDecoder for up to max_streams continuing Ogg Vorbis streams on this context.
+        setup_header: the setup header packet every stream's third packet must equal, or None; max_packet_bytes: the longest
+        audio packet that may stay open between pieces (0: the larger packet capacity); max_header_bytes: what the three
+        header packets may hold together (0: 1 MiB).  Closing the Analyzer closes it."""
+        if not hasattr(self, "_live"):
+            self._live = []
+        d = LiveOggDecoder(self, max_streams, setup_header, max_packet_bytes, max_header_bytes)
+        self._live.append(d)
+        return d
+
     def decode_ogg_prepare(self, files, setup_header=None, file_offset=None):
         """The descriptor of decode_ogg()'s group (vamd_decode_ogg_desc) with the host arrays it points into."""
         for f in files:
@@ -950,6 +962,70 @@ class LiveDecoder:
         per slot of the call; a dead stream -- one that has held a flagged packet -- gives [ch, 0] until a piece closes it.
         with_status, also the status bytes (numpy uint8).  See prepare() for the arguments."""
         return self.an._decoded_tensors(len(slots), *self.run(self.prepare(slots, pieces, close, end_granules)), with_status)
+
+
+class LiveOggDecoder:
+    """vamd_decode_ogg_live: continuing Ogg Vorbis streams decoded in pieces of bytes, a stream per slot
+    (Analyzer.live_ogg_decoder).  The pieces may be cut at any byte; for a clean stream that ends in an end-of-stream page
+    their samples laid end to end are what Analyzer.decode_ogg gives for the whole file."""
+
+    def __init__(self, analyzer, max_streams, setup_header=None, max_packet_bytes=0, max_header_bytes=0):
+        self.an, self.max_streams = analyzer, int(max_streams)
+        hdr = np.frombuffer(bytes(setup_header), np.uint8) if setup_header is not None else None
+        opts = _DecodeOggLiveOpts(_vp(hdr.ctypes.data) if hdr is not None and hdr.size else None, hdr.size if hdr is not None else 0,
+                                  int(max_packet_bytes), int(max_header_bytes))
+        h = _vp()
+        analyzer._check(analyzer.L.vamd_decode_ogg_live_create(analyzer.h, self.max_streams, C.byref(opts), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.an.L.vamd_decode_ogg_live_destroy(self.h)
+            self.h = None
+            if self in self.an._live:
+                self.an._live.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def prepare(self, slots, pieces, close=(), piece_offset=None):
+        """The descriptor of a call (vamd_decode_ogg_live_desc) with the host arrays it points into.  slots: the slots this
+        call names; pieces[i]: the next bytes of slot slots[i]'s stream -- any number of them, none included; close: the slots
+        whose stream ends with this piece.  piece_offset: a test hook, the descriptor's array as given."""
+        an = self.an
+        an._need(self.h is not None, "live Ogg decoder: closed")
+        an._need(len(slots) == len(pieces), "live Ogg decoder: one piece per slot")
+        for p in pieces:
+            an._need(isinstance(p, (bytes, bytearray, memoryview)), "live Ogg decoder: a piece must be bytes")
+        ns = len(slots)
+        data = np.frombuffer(b"".join(bytes(p) for p in pieces) + b"\0" * 8, np.uint8)
+        off = np.zeros(ns + 1, np.int64)
+        np.cumsum(np.array([len(p) for p in pieces], np.int64), out=off[1:])
+        if piece_offset is not None:
+            off = np.ascontiguousarray(piece_offset, np.int64)
+            an._need(off.size == ns + 1, "live Ogg decoder: piece_offset must hold nstreams + 1 values")
+        slot = np.array([int(s) for s in slots] + [0], np.int64)  # (never an empty array: its pointer is read as non-null)
+        closing = set(int(s) for s in close)
+        an._need(closing <= set(int(s) for s in slots), "live Ogg decoder: a closing slot that this call does not name")
+        cl = np.array([int(s) in closing for s in slots] + [0], np.uint8)
+        d = _DecodeOggLiveDesc(ns, _vp(slot.ctypes.data), _vp(data.ctypes.data), _vp(off.ctypes.data), _vp(cl.ctypes.data))
+        return dict(desc=d, keep=(data, off, slot, cl), nstreams=ns)
+
+    def run(self, prep, pcm=None):
+        """vamd_decode_ogg_live_plan + vamd_decode_ogg_live_wrote over prepare()'s descriptor; pcm and the result as
+        Analyzer.decode_run's: (pcm, frames, offset, status)"""
+        an, h = self.an, self.h
+        an._need(h is not None, "live Ogg decoder: closed")
+        return an._decode_run(lambda _, *a: an.L.vamd_decode_ogg_live_plan(h, *a), lambda _, *a: an.L.vamd_decode_ogg_live_wrote(h, *a), prep, pcm)
+
+    def write(self, slots, pieces, close=(), with_status=False):
+        """The next bytes of each named slot's stream -> a list of float32 tensors [ch, frames] on the context's device, one
+        per slot of the call: the samples of the audio packets those bytes complete; a dead stream -- one that has been
+        flagged -- gives [ch, 0] until a piece closes it.  with_status, also the status bytes (numpy uint8)."""
+        return self.an._decoded_tensors(len(slots), *self.run(self.prepare(slots, pieces, close)), with_status)
 
 
 def decode(setup_blob, streams, granules=None, with_status=False, device=None):

@@ -67,7 +67,48 @@ VAMD_OGG_FN void ogg_depage_copy(const uint8_t *src, uint8_t *dst, int64_t n, in
   for (int64_t i = lane; i < words; i += lanes) wd[i] = ogg_alignbytes(sh ? ogg_load32(wp + 4 * i + 4) : 0u, ogg_load32(wp + 4 * i), sh);
 }
 
+// A row of the live Ogg decoder's two byte-carry tables (vamd_demux_live.h): the audio packet a stream's whole pages have
+// left open lies in the slot's row of the carry, [slots][stride] bytes with stride a multiple of 4, so every row begins
+// on a dword.  `len` bytes of it are, or go to, arena[at ..].
+struct OggCarryRow {
+  int64_t at;
+  int32_t slot, len;
+};
+// the row is trusted no further than the two buffers reach
+VAMD_OGG_FN bool ogg_carry_inside(const OggCarryRow &r, int64_t arena_bytes, int64_t slots, int64_t stride) {
+  if (stride < 0 || (stride & 3) || r.slot < 0 || r.slot >= slots || r.len < 0 || r.len > stride) return false;
+  return r.at >= 0 && r.at <= arena_bytes && arena_bytes - r.at >= r.len;
+}
+// A lane's share of a row, one body for both directions: in, the carried bytes to the front of the stream's region of the
+// arena; out, the open packet's bytes at the end of that region back to the slot's row.  ogg_depage_copy's guarantee
+// holds: a carry row begins on a dword and belongs to one wave, so its whole dwords and its last bytes are that wave's; in
+// the arena the up to three bytes at either edge share their dwords with the neighbouring runs and are written as bytes.
+VAMD_OGG_FN void ogg_packet_carry(bool out, const OggCarryRow &r, uint8_t *arena, uint8_t *carry, int64_t stride, int lane, int lanes) {
+  uint8_t *row = carry + (int64_t)r.slot * stride;
+  if (out) ogg_depage_copy(arena + r.at, row, r.len, lane, lanes);
+  else ogg_depage_copy(row, arena + r.at, r.len, lane, lanes);
+}
+
 #if defined(__HIPCC__)
+// The live Ogg decoder's byte carries, a wave per row, around k_ogg_depage on the context's stream:
+//   k_ogg_packet_carry_in   carry[slot] -> arena[at ..]   the bytes of the packet the slot's earlier pages left open
+//   k_ogg_depage                                          this call's whole pages behind them
+//   k_ogg_packet_carry_out  arena[at ..] -> carry[slot]   the bytes of the packet still open behind this call's pages
+// A packet open across a whole piece goes carry -> arena -> carry, its new bytes joined to the old ones in the arena.
+// The three launches are on one stream, so each sees what the one before it wrote: carry_out reads bytes that carry_in and
+// k_ogg_depage have written, and writes a row that carry_in (the only reader of the carry in a call) has already read.
+// Inside one launch no two rows name the same slot or overlapping runs of the arena (the host's walk lays them out).
+__global__ __launch_bounds__(64) void k_ogg_packet_carry_in(const OggCarryRow *__restrict__ rows, uint8_t *arena, int64_t arena_bytes, uint8_t *carry,
+                                                            int64_t slots, int64_t stride) {
+  const OggCarryRow r = rows[blockIdx.x];
+  if (ogg_carry_inside(r, arena_bytes, slots, stride)) ogg_packet_carry(false, r, arena, carry, stride, threadIdx.x, 64);
+}
+__global__ __launch_bounds__(64) void k_ogg_packet_carry_out(const OggCarryRow *__restrict__ rows, uint8_t *arena, int64_t arena_bytes, uint8_t *carry,
+                                                             int64_t slots, int64_t stride) {
+  const OggCarryRow r = rows[blockIdx.x];
+  if (ogg_carry_inside(r, arena_bytes, slots, stride)) ogg_packet_carry(true, r, arena, carry, stride, threadIdx.x, 64);
+}
+
 // A wave per row of the page table (vamd_demux.h), files as they lay in host memory: the page's checksum -- every lane its
 // chunk (ogg_crc_range over header + lacing + body), the tree's six steps, the table in LDS -- against the stored field,
 // BADCRC into the page's status byte where they differ; and the page's audio bytes to their place in the packed arena
@@ -124,6 +165,14 @@ inline uint8_t ogg_depage_host(const uint8_t *files, int64_t files_bytes, const 
   }
   for (int l = 0; l < lanes && pg.body > pg.skip; l++) ogg_depage_copy(page + hlen + pg.skip, arena + pg.dst, pg.body - pg.skip, l, lanes);
   return part[0] == ogg_le32(page + 22) ? 0 : OGG_DEPAGE_BADCRC;
+}
+// k_ogg_packet_carry_in's (out = false) or _out's work on one row, the lanes in turn (tests/c/demux_live_host.cpp) -> false
+// for a row outside the buffers, which is left alone
+inline bool ogg_packet_carry_host(bool out, const OggCarryRow &r, uint8_t *arena, int64_t arena_bytes, uint8_t *carry, int64_t slots, int64_t stride,
+                                  int lanes) {
+  if (!ogg_carry_inside(r, arena_bytes, slots, stride)) return false;
+  for (int l = 0; l < lanes; l++) ogg_packet_carry(out, r, arena, carry, stride, l, lanes);
+  return true;
 }
 #endif
 

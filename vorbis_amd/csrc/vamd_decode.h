@@ -9,6 +9,8 @@
 // checksum and moves the audio bytes into the same packed arena -- from k_unpack on the two entries are one function.
 // The live decoder (vamd_decode_live.h) takes the next pieces of continuing streams through the same function, with the
 // blocks carried between pieces standing in the plan and two carry kernels between k_synth and k_lap (DecodeCarry).
+// The live Ogg decoder (vamd_decode_ogg_live.h) takes the next BYTES of continuing Ogg streams: both of the above at once,
+// with the packet that whole pages leave open carried on the device by two more kernels around k_ogg_depage.
 //
 // Workspace per block, in the context, grown on demand and released with it (ch channels, n the block's size, S submaps):
 //   rows     4 ch (post_valid) + ch n/2 (the integer curves) + S * 2048 (res_class) + 2 * vamd_residue_capacity
@@ -21,6 +23,7 @@
 #include "vamd_decode_plan.h"
 #include "vamd_decode_live_plan.h"
 #include "vamd_demux.h"
+#include "vamd_demux_live.h"
 
 static_assert(OGG_DEPAGE_BADCRC == VAMD_STATUS_BADPAGE, "k_ogg_depage's status byte is the stream's");
 
@@ -98,6 +101,8 @@ int vamd_decode_plan(vamd_ctx *c, const vamd_decode_desc *d, int64_t *frames, in
 // caller's host memory as they are (the packet entry), or the files' pages by way of k_ogg_depage (the Ogg entry).
 struct DecodeInput {
   const int64_t *offset = nullptr;   // [npackets + 1] bytes; the arena is [byte0, byte0 + nbytes) of this numbering
+  const int64_t *begin = nullptr;    // or [npackets]: where each packet begins, where they do not lie back to back (offset[]
+                                     // then gives the lengths alone: a live Ogg call's arena, vamd_demux_live.h)
   int64_t byte0 = 0, nbytes = 0;
   const uint8_t *packets = nullptr;  // the packet entry: the arena in host memory, from byte0 on
   const DemuxScan *scan = nullptr;   // the Ogg entry: the page table, the pages' streams ...
@@ -110,6 +115,10 @@ struct DecodeInput {
 struct DecodeCarry {
   const DecodeLivePlan *plan = nullptr;
   float *carry = nullptr;
+  // the live Ogg decoder's byte carry (vamd_decode_ogg_live.h): k_ogg_packet_carry_in ahead of k_ogg_depage, _out behind it
+  const std::vector<OggCarryRow> *bytes_in = nullptr, *bytes_out = nullptr;
+  uint8_t *bytes_carry = nullptr;  // [slots][stride]
+  int64_t slots = 0, stride = 0;
 };
 
 // The tail all entries share, behind a plan that holds and statuses the host has already set: workspace, the plan's
@@ -124,6 +133,7 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
   const std::vector<int64_t> &unpack_start = live ? live->plan->unpack_start : P.lap_start;
   const size_t nb = unpack.size(), nlap = P.order.size(), npg = in.scan ? in.scan->pages.size() : 0;
   const size_t nin = live ? live->plan->in.size() : 0, nout = live ? live->plan->out.size() : 0;
+  const size_t nbin = live && live->bytes_in ? live->bytes_in->size() : 0, nbout = live && live->bytes_out ? live->bytes_out->size() : 0;
   if (!nb && !npg) return VAMD_OK;
   vamd_ctx::Decode &D = c->dec;
   const int ch = c->B.channels;
@@ -149,12 +159,12 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
     src[W].res_entries = rows[W].res_entries, src[W].res_count = rows[W].res_count;
   }
   // the plan, one piece: order | stream_start | src per size class | the packets' bits | frames | offset_out | the page table
-  // | a live call's list for k_unpack and its two carry tables
+  // | a live call's list for k_unpack and its two carry tables | a live Ogg call's two byte-carry tables
   Arena a;
   const size_t o_order = a.take(4 * nlap), o_start = a.take(8 * ((size_t)ns + 1)), o_src0 = a.take(8 * P.src[0].size() + 8),
                o_src1 = a.take(8 * P.src[1].size() + 8), o_bits = a.take(16 * nb), o_frames = a.take(8 * (size_t)ns), o_off = a.take(8 * (size_t)ns),
                o_pages = a.take(sizeof(OggDepage) * npg), o_unpack = live ? a.take(4 * nb) : o_order, o_in = a.take(sizeof(CarryRow) * nin),
-               o_out = a.take(sizeof(CarryRow) * nout);
+               o_out = a.take(sizeof(CarryRow) * nout), o_bin = a.take(sizeof(OggCarryRow) * nbin), o_bout = a.take(sizeof(OggCarryRow) * nbout);
   const size_t plan_bytes = a.at, o_status = a.take(nb + npg);
   if ((r = pinned_get(c, D.h_plan, a.at, true))) return r;
   if ((r = dev_need(c, D.plan, plan_bytes))) return r;
@@ -163,13 +173,16 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
   if (live && nb) memcpy(h + o_unpack, unpack.data(), 4 * nb);
   if (nin) memcpy(h + o_in, live->plan->in.data(), sizeof(CarryRow) * nin);
   if (nout) memcpy(h + o_out, live->plan->out.data(), sizeof(CarryRow) * nout);
+  if (nbin) memcpy(h + o_bin, live->bytes_in->data(), sizeof(OggCarryRow) * nbin);
+  if (nbout) memcpy(h + o_bout, live->bytes_out->data(), sizeof(OggCarryRow) * nbout);
   memcpy(h + o_start, P.lap_start.data(), 8 * ((size_t)ns + 1));
   if (!P.src[0].empty()) memcpy(h + o_src0, P.src[0].data(), 8 * P.src[0].size());
   if (!P.src[1].empty()) memcpy(h + o_src1, P.src[1].data(), 8 * P.src[1].size());
   for (size_t k = 0; k < nb; k++) {
     const int64_t p = P.packet[k];
-    ((int64_t *)(h + o_bits))[2 * k] = 8 * (in.offset[p] - byte0);
-    ((int64_t *)(h + o_bits))[2 * k + 1] = 8 * (in.offset[p + 1] - byte0);
+    const int64_t at = in.begin ? in.begin[p] : in.offset[p];
+    ((int64_t *)(h + o_bits))[2 * k] = 8 * (at - byte0);
+    ((int64_t *)(h + o_bits))[2 * k + 1] = 8 * (at + (in.offset[p + 1] - in.offset[p]) - byte0);
   }
   memcpy(h + o_frames, P.frames.data(), 8 * (size_t)ns);
   for (int64_t s = 0; s < ns; s++) ((int64_t *)(h + o_off))[s] = P.frames[(size_t)s] > 0 ? offset_out[s] : 0;
@@ -178,8 +191,14 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
   HIP_TRY(c, hipMemcpyAsync(dp, h, plan_bytes, hipMemcpyHostToDevice, s));
   if (npg) {
     HIP_TRY(c, hipMemcpyAsync(D.files.p, in.files, (size_t)in.files_bytes, hipMemcpyHostToDevice, s));
+    if (nbin)
+      hipLaunchKernelGGL(k_ogg_packet_carry_in, dim3((unsigned)nbin), dim3(64), 0, s, (const OggCarryRow *)(dp + o_bin), (uint8_t *)D.bytes.p, nbytes,
+                         live->bytes_carry, live->slots, live->stride);
     hipLaunchKernelGGL(k_ogg_depage, dim3((unsigned)npg), dim3(64), 0, s, (const uint8_t *)D.files.p, in.files_bytes, (const OggDepage *)(dp + o_pages),
                        (uint8_t *)D.bytes.p, nbytes, (uint8_t *)D.status.p + nb);
+    if (nbout)
+      hipLaunchKernelGGL(k_ogg_packet_carry_out, dim3((unsigned)nbout), dim3(64), 0, s, (const OggCarryRow *)(dp + o_bout), (uint8_t *)D.bytes.p, nbytes,
+                         live->bytes_carry, live->slots, live->stride);
     HIP_TRY(c, hipGetLastError());
   } else if (nbytes) {
     HIP_TRY(c, hipMemcpyAsync(D.bytes.p, in.packets, (size_t)nbytes, hipMemcpyHostToDevice, s));

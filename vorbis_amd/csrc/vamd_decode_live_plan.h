@@ -30,13 +30,16 @@ struct DecodeLivePlan {
 
 // -> false with a reason for a bad descriptor.  Reads `slots` ([max_streams]) and changes nothing.  Every index the two
 // carry kernels use -- the slots, the extra rows, the last blocks' rows -- is set here and checked before it returns.
+// first: NULL, or per packet its first byte, as decode_plan_build takes them (the live Ogg decoder's packets lie together
+// on the device alone: vamd_demux_live.h); `bytes` is not read then.
 inline bool decode_live_plan_build(const int bs[2], int modes, int modebits, const std::vector<LiveSlot> &slots, int64_t nstreams, int64_t npackets,
                                    const int64_t *slot, const uint8_t *bytes, const int64_t *offset, const int64_t *stream_start,
-                                   const uint8_t *close, const int64_t *end_granule, DecodeLivePlan *L, std::string *err) {
+                                   const uint8_t *close, const int64_t *end_granule, DecodeLivePlan *L, std::string *err,
+                                   const uint8_t *first = nullptr) {
   *L = DecodeLivePlan();
   DecodePlan &P = L->P;
   const int64_t max_streams = (int64_t)slots.size();
-  if (!decode_desc_check(nstreams, npackets, bytes, offset, stream_start, end_granule, nullptr, err)) return false;
+  if (!decode_desc_check(nstreams, npackets, bytes, offset, stream_start, end_granule, first, err)) return false;
   if (nstreams > max_streams) return *err = "decode_live: more streams than the decoder has slots", false;
   if (nstreams && !slot) return *err = "decode_live: null slot", false;
   std::vector<uint8_t> named((size_t)max_streams, 0);
@@ -60,7 +63,7 @@ inline bool decode_live_plan_build(const int bs[2], int modes, int modebits, con
     cls.clear();
     uint8_t st = now.dead;
     for (int64_t p = p0; p < p1; p++) {
-      const int W = decode_packet_class(bytes + offset[p], offset[p + 1] - offset[p], modes, modebits);
+      const int W = decode_packet_class(first ? first + p : bytes + offset[p], offset[p + 1] - offset[p], modes, modebits);
       if (W < 0) st |= (uint8_t)-W;
       cls.push_back(W);
     }

@@ -46,6 +46,7 @@
 #include "vamd_decode_live_plan.h"
 #define VAMD_OGG_NO_FEED_KERNELS  // (k_ogg.h: k_ogg_plan / _pages / _carry are vamd_feed.hip's)
 #include "vamd_demux.h"
+#include "vamd_demux_live.h"
 
 using namespace vamd;
 
@@ -303,6 +304,7 @@ int vamd_envelope_geometry(const vamd_ctx *c, int *winlength, int *searchstep) {
 #include "vamd_batch.h"  // workspace planning, the launch sequence, the batch entry points
 #include "vamd_decode.h" // the packet decoder: plan on the host, k_unpack ahead of k_synth and k_lap
 #include "vamd_decode_live.h"  // ... and continuing streams in pieces: the lap carried between calls
+#include "vamd_decode_ogg_live.h"  // ... and their Ogg bytes in pieces, cut anywhere: open packets carried too
 #include "vamd_plan.h"   // the detector over streams, the walk, the plans
 #include "vamd_block.h"  // the host-pointer calls: a block, a look-ahead's blocks, a detector call
 
