@@ -709,7 +709,7 @@ int vamd_decode_live_wrote(vamd_decode_live *d, const vamd_decode_live_desc *des
  * DELIBERATE DEVIATIONS: libogg resynchronises behind a damaged page and reports a hole, and libvorbis decodes on out of
  * lap; here the stream is flagged.  A chained or multiplexed file is flagged BADPAGE at its second serial number, not
  * decoded.  Out of scope, as above: setups other than the context's (the setup header is compared, not parsed), streams
- * that begin at a nonzero granule, files that start in device memory, seeking. */
+ * that begin at a nonzero granule, files that start in device memory.  Seeking: "windows", below. */
 #define VAMD_STATUS_BADPAGE   32
 #define VAMD_STATUS_BADHEADER 64
 typedef struct vamd_decode_ogg_desc {
@@ -722,6 +722,76 @@ typedef struct vamd_decode_ogg_desc {
 int vamd_decode_ogg_plan(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
 int vamd_decode_ogg(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, const int64_t *offset_out /* host [nstreams] */,
                     float *pcm /* device */, uint8_t *status /* host [nstreams] */);
+
+/* ---- windows of streams and of Ogg files: a seek index, crops on the device (still ABI 9: additions only).  A caller who
+ * wants a second out of each of a hundred files pays for that second: a window's frames are, bit for bit, the same frames
+ * of the whole decode above (and therefore libvorbis'), out of the window's own blocks plus one
+ * (tests/test_decode_window_cpu.py, tests/test_decode_window_gpu.py).
+ *
+ * One rule for both entries.  Stream s has T[s] frames, as vamd_decode_plan / vamd_decode_ogg_plan give them, the end
+ * granule's cut included.  Window w names stream[w], start[w] >= 0 and count[w] >= 0; with a = min(start, T) and
+ * b = min(start + count, T) it has frames[w] = b - a frames, channel c frame k at pcm[offset_out[w] + c * frames[w] + k] --
+ * channel c, frame a + k of the whole decode of that stream.  Several windows of a call may name one stream, overlap, and
+ * come in any order.  The blocks taken are the FEWEST: with the stream's block centres C_0 = 0 < C_1 < ..., kA the first k
+ * with C_k > a and kB the first with C_k > b - 1, blocks kA - 1 .. kB and no others (a Vorbis block depends on its own
+ * packet alone, and a frame between two centres on those two blocks).  An empty window takes no block, no page and no
+ * byte.  nblocks[2] of the plan calls: the blocks taken per size class, summed over the windows -- a block two windows
+ * share is unpacked once per window; no work is shared across windows.
+ *
+ *   vamd_decode_window_plan / vamd_decode_window   packets as vamd_decode_desc lays them (all of the streams' packets: the
+ *     host reads their first bytes for the centres), and the window list.  Only the packets of the windows' blocks go up;
+ *     then k_unpack and k_synth as above and k_lap_window, k_lap's gather with a first frame per window.
+ *   vamd_ogg_index_create   one walk of the files and one block plan, kept: per stream the status (the host's bits:
+ *     BADPAGE for the container's structure, BADHEADER, NOTAUDIO / an empty packet), T, the file's length, the page rows,
+ *     the packet table with first bytes and centres.  It holds no pointer into the caller's bytes.  vamd_ogg_index_info
+ *     gives nstreams, frames[] and status[] (any may be NULL).  Destroy an index before its context.
+ *   vamd_decode_ogg_window_plan / vamd_decode_ogg_window   the caller hands the SAME files again (bytes, file_offset; the
+ *     offsets may differ from create's, the lengths may not) and the window list.  Per window the host picks the pages
+ *     from the one in which packet kA - 1 begins through the one that holds packet kB's last byte, copies exactly those
+ *     pages into a pinned staging buffer of the context (grown on demand, released with it) and uploads them in one copy;
+ *     k_ogg_depage runs over those rows alone; whole page bodies go to the arena and the window's packets are addressed
+ *     inside them.  No host work is proportional to the file: a window call never walks pages again.  The plan call's
+ *     staged[2] (or NULL): the bytes the call uploads and the pages they are.
+ *     channel_stride: NULL, or host [nwindows] -- channel c of window w then lies at offset_out[w] + c * channel_stride[w]
+ *     (>= frames[w]): a crop's row of fixed length whose tail the file's end cut stays as the caller left it.
+ *
+ * status[w]: a stream the index (or the packets' heads) flagged has T = 0; its windows have no frames and carry its bits.
+ * What the device finds -- a page's checksum, BADCODE, TRUNCATED -- is reported for the pages and packets the window USES
+ * and costs that window its frames, and no other window.  A DELIBERATE DEVIATION: damage outside a window is not seen by
+ * that window, though a whole decode of the file would flag the stream.  A file that changed since the index was made:
+ * another length is VAMD_EINVAL; other content of the same length is caught by the page checksums or the codebooks and
+ * flagged -- every offset used is the index's and lies inside the recorded length, and ogg_depage_inside bounds the device
+ * side -- never read out of range.
+ *
+ * VAMD_EINVAL with a reason, nothing enqueued: null pointers; negative nwindows; a stream out of range; start or count
+ * negative or above 2^62; file offsets not monotone or lengths differing from the index's; an index of another context; a
+ * channel stride below its window's frames.  VAMD_EIMPL as vamd_decode_plan gives it (at create already).  Every index
+ * the kernels use is computed and range-checked on the host before the first launch.
+ *
+ * Out of scope: streams that begin at a nonzero granule; chained files; an index built without a full walk of the files;
+ * bytes in device memory. */
+typedef struct vamd_ogg_index vamd_ogg_index;
+typedef struct vamd_ogg_window_desc {
+  int64_t nwindows;
+  const int64_t *stream;          /* host [nwindows]: the file of the index */
+  const int64_t *start;           /* host [nwindows] */
+  const int64_t *count;           /* host [nwindows] */
+  const uint8_t *bytes;           /* HOST: the index's files again, back to back */
+  const int64_t *file_offset;     /* host [nstreams + 1] */
+  const int64_t *channel_stride;  /* or NULL: frames[w] */
+} vamd_ogg_window_desc;
+int vamd_decode_window_plan(vamd_ctx *ctx, const vamd_decode_desc *desc, int64_t nwindows, const int64_t *stream, const int64_t *start,
+                            const int64_t *count, int64_t *frames /* host [nwindows] */, int64_t *nblocks /* [2] */);
+int vamd_decode_window(vamd_ctx *ctx, const vamd_decode_desc *desc, int64_t nwindows, const int64_t *stream, const int64_t *start,
+                       const int64_t *count, const int64_t *offset_out /* host [nwindows] */, float *pcm /* device */,
+                       uint8_t *status /* host [nwindows] */);
+int vamd_ogg_index_create(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, vamd_ogg_index **out);
+void vamd_ogg_index_destroy(vamd_ogg_index *index);
+int vamd_ogg_index_info(const vamd_ogg_index *index, int64_t *nstreams, int64_t *frames /* host [nstreams] */, uint8_t *status /* host [nstreams] */);
+int vamd_decode_ogg_window_plan(vamd_ctx *ctx, const vamd_ogg_index *index, const vamd_ogg_window_desc *desc, int64_t *frames /* host [nwindows] */,
+                                int64_t *nblocks /* [2] */, int64_t *staged /* or NULL; [2] */);
+int vamd_decode_ogg_window(vamd_ctx *ctx, const vamd_ogg_index *index, const vamd_ogg_window_desc *desc,
+                           const int64_t *offset_out /* host [nwindows] */, float *pcm /* device */, uint8_t *status /* host [nwindows] */);
 
 /* ---- the live Ogg decoder: continuing Ogg Vorbis streams decoded in pieces of BYTES (still ABI 9: additions only).  The
  * counterpart of a live Ogg feed (vamd_feed_ogg_headers_live / vamd_feed_ogg, with or without vamd_feed_ogg_flush), of a

@@ -67,6 +67,11 @@ class _DecodeOggDesc(C.Structure):  # vamd_decode_ogg_desc
     _fields_ = [("nstreams", C.c_int64), ("bytes", _vp), ("file_offset", _vp), ("setup_header", _vp), ("setup_header_bytes", C.c_int64)]
 
 
+class _OggWindowDesc(C.Structure):  # vamd_ogg_window_desc
+    _fields_ = [("nwindows", C.c_int64), ("stream", _vp), ("start", _vp), ("count", _vp), ("bytes", _vp), ("file_offset", _vp),
+                ("channel_stride", _vp)]
+
+
 class _DecodeOggLiveOpts(C.Structure):  # vamd_decode_ogg_live_opts
     _fields_ = [("setup_header", _vp), ("setup_header_bytes", C.c_int64), ("max_packet_bytes", C.c_int64), ("max_header_bytes", C.c_int64)]
 
@@ -112,6 +117,7 @@ _pvp, _pint, _plong, _pfloat, _pi32 = C.POINTER(_vp), C.POINTER(C.c_int), C.POIN
 _pDesc, _pIO, _pMIO, _pPlan, _pDecode = C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO), C.POINTER(_Plan), C.POINTER(_DecodeDesc)
 _pDecodeOgg, _pDecodeLive = C.POINTER(_DecodeOggDesc), C.POINTER(_DecodeLiveDesc)
 _pDecodeOggLive, _pDecodeOggLiveOpts = C.POINTER(_DecodeOggLiveDesc), C.POINTER(_DecodeOggLiveOpts)
+_pOggWindow = C.POINTER(_OggWindowDesc)
 _vp2 = _vp * 2
 _block = [_vp, _pvp, _int, _int, _int, _int, _float]   # (ctx, pcm[ch], lW, W, nW, blocktype, ampmax_in): how every per-block call begins
 
@@ -157,6 +163,13 @@ PROTOTYPES = {
     "vamd_decode_live_wrote": (_int, [_vp, _pDecodeLive, _vp, _vp, _vp]),
     "vamd_decode_ogg_plan": (_int, [_vp, _pDecodeOgg, _vp, _vp]),
     "vamd_decode_ogg": (_int, [_vp, _pDecodeOgg, _vp, _vp, _vp]),
+    "vamd_decode_window_plan": (_int, [_vp, _pDecode, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "vamd_decode_window": (_int, [_vp, _pDecode, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vamd_ogg_index_create": (_int, [_vp, _pDecodeOgg, _pvp]),
+    "vamd_ogg_index_destroy": (None, [_vp]),
+    "vamd_ogg_index_info": (_int, [_vp, _vp, _vp, _vp]),
+    "vamd_decode_ogg_window_plan": (_int, [_vp, _vp, _pOggWindow, _vp, _vp, _vp]),
+    "vamd_decode_ogg_window": (_int, [_vp, _vp, _pOggWindow, _vp, _vp, _vp]),
     "vamd_decode_ogg_live_create": (_int, [_vp, C.c_int64, _pDecodeOggLiveOpts, _pvp]),
     "vamd_decode_ogg_live_destroy": (None, [_vp]),
     "vamd_decode_ogg_live_plan": (_int, [_vp, _pDecodeOggLive, _vp, _vp]),

@@ -1,6 +1,6 @@
 """vamd_ctx in Python: the Analyzer -- batches, streams, plans, the bitrate manager's candidates, the detector, the packet
 decoder for packets and for Ogg files, the LiveDecoder and the LiveOggDecoder for continuing streams in pieces of packets and
-of Ogg bytes -- and decode() / decode_ogg() for
+of Ogg bytes; OggIndex, windows of files -- and decode() / decode_ogg() / ogg_index() for
 a caller who holds packets or files and no context."""
 import ctypes as C
 
@@ -8,7 +8,7 @@ import numpy as np
 
 from .abi import (ABI_VERSION, BLOCKTYPE_LONG, LEVEL_FULL, LEVEL_PSY, LEVEL_TRANSFORM, PACKETBLOBS, POSTS_STRIDE, QUANT_LIMIT_INT,
                   QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_RANGE, VAMD_EDOMAIN, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
-                  _DecodeDesc, _DecodeLiveDesc, _DecodeOggDesc, _DecodeOggLiveDesc, _DecodeOggLiveOpts, _Desc, _IO, _MIO, _Plan, _vp, load_library)
+                  _DecodeDesc, _DecodeLiveDesc, _DecodeOggDesc, _DecodeOggLiveDesc, _DecodeOggLiveOpts, _Desc, _OggWindowDesc, _IO, _MIO, _Plan, _vp, load_library)
 from .packets import packet_bytes
 
 
@@ -741,6 +741,54 @@ class Analyzer:
         bits -- has no frames."""
         return self._decoded_tensors(len(files), *self.decode_ogg_run(self.decode_ogg_prepare(files, setup_header, file_offset)), with_status)
 
+    @staticmethod
+    def _window_arrays(stream, start, count):
+        """the three int64 lists of a window call, one entry per window (never empty arrays: their pointers are read as non-null)"""
+        cols = [np.array([int(v) for v in col] + [0], np.int64) for col in (stream, start, count)]
+        return len(stream), cols
+
+    def _window_run(self, plan, run, nw, pcm, stride=None):
+        """a window call's plan call, output tensor and decode call: _decode_run with a window per "stream".  stride: None, or
+        every window's channel stride in a pcm the caller made (window w at w * channels * stride)"""
+        t = self.torch
+        frames, nblocks = np.zeros(max(nw, 1), np.int64), np.zeros(2, np.int64)
+        self._check(plan(_vp(frames.ctypes.data), _vp(nblocks.ctypes.data)))
+        per = frames if stride is None else np.full(max(nw, 1), int(stride), np.int64)
+        out_off = np.zeros(max(nw, 1), np.int64)
+        if nw > 1:
+            out_off[1:nw] = np.cumsum(per[:nw - 1] * self.channels)
+        total = int((per[:nw] * self.channels).sum())
+        if pcm is None:
+            pcm = t.zeros(total + 4, dtype=t.float32, device=self._dev())
+        self._need_tensor(pcm, t.float32, "pcm")
+        self._need(pcm.numel() >= total, "pcm must hold %d floats" % total)
+        status = np.zeros(max(nw, 1), np.uint8)
+        self._bind_stream()
+        self._check(run(_vp(out_off.ctypes.data), _vp(pcm.data_ptr()), _vp(status.ctypes.data)))
+        return pcm, frames[:nw], out_off[:nw], status[:nw]
+
+    def decode_window(self, streams, granules, stream, start, count, with_status=False, offset=None, stream_start=None):
+        """vamd_decode_window_plan + vamd_decode_window: windows of packet streams.  streams / granules (or None) as
+        decode_streams() takes them; window w is frames [start[w], start[w] + count[w]) of streams[stream[w]], cut to the
+        stream's end.  Only the packets of the blocks a window needs go up.  -> a list of float32 tensors [ch, frames], one
+        per window, bit for bit those frames of decode_streams()'s tensors; with_status, also the windows' status bytes."""
+        self._need(len(stream) == len(start) == len(count), "decode_window: stream, start and count must be as long as each other")
+        prep = self.decode_prepare(streams, granules, offset, stream_start)
+        nw, (ws, wa, wc) = self._window_arrays(stream, start, count)
+        args = (self.h, C.byref(prep["desc"]), nw, _vp(ws.ctypes.data), _vp(wa.ctypes.data), _vp(wc.ctypes.data))
+        res = self._window_run(lambda *a: self.L.vamd_decode_window_plan(*args, *a), lambda *a: self.L.vamd_decode_window(*args, *a), nw, None)
+        return self._decoded_tensors(nw, *res, with_status)
+
+    def ogg_index(self, files, setup_header=None, file_offset=None):
+        """vamd_ogg_index_create: one walk of whole Ogg Vorbis files, kept -> an OggIndex, whose decode() / crops() give
+        windows of those files without walking or uploading them whole again.  files / setup_header / file_offset as
+        decode_ogg() takes them; the index keeps the files' bytes (one joined copy).  Closing the Analyzer closes it."""
+        if not hasattr(self, "_live"):
+            self._live = []
+        x = OggIndex(self, files, setup_header, file_offset)
+        self._live.append(x)
+        return x
+
     def analyze_block(self, pcm, lW=1, W=1, nW=1, blocktype=BLOCKTYPE_LONG, ampmax_in=-9999.0):
         """vamd_analyze_block: host numpy pcm[ch][n] in, host numpy results out (the per-block
         compatibility path that sits behind vorbis_analysis())."""
@@ -1026,6 +1074,92 @@ class LiveOggDecoder:
         per slot of the call: the samples of the audio packets those bytes complete; a dead stream -- one that has been
         flagged -- gives [ch, 0] until a piece closes it.  with_status, also the status bytes (numpy uint8)."""
         return self.an._decoded_tensors(len(slots), *self.run(self.prepare(slots, pieces, close)), with_status)
+
+
+class OggIndex:
+    """vamd_ogg_index: the seek index of a group of Ogg Vorbis files (Analyzer.ogg_index).  frames[s] and status[s] are what
+    a whole decode_ogg() plans for file s on the host; decode() and crops() give windows of the files, bit for bit the same
+    frames of the whole decode.  Damage outside a window's own pages is not seen by that window."""
+
+    def __init__(self, analyzer, files, setup_header=None, file_offset=None, own=False):
+        self.an, self._own, self.h = analyzer, own, None
+        prep = analyzer.decode_ogg_prepare(files, setup_header, file_offset)
+        self._data, self._off = prep["keep"][0], prep["keep"][1]
+        self.nstreams = prep["nstreams"]
+        h = _vp()
+        analyzer._check(analyzer.L.vamd_ogg_index_create(analyzer.h, C.byref(prep["desc"]), C.byref(h)))
+        self.h = h
+        self.frames, self.status = np.zeros(max(self.nstreams, 1), np.int64), np.zeros(max(self.nstreams, 1), np.uint8)
+        analyzer._check(analyzer.L.vamd_ogg_index_info(h, None, _vp(self.frames.ctypes.data), _vp(self.status.ctypes.data)))
+        self.frames, self.status = self.frames[:self.nstreams], self.status[:self.nstreams]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.an.L.vamd_ogg_index_destroy(self.h)
+            self.h = None
+            if self in getattr(self.an, "_live", ()):
+                self.an._live.remove(self)
+            if self._own:
+                self.an.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _run(self, stream, start, count, pcm=None, stride=None, files=None, file_offset=None):
+        """vamd_decode_ogg_window_plan + vamd_decode_ogg_window -> (pcm, frames, offset, status) per window.  files /
+        file_offset: test hooks, other bytes than the index was made of."""
+        an = self.an
+        an._need(self.h is not None, "ogg index: closed")
+        an._need(len(stream) == len(start) == len(count), "ogg index: stream, start and count must be as long as each other")
+        data, off = self._data, self._off
+        if files is not None:
+            data = np.frombuffer(b"".join(bytes(f) for f in files) + b"\0" * 8, np.uint8)
+            off = np.zeros(len(files) + 1, np.int64)
+            np.cumsum(np.array([len(f) for f in files], np.int64), out=off[1:])
+            an._need(len(files) == self.nstreams, "ogg index: as many files as the index has")
+        if file_offset is not None:
+            off = np.ascontiguousarray(file_offset, np.int64)
+            an._need(off.size == self.nstreams + 1, "ogg index: file_offset must hold nstreams + 1 values")
+        nw, (ws, wa, wc) = an._window_arrays(stream, start, count)
+        cs = np.full(max(nw, 1), int(stride), np.int64) if stride is not None else None
+        d = _OggWindowDesc(nw, _vp(ws.ctypes.data), _vp(wa.ctypes.data), _vp(wc.ctypes.data), _vp(data.ctypes.data), _vp(off.ctypes.data),
+                           _vp(cs.ctypes.data) if cs is not None else None)
+        args = (an.h, self.h, C.byref(d))
+        return an._window_run(lambda *a: an.L.vamd_decode_ogg_window_plan(*args, *a, None), lambda *a: an.L.vamd_decode_ogg_window(*args, *a), nw, pcm, stride)
+
+    def decode(self, stream, start, count, with_status=False, files=None, file_offset=None):
+        """Window w = frames [start[w], start[w] + count[w]) of file stream[w], cut to the file's end -> a list of float32
+        tensors [ch, frames] on the context's device, one per window; a flagged window has no frames.  with_status, also
+        the windows' status bytes (numpy uint8)."""
+        return self.an._decoded_tensors(len(stream), *self._run(stream, start, count, files=files, file_offset=file_offset), with_status)
+
+    def crops(self, stream, start, length, with_status=False):
+        """Crops of ONE length: -> (a float32 tensor [n, ch, length] on the context's device, the valid lengths (numpy int64
+        [n])).  Row w holds frames [start[w], start[w] + length) of file stream[w]; behind what the file's end (or a flag)
+        cut short the row is zero: the tensor is made zeroed and the kernel writes the valid part alone."""
+        an, t = self.an, self.an.torch
+        n, length = len(stream), int(length)
+        an._need(length >= 0, "crops: a negative length")
+        pcm = t.zeros((n, an.channels, length), dtype=t.float32, device=an._dev())
+        _, frames, _, status = self._run(stream, start, [length] * n, pcm=pcm.view(-1), stride=length)
+        valid = np.where(status != 0, 0, frames).astype(np.int64)
+        for w in np.nonzero((status != 0) & (frames > 0))[0]:  # (a window the device flagged has no frames: its row goes back to zero)
+            pcm[int(w)].zero_()
+        return (pcm, valid, status.copy()) if with_status else (pcm, valid)
+
+
+def ogg_index(setup_blob, files, setup_header=None, device=None):
+    """Analyzer(setup_blob).ogg_index(...) for a caller who holds files and no context: closing the index closes the context."""
+    a = Analyzer(setup_blob, device)
+    try:
+        x = OggIndex(a, files, setup_header, own=True)
+    except Exception:
+        a.close()
+        raise
+    return x
 
 
 def decode(setup_blob, streams, granules=None, with_status=False, device=None):

@@ -429,6 +429,23 @@ VAMD_DEV float lap_sample(const LapP &L, long long k, long long at, int c) {
   return B[d + i];
 }
 
+// ---- the lap for a window: frames [a, a + F) of a stream out of the blocks around them alone (vamd_decode_window.h) ---------
+// Blocks [k0, k1) of order[] are the window's own, src[] in the stream's coordinates: centre(k0) <= a and
+// a + F - 1 < centre(k1 - 1) (vamd_decode_window_plan.h picks the fewest such).  Thread q of the window takes frames
+// 4q .. 4q + 3 as k_lap's does: one search for the block pair of the first, a step along order[] where a later one lies
+// past the pair's end.  Channel c goes to out[c * stride ..]: stride >= F (a crop's row may be longer than what the file
+// still holds).  A window the plan did not bound as above is left alone.
+VAMD_DEV void lap_window(const LapP &L, long long k0, long long k1, long long a, long long F, long long stride, long long q, float *out) {
+  if (k1 - k0 < 2 || a < lap_centre(L, k0)) return;
+  const long long span = lap_centre(L, k1 - 1) - a, count = F < span ? F : span;
+  if (4 * q >= count) return;
+  long long k = lap_find(L, k0, k1, a + 4 * q), end = lap_centre(L, k);
+  for (long long t = 4 * q; t < 4 * q + 4 && t < count; t++) {
+    while (a + t >= end && k < k1 - 1) end = lap_centre(L, ++k);
+    for (int c = 0; c < L.ch; c++) out[c * stride + t] = lap_sample(L, k, a + t, c);
+  }
+}
+
 // ---- the lap across pieces: a continuing stream's last block, carried between calls (vamd_decode_live.h) --------------------
 // lap_sample reads, of the block in front, its second half and its size class.  A live decoder keeps that half per slot
 // in `carry` ([slots][ch][bs1/2]; a short block's half fills the front of its row) and, in the next call, stands it in an

@@ -75,6 +75,7 @@ struct vamd_ctx {
     DevBuf bytes, plan, status, files;
     DevBuf post_valid[2], ilogmask[2], res_class[2], res_entries[2], res_count[2], synth[2];
     HostBuf h_plan;
+    HostBuf h_stage;  // a window call's bytes on their way up: the windows' packets, or their pages (vamd_decode_window.h)
   } dec;
 };
 

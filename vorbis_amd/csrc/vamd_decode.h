@@ -11,6 +11,8 @@
 // blocks carried between pieces standing in the plan and two carry kernels between k_synth and k_lap (DecodeCarry).
 // The live Ogg decoder (vamd_decode_ogg_live.h) takes the next BYTES of continuing Ogg streams: both of the above at once,
 // with the packet that whole pages leave open carried on the device by two more kernels around k_ogg_depage.
+// The window entries (vamd_decode_window.h) take WINDOWS of streams or of indexed files through the same function too: the
+// plan's "streams" are the windows, only their packets or pages go up, and k_lap_window stands in k_lap's place.
 //
 // Workspace per block, in the context, grown on demand and released with it (ch channels, n the block's size, S submaps):
 //   rows     4 ch (post_valid) + ch n/2 (the integer curves) + S * 2048 (res_class) + 2 * vamd_residue_capacity
@@ -46,6 +48,7 @@ static void decode_release(vamd_ctx *c) {
   for (DevBuf *b : all)
     if (b->p) (void)hipFree(b->p);
   if (D.h_plan.p) (void)hipHostFree(D.h_plan.p);
+  if (D.h_stage.p) (void)hipHostFree(D.h_stage.p);
   if (D.d_tab) (void)hipFree(D.d_tab);
 }
 
@@ -121,13 +124,20 @@ struct DecodeCarry {
   int64_t slots = 0, stride = 0;
 };
 
+// What a window call adds (vamd_decode_window.h): P's "streams" are windows, and k_lap_window takes k_lap's place with
+// each window's first frame in its stream and its channel stride in pcm.
+struct DecodeWindows {
+  const int64_t *first = nullptr, *stride = nullptr;  // [ns]
+};
+
 // The tail all entries share, behind a plan that holds and statuses the host has already set: workspace, the plan's
 // upload, the arena (uploaded, or unpaged on the device), k_unpack, k_synth, k_lap, and the statuses back in one copy --
 // the blocks' and, behind them, the pages' -- folded into their streams.  With `live`, P is live->plan->P: order[] holds
 // carried blocks that have no packet, k_unpack takes the plan's own list, and the carries move between k_synth and k_lap;
-// without, nothing is enqueued or uploaded that was not before.
+// without, nothing is enqueued or uploaded that was not before.  With `win`, the two lists go up behind the plan and the
+// lap is k_lap_window's; without, likewise nothing changes.
 static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const DecodeInput &in, const int64_t *offset_out, float *pcm, uint8_t *status,
-                      const DecodeCarry *live = nullptr) {
+                      const DecodeCarry *live = nullptr, const DecodeWindows *win = nullptr) {
   int r;
   const std::vector<int32_t> &unpack = live ? live->plan->unpack : P.order;
   const std::vector<int64_t> &unpack_start = live ? live->plan->unpack_start : P.lap_start;
@@ -164,7 +174,8 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
   const size_t o_order = a.take(4 * nlap), o_start = a.take(8 * ((size_t)ns + 1)), o_src0 = a.take(8 * P.src[0].size() + 8),
                o_src1 = a.take(8 * P.src[1].size() + 8), o_bits = a.take(16 * nb), o_frames = a.take(8 * (size_t)ns), o_off = a.take(8 * (size_t)ns),
                o_pages = a.take(sizeof(OggDepage) * npg), o_unpack = live ? a.take(4 * nb) : o_order, o_in = a.take(sizeof(CarryRow) * nin),
-               o_out = a.take(sizeof(CarryRow) * nout), o_bin = a.take(sizeof(OggCarryRow) * nbin), o_bout = a.take(sizeof(OggCarryRow) * nbout);
+               o_out = a.take(sizeof(CarryRow) * nout), o_bin = a.take(sizeof(OggCarryRow) * nbin), o_bout = a.take(sizeof(OggCarryRow) * nbout),
+               o_first = a.take(win ? 8 * (size_t)ns : 0), o_stride = a.take(win ? 8 * (size_t)ns : 0);
   const size_t plan_bytes = a.at, o_status = a.take(nb + npg);
   if ((r = pinned_get(c, D.h_plan, a.at, true))) return r;
   if ((r = dev_need(c, D.plan, plan_bytes))) return r;
@@ -187,6 +198,7 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
   memcpy(h + o_frames, P.frames.data(), 8 * (size_t)ns);
   for (int64_t s = 0; s < ns; s++) ((int64_t *)(h + o_off))[s] = P.frames[(size_t)s] > 0 ? offset_out[s] : 0;
   if (npg) memcpy(h + o_pages, in.scan->pages.data(), sizeof(OggDepage) * npg);
+  if (win && ns) memcpy(h + o_first, win->first, 8 * (size_t)ns), memcpy(h + o_stride, win->stride, 8 * (size_t)ns);
   hipStream_t s = c->stream;
   HIP_TRY(c, hipMemcpyAsync(dp, h, plan_bytes, hipMemcpyHostToDevice, s));
   if (npg) {
@@ -229,8 +241,13 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
     L.src0 = (const long long *)(dp + o_src0), L.src1 = (const long long *)(dp + o_src1);
     L.synth0 = (const float *)D.synth[0].p, L.synth1 = (const float *)D.synth[1].p;
     const long per_stream = (long)((P.max_frames + 1023) / 1024);  // (as vamd_synth_streams sizes it)
-    hipLaunchKernelGGL(k_lap, dim3((unsigned)(per_stream < 1024 ? per_stream : 1024), (unsigned)(ns < 1024 ? ns : 1024)), dim3(256), 0, s, L, (long)ns,
-                       (const long long *)(dp + o_frames), (const long long *)(dp + o_off), pcm);
+    if (win)
+      hipLaunchKernelGGL(k_lap_window, dim3((unsigned)(per_stream < 1024 ? per_stream : 1024), (unsigned)(ns < 1024 ? ns : 1024)), dim3(256), 0, s, L, (long)ns,
+                         (const long long *)(dp + o_first), (const long long *)(dp + o_frames), (const long long *)(dp + o_stride),
+                         (const long long *)(dp + o_off), pcm);
+    else
+      hipLaunchKernelGGL(k_lap, dim3((unsigned)(per_stream < 1024 ? per_stream : 1024), (unsigned)(ns < 1024 ? ns : 1024)), dim3(256), 0, s, L, (long)ns,
+                         (const long long *)(dp + o_frames), (const long long *)(dp + o_off), pcm);
     HIP_TRY(c, hipGetLastError());
   }
   HIP_TRY(c, hipMemcpyAsync(h + o_status, D.status.p, nb + npg, hipMemcpyDeviceToHost, s));

@@ -303,6 +303,7 @@ int vamd_envelope_geometry(const vamd_ctx *c, int *winlength, int *searchstep) {
 
 #include "vamd_batch.h"  // workspace planning, the launch sequence, the batch entry points
 #include "vamd_decode.h" // the packet decoder: plan on the host, k_unpack ahead of k_synth and k_lap
+#include "vamd_decode_window.h"  // ... windows of streams and of files: a seek index, k_lap_window
 #include "vamd_decode_live.h"  // ... and continuing streams in pieces: the lap carried between calls
 #include "vamd_decode_ogg_live.h"  // ... and their Ogg bytes in pieces, cut anywhere: open packets carried too
 #include "vamd_plan.h"   // the detector over streams, the walk, the plans

@@ -1686,6 +1686,19 @@ __global__ __launch_bounds__(256) void k_lap(LapP L, long nstreams, const long l
   }
 }
 
+// The windows' decoded samples (k_synth.h, "the lap for a window"): k_lap's gather with a first frame per window.  Window w
+// has blocks [window_start[w], window_start[w + 1]) of order[]; its frame t is the stream's frame first[w] + t; frames[w] of
+// them, channel c at out + offset[w] + c * stride[w].
+__global__ __launch_bounds__(256) void k_lap_window(LapP L, long nwindows, const long long *__restrict__ first, const long long *__restrict__ frames,
+                                                    const long long *__restrict__ stride, const long long *__restrict__ offset,
+                                                    float *__restrict__ out) {
+  for (long w = blockIdx.y; w < nwindows; w += gridDim.y) {
+    const long long k0 = L.stream_start[w], k1 = L.stream_start[w + 1], F = frames[w];
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; 4 * q < F; q += (long long)gridDim.x * blockDim.x)
+      lap_window(L, k0, k1, first[w], F, stride[w], q, out + offset[w]);
+  }
+}
+
 // The live decoder's carries (k_synth.h, "the lap across pieces"): a workgroup per (row of the table, channel), striding
 // over the pairs; a wave's lanes move 16 bytes each.  k_decode_carry_in before k_lap, k_decode_carry_out behind k_synth,
 // in-before-out on one stream: a slot may be read and written in one call.
