@@ -34,7 +34,9 @@ extern "C" {
 #define VAMD_EFAULT   (-129) /* OV_EFAULT: HIP runtime failure; see vamd_last_error() */
 #define VAMD_EIMPL    (-130) /* OV_EIMPL: setup/feature outside the covered path */
 #define VAMD_EINVAL   (-131) /* OV_EINVAL: bad argument */
-#define VAMD_EVERSION (-134) /* OV_EVERSION: setup blob version mismatch */
+#define VAMD_ENOTVORBIS (-132) /* OV_ENOTVORBIS: vamd_create_decoder: a packet is no Vorbis header */
+#define VAMD_EBADHEADER (-133) /* OV_EBADHEADER: vamd_create_decoder: a header vorbis_synthesis_headerin refuses */
+#define VAMD_EVERSION (-134) /* OV_EVERSION: setup blob version mismatch; an identification header of another Vorbis version */
 /* NOT libvorbis codes: the input (not the call) was outside the domain the reference's own arithmetic is defined on ("Input
  * domain" below).  Kept apart from VAMD_EINVAL so that a binding can tell such a block -- which it reports as OV_EINVAL out
  * of vorbis_analysis() -- from a programming error in its own arguments, which it should not swallow.
@@ -704,11 +706,14 @@ int vamd_decode_live_wrote(vamd_decode_live *d, const vamd_decode_live_desc *des
  *                          channels, rate and two block sizes are the blob's; packet 1 is no well-formed comment header
  *                          (type 3, "vorbis", the lengths inside the packet, the framing bit); packet 2 is not type 5 +
  *                          "vorbis", or differs from setup_header where one is given
- * The header packets are not parsed beyond that: the context's blob stays the setup.  A flagged stream costs only itself.
+ * The header packets are not parsed beyond that: the context's setup stays the setup -- its blob, or the headers a
+ * decode-only context was made from (vamd_create_decoder, below: such a context holds every file's third packet to its own
+ * setup header packet where setup_header is NULL).  A flagged stream costs only itself.
  *
  * DELIBERATE DEVIATIONS: libogg resynchronises behind a damaged page and reports a hole, and libvorbis decodes on out of
  * lap; here the stream is flagged.  A chained or multiplexed file is flagged BADPAGE at its second serial number, not
- * decoded.  Out of scope, as above: setups other than the context's (the setup header is compared, not parsed), streams
+ * decoded.  Out of scope, as above: setups other than the context's (per call the setup header is compared; a context
+ * for ANY floor-1 file's setup is made from the file's own headers: vamd_create_decoder, vamd_ogg_read_headers), streams
  * that begin at a nonzero granule, files that start in device memory.  Seeking: "windows", below. */
 #define VAMD_STATUS_BADPAGE   32
 #define VAMD_STATUS_BADHEADER 64
@@ -722,6 +727,33 @@ typedef struct vamd_decode_ogg_desc {
 int vamd_decode_ogg_plan(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
 int vamd_decode_ogg(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, const int64_t *offset_out /* host [nstreams] */,
                     float *pcm /* device */, uint8_t *status /* host [nstreams] */);
+
+/* ---- a decoder for a stream the caller did not encode: the context from the stream's own headers (still ABI 9: additions
+ * only).  vamd_create_decoder parses the identification and setup header packets (Vorbis I 4.2.2, 4.2.4) as
+ * vorbis_synthesis_headerin does and builds a DECODE-ONLY context: every decode entry above and below works on it as on a
+ * blob context, bit for bit libvorbis' output under those headers.
+ *   VAMD_ENOTVORBIS / VAMD_EBADHEADER / VAMD_EVERSION  what vorbis_synthesis_headerin answers for the packet
+ *   VAMD_EIMPL   headers it accepts that lie outside the covered shape: floor 1; residue types 1 and 2; at most 8 channels, 2
+ *                submaps and 4 coupling steps; block sizes 64 .. 4096; one mode, or two with mode i of block flag i; at
+ *                most 255 books of at most 65 536 entries with a complete code tree (or one used entry of length 1, read from a bit of either value); and
+ *                what the decode kernels take for granted of a setup ("Setups in", has the list)
+ * with the reason in vamd_last_error(NULL) (per thread; no context exists to hold it).
+ * Residue books whose values are the centred integer lattice of libvorbisenc's books -- decided by comparing values -- are
+ * decoded by the arithmetic a blob context uses, and a setup that has only such books launches the kernels a blob context
+ * launches; any other residue book (explicit value lists, non-integer steps, q_sequencep, another quantlist order) has its
+ * value list [entries][dim], as _book_unquantize leaves it, in device memory (64 MiB a setup at most), read by k_synth_values.
+ * The context keeps a copy of the setup header packet: vamd_decode_ogg*, vamd_ogg_index_create and the live Ogg decoder
+ * hold every file's third packet to it where the call gives no setup_header (VAMD_STATUS_BADHEADER for another setup).
+ * Every analysis, encode, envelope, stream-plan and bitrate entry, vamd_synth_streams and its kin and
+ * vamd_mdct_forward_batch answer VAMD_EIMPL "decode-only context" and launch nothing; the context stays usable.
+ * vamd_channels, vamd_blocksize, vamd_submaps and vamd_residue_capacity work.
+ *
+ * vamd_ogg_read_headers (host only): the three header packets of a file's first logical stream, which may span pages, back
+ * to back into out[0 .. cap) with len[3] their sizes.  -> VAMD_OK; VAMD_EINVAL where cap is too small (len[] then holds
+ * the sizes needed) or an argument is null; VAMD_EBADHEADER where the file's pages do not hold three packets (a broken
+ * container, a file that ends first).  No byte outside file[0 .. bytes) is read. */
+int vamd_create_decoder(vamd_ctx **ctx, const void *id_header, size_t id_bytes, const void *setup_header, size_t setup_bytes, int device);
+int vamd_ogg_read_headers(const uint8_t *file, int64_t bytes, uint8_t *out, int64_t cap, int64_t len[3]);
 
 /* ---- windows of streams and of Ogg files: a seek index, crops on the device (still ABI 9: additions only).  A caller who
  * wants a second out of each of a hundred files pays for that second: a window's frames are, bit for bit, the same frames

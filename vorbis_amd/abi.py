@@ -9,6 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 VAMD_OK, VAMD_EFAULT, VAMD_EIMPL, VAMD_EINVAL, VAMD_EVERSION, VAMD_EDOMAIN, VAMD_ENONFINITE = 0, -129, -130, -131, -134, -140, -141
+VAMD_ENOTVORBIS, VAMD_EBADHEADER = -132, -133  # vamd_create_decoder: what vorbis_synthesis_headerin answers for a header packet
 ABI_VERSION = 9             # VAMD_ABI_VERSION of the header this mirror was written against
 QUANT_LIMIT_SQUARE, QUANT_LIMIT_INT = 46340, 0x7fffff80
 STATUS_RANGE, STATUS_NONFINITE = 1, 2   # bits of the `status` output (vorbis_amd.h, "Input domain")
@@ -125,6 +126,8 @@ _block = [_vp, _pvp, _int, _int, _int, _int, _float]   # (ctx, pcm[ch], lW, W, n
 # tests/test_binding_cpu.py holds each entry against the header's declaration (parameter count, kind of return value).
 PROTOTYPES = {
     "vamd_create_abi": (_int, [_pvp, _vp, _size, _int, _int]),
+    "vamd_create_decoder": (_int, [_pvp, _vp, _size, _vp, _size, _int]),
+    "vamd_ogg_read_headers": (_int, [_vp, C.c_int64, _vp, C.c_int64, _vp]),
     "vamd_quant_limit": (_int, [_vp, _int, _int, _pint, _pint, _pint]),
     "vamd_clock_probe": (_int, [_vp, _vp]),
     "vamd_config_string": (C.c_char_p, [_vp]),

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from .abi import (ABI_VERSION, BLOCKTYPE_LONG, LEVEL_FULL, LEVEL_PSY, LEVEL_TRANSFORM, PACKETBLOBS, POSTS_STRIDE, QUANT_LIMIT_INT,
-                  QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_RANGE, VAMD_EDOMAIN, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
+                  QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_BADHEADER, STATUS_RANGE, VAMD_EDOMAIN, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
                   _DecodeDesc, _DecodeLiveDesc, _DecodeOggDesc, _DecodeOggLiveDesc, _DecodeOggLiveOpts, _Desc, _OggWindowDesc, _IO, _MIO, _Plan, _vp, load_library)
 from .packets import packet_bytes
 
@@ -50,23 +50,40 @@ _OUTPUTS = {
 class Analyzer:
     """One vamd_ctx: the GPU-side counterpart of a vorbis_dsp_state's lookups."""
 
-    def __init__(self, setup_blob, device=None):
+    def __init__(self, setup_blob, device=None, _headers=None):
         import torch
         self.torch = torch
         self.L = load_library()
         if not torch.cuda.is_available():
             raise RuntimeError("vorbis_amd needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback")
         self.device = torch.cuda.current_device() if device is None else int(device)
-        blob = np.ascontiguousarray(np.frombuffer(bytes(setup_blob), dtype=np.uint8) if not isinstance(setup_blob, np.ndarray)
-                                    else setup_blob.astype(np.uint8))
         h = _vp()
-        r = self.L.vamd_create_abi(C.byref(h), blob.ctypes.data_as(_vp), blob.size, self.device, ABI_VERSION)
-        if r != VAMD_OK:
-            raise VamdError(r, "vamd_create failed (see stderr)")
+        self.decode_only = _headers is not None
+        if self.decode_only:
+            ident, setup = (bytes(p) for p in _headers)
+            r = self.L.vamd_create_decoder(C.byref(h), ident, len(ident), setup, len(setup), self.device)
+            if r != VAMD_OK:
+                raise VamdError(r, self.L.vamd_last_error(None).decode())
+        else:
+            blob = np.ascontiguousarray(np.frombuffer(bytes(setup_blob), dtype=np.uint8) if not isinstance(setup_blob, np.ndarray)
+                                        else setup_blob.astype(np.uint8))
+            r = self.L.vamd_create_abi(C.byref(h), blob.ctypes.data_as(_vp), blob.size, self.device, ABI_VERSION)
+            if r != VAMD_OK:
+                raise VamdError(r, "vamd_create failed (see stderr)")
         self.h = h
         self.channels = self.L.vamd_channels(h)
         self.blocksizes = (self.L.vamd_blocksize(h, 0), self.L.vamd_blocksize(h, 1))
         self.posts = (self.L.vamd_posts(h, 0), self.L.vamd_posts(h, 1))
+
+    @classmethod
+    def from_headers(cls, id_header, setup_header, device=None):
+        """vamd_create_decoder: a DECODE-ONLY Analyzer out of a stream's identification and setup header packets (`bytes`;
+        read_ogg_headers() gives a file's).  decode_streams, decode_ogg, decode_window, ogg_index, live_decoder and
+        live_ogg_decoder work as on a blob context -- the Ogg ones hold every file's third packet to setup_header unless
+        they are given another -- and the encode methods raise VamdError(VAMD_EIMPL).  Raises VamdError with
+        VAMD_ENOTVORBIS / _EBADHEADER / _EVERSION for headers libvorbis refuses, VAMD_EIMPL (and the reason) for a setup
+        outside the covered shape."""
+        return cls(None, device, _headers=(id_header, setup_header))
 
     def close(self):
         if getattr(self, "h", None):
@@ -1170,6 +1187,51 @@ def decode(setup_blob, streams, granules=None, with_status=False, device=None):
         return a.decode_streams(streams, granules, with_status)
     finally:
         a.close()
+
+
+def read_ogg_headers(file):
+    """vamd_ogg_read_headers: (identification, comment, setup) -- the three header packets of an Ogg file's first logical
+    stream, as `bytes`.  Raises VamdError(VAMD_EBADHEADER) where the file's pages do not hold three packets."""
+    L = load_library()
+    data = bytes(file)
+    lens = (C.c_int64 * 3)()
+    out = C.create_string_buffer(max(len(data), 1))  # (the packets are part of the file: never longer)
+    r = L.vamd_ogg_read_headers(data, len(data), out, len(data), lens)
+    if r != VAMD_OK:
+        raise VamdError(r, "read_ogg_headers: the file's pages do not hold three header packets")
+    a, b, c = (int(v) for v in lens)
+    return out.raw[:a], out.raw[a:a + b], out.raw[a + b:a + b + c]
+
+
+def decode_ogg_files(files, with_status=False, device=None):
+    """Ogg Vorbis files of ANY covered setups in, PCM out: no blob and no settings.  Each file's headers are read
+    (read_ogg_headers); the files are grouped by (identification fields, setup header bytes); one decode-only context is
+    made per distinct setup (Analyzer.from_headers) and decodes its group in one decode_ogg call.  -> a list of float32
+    tensors [ch, frames] in the caller's order; with_status, also the status bytes.  A file whose headers are rejected or
+    refused gets a [0, 0] tensor and STATUS_BADHEADER: it costs only itself."""
+    import torch
+    groups, out, status = {}, [None] * len(files), np.zeros(len(files), np.uint8)
+    for i, f in enumerate(files):
+        try:
+            ident, _, setup = read_ogg_headers(f)
+            groups.setdefault((ident[7:16] + ident[28:29], setup), (ident, []))[1].append(i)  # version, channels, rate; the block sizes
+        except VamdError:
+            status[i] = STATUS_BADHEADER
+    for (_, setup), (ident, members) in groups.items():
+        try:
+            a = Analyzer.from_headers(ident, setup, device)
+        except VamdError:
+            status[members] = STATUS_BADHEADER
+            continue
+        try:
+            pcm, st = a.decode_ogg([files[i] for i in members], with_status=True)
+            for i, p, v in zip(members, pcm, st):
+                out[i], status[i] = p.clone(), v
+        finally:
+            a.close()
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    out = [torch.zeros((0, 0), dtype=torch.float32, device=dev) if p is None else p for p in out]
+    return (out, status) if with_status else out
 
 
 def decode_ogg(setup_blob, files, setup_header=None, with_status=False, device=None):

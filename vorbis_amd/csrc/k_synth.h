@@ -197,20 +197,32 @@ VAMD_DEV void mdct_backward_wave(const XformP &P, const float *in, float *w2, fl
 
 // component `digit` of a lattice book's vector (_book_unquantize maptype 1): the quantlist runs ze, ze-1, ze+1, ze-2, ... --
 // the order local_book_besterror numbers its steps in (lib/res0.c:336,343) -- and a step v is worth v * delta + minval
-VAMD_DEV float synth_lattice_value(int digit, int ze, int delta, int minval) {
+VAMD_HOSTDEV float synth_lattice_value(int digit, int ze, int delta, int minval) {
   const int v = (digit & 1) ? ze - ((digit + 1) >> 1) : ze + (digit >> 1);
   return (float)(v * delta + minval);
 }
 
+// The residue books whose values are NOT that lattice (a setup made from a stream's own headers, vamd_headers.h: explicit
+// value lists, non-integer steps, q_sequencep, a quantlist in another order): component j of entry e of book b is
+// values[book_off[b] + e * dim + j], the float _book_unquantize leaves (lib/sharedbook.c:285-334); book_off[b] < 0: b is
+// a lattice book.  Only the TABLE form of synth_residue reads it.
+struct ValueP {
+  const int *book_off;   // [nbooks]
+  const float *values;
+};
+
 // One submap's residue added into the spectrum (res1_inverse / res2_inverse with the entropy decode already done).
+//   TABLE: a book's vectors come from ValueP where it has a value list -- the same stage order, the same positions, one
+//          float addition per component as without.  A setup whose residue books are all lattice books never takes it.
 //   chans LDS [VAMD_MAX_CH]: the bundle's channels in order (type 2), or those of them that take part (type 1: the
 //                            streams, lib/res0.c:757-767); filled here
 //   coded                    bit c: channel c takes part in a residue (mapping0_inverse's nonzero[], :715-733)
 //   res_class / res_entries / res_count: this submap's rows of one block (k_residue.h)
 //   spec LDS [ch][n2]; cls LDS [slots]; off LDS [stages*slots + 1]; info LDS [stages*slots]
+template <bool TABLE = false>
 VAMD_DEV void synth_residue(const ResP &R, const ChMap &cm, int sm, int ch, int n2, unsigned coded, const int *__restrict__ res_class,
                             const unsigned short *__restrict__ res_entries, const int *__restrict__ res_count, float *spec,
-                            int *chans, int *cls, int *off, int *info) {
+                            int *chans, int *cls, int *off, int *info, const ValueP &V = ValueP()) {
   const vamd_residue_tab &t = *R.tab;
   const int slots = res_count[0];
   if (slots <= 0 || slots > R.slots) return;  // no channel of the bundle is coded: res*_inverse reads nothing
@@ -239,14 +251,26 @@ VAMD_DEV void synth_residue(const ResP &R, const ChMap &cm, int sm, int ch, int 
       }
       const int q = lo, k = v - (so[q] - base);
       const int i = q / ns, strm = q - i * ns;
-      const vamd_book_tab &bk = R.books[info[s * slots + q]];
+      const int bn = info[s * slots + q];
+      const vamd_book_tab &bk = R.books[bn];
       const int dim = bk.dim, qv = bk.quantvals, ze = qv >> 1, delta = bk.delta, minval = bk.minval;
       unsigned e = base + v < R.cap ? (unsigned)res_entries[base + v] : 0u;
       const int pos = t.begin + i * spp + k * dim;
+      // (an entry number is k_unpack's: below the book's entries; held there all the same, the list is read by it)
+      const float *row = nullptr;
+      if (TABLE) {
+        const int at = V.book_off[bn];
+        if (at >= 0) row = V.values + (size_t)at + (size_t)(e < (unsigned)bk.entries ? e : 0u) * dim;
+      }
       for (int j = 0; j < dim; j++) {
-        const unsigned d = e / (unsigned)qv;
-        const float val = synth_lattice_value((int)(e - d * (unsigned)qv), ze, delta, minval);
-        e = d;
+        float val;
+        if (TABLE && row) {
+          val = row[j];
+        } else {
+          const unsigned d = e / (unsigned)qv;
+          val = synth_lattice_value((int)(e - d * (unsigned)qv), ze, delta, minval);
+          e = d;
+        }
         float *p;
         if (interleaved) {
           const int at = pos + j, bin = at / bundle;
@@ -293,10 +317,11 @@ VAMD_DEV int synth_line_at(int x, int x1, int y0, int y1) {
 //   post_valid [ch]; ilogmask [ch][n2]; res_class [submaps][VAMD_RES_CLASS_STRIDE], res_entries [row], res_count [submaps][2]
 //   lds: synth_lds_words(ch, n2, waves, off_ints) words, 16-byte aligned
 //   stopwatch marks (per wave): 0 the residue walk (the spectrum's zeroing included), 1 inverse coupling + floor, 2-5 the transform
+template <bool TABLE = false>
 VAMD_DEV void synth_block(const XformP &X, const ResP &R0, const ResP &R1, const ChMap &cm, const CoupleP &C, const SynthFloorP &S, int ch, int off_ints,
                           const int *__restrict__ post_valid, const ilog_t *__restrict__ ilogmask, const int *__restrict__ res_class,
                           const unsigned short *__restrict__ res_entries, const int *__restrict__ res_count, float *lds,
-                          float *__restrict__ out, PhaseClock &pc) {
+                          float *__restrict__ out, PhaseClock &pc, const ValueP &V = ValueP()) {
   const int n = X.n, n2 = n >> 1;
   float *spec = lds;
   int *chans = (int *)(spec + (size_t)ch * n2), *cls = chans + VAMD_MAX_CH, *off = cls + VAMD_RES_CLASS_STRIDE, *info = off + off_ints;
@@ -311,8 +336,8 @@ VAMD_DEV void synth_block(const XformP &X, const ResP &R0, const ResP &R1, const
   TEAM_SYNC();
   for (int sm = 0; sm < cm.submaps; sm++) {
     const ResP &R = sm ? R1 : R0;
-    synth_residue(R, cm, sm, ch, n2, coded, res_class + R.cls_base, res_entries + R.ent_base, res_count + 2 * sm, spec, chans, cls,
-                  off, info);
+    synth_residue<TABLE>(R, cm, sm, ch, n2, coded, res_class + R.cls_base, res_entries + R.ent_base, res_count + 2 * sm, spec, chans, cls,
+                         off, info, V);
   }
   pc.mark(0);
   // four bins a trip: every channel's four curve bytes are one load, all of them in flight before the first is used

@@ -66,6 +66,7 @@ static int plan(vamd_ctx *c, int W, long nb, const vamd_batch_io *io, int level,
 }
 
 int vamd_reserve(vamd_ctx *c, int W, long max_blocks) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c || (W != 0 && W != 1) || max_blocks < 1) return VAMD_EINVAL;
   WsPlan p;
@@ -116,6 +117,7 @@ const char *vamd_launch_record(const vamd_ctx *c, int W) { return c && (W == 0 |
   }
 
 int vamd_mdct_forward_batch(vamd_ctx *c, int W, const float *in, float *out, long nframes) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c || (W != 0 && W != 1) || nframes < 0) return VAMD_EINVAL;
   if (nframes == 0) return VAMD_OK;
@@ -666,6 +668,7 @@ static int run_batch(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_
 }
 
 int vamd_analyze_batch(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io, int level) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   int r = check_desc(c, desc, io);
   if (r) return r;
@@ -697,9 +700,14 @@ static int launch_synth(vamd_ctx *c, int W, const vamd_ctx::SynthSrc &y, float *
   if (r) return r;
   if (y.nb < 1) return VAMD_OK;
   const int ch = c->B.channels, n2 = c->B.bs[W] / 2;
-  hipLaunchKernelGGL(k_synth, dim3((unsigned)y.nb), dim3(64 * ch), synth_lds_bytes(c, W), c->stream,
-                     c->B.xf[W], c->B.res[W][0], c->B.res[W][1], c->B.chmap[W], c->B.couple[W], S, ch, c->B.res_cap[W], c->B.res_off_ints[W],
-                     c->d_dbg ? c->d_dbg + 8 : nullptr, y.post_valid, y.ilogmask, y.res_class, y.res_entries, y.res_count, synth);
+  if (c->V.values)  // (a header-made setup with a residue book that is no lattice book: vamd_ctx::V)
+    hipLaunchKernelGGL(k_synth_values, dim3((unsigned)y.nb), dim3(64 * ch), synth_lds_bytes(c, W), c->stream,
+                       c->B.xf[W], c->B.res[W][0], c->B.res[W][1], c->B.chmap[W], c->B.couple[W], S, ch, c->B.res_cap[W], c->B.res_off_ints[W],
+                       c->d_dbg ? c->d_dbg + 8 : nullptr, y.post_valid, y.ilogmask, y.res_class, y.res_entries, y.res_count, synth, c->V);
+  else
+    hipLaunchKernelGGL(k_synth, dim3((unsigned)y.nb), dim3(64 * ch), synth_lds_bytes(c, W), c->stream,
+                       c->B.xf[W], c->B.res[W][0], c->B.res[W][1], c->B.chmap[W], c->B.couple[W], S, ch, c->B.res_cap[W], c->B.res_off_ints[W],
+                       c->d_dbg ? c->d_dbg + 8 : nullptr, y.post_valid, y.ilogmask, y.res_class, y.res_entries, y.res_count, synth);
   HIP_TRY(c, hipGetLastError());
   return VAMD_OK;
 }
@@ -711,6 +719,7 @@ int vamd_synth_check(vamd_ctx *c, int W) {
 }
 
 int vamd_analyze_batch_synth(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io, float *synth) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   int r = check_desc(c, desc, io);
   if (r) return r;
@@ -723,6 +732,7 @@ int vamd_analyze_batch_synth(vamd_ctx *c, const vamd_batch_desc *desc, const vam
 
 int vamd_synth_streams(vamd_ctx *c, const vamd_stream_plan *plan, long nstreams, long max_frames, const int64_t *frames,
                        const int64_t *offset, float *scratch_short, float *scratch_long, float *pcm) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!plan || nstreams < 1 || plan->nstreams != nstreams || max_frames < 1 || !frames || !offset || !pcm)
@@ -776,6 +786,7 @@ static vamd_batch_io shared_io(const vamd_batch_io &io) {
 
 int vamd_analyze_batch_managed(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io,
                                const vamd_managed_io *m) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   int r = check_desc(c, desc, io);
   if (r) return r;
@@ -785,6 +796,7 @@ int vamd_analyze_batch_managed(vamd_ctx *c, const vamd_batch_desc *desc, const v
 }
 
 int vamd_analyze_stream(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io, float *ampmax_state) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   int r = check_desc(c, desc, io);
   if (r) return r;
@@ -869,6 +881,7 @@ static int run_streams_mixed(vamd_ctx *c, const vamd_batch_desc *desc_short, con
 int vamd_analyze_stream_mixed(vamd_ctx *c, const vamd_batch_desc *desc_short, const vamd_batch_io *io_short,
                               const vamd_batch_desc *desc_long, const vamd_batch_io *io_long, const int32_t *order,
                               long nblocks_total, float *ampmax_state) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!desc_short || !desc_long || !ampmax_state) return fail(c, VAMD_EINVAL, "null argument");
@@ -878,6 +891,7 @@ int vamd_analyze_stream_mixed(vamd_ctx *c, const vamd_batch_desc *desc_short, co
 int vamd_analyze_streams_mixed(vamd_ctx *c, const vamd_batch_desc *desc_short, const vamd_batch_io *io_short,
                                const vamd_batch_desc *desc_long, const vamd_batch_io *io_long, const int32_t *order,
                                const int64_t *stream_start, long nstreams, long nblocks_total, float *ampmax_states) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!desc_short || !desc_long) return fail(c, VAMD_EINVAL, "null argument");
@@ -890,6 +904,7 @@ int vamd_analyze_streams_mixed_managed(vamd_ctx *c, const vamd_batch_desc *desc_
                                        const vamd_managed_io *m_short, const vamd_batch_desc *desc_long,
                                        const vamd_batch_io *io_long, const vamd_managed_io *m_long, const int32_t *order,
                                        const int64_t *stream_start, long nstreams, long nblocks_total, float *ampmax_states) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!desc_short || !desc_long) return fail(c, VAMD_EINVAL, "null argument");
@@ -911,6 +926,7 @@ int vamd_analyze_streams_mixed_managed(vamd_ctx *c, const vamd_batch_desc *desc_
 }
 
 int vamd_bitrate_init_states(vamd_ctx *c, vamd_bitrate_state *states, long nstreams) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!c->B.has_bitrate) return fail(c, VAMD_EIMPL, "the setup blob carries no bitrate manager (a VBR setup, or one packed without the section)");
@@ -923,6 +939,7 @@ int vamd_bitrate_init_states(vamd_ctx *c, vamd_bitrate_state *states, long nstre
 int vamd_bitrate_walk(vamd_ctx *c, const int32_t *order, const int64_t *stream_start, long nstreams,
                       const int32_t *const packet_bits[2], const uint8_t *const status[2], vamd_bitrate_state *states,
                       int32_t *const choice[2], int32_t *const final_bits[2]) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!c->B.has_bitrate) return fail(c, VAMD_EIMPL, "the setup blob carries no bitrate manager (a VBR setup, or one packed without the section)");

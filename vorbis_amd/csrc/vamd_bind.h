@@ -16,6 +16,8 @@
 namespace vamd {
 
 #define VAMD_QPL_GPU 4  // must equal VAMD_QPL of the HIP build (vamd_wave.h)
+#define VAMD_PSY_LOOKS 4      // the psy looks of a setup: PsyDerived per look
+#define VAMD_DERIVED_SLOTS 55  // the derived tables build_image appends and bind_params reads by slot: derived_off[0 .. 54]
 
 struct Bound {
   int channels, rate;
@@ -479,6 +481,10 @@ inline int build_image(const void *blob_v, size_t bytes, std::vector<unsigned ch
     }
   }
   while (image->size() & 15) image->push_back(0);
+  if (derived_off->size() != VAMD_DERIVED_SLOTS || derived->size() != VAMD_PSY_LOOKS) {  // (a slot added here and not there)
+    *err = "build_image: the derived tables are not VAMD_DERIVED_SLOTS";
+    return VAMD_EFAULT;
+  }
   return VAMD_OK;
 }
 

@@ -54,6 +54,7 @@ int vamd_analyze_block_managed(vamd_ctx *c, const float *const *pcm, int lW, int
                                float ampmax_in, float *mdct, float *ampmax_out, int32_t *posts,
                                int32_t *post_valid, int32_t *iwork, int32_t *nonzero, int32_t *res_class,
                                uint16_t *res_entries, int32_t *res_count) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!pcm || (W != 0 && W != 1)) return fail(c, VAMD_EINVAL, "bad pcm / W");
@@ -115,6 +116,7 @@ int vamd_analyze_block_managed(vamd_ctx *c, const float *const *pcm, int lW, int
 int vamd_analyze_block(vamd_ctx *c, const float *const *pcm, int lW, int W, int nW, int blocktype, float ampmax_in,
                        float *mdct, float *logmask, int32_t *posts, int32_t *post_valid, int32_t *iwork,
                        int32_t *nonzero, float *ampmax_out) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   return vamd_analyze_block_res(c, pcm, lW, W, nW, blocktype, ampmax_in, mdct, logmask, posts, post_valid, iwork,
                                 nonzero, ampmax_out, nullptr, nullptr, nullptr);
@@ -124,6 +126,7 @@ int vamd_analyze_block_res(vamd_ctx *c, const float *const *pcm, int lW, int W, 
                            float ampmax_in, float *mdct, float *logmask, int32_t *posts, int32_t *post_valid,
                            int32_t *iwork, int32_t *nonzero, float *ampmax_out, int32_t *res_class,
                            uint16_t *res_entries, int32_t *res_count) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!pcm || (W != 0 && W != 1)) return fail(c, VAMD_EINVAL, "bad pcm / W");
@@ -185,6 +188,7 @@ int vamd_analyze_block_res(vamd_ctx *c, const float *const *pcm, int lW, int W, 
 
 int vamd_encode_block(vamd_ctx *c, const float *const *pcm, int lW, int W, int nW, int blocktype, float ampmax_in,
                       int managed, float *ampmax_out, uint8_t *packets, long packet_stride, int32_t *packet_bits) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!pcm || (W != 0 && W != 1)) return fail(c, VAMD_EINVAL, "bad pcm / W");
@@ -257,6 +261,7 @@ int vamd_encode_block(vamd_ctx *c, const float *const *pcm, int lW, int W, int n
 int vamd_encode_blocks(vamd_ctx *c, long nblocks, const float *const *pcm, const int32_t *lW, const int32_t *W,
                        const int32_t *nW, const int32_t *blocktype, float ampmax_in_first, int managed, float *ampmax_in,
                        float *ampmax_out, uint8_t *packets, long packet_stride, int32_t *packet_bits, int32_t *verdict) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (nblocks < 0 || nblocks > 0x3fffffffL) return fail(c, VAMD_EINVAL, "nblocks out of range");
@@ -379,6 +384,7 @@ int vamd_encode_blocks(vamd_ctx *c, long nblocks, const float *const *pcm, const
 
 int vamd_envelope_search(vamd_ctx *c, const float *const *pcm, long nsteps, vamd_envelope_state *state,
                          unsigned char *ret) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (nsteps < 0) return fail(c, VAMD_EINVAL, "negative step count");

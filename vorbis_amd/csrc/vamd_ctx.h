@@ -77,7 +77,19 @@ struct vamd_ctx {
     HostBuf h_plan;
     HostBuf h_stage;  // a window call's bytes on their way up: the windows' packets, or their pages (vamd_decode_window.h)
   } dec;
+  // a context made from a stream's headers (vamd_create_decoder, vamd_headers.h): no encode-side tables, so every encode
+  // entry refuses it; the setup header packet it was made from, which every Ogg entry holds a file's third packet to;
+  // and, where a residue book is no lattice book, the value lists in device memory ([nbooks] offsets, then the floats) --
+  // launch_synth then takes k_synth_values
+  bool decode_only = false;
+  std::vector<uint8_t> setup_packet;
+  unsigned char *d_values = nullptr;
+  ValueP V = {nullptr, nullptr};
 };
+
+// what an encode entry answers a decode-only context, before it looks at anything else
+#define VAMD_NEEDS_ENCODER(c) \
+  if ((c) && (c)->decode_only) return fail((c), VAMD_EIMPL, "decode-only context: made from a stream's headers, it holds no encoder tables")
 
 // stage ids of vamd_stage_ms(); a mark closes the interval of the stage it names (VAMD_ST_BEGIN: opens one)
 enum { VAMD_ST_BEGIN = -1, VAMD_ST_TRANSFORM = 0, VAMD_ST_AMPMAX, VAMD_ST_NOISE, VAMD_ST_TONE, VAMD_ST_FLOOR, VAMD_ST_COUPLE,

@@ -78,6 +78,13 @@ static int decode_ready(vamd_ctx *c) {
   return VAMD_OK;
 }
 
+// a context made from a stream's headers holds every file's third packet to its own setup header packet where the call
+// names none (vamd_create_decoder); a blob context has none to hold it to
+static void demux_own_setup(const vamd_ctx *c, DemuxSetup *S) {
+  if (!S->setup_header && !S->setup_header_bytes && !c->setup_packet.empty())
+    S->setup_header = c->setup_packet.data(), S->setup_header_bytes = (int64_t)c->setup_packet.size();
+}
+
 static int decode_plan(vamd_ctx *c, const vamd_decode_desc *d, DecodePlan *P) {
   if (!d) return fail(c, VAMD_EINVAL, "decode: null descriptor");
   int r = decode_ready(c);
@@ -292,6 +299,7 @@ static int decode_ogg_plan(vamd_ctx *c, const vamd_decode_ogg_desc *d, DemuxScan
   DemuxSetup S;
   S.channels = c->B.channels, S.rate = c->B.rate, S.bs[0] = c->B.bs[0], S.bs[1] = c->B.bs[1];
   S.setup_header = d->setup_header, S.setup_header_bytes = d->setup_header_bytes;
+  demux_own_setup(c, &S);
   std::string err;
   if (!demux_scan(d->nstreams, d->bytes, d->file_offset, S, X, &err)) return fail(c, VAMD_EINVAL, err.c_str());
   if (X->pages.size() > 0x7fffffffu) return fail(c, VAMD_EINVAL, "decode_ogg: more than 2^31 pages");
@@ -326,4 +334,20 @@ int vamd_decode_ogg(vamd_ctx *c, const vamd_decode_ogg_desc *d, const int64_t *o
   in.offset = X.offset.data(), in.byte0 = 0, in.nbytes = X.offset.back();
   in.scan = &X, in.files = d->bytes + d->file_offset[0], in.files_bytes = d->file_offset[d->nstreams] - d->file_offset[0];
   return decode_run(c, P, d->nstreams, in, offset_out, pcm, status);
+}
+
+// ---- a file's three header packets (host only) ----
+int vamd_ogg_read_headers(const uint8_t *file, int64_t bytes, uint8_t *out, int64_t cap, int64_t len[3]) {
+  if (!file || bytes < 0 || !len || cap < 0 || (cap > 0 && !out)) return VAMD_EINVAL;
+  std::vector<uint8_t> header[3];
+  len[0] = len[1] = len[2] = 0;
+  if (!demux_read_headers(file, bytes, header)) return VAMD_EBADHEADER;
+  int64_t total = 0;
+  for (int k = 0; k < 3; k++) total += len[k] = (int64_t)header[k].size();
+  if (total > cap) return VAMD_EINVAL;
+  for (int k = 0; k < 3; k++) {
+    if (!header[k].empty()) memcpy(out, header[k].data(), header[k].size());
+    out += header[k].size();
+  }
+  return VAMD_OK;
 }

@@ -78,6 +78,7 @@ static int decode_ogg_live_plan(vamd_decode_ogg_live *d, const vamd_decode_ogg_l
   DemuxSetup S;
   S.channels = c->B.channels, S.rate = c->B.rate, S.bs[0] = c->B.bs[0], S.bs[1] = c->B.bs[1];
   S.setup_header = d->has_setup_header ? d->setup_header.data() : nullptr, S.setup_header_bytes = (int64_t)d->setup_header.size();
+  demux_own_setup(c, &S);
   std::string err;
   if (!demux_live_scan(d->demux, desc->nstreams, desc->slot, desc->bytes, desc->piece_offset, desc->close, S, d->max_packet_bytes, d->max_header_bytes, X, &err))
     return fail(c, VAMD_EINVAL, err.c_str());

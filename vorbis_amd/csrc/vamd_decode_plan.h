@@ -99,7 +99,10 @@ inline void unpack_build_tables(const std::vector<unsigned char> &image, std::ve
       if (l <= 0) continue;
       const uint32_t c = l < 32 ? code[i] & ((1u << l) - 1u) : code[i];
       if (l <= k) {
-        for (uint32_t s = c; s < (1u << k); s += 1u << l) first[2 * s] = (uint32_t)i, first[2 * s + 1] = (uint32_t)l;
+        // (a book whose one used entry has length 1: the reference reads that entry from one bit of either value,
+        // lib/sharedbook.c:523-530 -- every slot is its)
+        const uint32_t step = used == 1 && l == 1 ? 1u : 1u << l;
+        for (uint32_t s = c & (step - 1u); s < (1u << k); s += step) first[2 * s] = (uint32_t)i, first[2 * s + 1] = (uint32_t)l;
       } else {
         longs.push_back({rev(c), (uint32_t)i | (uint32_t)l << 24});
       }

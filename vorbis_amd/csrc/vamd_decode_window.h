@@ -85,6 +85,7 @@ int vamd_ogg_index_create(vamd_ctx *c, const vamd_decode_ogg_desc *d, vamd_ogg_i
   DemuxSetup S;
   S.channels = c->B.channels, S.rate = c->B.rate, S.bs[0] = c->B.bs[0], S.bs[1] = c->B.bs[1];
   S.setup_header = d->setup_header, S.setup_header_bytes = d->setup_header_bytes;
+  demux_own_setup(c, &S);
   std::string err;
   if (!ogg_index_build(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->nstreams, d->bytes, d->file_offset, S, &x->I, &err)) {
     delete x;

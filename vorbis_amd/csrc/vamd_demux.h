@@ -120,6 +120,35 @@ inline uint8_t demux_scan_file(const uint8_t *f, int64_t n, int64_t base, int st
   return st;
 }
 
+// The three header packets of a file's first logical stream (vamd_ogg_read_headers): the walk above as far as the third
+// packet's end, pages of another serial number passed over.  -> false where the pages do not hold three packets: a broken
+// page header, a file that ends first.  Every length is held against what is left of the file before it is used.
+inline bool demux_read_headers(const uint8_t *f, int64_t n, std::vector<uint8_t> header[3]) {
+  int64_t pos = 0;
+  int npackets = 0;
+  uint32_t serial = 0;
+  for (int64_t page = 0; npackets < 3; page++) {
+    if (n - pos < OGG_HEADER || memcmp(f + pos, "OggS", 4) != 0 || f[pos + 4] != 0) return false;
+    const int nseg = f[pos + 26];
+    const uint32_t ser = ogg_le32(f + pos + 14);
+    if (page == 0) serial = ser;
+    if (n - pos - OGG_HEADER < nseg) return false;
+    const uint8_t *lace = f + pos + OGG_HEADER;
+    int64_t body = 0, at = 0;
+    for (int q = 0; q < nseg; q++) body += lace[q];
+    if (n - pos - OGG_HEADER - nseg < body) return false;
+    const uint8_t *data = lace + nseg;
+    for (int q = 0; q < nseg && npackets < 3 && ser == serial; q++) {
+      const int v = lace[q];
+      header[npackets].insert(header[npackets].end(), data + at, data + at + v);
+      at += v;
+      if (v < 255) npackets++;
+    }
+    pos += OGG_HEADER + nseg + body;
+  }
+  return true;
+}
+
 // -> false with a reason for a bad descriptor: nothing of the files has been read then
 inline bool demux_scan(int64_t nstreams, const uint8_t *bytes, const int64_t *file_offset, const DemuxSetup &S, DemuxScan *out, std::string *err) {
   *out = DemuxScan();

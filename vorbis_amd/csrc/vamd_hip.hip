@@ -2,7 +2,7 @@
 // __global__ shells around the wave-level bodies in k_*.h).  One translation unit, seven files: this root with the context's
 // life cycle and the small getters, the context (vamd_ctx.h), and the host side in three parts by topic -- the batch calls
 // and their launch sequence (vamd_batch.h), stream planning (vamd_plan.h), the host-pointer per-block calls (vamd_block.h) --
-// and the packet decoder (vamd_decode.h).
+// and the packet decoder (vamd_decode.h); a decode-only context is made from a stream's headers by vamd_headers.h (plain C++).
 // (Round 5 took the kernels and the context out of one file of 2 700 lines; round 10 the three parts out of 2 000.)
 //
 // Launch geometry: one 64-lane wavefront per workgroup, one workgroup per
@@ -47,6 +47,7 @@
 #define VAMD_OGG_NO_FEED_KERNELS  // (k_ogg.h: k_ogg_plan / _pages / _carry are vamd_feed.hip's)
 #include "vamd_demux.h"
 #include "vamd_demux_live.h"
+#include "vamd_headers.h"
 
 using namespace vamd;
 
@@ -66,6 +67,70 @@ static int create_failed(vamd_ctx *c, int caller_device) {
   vamd_destroy(c);
   if (caller_device >= 0) (void)hipSetDevice(caller_device);
   return VAMD_EFAULT;
+}
+
+// the part of a context's creation that both kinds share, from the image on: the device, its streams and events, the
+// image and the parameter block in HBM.  c: a new context with its knobs read; on failure it is destroyed.
+static int create_on_device(vamd_ctx *c, const std::vector<unsigned char> &image, const std::vector<uint32_t> &doff,
+                            const std::vector<PsyDerived> &derived, int device, vamd_ctx **out) {
+  hipError_t e = hipSuccess;
+  int caller_device = -1;
+  (void)hipGetDevice(&caller_device);  // put back before returning: creating a context must not move the caller
+  if (device >= 0) e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipGetDevice(&c->device);
+  if (e == hipSuccess) {
+    hipDeviceProp_t prop;
+    e = hipGetDeviceProperties(&prop, c->device);
+    if (e == hipSuccess) {
+      c->num_cus = prop.multiProcessorCount;
+      c->lds_per_block = prop.sharedMemPerBlock;
+      // opt in to the full LDS for the persistent transform kernels (a no-op where the
+      // runtime does not require it)
+#define VAMD_OPT_IN(LOGN)                                                                                      \
+  (void)hipFuncSetAttribute((const void *)k_transform<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
+                            (int)c->lds_per_block);                                                            \
+  (void)hipFuncSetAttribute((const void *)k_mdct_only<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
+                            (int)c->lds_per_block);
+      VAMD_OPT_IN(0) VAMD_OPT_IN(8) VAMD_OPT_IN(9) VAMD_OPT_IN(10) VAMD_OPT_IN(11) VAMD_OPT_IN(12)
+#undef VAMD_OPT_IN
+      (void)hipFuncSetAttribute((const void *)k_synth, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block);
+      if (c->decode_only) (void)hipFuncSetAttribute((const void *)k_synth_values, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block);
+      (void)hipGetLastError();
+      if (c->K.verbose)
+        fprintf(stderr, "vamd_create: %d CUs, %zu B LDS per workgroup\n", c->num_cus, c->lds_per_block);
+    }
+  }
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming);
+  c->overlap = !c->K.no_overlap;
+  // (test aid: k_couple's estimate-then-verify margin as a power of two; 1 sends every quad through the exact path)
+  c->couple_band = c->K.couple_band_set ? ldexpf(1.f, c->K.couple_band_log2) : VAMD_COUPLE_BAND;
+  if (e == hipSuccess) e = hipMalloc((void **)&c->d_image, image.size());
+  if (e == hipSuccess) e = hipMemcpy(c->d_image, image.data(), image.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    fprintf(stderr, "vamd_create: HIP failure: %s\n", hipGetErrorString(e));
+    return create_failed(c, caller_device);
+  }
+  c->image_bytes = image.size();
+  bind_params(image, doff, derived, c->d_image, &c->B);
+  if (!c->decode_only) {  // ... and which stack walk a large batch of either size class takes (not a knob: the build and the setup decide)
+    const size_t n = strlen(c->config);
+    snprintf(c->config + n, sizeof(c->config) - n, " chase_walk=%s,%s", chase_walk_regs(c->B.psy[0], c->B.psy[1]) ? "regs" : "ring",
+             chase_walk_regs(c->B.psy[2], c->B.psy[3]) ? "regs" : "ring");
+  }
+  const size_t bound_bytes = (sizeof(Bound) + 15) & ~(size_t)15;
+  if (hipMalloc((void **)&c->d_bound, bound_bytes + 16) != hipSuccess ||
+      hipMemset(c->d_bound, 0, bound_bytes + 16) != hipSuccess ||
+      hipMemcpy(c->d_bound, &c->B, sizeof(Bound), hipMemcpyHostToDevice) != hipSuccess) {
+    fprintf(stderr, "vamd_create: HIP failure uploading the parameter block\n");
+    return create_failed(c, caller_device);
+  }
+  c->d_bad = (unsigned int *)((unsigned char *)c->d_bound + bound_bytes);
+  if (caller_device >= 0 && caller_device != c->device) (void)hipSetDevice(caller_device);
+  *out = c;
+  return VAMD_OK;
 }
 
 int vamd_create_abi(vamd_ctx **out, const void *setup_blob, size_t blob_bytes, int device, int caller_abi_version) {
@@ -89,61 +154,60 @@ int vamd_create_abi(vamd_ctx **out, const void *setup_blob, size_t blob_bytes, i
     delete c;
     return r;
   }
-  hipError_t e = hipSuccess;
-  int caller_device = -1;
-  (void)hipGetDevice(&caller_device);  // put back before returning: creating a context must not move the caller
-  if (device >= 0) e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipGetDevice(&c->device);
-  if (e == hipSuccess) {
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, c->device);
-    if (e == hipSuccess) {
-      c->num_cus = prop.multiProcessorCount;
-      c->lds_per_block = prop.sharedMemPerBlock;
-      // opt in to the full LDS for the persistent transform kernels (a no-op where the
-      // runtime does not require it)
-#define VAMD_OPT_IN(LOGN)                                                                                      \
-  (void)hipFuncSetAttribute((const void *)k_transform<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                            (int)c->lds_per_block);                                                            \
-  (void)hipFuncSetAttribute((const void *)k_mdct_only<LOGN>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                            (int)c->lds_per_block);
-      VAMD_OPT_IN(0) VAMD_OPT_IN(8) VAMD_OPT_IN(9) VAMD_OPT_IN(10) VAMD_OPT_IN(11) VAMD_OPT_IN(12)
-#undef VAMD_OPT_IN
-      (void)hipFuncSetAttribute((const void *)k_synth, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block);
-      (void)hipGetLastError();
-      if (c->K.verbose)
-        fprintf(stderr, "vamd_create: %d CUs, %zu B LDS per workgroup\n", c->num_cus, c->lds_per_block);
+  return create_on_device(c, image, doff, derived, device, out);
+}
+
+// A decode-only context out of a stream's identification and setup header packets (vamd_headers.h).  A refusal's text
+// has no context to live in: it is kept here per thread, and vamd_last_error(NULL) hands it out.
+static thread_local std::string g_decoder_err;
+
+static int synth_covered(vamd_ctx *c, int W, SynthFloorP *S);  // vamd_batch.h
+
+int vamd_create_decoder(vamd_ctx **out, const void *id_header, size_t id_bytes, const void *setup_header, size_t setup_bytes, int device) {
+  if (!out) return VAMD_EINVAL;
+  *out = nullptr;
+  g_decoder_err.clear();
+  HeaderImage H;
+  int r = headers_to_image(id_header, id_bytes, setup_header, setup_bytes, &H, &g_decoder_err);
+  if (r != VAMD_OK) return r;
+  vamd_ctx *c = new (std::nothrow) vamd_ctx;
+  if (!c) return VAMD_EFAULT;
+  c->K = read_knobs();
+  knobs_string(c->K, c->config, sizeof(c->config));
+  c->decode_only = true;
+  c->setup_packet.assign((const uint8_t *)setup_header, (const uint8_t *)setup_header + setup_bytes);
+  vamd_ctx *made = nullptr;
+  if ((r = create_on_device(c, H.image, H.derived_off, H.derived, device, &made)) != VAMD_OK) {  // (c is gone)
+    g_decoder_err = "vamd_create_decoder: the device part failed (the device ordinal, an allocation or a copy: HIP's reason is on stderr)";
+    return r;
+  }
+  DeviceGuard dev_guard(c);
+  vamd_setup_header made_h;
+  memcpy(&made_h, H.image.data(), sizeof(made_h));
+  for (int W = 0; W < made_h.modes && r == VAMD_OK; W++) {  // (a workgroup's LDS is the device's to say)
+    SynthFloorP S;
+    r = synth_covered(c, W, &S);
+  }
+  if (r == VAMD_OK && H.table_books) {  // the value lists, behind their offsets
+    const size_t head = ((size_t)H.value_off.size() * 4 + 15) & ~(size_t)15, bytes = head + 4 * H.values.size();
+    if (hipMalloc((void **)&c->d_values, bytes) != hipSuccess ||
+        hipMemcpy(c->d_values, H.value_off.data(), 4 * H.value_off.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_values + head, H.values.data(), 4 * H.values.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      g_decoder_err = "vamd_create_decoder: HIP failure uploading the residue books' values";
+      r = VAMD_EFAULT;
+    } else {
+      c->V.book_off = (const int *)c->d_values, c->V.values = (const float *)(c->d_values + head);
     }
   }
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming);
-  c->overlap = !c->K.no_overlap;
-  // (test aid: k_couple's estimate-then-verify margin as a power of two; 1 sends every quad through the exact path)
-  c->couple_band = c->K.couple_band_set ? ldexpf(1.f, c->K.couple_band_log2) : VAMD_COUPLE_BAND;
-  if (e == hipSuccess) e = hipMalloc((void **)&c->d_image, image.size());
-  if (e == hipSuccess) e = hipMemcpy(c->d_image, image.data(), image.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    fprintf(stderr, "vamd_create: HIP failure: %s\n", hipGetErrorString(e));
-    return create_failed(c, caller_device);
+  if (r != VAMD_OK) {
+    if (g_decoder_err.empty()) g_decoder_err = c->err;
+    vamd_destroy(c);
+    return r;
   }
-  c->image_bytes = image.size();
-  bind_params(image, doff, derived, c->d_image, &c->B);
-  {  // ... and which stack walk a large batch of either size class takes (not a knob: the build and the setup decide)
+  {
     const size_t n = strlen(c->config);
-    snprintf(c->config + n, sizeof(c->config) - n, " chase_walk=%s,%s", chase_walk_regs(c->B.psy[0], c->B.psy[1]) ? "regs" : "ring",
-             chase_walk_regs(c->B.psy[2], c->B.psy[3]) ? "regs" : "ring");
+    snprintf(c->config + n, sizeof(c->config) - n, " decode_only=1 value_books=%d lattice_books=%d", H.table_books, H.lattice_books);
   }
-  const size_t bound_bytes = (sizeof(Bound) + 15) & ~(size_t)15;
-  if (hipMalloc((void **)&c->d_bound, bound_bytes + 16) != hipSuccess ||
-      hipMemset(c->d_bound, 0, bound_bytes + 16) != hipSuccess ||
-      hipMemcpy(c->d_bound, &c->B, sizeof(Bound), hipMemcpyHostToDevice) != hipSuccess) {
-    fprintf(stderr, "vamd_create: HIP failure uploading the parameter block\n");
-    return create_failed(c, caller_device);
-  }
-  c->d_bad = (unsigned int *)((unsigned char *)c->d_bound + bound_bytes);
-  if (caller_device >= 0 && caller_device != c->device) (void)hipSetDevice(caller_device);
   *out = c;
   return VAMD_OK;
 }
@@ -168,6 +232,7 @@ void vamd_destroy(vamd_ctx *c) {
   if (c->side) (void)hipStreamDestroy(c->side);
   if (c->d_image) (void)hipFree(c->d_image);
   if (c->d_bound) (void)hipFree(c->d_bound);
+  if (c->d_values) (void)hipFree(c->d_values);
   delete c;
 }
 
@@ -178,7 +243,7 @@ int vamd_device_count(void) {
   return hipGetDeviceCount(&n) == hipSuccess ? n : VAMD_EFAULT;
 }
 
-const char *vamd_last_error(const vamd_ctx *c) { return c ? c->err.c_str() : "null context"; }
+const char *vamd_last_error(const vamd_ctx *c) { return c ? c->err.c_str() : (g_decoder_err.empty() ? "null context" : g_decoder_err.c_str()); }
 
 int vamd_set_stream(vamd_ctx *c, void *s) {
   if (!c) return VAMD_EINVAL;

@@ -1741,3 +1741,20 @@ __global__ __launch_bounds__(64) void k_unpack(const Bound *B, UnpackP U, int la
   }
   pc.flush();
 }
+
+// ---- the decoder's back half for a setup with residue books that are no lattice books (a decode-only context made from a
+// stream's headers, vamd_headers.h): k_synth with the table form of the residue add (k_synth.h, ValueP).  Every other context launches k_synth.
+__global__ __launch_bounds__(64 * VAMD_MAX_CH) void k_synth_values(XformP X, ResP R0, ResP R1, ChMap cm, CoupleP C, SynthFloorP S, int ch, int ent_row,
+                                                                 int off_ints, unsigned long long *dbg, const int *__restrict__ post_valid,
+                                                                 const ilog_t *__restrict__ ilogmask, const int *__restrict__ res_class,
+                                                                 const unsigned short *__restrict__ res_entries,
+                                                                 const int *__restrict__ res_count, float *__restrict__ synth, ValueP V) {
+  const long u = blockIdx.x;
+  const int n = X.n, n2 = n >> 1;
+  PhaseClock pc;
+  pc.start(dbg);
+  synth_block<true>(X, R0, R1, cm, C, S, ch, off_ints, post_valid + u * ch, ilogmask + u * ch * n2,
+                    res_class + u * (cm.submaps * VAMD_RES_CLASS_STRIDE), res_entries + u * (long)ent_row, res_count + u * cm.submaps * 2,
+                    (float *)vamd_smem, synth + u * ch * n, pc, V);
+  pc.flush();
+}

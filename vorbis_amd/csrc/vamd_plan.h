@@ -69,6 +69,7 @@ static int envelope_search_batch(vamd_ctx *c, const float *pcm, long stream_stri
 
 int vamd_envelope_search_batch(vamd_ctx *c, const float *pcm, long stream_stride, long channel_stride, long nstreams,
                                long nsteps, vamd_envelope_state *states, unsigned char *ret) {
+  VAMD_NEEDS_ENCODER(c);
   return envelope_search_batch(c, pcm, stream_stride, channel_stride, nstreams, nsteps, states, ret, c ? c->d_bad + 1 : nullptr);
 }
 
@@ -290,17 +291,20 @@ static int plan_streams(vamd_ctx *c, float *pcm, long stream_stride, long channe
 
 int vamd_plan_streams(vamd_ctx *c, const float *pcm, long stream_stride, long channel_stride, long nstreams, long nsamples,
                       vamd_envelope_state *states, vamd_stream_plan *plan) {
+  VAMD_NEEDS_ENCODER(c);
   return plan_streams(c, (float *)pcm, stream_stride, channel_stride, nstreams, nsamples, states, plan, 0);
 }
 
 int vamd_plan_streams_whole(vamd_ctx *c, float *pcm, long stream_stride, long channel_stride, long nstreams, long nframes,
                             vamd_envelope_state *states, vamd_stream_plan *plan) {
+  VAMD_NEEDS_ENCODER(c);
   if (c && nframes < 0) return fail(c, VAMD_EINVAL, "negative frame count");
   return plan_streams(c, pcm, stream_stride, channel_stride, nstreams, c ? c->B.bs[1] / 2 + nframes : 0, states, plan, 1);
 }
 
 int vamd_plan_streams_whole_v(vamd_ctx *c, float *pcm, long stream_stride, long channel_stride, long nstreams, long max_frames,
                               const int64_t *nframes, vamd_envelope_state *states, vamd_stream_plan *plan) {
+  VAMD_NEEDS_ENCODER(c);
   if (c && (max_frames < 0 || !nframes)) return fail(c, VAMD_EINVAL, "negative frame count / null lengths");
   return plan_streams(c, pcm, stream_stride, channel_stride, nstreams, c ? c->B.bs[1] / 2 + max_frames : 0, states, plan, 1, nframes);
 }
@@ -331,6 +335,7 @@ const char *vamd_live_check(const vamd_ctx *c, int write_frames, long max_frames
 int vamd_live_plan(vamd_ctx *c, float *pcm, long ss, long cs, long nstreams, const vamd_live_geo *lg, int n_head,
                    void *walk, unsigned char *rows, long row_stride, vamd_envelope_state *states, long long *shift,
                    vamd_stream_plan *plan) {
+  VAMD_NEEDS_ENCODER(c);
   DeviceGuard dev_guard(c);
   if (!c) return VAMD_EINVAL;
   if (!plan || !lg || !pcm || !walk || !rows || !states || !shift || nstreams < 1) return fail(c, VAMD_EINVAL, "live plan: null argument");
