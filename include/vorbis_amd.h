@@ -595,20 +595,22 @@ int vamd_synth_streams(vamd_ctx *ctx, const vamd_stream_plan *plan, long nstream
  *   VAMD_STATUS_NOTAUDIO   the packet-type bit is set, or the mode number names no mode
  *   VAMD_STATUS_BADCODE    bits that are no codeword of the book they are read with, or a phrase word beyond the classes
  *   VAMD_STATUS_TRUNCATED  the packet ends before its block is complete (an empty packet too)
- * A DELIBERATE DEVIATION: libvorbis decodes what a truncated packet still holds (a floor that meets the end is no floor, a
- * residue keeps what it has -- eopbreak, lib/res0.c:650,709) and returns 0; here the stream is flagged, as a decoded feed's
- * stream with a missing packet is.  The packets a bitrate-managed encoder CUT to fit its reservoir are such packets.
+ * BY DEFAULT A DELIBERATE DEVIATION: libvorbis decodes what a truncated packet still holds (a floor that meets the end is
+ * no floor, a residue keeps what it has -- eopbreak, lib/res0.c:650,709) and returns 0; here the stream is flagged, as a
+ * decoded feed's stream with a missing packet is.  The packets a bitrate-managed encoder CUT to fit its reservoir are such
+ * packets.  vamd_decode_partial, below, closes it for a context that asks.
  *
  * Workspace: in the context, grown on demand, released with it -- per block 4 ch + ch n/2 + 2048 S + 2 *
  * vamd_residue_capacity + 8 S bytes of rows, 4 ch n of vb->pcm and 29 of plan (ch channels, n the block's size, S its
  * submaps), and the packets themselves.
  *
  * Out of scope: header packets and setups other than the context's; packets in device memory; streams that begin at a
- * nonzero granule (the first page's trim); eopbreak semantics (above).  Ogg files: vamd_decode_ogg, below.  A stream that
- * is still being made, its packets in pieces: vamd_decode_live, below. */
+ * nonzero granule (the first page's trim); skipping a packet vorbis_synthesis refuses (vamd_decode_partial, below).  Ogg
+ * files: vamd_decode_ogg, below.  A stream that is still being made, its packets in pieces: vamd_decode_live, below. */
 #define VAMD_STATUS_NOTAUDIO  4
 #define VAMD_STATUS_BADCODE   8
 #define VAMD_STATUS_TRUNCATED 16
+#define VAMD_STATUS_PARTIAL   128
 typedef struct vamd_decode_desc {
   int64_t nstreams, npackets;
   const uint8_t *bytes;          /* HOST: the audio packets, back to back */
@@ -619,6 +621,37 @@ typedef struct vamd_decode_desc {
 int vamd_decode_plan(vamd_ctx *ctx, const vamd_decode_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
 int vamd_decode_streams(vamd_ctx *ctx, const vamd_decode_desc *desc, const int64_t *offset_out /* host [nstreams] */,
                         float *pcm /* device */, uint8_t *status /* host [nstreams] */);
+
+/* ---- packets libvorbis decodes in part (still ABI 9: an addition).  A policy of the context, off by default: with keep
+ * != 0 every later decode call on the context -- vamd_decode_streams, vamd_decode_ogg, vamd_decode_live_wrote,
+ * vamd_decode_ogg_live_wrote, vamd_decode_window, vamd_decode_ogg_window -- decodes an audio packet for which libvorbis'
+ * vorbis_synthesis() returns 0 to what libvorbis leaves in vb->pcm for it, bit for bit, and laps it like any other block
+ * (tests/test_unpack_partial_cpu.py, tests/test_decode_partial_gpu.py).  keep > 0 turns it on, 0 off, keep < 0 changes
+ * nothing (a query).  -> the setting before the call (0 or 1); VAMD_EINVAL for a null context; VAMD_EIMPL as
+ * vamd_decode_plan gives it.  Nothing is enqueued.
+ *
+ * WHAT IS KEPT.  A packet that stops being read before its block is complete, as libvorbis reads it:
+ *   - a read past the packet's end fails, and so does every read after it;
+ *   - a channel whose floor meets such a read has no floor (a floor of two posts and no codeword -- the 5.1 LFE's -- whose
+ *     posts are missing is, as in libvorbis, a flat floor); the next channel reads on;
+ *   - a submap whose residue meets one -- or a phrase word beyond the classes, or a phrase book without used entries, which
+ *     fail without moving the reader -- ends there with every vector it had added, an entry whole or not at all; the next
+ *     submap reads on.
+ * Such a packet sets VAMD_STATUS_PARTIAL in its stream's status[s]: INFORMATIVE.  A stream whose status is 0 or
+ * VAMD_STATUS_PARTIAL alone has its planned frames, and they are its signal; a live stream stays alive.  "A flagged stream
+ * has no frames" reads status[s] & ~VAMD_STATUS_PARTIAL everywhere.  The _plan calls do not change: a kept packet is a
+ * whole block.
+ * WHAT STILL FLAGS A STREAM, as by default: a packet vorbis_synthesis() refuses -- the packet-type bit set, a mode number
+ * that names no mode or whose block size is not the plan's (VAMD_STATUS_NOTAUDIO), an empty packet or a head that does
+ * not complete (VAMD_STATUS_TRUNCATED); and all container damage (VAMD_STATUS_BADPAGE / _BADHEADER, a file that ends inside a page).
+ * A LIMIT OF HEADER-MADE SETUPS (vamd_create_decoder): a setup may hold a residue VALUE book without used entries.  libvorbis
+ * adds nothing for such a book, reads on and returns 0; here a packet that reaches one is VAMD_STATUS_BADCODE under either
+ * policy and its stream has no frames -- flagged, never decoded to something else.  No encoder's setup has such a book.
+ * OUT OF SCOPE: skipping a refused packet as a caller of libvorbis does -- that takes per-packet granule positions to lap
+ * and count as the reference then does; resynchronising a damaged container.
+ * The encoder side and the default policy run the kernels they ran before; the policy launches k_unpack_partial and the
+ * bounded k_synth forms in their place. */
+int vamd_decode_partial(vamd_ctx *ctx, int keep);
 
 /* ---- the live decoder: continuing streams decoded in pieces (still ABI 9: additions only).  The counterpart of a live
  * feed (vamd_feed_create_live): a caller who receives a stream's packets while the stream is still being made -- a live

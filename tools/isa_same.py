@@ -3,7 +3,7 @@
 
 Each of vamd_hip, vamd_feed and vamd_batcher is compiled in both trees with build_hip's flags plus
 --cuda-device-only -S -cuid=0 (a fixed unit id, so the __hip_cuid_ symbol does not differ), and the assembly is compared as
-text: whole files first, then -- if only the order of functions moved -- per symbol with local label numbers normalised.  Prints
+text: whole files first, then -- if only the order of functions moved -- per symbol with local label numbers normalised and comments dropped.  Prints
 the symbols that differ; exits non-zero unless every unit is the same.  A comparison compiles for several minutes."""
 import os
 import re
@@ -29,7 +29,10 @@ def symbols(text):
     func = re.compile(r"^([A-Za-z_][\w.$]*):[^\n]*\n(.*?)^\.Lfunc_end\d+:", re.M | re.S)
     for m in func.finditer(text):
         names = {}
-        bodies[m.group(1)] = re.sub(r"\.L[A-Za-z_]*\d+(?:_\d+)?", lambda l: names.setdefault(l.group(0), ".L%d" % len(names)), m.group(2))
+        # (comments are no code, and the loop comments name basic blocks by the function's number in the file, which moves
+        # when a kernel is added in front)
+        body = re.sub(r"[ \t]*;[^\n]*", "", m.group(2))
+        bodies[m.group(1)] = re.sub(r"\.L[A-Za-z_]*\d+(?:_\d+)?", lambda l: names.setdefault(l.group(0), ".L%d" % len(names)), body)
     # what is no function body (data, kernel descriptors, metadata) is held as a bag of lines
     bodies["(outside the functions)"] = sorted(re.sub(r"\.L[A-Za-z_]*\d+(?:_\d+)?", ".L", func.sub("", text)).split("\n"))
     return bodies, set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M))

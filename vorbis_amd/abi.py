@@ -14,6 +14,7 @@ ABI_VERSION = 9             # VAMD_ABI_VERSION of the header this mirror was wri
 QUANT_LIMIT_SQUARE, QUANT_LIMIT_INT = 46340, 0x7fffff80
 STATUS_RANGE, STATUS_NONFINITE = 1, 2   # bits of the `status` output (vorbis_amd.h, "Input domain")
 STATUS_NOTAUDIO, STATUS_BADCODE, STATUS_TRUNCATED = 4, 8, 16  # a decoded stream's status (vorbis_amd.h, "the packet decoder")
+STATUS_PARTIAL = 128  # informative, under Analyzer.keep_partial: a packet of the stream was decoded in part, as libvorbis decodes it
 STATUS_BADPAGE, STATUS_BADHEADER = 32, 64  # ... of a decoded file on top (vorbis_amd.h, "Ogg Vorbis files in")
 LEVEL_TRANSFORM, LEVEL_PSY, LEVEL_FULL = 1, 2, 3
 POSTS_STRIDE = 32
@@ -160,6 +161,7 @@ PROTOTYPES = {
     "vamd_synth_streams": (_int, [_vp, _pPlan, _long, _long, _vp, _vp, _vp, _vp, _vp]),
     "vamd_decode_plan": (_int, [_vp, _pDecode, _vp, _vp]),
     "vamd_decode_streams": (_int, [_vp, _pDecode, _vp, _vp, _vp]),
+    "vamd_decode_partial": (_int, [_vp, _int]),
     "vamd_decode_live_create": (_int, [_vp, C.c_int64, _pvp]),
     "vamd_decode_live_destroy": (None, [_vp]),
     "vamd_decode_live_plan": (_int, [_vp, _pDecodeLive, _vp, _vp]),

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from .abi import (ABI_VERSION, BLOCKTYPE_LONG, LEVEL_FULL, LEVEL_PSY, LEVEL_TRANSFORM, PACKETBLOBS, POSTS_STRIDE, QUANT_LIMIT_INT,
-                  QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_BADHEADER, STATUS_RANGE, VAMD_EDOMAIN, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
+                  QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_BADHEADER, STATUS_PARTIAL, STATUS_RANGE, VAMD_EDOMAIN, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
                   _DecodeDesc, _DecodeLiveDesc, _DecodeOggDesc, _DecodeOggLiveDesc, _DecodeOggLiveOpts, _Desc, _OggWindowDesc, _IO, _MIO, _Plan, _vp, load_library)
 from .packets import packet_bytes
 
@@ -693,10 +693,24 @@ class Analyzer:
         self._check(run(self.h, C.byref(d), _vp(out_off.ctypes.data), _vp(pcm.data_ptr()), _vp(status.ctypes.data)))
         return pcm, frames[:ns], out_off[:ns], status[:ns]
 
+    @property
+    def keep_partial(self):
+        """vamd_decode_partial: whether every decode call on this context decodes a packet that stops being read early to
+        what libvorbis makes of it (vorbis_synthesis() returns 0: a floor that meets the end is no floor, a residue keeps
+        what it has) and gives its stream its frames, with STATUS_PARTIAL in its status -- instead of flagging the stream
+        STATUS_TRUNCATED, the default.  Packets libvorbis refuses flag their stream either way."""
+        r = self.L.vamd_decode_partial(self.h, -1)  # (a negative value asks and changes nothing)
+        self._check(min(r, 0))
+        return r > 0
+
+    @keep_partial.setter
+    def keep_partial(self, keep):
+        self._check(min(self.L.vamd_decode_partial(self.h, 1 if keep else 0), 0))
+
     def _decoded_tensors(self, n, pcm, frames, out_off, status, with_status):
         out = []
         for s in range(n):
-            f = 0 if status[s] else int(frames[s])
+            f = 0 if int(status[s]) & ~STATUS_PARTIAL else int(frames[s])  # (a packet kept under keep_partial costs its stream nothing)
             out.append(pcm[int(out_off[s]):int(out_off[s]) + self.channels * f].view(self.channels, f))
         return (out, status.copy()) if with_status else out
 
@@ -706,7 +720,8 @@ class Analyzer:
         [[p for p, _, _, _ in row] for row in rows]); granules: per stream the last packet's granule position (None or -1:
         none), which cuts the last block's frames.  offset / stream_start: test hooks, the descriptor's arrays as given
         instead of as derived.  -> a list of float32 tensors [ch, frames] on the context's device; with_status, also the
-        streams' status bytes (numpy uint8): a flagged stream -- STATUS_NOTAUDIO / _BADCODE / _TRUNCATED -- has no frames."""
+        streams' status bytes (numpy uint8): a flagged stream -- STATUS_NOTAUDIO / _BADCODE / _TRUNCATED -- has no frames
+        (STATUS_PARTIAL alone, under keep_partial, is no flag: the stream has its frames)."""
         return self._decoded_tensors(len(streams), *self.decode_run(self.decode_prepare(streams, granules, offset, stream_start)), with_status)
 
     def live_decoder(self, max_streams):
@@ -1162,8 +1177,9 @@ class OggIndex:
         an._need(length >= 0, "crops: a negative length")
         pcm = t.zeros((n, an.channels, length), dtype=t.float32, device=an._dev())
         _, frames, _, status = self._run(stream, start, [length] * n, pcm=pcm.view(-1), stride=length)
-        valid = np.where(status != 0, 0, frames).astype(np.int64)
-        for w in np.nonzero((status != 0) & (frames > 0))[0]:  # (a window the device flagged has no frames: its row goes back to zero)
+        flagged = (status & ~np.uint8(STATUS_PARTIAL)) != 0
+        valid = np.where(flagged, 0, frames).astype(np.int64)
+        for w in np.nonzero(flagged & (frames > 0))[0]:  # (a window the device flagged has no frames: its row goes back to zero)
             pcm[int(w)].zero_()
         return (pcm, valid, status.copy()) if with_status else (pcm, valid)
 
@@ -1179,11 +1195,12 @@ def ogg_index(setup_blob, files, setup_header=None, device=None):
     return x
 
 
-def decode(setup_blob, streams, granules=None, with_status=False, device=None):
+def decode(setup_blob, streams, granules=None, with_status=False, device=None, keep_partial=False):
     """Analyzer(setup_blob).decode_streams(...) for a caller who holds packets and no context: the packets must come from an
-    encoder of that setup."""
+    encoder of that setup.  keep_partial: Analyzer.keep_partial for the call."""
     a = Analyzer(setup_blob, device)
     try:
+        a.keep_partial = keep_partial
         return a.decode_streams(streams, granules, with_status)
     finally:
         a.close()
@@ -1203,12 +1220,12 @@ def read_ogg_headers(file):
     return out.raw[:a], out.raw[a:a + b], out.raw[a + b:a + b + c]
 
 
-def decode_ogg_files(files, with_status=False, device=None):
+def decode_ogg_files(files, with_status=False, device=None, keep_partial=False):
     """Ogg Vorbis files of ANY covered setups in, PCM out: no blob and no settings.  Each file's headers are read
     (read_ogg_headers); the files are grouped by (identification fields, setup header bytes); one decode-only context is
     made per distinct setup (Analyzer.from_headers) and decodes its group in one decode_ogg call.  -> a list of float32
     tensors [ch, frames] in the caller's order; with_status, also the status bytes.  A file whose headers are rejected or
-    refused gets a [0, 0] tensor and STATUS_BADHEADER: it costs only itself."""
+    refused gets a [0, 0] tensor and STATUS_BADHEADER: it costs only itself.  keep_partial: Analyzer.keep_partial for every context."""
     import torch
     groups, out, status = {}, [None] * len(files), np.zeros(len(files), np.uint8)
     for i, f in enumerate(files):
@@ -1224,6 +1241,7 @@ def decode_ogg_files(files, with_status=False, device=None):
             status[members] = STATUS_BADHEADER
             continue
         try:
+            a.keep_partial = keep_partial
             pcm, st = a.decode_ogg([files[i] for i in members], with_status=True)
             for i, p, v in zip(members, pcm, st):
                 out[i], status[i] = p.clone(), v
@@ -1234,11 +1252,12 @@ def decode_ogg_files(files, with_status=False, device=None):
     return (out, status) if with_status else out
 
 
-def decode_ogg(setup_blob, files, setup_header=None, with_status=False, device=None):
+def decode_ogg(setup_blob, files, setup_header=None, with_status=False, device=None, keep_partial=False):
     """Analyzer(setup_blob).decode_ogg(...) for a caller who holds files and no context: the files must come from an
-    encoder of that setup."""
+    encoder of that setup.  keep_partial: Analyzer.keep_partial for the call."""
     a = Analyzer(setup_blob, device)
     try:
+        a.keep_partial = keep_partial
         return a.decode_ogg(files, setup_header, with_status)
     finally:
         a.close()

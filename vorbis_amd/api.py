@@ -4,7 +4,7 @@ feed.py (Feed, DeviceSource, device_source) -- and is importable from here as be
 from .abi import (ABI_VERSION, BLOCKTYPE_IMPULSE, BLOCKTYPE_LONG, BLOCKTYPE_PADDING, BLOCKTYPE_TRANSITION, EXPORTED_SYMBOLS,  # noqa: F401
                   FEED_DECODED, FEED_F32, FEED_NO_ARENA, FEED_S16, LEVEL_FULL, LEVEL_PSY, LEVEL_TRANSFORM, MAX_CH, PACKETBLOBS,
                   POSTS_STRIDE, PROTOTYPES, QUANT_LIMIT_INT, QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, SRC_BF16, SRC_F16, SRC_F32, SRC_S16,
-                  STATUS_BADCODE, STATUS_BADHEADER, STATUS_BADPAGE, STATUS_NONFINITE, STATUS_NOTAUDIO, STATUS_RANGE, STATUS_TRUNCATED, UNBOUND_SYMBOLS, VAMD_EDOMAIN,
+                  STATUS_BADCODE, STATUS_BADHEADER, STATUS_BADPAGE, STATUS_NONFINITE, STATUS_NOTAUDIO, STATUS_PARTIAL, STATUS_RANGE, STATUS_TRUNCATED, UNBOUND_SYMBOLS, VAMD_EDOMAIN,
                   VAMD_EBADHEADER, VAMD_EFAULT, VAMD_EIMPL, VAMD_EINVAL, VAMD_ENONFINITE, VAMD_ENOTVORBIS, VAMD_EVERSION, VAMD_OK, EnvelopeState, VamdError,
                   default_setup_blob, library_path, load_library)
 from .analyzer import (Analyzer, LiveDecoder, LiveOggDecoder, OggIndex, decode, decode_ogg, decode_ogg_files, ogg_index,  # noqa: F401

@@ -214,12 +214,17 @@ struct ValueP {
 // One submap's residue added into the spectrum (res1_inverse / res2_inverse with the entropy decode already done).
 //   TABLE: a book's vectors come from ValueP where it has a value list -- the same stage order, the same positions, one
 //          float addition per component as without.  A setup whose residue books are all lattice books never takes it.
+//   BOUNDED: the rows of a packet that stopped being read early (k_unpack.h, the keep policy): res_count[1] is the number of
+//          entries READ, and a vector whose place in reading order (base + v: stage-major, slots ascending, as the rows are
+//          written) is at or past it is not added.  Exact: a slot's stage-0 offset depends only on the classes of the slots
+//          before it, which were read, and every stage behind the stop begins at or past the count.  The other forms add a
+//          vector beyond R.cap as entry 0, which the encoder's rows rely on; only the decoder under that policy takes this one.
 //   chans LDS [VAMD_MAX_CH]: the bundle's channels in order (type 2), or those of them that take part (type 1: the
 //                            streams, lib/res0.c:757-767); filled here
 //   coded                    bit c: channel c takes part in a residue (mapping0_inverse's nonzero[], :715-733)
 //   res_class / res_entries / res_count: this submap's rows of one block (k_residue.h)
 //   spec LDS [ch][n2]; cls LDS [slots]; off LDS [stages*slots + 1]; info LDS [stages*slots]
-template <bool TABLE = false>
+template <bool TABLE = false, bool BOUNDED = false>
 VAMD_DEV void synth_residue(const ResP &R, const ChMap &cm, int sm, int ch, int n2, unsigned coded, const int *__restrict__ res_class,
                             const unsigned short *__restrict__ res_entries, const int *__restrict__ res_count, float *spec,
                             int *chans, int *cls, int *off, int *info, const ValueP &V = ValueP()) {
@@ -228,6 +233,7 @@ VAMD_DEV void synth_residue(const ResP &R, const ChMap &cm, int sm, int ch, int 
   if (slots <= 0 || slots > R.slots) return;  // no channel of the bundle is coded: res*_inverse reads nothing
   const int partvals = R.partvals, ns = slots / partvals, spp = t.grouping, stages = t.stages, bundle = R.bundle;
   const bool interleaved = t.type == 2;
+  const int count = BOUNDED ? res_count[1] : 0;
   if (TEAM_LEADER) {
     int k = 0;
     for (int c = 0; c < ch; c++)
@@ -244,6 +250,7 @@ VAMD_DEV void synth_residue(const ResP &R, const ChMap &cm, int sm, int ch, int 
     const int *so = off + s * slots;
     const int base = so[0], total = so[slots] - base;
     TEAM_FOR(v, total) {
+      if (BOUNDED && base + v >= count) continue;
       int lo = 0, hi = slots - 1;  // the slot whose vectors include v (residue_block's search)
       while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -317,7 +324,7 @@ VAMD_DEV int synth_line_at(int x, int x1, int y0, int y1) {
 //   post_valid [ch]; ilogmask [ch][n2]; res_class [submaps][VAMD_RES_CLASS_STRIDE], res_entries [row], res_count [submaps][2]
 //   lds: synth_lds_words(ch, n2, waves, off_ints) words, 16-byte aligned
 //   stopwatch marks (per wave): 0 the residue walk (the spectrum's zeroing included), 1 inverse coupling + floor, 2-5 the transform
-template <bool TABLE = false>
+template <bool TABLE = false, bool BOUNDED = false>
 VAMD_DEV void synth_block(const XformP &X, const ResP &R0, const ResP &R1, const ChMap &cm, const CoupleP &C, const SynthFloorP &S, int ch, int off_ints,
                           const int *__restrict__ post_valid, const ilog_t *__restrict__ ilogmask, const int *__restrict__ res_class,
                           const unsigned short *__restrict__ res_entries, const int *__restrict__ res_count, float *lds,
@@ -336,7 +343,7 @@ VAMD_DEV void synth_block(const XformP &X, const ResP &R0, const ResP &R1, const
   TEAM_SYNC();
   for (int sm = 0; sm < cm.submaps; sm++) {
     const ResP &R = sm ? R1 : R0;
-    synth_residue<TABLE>(R, cm, sm, ch, n2, coded, res_class + R.cls_base, res_entries + R.ent_base, res_count + 2 * sm, spec, chans, cls,
+    synth_residue<TABLE, BOUNDED>(R, cm, sm, ch, n2, coded, res_class + R.cls_base, res_entries + R.ent_base, res_count + 2 * sm, spec, chans, cls,
                          off, info, V);
   }
   pc.mark(0);

@@ -12,13 +12,33 @@
 // stream's; a table index taken from the stream is an entry number the decode table produced (< the book's entries, the
 // table's builder saw to it) or a digit of one (< the residue's classes), or it is masked to its table (the floor's
 // cascade word); every read is held against the packet's end.  A malformed packet ends in a status, with rows that name
-// nothing (post_valid and res_count zero): never in an access outside the rows, never in a loop without an end.
+// nothing (post_valid and res_count zero) -- or, under the keep policy below, with the rows of what was read and class 0 in
+// every slot that was not: never in an access outside the rows, never in a loop without an end, under either policy.
 //
-// TRUNCATED PACKETS -- a deliberate deviation.  libvorbis treats a packet that ends early as "stop working": a floor that
-// meets the end is no floor, a residue that meets it keeps what it has (eopbreak, lib/res0.c:650,709-710), and
-// vorbis_synthesis returns 0.  Here such a packet carries VAMD_STATUS_TRUNCATED and its stream yields no frames, as a
-// decoded feed's stream with a missing packet does.  A bitrate-managed feed's CUT packets (lib/bitrate.c trims a packet to
-// the byte count the reservoir allows) are truncated packets in this sense.
+// TRUNCATED PACKETS -- two policies, the context's choice (vamd_decode_partial, include/vorbis_amd.h).  libvorbis treats a
+// packet that ends early as "stop working": a floor that meets the end is no floor, a residue that meets it keeps what it
+// has (eopbreak, lib/res0.c:650,709-710), and vorbis_synthesis returns 0.
+//   The default (unpack_packet): such a packet carries VAMD_STATUS_TRUNCATED and its stream yields no frames, as a decoded
+//   feed's stream with a missing packet does.  A bitrate-managed feed's CUT packets (lib/bitrate.c trims a packet to the
+//   byte count the reservoir allows) are truncated packets in this sense.
+//   The keep policy (unpack_packet_partial, the same walk's second instantiation): the packet decodes to what libvorbis
+//   leaves in vb->pcm for it, and carries VAMD_STATUS_PARTIAL, which costs its stream nothing.  The reference's rules,
+//   restated:
+//     the reader   a read or advance past the packet's end leaves nothing to read: every later read fails (oggpack_read,
+//                  and decode_packed_entry_number's advance over what is left, lib/codebook.c:336-369) -- bits_poison;
+//     a floor      the flag bit that fails, or a codeword that does, is no floor for that channel (floor1_inverse1's eop);
+//                  the two end posts are read UNCHECKED (lib/floor1.c:967-968): a read that fails leaves -1 there, and
+//                  a floor with no codeword behind them -- two posts, the 5.1 LFE's -- is a floor all the same, flat at
+//                  the first post's height (0 where that is the -1).  The next channel reads on where the reader stands;
+//     a residue    a phrase word or an entry that fails ends its SUBMAP (eopbreak), and so do a phrase word beyond the
+//                  classes and a phrase book without used entries, which leave the reader as it is.  Every vector added
+//                  before stays: res_count = {slots, entries read}, and the bounded synthesis (k_synth.h) adds exactly
+//                  those.  Slots never reached hold class 0.  The next submap reads on where the reader stands.
+//   Fatal under both: what vorbis_synthesis refuses (the type bit, a mode that is none or not the plan's, an empty
+//   packet, a head that does not complete: lib/synthesis.c:44-66) -- a caller of libvorbis skips such a packet, which
+//   takes per-packet granule positions to lap and count as it does, and is not done here.  And what no complete book
+//   can give: a residue value book without used entries (VAMD_STATUS_BADCODE) -- a limit of header-made setups, which may
+//   hold such a book: libvorbis adds nothing for it and reads on, and its vectors have no numbers in the rows.
 #pragma once
 #include "vamd_wave.h"
 #include "vamd_params.h"
@@ -28,6 +48,7 @@
 #define VAMD_STATUS_NOTAUDIO 4    // the packet-type bit is set, the mode number names no mode, or its size class is not the plan's
 #define VAMD_STATUS_BADCODE 8     // bits that are no codeword of the book they are read with, or a phrase word beyond the classes
 #define VAMD_STATUS_TRUNCATED 16  // the packet ends before the block is complete
+#define VAMD_STATUS_PARTIAL 128   // (the keep policy, informative) the packet stopped being read early and decoded as libvorbis decodes it
 
 // Packets a wave of k_unpack (vamd_kernels.h), the rest of its lanes idle.  Measured (profiles/r22_decode.txt).
 #define VAMD_UNPACK_LANES 64
@@ -40,7 +61,7 @@ namespace vamd {
 // (bit-reversed as the stream holds it, left aligned in 32 bits): the codeword that matches is the last one not above
 // the next 32 bits of the stream, read the same way.
 struct UnpackBook {
-  int32_t entries, k, nsorted, pad;
+  int32_t entries, k, nsorted, used;  // used: the entries that have a codeword (0: vorbis_book_decode gives -1 and reads nothing)
   uint32_t off_first;  // uint32 [1 << k][2]: {entry, length} (length > 0), or {lo, hi << 8} (low byte 0)
   uint32_t off_codes;  // uint32 [nsorted]
   uint32_t off_info;   // uint32 [nsorted]: entry | length << 24
@@ -93,6 +114,24 @@ VAMD_DEV bool bits_read(BitIn &b, int k, unsigned &v) {
   return true;
 }
 
+// the keep policy's reader: once a read has failed nothing is left, whatever a later read asks for
+VAMD_DEV void bits_poison(BitIn &b) { b.end = b.pos; }
+template <bool PARTIAL>
+VAMD_DEV bool bits_take(BitIn &b, int k, unsigned &v) {
+  if constexpr (!PARTIAL) return bits_read(b, k, v);
+  if (bits_read(b, k, v)) return true;
+  bits_poison(b);
+  return false;
+}
+
+// Where a walk under the keep policy stopped, for the one-lane test program (tests/c/unpack_partial_host.cpp), which
+// holds its cases to having met every one of them; the kernels pass UnpackNoNote, which is nothing.
+enum { UNPACK_AT_FLAG = 1, UNPACK_AT_POST, UNPACK_AT_FLOORBOOK, UNPACK_AT_PHRASE, UNPACK_AT_CLASSES, UNPACK_AT_ENTRY };
+struct UnpackNoNote {
+  VAMD_MEM void stop(int, int, int) {}  // (place, channel or submap, stage)
+  VAMD_MEM void entry(int, long long) {}  // (submap, the reader's place behind an entry that was read)
+};
+
 // vorbis_book_decode: the entry (< the book's entries), or -VAMD_STATUS_* .  A codeword that fits what is left of the
 // packet is found whatever follows it (the reference retries with fewer bits, lib/codebook.c:312-318).
 VAMD_DEV int unpack_book(const UnpackP &U, int booknum, BitIn &in) {
@@ -122,6 +161,20 @@ VAMD_DEV int unpack_book(const UnpackP &U, int booknum, BitIn &in) {
   if ((long long)len > left) return -VAMD_STATUS_TRUNCATED;
   bits_adv(in, len);
   return entry;
+}
+
+// vorbis_book_decode under either policy.  PARTIAL: -VAMD_STATUS_PARTIAL where libvorbis gives -1 -- the packet ends
+// inside the codeword (the reader is left with nothing) or the book has no used entries (the reader is left alone)
+template <bool PARTIAL>
+VAMD_DEV int unpack_code(const UnpackP &U, int booknum, BitIn &in) {
+  if constexpr (!PARTIAL) return unpack_book(U, booknum, in);
+  if (booknum >= 0 && booknum < U.nbooks && !((const UnpackBook *)U.tab)[booknum].used) return -VAMD_STATUS_PARTIAL;
+  const int r = unpack_book(U, booknum, in);
+  if (r == -VAMD_STATUS_TRUNCATED) {
+    bits_poison(in);
+    return -VAMD_STATUS_PARTIAL;
+  }
+  return r;
 }
 
 // render_point, lib/floor1.c:257-272
@@ -154,17 +207,31 @@ struct CurveOut {
 // the posts in use at the SETUP's places, flat behind the last.  (Where the range is no power of two -- one line, the 5.1
 // LFE floor -- a decoder draws to another place; k_synth redraws that line from curve[0] and curve[range]: SynthFloorP.)
 //   fit: the lane's [posts] ints, element i at fit[i * fs]
-// -> 0 or a status; *valid = the floor's nonzero flag
+// -> 0 or a status; *valid = the floor's nonzero flag.  PARTIAL (the head of the file): VAMD_STATUS_PARTIAL alone is a
+// read that failed -- no floor, or the floor of end posts that were not there; c: the channel, for the note
+template <bool PARTIAL, class Note>
 VAMD_DEV int unpack_floor(const FloorP &F, const vamd_floor1_tab &f, int qbits, const UnpackP &U, BitIn &in, int *fit, int fs,
-                          ilog_t *curve, int n2, int *valid) {
+                          ilog_t *curve, int n2, int *valid, int c, Note &note) {
   unsigned v;
+  int stopped = 0;  // (PARTIAL: VAMD_STATUS_PARTIAL once an end post was not there)
   *valid = 0;
-  if (!bits_read(in, 1, v)) return VAMD_STATUS_TRUNCATED;
+  if (!bits_take<PARTIAL>(in, 1, v)) {
+    if constexpr (PARTIAL) {
+      note.stop(UNPACK_AT_FLAG, c, 0);
+      return VAMD_STATUS_PARTIAL;
+    }
+    return VAMD_STATUS_TRUNCATED;
+  }
   if (!v) return 0;
   const int posts = F.posts < VAMD_POSIT ? F.posts : VAMD_POSIT;
   if (posts < 2) return VAMD_STATUS_NOTAUDIO;
   for (int i = 0; i < 2; i++) {
-    if (!bits_read(in, qbits, v)) return VAMD_STATUS_TRUNCATED;
+    if (!bits_take<PARTIAL>(in, qbits, v)) {
+      if constexpr (!PARTIAL) return VAMD_STATUS_TRUNCATED;
+      if (!stopped) note.stop(UNPACK_AT_POST, c, 0);
+      stopped = VAMD_STATUS_PARTIAL;
+      v = ~0u;  // (oggpack_read's -1, kept: lib/floor1.c:967-968)
+    }
     fit[i * fs] = (int)v;
   }
   const int parts = f.partitions < VAMD_FLOOR_PARTS ? f.partitions : VAMD_FLOOR_PARTS;
@@ -174,7 +241,10 @@ VAMD_DEV int unpack_floor(const FloorP &F, const vamd_floor1_tab &f, int qbits, 
     const int cdim = f.class_dim[cls], csubbits = f.class_subs[cls] & 3, csub = 1 << csubbits;
     int cval = 0;
     if (csubbits) {
-      cval = unpack_book(U, f.class_book[cls], in);
+      cval = unpack_code<PARTIAL>(U, f.class_book[cls], in);
+      if constexpr (PARTIAL) {
+        if (cval == -VAMD_STATUS_PARTIAL && !stopped) note.stop(UNPACK_AT_FLOORBOOK, c, 0);
+      }
       if (cval < 0) return -cval;
     }
     for (int k = 0; k < cdim && j < posts; k++, j++) {
@@ -182,7 +252,10 @@ VAMD_DEV int unpack_floor(const FloorP &F, const vamd_floor1_tab &f, int qbits, 
       cval >>= csubbits;
       int val = 0;
       if (book >= 0) {
-        val = unpack_book(U, book, in);
+        val = unpack_code<PARTIAL>(U, book, in);
+        if constexpr (PARTIAL) {
+          if (val == -VAMD_STATUS_PARTIAL && !stopped) note.stop(UNPACK_AT_FLOORBOOK, c, 1);
+        }
         if (val < 0) return -val;
       }
       fit[j * fs] = val;
@@ -216,6 +289,7 @@ VAMD_DEV int unpack_floor(const FloorP &F, const vamd_floor1_tab &f, int qbits, 
   CurveOut o;
   o.w = (unsigned *)curve, o.acc = 0, o.x = 0, o.n = n2;
   int lx = 0, ly = height(fit[0] & 0x7fff);
+  if constexpr (PARTIAL) ly = fit[0] < 0 ? 0 : ly;  // (the -1 of a failed read times mult, clamped: lib/floor1.c:1055-1057)
   for (int q = 1; q < posts; q++) {
     const int current = F.forward_index[q] & 127;
     if (current >= posts) continue;
@@ -243,14 +317,27 @@ VAMD_DEV int unpack_floor(const FloorP &F, const vamd_floor1_tab &f, int qbits, 
   }
   while (o.x < n2) o.put(ly);
   *valid = 1;
+  if constexpr (PARTIAL) return stopped;
   return 0;
+}
+
+// The keep policy's end of a submap: the slots from partition p0 on -- of its phrase word's partitions only the streams from
+// j0 on -- were never given a class and get class 0; e entries were read.
+VAMD_DEV int unpack_residue_stop(const ResP &R, int partvals, int ns, int ppw, int p0, int j0, int e, int *res_class, int *res_count) {
+  for (int p = p0; p < partvals; p++)
+    for (int j = p < p0 + ppw ? j0 : 0; j < ns; j++) res_class[p * ns + j] = 0;
+  res_count[0] = partvals * ns, res_count[1] = e < R.cap ? e : R.cap;
+  return VAMD_STATUS_PARTIAL;
 }
 
 // One submap's residue: the phrase words into classes, the codewords into entries, in the order they are read -- which
 // is the order residue_block leaves them in and synth_residue walks (k_residue.h).
 //   coded: bit c = channel c takes part (mapping0_inverse's nonzero[] after the coupling rule)
+// PARTIAL (the head of the file): VAMD_STATUS_PARTIAL is a submap that ended early, with res_count = {slots, the entries
+// read} and class 0 in the slots that were never reached.
+template <bool PARTIAL, class Note>
 VAMD_DEV int unpack_residue(const ResP &R, const ChMap &cm, int sm, int ch, unsigned coded, const UnpackP &U, BitIn &in, int *res_class,
-                            unsigned short *res_entries, int *res_count) {
+                            unsigned short *res_entries, int *res_count, Note &note) {
   const vamd_residue_tab &t = *R.tab;
   int ns = 0;
   for (int c = 0; c < ch; c++)
@@ -270,7 +357,13 @@ VAMD_DEV int unpack_residue(const ResP &R, const ChMap &cm, int sm, int ch, unsi
     for (int i = 0; i < partvals; i += ppw) {
       if (s == 0)
         for (int j = 0; j < ns; j++) {
-          int temp = unpack_book(U, R.groupbook, in);
+          int temp = unpack_code<PARTIAL>(U, R.groupbook, in);
+          if constexpr (PARTIAL) {
+            if (temp == -VAMD_STATUS_PARTIAL || temp >= words) {
+              note.stop(temp < 0 ? UNPACK_AT_PHRASE : UNPACK_AT_CLASSES, sm, 0);
+              return unpack_residue_stop(R, partvals, ns, ppw, i, j, e, res_class, res_count);
+            }
+          }
           if (temp < 0) return -temp;
           if (temp >= words) return VAMD_STATUS_BADCODE;
           for (int k = ppw - 1; k >= 0; k--) {  // decodemap (lib/res0.c:226-241): the first partition's class is the highest digit
@@ -287,8 +380,16 @@ VAMD_DEV int unpack_residue(const ResP &R, const ChMap &cm, int sm, int ch, unsi
           if (bn < 0 || bn >= U.nbooks) continue;
           const int dim = R.books[bn].dim, nv = dim > 0 ? spp / dim : 0;
           for (int v = 0; v < nv; v++) {
-            const int ent = unpack_book(U, bn, in);
+            const int ent = unpack_code<PARTIAL>(U, bn, in);
+            if constexpr (PARTIAL) {
+              if (ent == -VAMD_STATUS_PARTIAL) {
+                if (!((const UnpackBook *)U.tab)[bn].used) return VAMD_STATUS_BADCODE;  // (libvorbis adds nothing and reads on: the head of the file)
+                note.stop(UNPACK_AT_ENTRY, sm, s);
+                return unpack_residue_stop(R, partvals, ns, ppw, s ? partvals : i + ppw, 0, e, res_class, res_count);
+              }
+            }
             if (ent < 0) return -ent;
+            if constexpr (PARTIAL) note.entry(sm, in.pos);
             if (e < R.cap) res_entries[e] = (unsigned short)ent;
             e++;
           }
@@ -303,15 +404,17 @@ VAMD_DEV int unpack_residue(const ResP &R, const ChMap &cm, int sm, int ch, unsi
 //   post_valid [ch]; ilogmask [ch][n2] (4-byte aligned); res_class [submaps][VAMD_RES_CLASS_STRIDE]; res_entries [row];
 //   res_count [submaps][2]; fit: the lane's [VAMD_POSIT] ints, fs apart
 //   stopwatch marks: 0 the head, 1 the floors, 2 the residues
-// -> 0, or VAMD_STATUS_* with post_valid and res_count zero
-VAMD_DEV int unpack_packet(const Bound &B, const UnpackP &U, const uint32_t *words, long long nwords, long long bit0, long long bit1, int W,
+// -> 0, or VAMD_STATUS_* with post_valid and res_count zero.  PARTIAL: or VAMD_STATUS_PARTIAL alone, with the rows of what
+// was read (the head of the file)
+template <bool PARTIAL, class Note>
+VAMD_DEV int unpack_walk(const Bound &B, const UnpackP &U, const uint32_t *words, long long nwords, long long bit0, long long bit1, int W,
                            int *post_valid, ilog_t *ilogmask, int *res_class, unsigned short *res_entries, int *res_count, int *fit, int fs,
-                           PhaseClock &pc) {
+                           PhaseClock &pc, Note &note) {
   const int ch = B.channels < VAMD_MAX_CH ? B.channels : VAMD_MAX_CH, n2 = B.bs[W] >> 1;
   const ChMap &cm = B.chmap[W];
   BitIn in;
   bits_open(in, words, nwords, bit0, bit1 > bit0 ? bit1 : bit0);
-  int status = 0;
+  int status = 0, partial = 0;
   unsigned v = 0, floored = 0;
   // the head (lib/synthesis.c:44-66): packet type, mode number, a long block's neighbours
   if (!bits_read(in, 1, v)) status = VAMD_STATUS_TRUNCATED;
@@ -325,7 +428,8 @@ VAMD_DEV int unpack_packet(const Bound &B, const UnpackP &U, const uint32_t *wor
   for (int c = 0; c < ch && !status; c++) {
     const int sm = cm.sub[c] ? 1 : 0;
     int valid = 0;
-    status = unpack_floor(B.floor[W][sm], *B.pack[W].ftab[sm], B.pack[W].qbits[sm], U, in, fit, fs, ilogmask + (size_t)c * n2, n2, &valid);
+    status = unpack_floor<PARTIAL>(B.floor[W][sm], *B.pack[W].ftab[sm], B.pack[W].qbits[sm], U, in, fit, fs, ilogmask + (size_t)c * n2, n2, &valid, c, note);
+    if constexpr (PARTIAL) partial |= status & VAMD_STATUS_PARTIAL, status &= ~VAMD_STATUS_PARTIAL;
     post_valid[c] = valid;
     floored |= (valid ? 1u : 0u) << c;
   }
@@ -337,7 +441,8 @@ VAMD_DEV int unpack_packet(const Bound &B, const UnpackP &U, const uint32_t *wor
       if (i < C.coupling_steps && (((coded >> C.mag[i]) | (coded >> C.ang[i])) & 1u)) coded |= (1u << C.mag[i]) | (1u << C.ang[i]);
     for (int sm = 0; sm < cm.submaps && sm < VAMD_MAX_SUBMAPS && !status; sm++) {
       const ResP &R = B.res[W][sm];
-      status = unpack_residue(R, cm, sm, ch, coded, U, in, res_class + R.cls_base, res_entries + R.ent_base, res_count + 2 * sm);
+      status = unpack_residue<PARTIAL>(R, cm, sm, ch, coded, U, in, res_class + R.cls_base, res_entries + R.ent_base, res_count + 2 * sm, note);
+      if constexpr (PARTIAL) partial |= status & VAMD_STATUS_PARTIAL, status &= ~VAMD_STATUS_PARTIAL;
     }
   }
   if (status) {
@@ -345,7 +450,21 @@ VAMD_DEV int unpack_packet(const Bound &B, const UnpackP &U, const uint32_t *wor
     for (int sm = 0; sm < cm.submaps && sm < VAMD_MAX_SUBMAPS; sm++) res_count[2 * sm] = 0, res_count[2 * sm + 1] = 0;
   }
   pc.mark(2);
+  if constexpr (PARTIAL) return status ? status : partial;
   return status;
+}
+VAMD_DEV int unpack_packet(const Bound &B, const UnpackP &U, const uint32_t *words, long long nwords, long long bit0, long long bit1, int W,
+                           int *post_valid, ilog_t *ilogmask, int *res_class, unsigned short *res_entries, int *res_count, int *fit, int fs,
+                           PhaseClock &pc) {
+  UnpackNoNote note;
+  return unpack_walk<false>(B, U, words, nwords, bit0, bit1, W, post_valid, ilogmask, res_class, res_entries, res_count, fit, fs, pc, note);
+}
+// the keep policy (the head of the file)
+template <class Note>
+VAMD_DEV int unpack_packet_partial(const Bound &B, const UnpackP &U, const uint32_t *words, long long nwords, long long bit0, long long bit1, int W,
+                                   int *post_valid, ilog_t *ilogmask, int *res_class, unsigned short *res_entries, int *res_count, int *fit,
+                                   int fs, PhaseClock &pc, Note &note) {
+  return unpack_walk<true>(B, U, words, nwords, bit0, bit1, W, post_valid, ilogmask, res_class, res_entries, res_count, fit, fs, pc, note);
 }
 
 }  // namespace vamd

@@ -630,7 +630,7 @@ static void launch_floor_on(vamd_ctx *c, BatchRun *R, int level) {
   }
 }
 
-static int launch_synth(vamd_ctx *c, int W, const vamd_ctx::SynthSrc &y, float *synth);
+static int launch_synth(vamd_ctx *c, int W, const vamd_ctx::SynthSrc &y, float *synth, bool bounded = false);
 
 static int run_batch(vamd_ctx *c, const vamd_batch_desc *desc, const vamd_batch_io *io, int level, bool stream_mode,
                      float *ampmax_state, const vamd_managed_io *M = nullptr, float *synth = nullptr) {
@@ -693,14 +693,22 @@ static int synth_covered(vamd_ctx *c, int W, SynthFloorP *S) {
   return VAMD_OK;
 }
 // k_synth over y's blocks of size class W -- what the last run left (vamd_ctx::synth_src), or the rows k_unpack wrote
-// (vamd_decode.h) -- on the context's stream
-static int launch_synth(vamd_ctx *c, int W, const vamd_ctx::SynthSrc &y, float *synth) {
+// (vamd_decode.h) -- on the context's stream.  bounded: the rows are k_unpack_partial's (res_count[1] = the entries read)
+static int launch_synth(vamd_ctx *c, int W, const vamd_ctx::SynthSrc &y, float *synth, bool bounded) {
   SynthFloorP S;
   int r = synth_covered(c, W, &S);
   if (r) return r;
   if (y.nb < 1) return VAMD_OK;
   const int ch = c->B.channels, n2 = c->B.bs[W] / 2;
-  if (c->V.values)  // (a header-made setup with a residue book that is no lattice book: vamd_ctx::V)
+  if (bounded && c->V.values)
+    hipLaunchKernelGGL(k_synth_values_bounded, dim3((unsigned)y.nb), dim3(64 * ch), synth_lds_bytes(c, W), c->stream,
+                       c->B.xf[W], c->B.res[W][0], c->B.res[W][1], c->B.chmap[W], c->B.couple[W], S, ch, c->B.res_cap[W], c->B.res_off_ints[W],
+                       c->d_dbg ? c->d_dbg + 8 : nullptr, y.post_valid, y.ilogmask, y.res_class, y.res_entries, y.res_count, synth, c->V);
+  else if (bounded)
+    hipLaunchKernelGGL(k_synth_bounded, dim3((unsigned)y.nb), dim3(64 * ch), synth_lds_bytes(c, W), c->stream,
+                       c->B.xf[W], c->B.res[W][0], c->B.res[W][1], c->B.chmap[W], c->B.couple[W], S, ch, c->B.res_cap[W], c->B.res_off_ints[W],
+                       c->d_dbg ? c->d_dbg + 8 : nullptr, y.post_valid, y.ilogmask, y.res_class, y.res_entries, y.res_count, synth);
+  else if (c->V.values)  // (a header-made setup with a residue book that is no lattice book: vamd_ctx::V)
     hipLaunchKernelGGL(k_synth_values, dim3((unsigned)y.nb), dim3(64 * ch), synth_lds_bytes(c, W), c->stream,
                        c->B.xf[W], c->B.res[W][0], c->B.res[W][1], c->B.chmap[W], c->B.couple[W], S, ch, c->B.res_cap[W], c->B.res_off_ints[W],
                        c->d_dbg ? c->d_dbg + 8 : nullptr, y.post_valid, y.ilogmask, y.res_class, y.res_entries, y.res_count, synth, c->V);

@@ -223,7 +223,13 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
     HIP_TRY(c, hipMemcpyAsync(D.bytes.p, in.packets, (size_t)nbytes, hipMemcpyHostToDevice, s));
   }
   const int lanes = D.lanes;
-  if (nb) {
+  if (nb && D.partial) {
+    hipLaunchKernelGGL(k_unpack_partial, dim3((unsigned)((nb + lanes - 1) / lanes)), dim3(64), (size_t)VAMD_POSIT * lanes * 4, s, (const Bound *)c->d_bound, D.U, lanes, (long)nb,
+                       (const uint32_t *)D.bytes.p, nwords,
+                       (const long long *)(dp + o_bits), (const int *)(dp + o_unpack), c->B.res_cap[0], c->B.res_cap[1], c->d_dbg ? c->d_dbg + 56 : nullptr,
+                       rows[0], rows[1], (unsigned char *)D.status.p);
+    HIP_TRY(c, hipGetLastError());
+  } else if (nb) {
     hipLaunchKernelGGL(k_unpack, dim3((unsigned)((nb + lanes - 1) / lanes)), dim3(64), (size_t)VAMD_POSIT * lanes * 4, s, (const Bound *)c->d_bound, D.U, lanes, (long)nb,
                        (const uint32_t *)D.bytes.p, nwords,
                        (const long long *)(dp + o_bits), (const int *)(dp + o_unpack), c->B.res_cap[0], c->B.res_cap[1], c->d_dbg ? c->d_dbg + 56 : nullptr,
@@ -231,7 +237,7 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
     HIP_TRY(c, hipGetLastError());
   }
   for (int W = 0; W < 2; W++)
-    if (src[W].nb > 0 && (r = launch_synth(c, W, src[W], (float *)D.synth[W].p))) return r;
+    if (src[W].nb > 0 && (r = launch_synth(c, W, src[W], (float *)D.synth[W].p, D.partial))) return r;
   if (nin || nout) {
     CarryP C;
     C.ch = ch, C.bs0 = c->B.bs[0], C.bs1 = c->B.bs[1];
@@ -274,6 +280,24 @@ static int decode_outputs(vamd_ctx *c, const DecodePlan &P, int64_t ns, const in
     status[s] = P.status[(size_t)s];
   }
   return VAMD_OK;
+}
+
+// the policy for packets libvorbis decodes in part (include/vorbis_amd.h; k_unpack.h, "TRUNCATED PACKETS"): decode_run picks
+// its kernels by it, so every entry follows
+int vamd_decode_partial(vamd_ctx *c, int keep) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  int r = decode_ready(c);
+  if (r) return r;
+  const int was = c->dec.partial ? 1 : 0;
+  if (keep < 0) return was;  // (a query)
+  if (keep && !was) {  // (as vamd_create opts k_synth in to the full LDS; a no-op where the runtime does not require it)
+    (void)hipFuncSetAttribute((const void *)k_synth_bounded, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block);
+    (void)hipFuncSetAttribute((const void *)k_synth_values_bounded, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_per_block);
+    (void)hipGetLastError();
+  }
+  c->dec.partial = keep != 0;
+  return was;
 }
 
 int vamd_decode_streams(vamd_ctx *c, const vamd_decode_desc *d, const int64_t *offset_out, float *pcm, uint8_t *status) {

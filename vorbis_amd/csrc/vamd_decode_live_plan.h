@@ -128,7 +128,8 @@ inline void decode_live_commit(std::vector<LiveSlot> *slots, const DecodeLivePla
                                const uint8_t *status) {
   for (int64_t s = 0; s < nstreams; s++) {
     LiveSlot now = L.next[(size_t)s];
-    if (status[s] && !(close && close[s])) now.dead = status[s], now.carry = -1;
+    const uint8_t flagged = status[s] & (uint8_t)~VAMD_STATUS_PARTIAL;  // (a packet kept under vamd_decode_partial costs its stream nothing)
+    if (flagged && !(close && close[s])) now.dead = flagged, now.carry = -1;
     (*slots)[(size_t)slot[s]] = now;
   }
 }

@@ -117,7 +117,7 @@ inline void unpack_build_tables(const std::vector<unsigned char> &image, std::ve
     }
     UnpackBook &o = head[(size_t)b];
     memset(&o, 0, sizeof(o));
-    o.entries = bk[b].entries, o.k = k, o.nsorted = (int)longs.size();
+    o.entries = bk[b].entries, o.k = k, o.nsorted = (int)longs.size(), o.used = used;
     o.off_first = (uint32_t)(body_at + 4 * body.size());
     body.insert(body.end(), first.begin(), first.end());
     o.off_codes = (uint32_t)(body_at + 4 * body.size());

@@ -21,6 +21,9 @@
 #define VAMD_STATUS_BADPAGE 32
 #define VAMD_STATUS_BADHEADER 64
 #endif
+#ifndef VAMD_STATUS_PARTIAL  // (k_unpack.h)
+#define VAMD_STATUS_PARTIAL 128
+#endif
 
 namespace vamd {
 

@@ -217,8 +217,9 @@ inline void demux_live_commit(std::vector<DemuxLiveSlot> *slots, DemuxLiveCall *
                               const uint8_t *status) {
   for (int64_t s = 0; s < nstreams; s++) {
     DemuxLiveSlot &now = L->next[(size_t)s];
-    if (status[s] && !(close && close[s])) {
-      now.dead = status[s];
+    const uint8_t flagged = status[s] & (uint8_t)~VAMD_STATUS_PARTIAL;  // (a packet kept under vamd_decode_partial costs its stream nothing)
+    if (flagged && !(close && close[s])) {
+      now.dead = flagged;
       now.held.clear();
     }
     (*slots)[(size_t)slot[s]] = std::move(now);

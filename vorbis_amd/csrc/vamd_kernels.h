@@ -1758,3 +1758,55 @@ __global__ __launch_bounds__(64 * VAMD_MAX_CH) void k_synth_values(XformP X, Res
                     (float *)vamd_smem, synth + u * ch * n, pc, V);
   pc.flush();
 }
+
+// ---- the decoder under the keep policy (vamd_decode_partial; k_unpack.h, "TRUNCATED PACKETS"): a packet that stops being
+// read early decodes as libvorbis decodes it.  k_unpack with the walk's second instantiation -- status[k] may then be
+// VAMD_STATUS_PARTIAL, with the rows of what was read -- and k_synth / k_synth_values with the bounded residue add, which
+// takes res_count[1] as the number of entries read.  Launched under that policy alone: every other path keeps the kernels above.
+__global__ __launch_bounds__(64) void k_unpack_partial(const Bound *B, UnpackP U, int lanes, long nblocks, const uint32_t *__restrict__ words, long long nwords,
+                                                       const long long *__restrict__ bits, const int *__restrict__ order, int ent_row0, int ent_row1,
+                                                       unsigned long long *dbg, UnpackRows r0, UnpackRows r1, unsigned char *__restrict__ status) {
+  int *fit = (int *)vamd_smem;
+  PhaseClock pc;
+  pc.start(dbg);
+  const long k = (long)blockIdx.x * lanes + LANE;
+  if (LANE < lanes && k < nblocks) {
+    const int o = order[k], W = (o >> 30) & 1;
+    const long u = o & 0x3fffffff;
+    const UnpackRows &r = W ? r1 : r0;
+    const int ch = B->channels, n2 = B->bs[W] >> 1, S = B->chmap[W].submaps;
+    UnpackNoNote note;
+    status[k] = (unsigned char)unpack_packet_partial(*B, U, words, nwords, bits[2 * k], bits[2 * k + 1], W, r.post_valid + u * ch, r.ilogmask + u * ch * n2,
+                                                     r.res_class + u * (S * VAMD_RES_CLASS_STRIDE), r.res_entries + u * (long)(W ? ent_row1 : ent_row0),
+                                                     r.res_count + u * S * 2, fit + LANE, lanes, pc, note);
+  }
+  pc.flush();
+}
+__global__ __launch_bounds__(64 * VAMD_MAX_CH) void k_synth_bounded(XformP X, ResP R0, ResP R1, ChMap cm, CoupleP C, SynthFloorP S, int ch, int ent_row,
+                                                                  int off_ints, unsigned long long *dbg, const int *__restrict__ post_valid,
+                                                                  const ilog_t *__restrict__ ilogmask, const int *__restrict__ res_class,
+                                                                  const unsigned short *__restrict__ res_entries,
+                                                                  const int *__restrict__ res_count, float *__restrict__ synth) {
+  const long u = blockIdx.x;
+  const int n = X.n, n2 = n >> 1;
+  PhaseClock pc;
+  pc.start(dbg);
+  synth_block<false, true>(X, R0, R1, cm, C, S, ch, off_ints, post_valid + u * ch, ilogmask + u * ch * n2,
+                           res_class + u * (cm.submaps * VAMD_RES_CLASS_STRIDE), res_entries + u * (long)ent_row, res_count + u * cm.submaps * 2,
+                           (float *)vamd_smem, synth + u * ch * n, pc);
+  pc.flush();
+}
+__global__ __launch_bounds__(64 * VAMD_MAX_CH) void k_synth_values_bounded(XformP X, ResP R0, ResP R1, ChMap cm, CoupleP C, SynthFloorP S, int ch, int ent_row,
+                                                                         int off_ints, unsigned long long *dbg, const int *__restrict__ post_valid,
+                                                                         const ilog_t *__restrict__ ilogmask, const int *__restrict__ res_class,
+                                                                         const unsigned short *__restrict__ res_entries,
+                                                                         const int *__restrict__ res_count, float *__restrict__ synth, ValueP V) {
+  const long u = blockIdx.x;
+  const int n = X.n, n2 = n >> 1;
+  PhaseClock pc;
+  pc.start(dbg);
+  synth_block<true, true>(X, R0, R1, cm, C, S, ch, off_ints, post_valid + u * ch, ilogmask + u * ch * n2,
+                          res_class + u * (cm.submaps * VAMD_RES_CLASS_STRIDE), res_entries + u * (long)ent_row, res_count + u * cm.submaps * 2,
+                          (float *)vamd_smem, synth + u * ch * n, pc, V);
+  pc.flush();
+}
