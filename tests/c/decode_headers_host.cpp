@@ -4,8 +4,9 @@
 // has a book that is no lattice book).  Every buffer has exactly the size the GPU launch gives it.
 //   decode_headers_host image   id setup blob      the image's decode-side fields against the reference packer's blob
 //   decode_headers_host window  n out              the derived rising half window of a block of n samples: float [n/2]
-//   decode_headers_host streams id setup job out   job / out as unpack_host's `streams`; a first line of text on stdout:
-//                                                  "books <lattice> <table>"
+//   decode_headers_host streams id setup job out   job / out as unpack_host's `streams`; two lines of text on stdout first:
+//                                                  "books <lattice> <table>" and "lds <bytes W0> <bytes W1> off <ints W0> <ints W1>"
+//                                                  (k_synth's LDS per size class, Bound::res_off_ints)
 //   decode_headers_host codes   job out            job: int32 ncases | per case: the identification packet, the setup packet
 //                                                  (int32 bytes, the bytes padded to 4); out: int32 [ncases] return codes,
 //                                                  then per VAMD_EIMPL case its text, a line each, on stdout
@@ -228,6 +229,9 @@ static int run_streams(const char *idp, const char *setupp, const char *job, con
   printf("books %d %d\n", H.lattice_books, H.table_books);
   Bound B;
   bind_params(H.image, H.derived_off, H.derived, H.image.data(), &B);
+  // k_synth's LDS per size class as the library's launch asks for it (vamd_batch.h: synth_lds_bytes), and the offsets row behind it
+  printf("lds %zu %zu off %d %d\n", 4 * synth_lds_words(B.channels, B.bs[0] / 2, B.channels, B.res_off_ints[0]),
+         4 * synth_lds_words(B.channels, B.bs[1] / 2, B.channels, B.res_off_ints[1]), B.res_off_ints[0], B.res_off_ints[1]);
   std::vector<unsigned char> tab;
   UnpackP U;
   unpack_build_tables(H.image, &tab, &U);

@@ -65,7 +65,7 @@ inline int build_image(const void *blob_v, size_t bytes, std::vector<unsigned ch
     return VAMD_EINVAL;
   }
   if (h.channels < 1 || h.channels > VAMD_MAX_CH) {
-    *err = "channel count not covered (1 or 2)";
+    *err = "channel count not covered (1 .. " + std::to_string(VAMD_MAX_CH) + ")";
     return VAMD_EIMPL;
   }
   for (int W = 0; W < 2; W++) {

@@ -12,6 +12,7 @@
 #pragma once
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 #include "vamd_setup.h"
 #include "vamd_params.h"
@@ -218,7 +219,7 @@ inline std::vector<uint32_t> derive_div_magic() {
 // (lib/floor1.c:708-724,790-831).  The neighbours are fixed by the look, so posts can be
 // settled level by level: level[i] = 1 + max(level[lo], level[hi]), posts 0 and 1 at level 0.
 inline std::vector<int32_t> derive_post_levels(const vamd_floor1_tab &f, int *nlevels) {
-  std::vector<int32_t> lv(64, 0);
+  std::vector<int32_t> lv((size_t)std::max(64, f.posts), 0);  // (the image's slot is max(64, posts) ints: 64 as ever, 65 for a floor of all VAMD_POSIT posts)
   int mx = 0;
   for (int i = 2; i < f.posts; i++) {
     const int a = lv[f.loneighbor[i - 2]], b = lv[f.hineighbor[i - 2]];
