@@ -44,7 +44,9 @@ __device__ __forceinline__ void flag_range(const DescP &d, long i) {
 struct XformLds {
   XformP P;       // table pointers rebound to the LDS copies
   float *A, *B;   // this wave's work buffers
+  unsigned *next; // the workgroup's ticket counter (k_transform), behind the last wave's buffers
 };
+#define VAMD_XF_TICKET_BYTES 16
 
 template <int LOGN>
 __device__ __forceinline__ XformLds stage_transform_tables(const XformP &G) {
@@ -65,8 +67,12 @@ __device__ __forceinline__ XformLds stage_transform_tables(const XformP &G) {
     mdct_tpack_fill((float *)bitrev, G.trig, n, threadIdx.x, blockDim.x);
   else
     for (int i = threadIdx.x; i < n / 4; i += blockDim.x) bitrev[i] = G.bitrev[i];
+  const int waves = blockDim.x >> 6;
+  unsigned *next = (unsigned *)(work + waves * (VAMD_XF_A_FLOATS(n) + VAMD_XF_B_FLOATS(n)));
+  if (threadIdx.x == 0) *next = 2u * waves;  // (tickets 0 .. 2 * waves - 1 are the waves' first two blocks: k_transform)
   __syncthreads();
   XformLds L;
+  L.next = next;
   L.P = G;
   L.P.trig = trig;
   L.P.wa = wa;
@@ -83,7 +89,7 @@ __device__ __forceinline__ XformLds stage_transform_tables(const XformP &G) {
 
 static size_t transform_lds_bytes(const XformP &P, int waves) {
   const size_t tables = (size_t)(P.n + P.n / 4) + P.n + P.bs1 / 2 + P.bs0 / 2 + P.n / 4;
-  return (tables + (size_t)waves * (VAMD_XF_A_FLOATS(P.n) + VAMD_XF_B_FLOATS(P.n))) * 4;
+  return (tables + (size_t)waves * (VAMD_XF_A_FLOATS(P.n) + VAMD_XF_B_FLOATS(P.n))) * 4 + VAMD_XF_TICKET_BYTES;
 }
 
 // mdct_forward only (BASELINE config 2): in[nframes][n] -> out[nframes][n/2].  The one HBM-bound
@@ -127,6 +133,14 @@ __global__ __launch_bounds__(64 * VAMD_MD_WAVES) void k_mdct_only(XformP G, int 
 
 // stage 1: window + MDCT + FFT + logs, one wave per channel-block.  Instantiated per block size (LOGN =
 // log2 n; 0 = any size, read from the parameters).
+// Which wave takes which block: a workgroup owns every gridDim.x-th channel-block -- its local block t is blockIdx.x +
+// t * gridDim.x -- and its waves take them by ticket from a counter in the workgroup's LDS, not by a static stride.  The
+// two waves of a SIMD do not run at the same speed (issue goes to the older first: 8.0 against 9.9 us a block at
+// n = 2048, every CU alike, profiles/r33_tickets.txt); with equal quotas the older four were done at 0.78 of the kernel
+// and the others ran the rest alone, with nothing to cover their LDS waits.
+// The imbalance is inside the workgroup, so the counter is too: one ds_add a block, no traffic to device memory, nothing
+// to reset between launches.  (One counter per launch in device memory was tried first: 262 144 atomics on one address
+// take 3.0 ms, whatever the kernel.)
 template <int LOGN>
 __global__ __launch_bounds__(64 * VAMD_XF_WAVES) __attribute__((amdgpu_num_vgpr(256))) void k_transform(XformP G, int W, DescP d, int ch, long ncb,
                                                                  const float *__restrict__ pcm,
@@ -142,14 +156,17 @@ __global__ __launch_bounds__(64 * VAMD_XF_WAVES) __attribute__((amdgpu_num_vgpr(
   PhaseClock pc;
   pc.start(d.dbg);
   // cb = channel-block index = block*ch + channel
-  const long cstride = (long)gridDim.x * nw;
-  long cb = (long)blockIdx.x * nw + (threadIdx.x >> 6);
+  auto local_block = [&](unsigned t) -> long { return (long)blockIdx.x + (long)t * gridDim.x; };
+  long cb = local_block(threadIdx.x >> 6);
   constexpr int QPT = LOGN ? ((1 << LOGN) / 4 + 63) / 64 : 4096 / 4 / 64;  // quads of a block per lane
   const WaveTeam tm;
   PcmTile<QPT> tile;
   // A block's samples AND its window flags are fetched one block ahead: a load issued at the top of the loop -- even a
   // conditional one that is not taken -- makes the wait there a wait for everything outstanding, the stores of the
-  // previous block's spectra included.
+  // previous block's spectra included.  So a wave knows its next block while it works on this one, and draws the ticket
+  // of the block after next beside the fetch of the next: lane 0's ds_add, whose answer is a block old when it is read.
+  // Local blocks rise with the ticket, so the first ticket past the batch is a wave's last.
+  unsigned ticket = (unsigned)nw + (threadIdx.x >> 6);  // lane 0's: the wave's next local block
   int lW = 0, nW = 0;
   I2 rid[VAMD_XF_QPS(LOGN)] = {};  // which run of bins each of this lane's bins belongs to: the same for every block
   if constexpr (xf_size_path<LOGN, WaveTeam>()) {  // (the same registers either way: logfft is tapped or not for the whole launch)
@@ -169,12 +186,14 @@ __global__ __launch_bounds__(64 * VAMD_XF_WAVES) __attribute__((amdgpu_num_vgpr(
     lW = d_lW(d, blk), nW = d_nW(d, blk);
     pcm_fetch(tile, samples(cb, blk), n, tm);
   }
-  for (; cb < ncb; cb += cstride) {
+  while (cb < ncb) {
     transform_window(P, W, lW, nW, tile, L.A, pc, tm);
-    if (cb + cstride < ncb) {  // next block, one ahead
-      const long blk = (long)((unsigned)(cb + cstride) / (unsigned)ch);
+    const long nx = local_block((unsigned)wave_first((int)ticket));
+    if (nx < ncb) {  // next block, one ahead
+      const long blk = (long)((unsigned)nx / (unsigned)ch);
       lW = d_lW(d, blk), nW = d_nW(d, blk);
-      pcm_fetch(tile, samples(cb + cstride, blk), n, tm);
+      pcm_fetch(tile, samples(nx, blk), n, tm);
+      if (LANE == 0) ticket = atomicAdd(L.next, 1u);
     }
     float raw;
     // (logfft goes out as what the tone stage reads of it -- its peak over each run of bins of one octave line, nrp
@@ -191,6 +210,7 @@ __global__ __launch_bounds__(64 * VAMD_XF_WAVES) __attribute__((amdgpu_num_vgpr(
         atomicAdd(d.bad + 2, 1u);
       }
     }
+    cb = nx;
   }
   pc.flush();
 }
