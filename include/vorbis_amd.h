@@ -604,9 +604,9 @@ int vamd_synth_streams(vamd_ctx *ctx, const vamd_stream_plan *plan, long nstream
  * vamd_residue_capacity + 8 S bytes of rows, 4 ch n of vb->pcm and 29 of plan (ch channels, n the block's size, S its
  * submaps), and the packets themselves.
  *
- * Out of scope: header packets and setups other than the context's; packets in device memory; streams that begin at a
- * nonzero granule (the first page's trim); skipping a packet vorbis_synthesis refuses (vamd_decode_partial, below).  Ogg
- * files: vamd_decode_ogg, below.  A stream that is still being made, its packets in pieces: vamd_decode_live, below. */
+ * Out of scope: header packets and setups other than the context's; packets in device memory; skipping a packet
+ * vorbis_synthesis refuses (vamd_decode_partial, below).  Streams that begin at a nonzero granule and the first page's trim
+ * take per-packet marks: vamd_decode_streams_marked, below.  Ogg files: vamd_decode_ogg, below.  A stream that is still being made, its packets in pieces: vamd_decode_live, below. */
 #define VAMD_STATUS_NOTAUDIO  4
 #define VAMD_STATUS_BADCODE   8
 #define VAMD_STATUS_TRUNCATED 16
@@ -653,6 +653,36 @@ int vamd_decode_streams(vamd_ctx *ctx, const vamd_decode_desc *desc, const int64
  * bounded k_synth forms in their place. */
 int vamd_decode_partial(vamd_ctx *ctx, int keep);
 
+/* ---- packets with marks: the reader's granule walk (still ABI 9: additions only).  vamd_decode_plan / vamd_decode_streams
+ * with what a reader of the container knows of every packet in end_granule's place (desc->end_granule is ignored):
+ *   granule[p]  the granule position of the page on which packet p completes, where p is the LAST packet to complete there;
+ *               -1 elsewhere.  A position below -1 is none, as the page walk reads it.
+ *   eos[p]      libogg's e_o_s: the packet is the last to complete on a page with the end-of-stream flag.  NULL: each
+ *               stream's last packet.
+ * The frames a stream keeps are those vorbis_synthesis_blockin leaves a caller who drains after every packet
+ * (lib/block.c:858-937; examples/decoder_example.c, vorbisfile).  With W_p the packets' size classes, add_0 = 0 and
+ * add_p = bs[W_{p-1}]/4 + bs[W_p]/4, `count` the frames added so far and `pos` the tracked position, -1 at first: after
+ * packet p has added its frames,
+ *   while pos == -1 and granule[p] != -1:  pos = granule[p]; if count > granule[p], min(count - granule[p], add_p) of packet
+ *     p's OWN frames are cut -- from their end if eos[p], else from their beginning;
+ *   otherwise, when pos != -1:  pos += add_p; if granule[p] != -1 and pos != granule[p]: where pos > granule[p] and eos[p],
+ *     min(pos - granule[p], add_p) frames are cut from the end of packet p's; pos = granule[p] either way.
+ * So a stream that begins at a large granule is cut at its end against the position the pages give, not against a count
+ * from 0; a first page whose granule is short of its samples costs frames of the LAST packet of that page; a last page
+ * without the end-of-stream flag cuts nothing; no cut exceeds what its packet adds.  Bit for bit the reference over the
+ * same marks (tests/test_decode_links_cpu.py, tests/test_decode_links_gpu.py).
+ * frames[s], nblocks, offset_out, pcm's layout, status and the errors are vamd_decode_plan's / vamd_decode_streams'; the
+ * lap is k_lap_segments, a row per run of kept frames.  Packets vorbis_synthesis refuses flag their stream as before:
+ * skipping them stays out of scope.  vamd_decode_partial applies as everywhere. */
+typedef struct vamd_decode_marks {
+  const int64_t *granule;  /* host [npackets] */
+  const uint8_t *eos;      /* host [npackets], or NULL: each stream's last packet */
+} vamd_decode_marks;
+int vamd_decode_plan_marked(vamd_ctx *ctx, const vamd_decode_desc *desc, const vamd_decode_marks *marks, int64_t *frames /* host [nstreams] */,
+                            int64_t *nblocks /* [2] */);
+int vamd_decode_streams_marked(vamd_ctx *ctx, const vamd_decode_desc *desc, const vamd_decode_marks *marks, const int64_t *offset_out /* host [nstreams] */,
+                               float *pcm /* device */, uint8_t *status /* host [nstreams] */);
+
 /* ---- the live decoder: continuing streams decoded in pieces (still ABI 9: additions only).  The counterpart of a live
  * feed (vamd_feed_create_live): a caller who receives a stream's packets while the stream is still being made -- a live
  * feed's consumer, a receiver -- hands over the next piece of up to max_streams streams per call and gets that piece's
@@ -692,7 +722,8 @@ int vamd_decode_partial(vamd_ctx *ctx, int keep);
  * -- the slots, the carried rows, the last blocks' rows -- is computed and range-checked on the host before the first launch.
  *
  * Destroy a live decoder before its context.  Calls on one context are not concurrent, as everywhere.
- * Out of scope: streams that begin at a nonzero granule; packets in device memory; the feed itself is unchanged
+ * Out of scope: streams that begin at a nonzero granule (per-packet marks are the whole-stream entry's:
+ * vamd_decode_streams_marked); packets in device memory; the feed itself is unchanged
  * (VAMD_FEED_DECODED on a live feed is still refused: decode its packets here).  Ogg pages in pieces:
  * vamd_decode_ogg_live, below. */
 typedef struct vamd_decode_live vamd_decode_live;
@@ -744,10 +775,11 @@ int vamd_decode_live_wrote(vamd_decode_live *d, const vamd_decode_live_desc *des
  * setup header packet where setup_header is NULL).  A flagged stream costs only itself.
  *
  * DELIBERATE DEVIATIONS: libogg resynchronises behind a damaged page and reports a hole, and libvorbis decodes on out of
- * lap; here the stream is flagged.  A chained or multiplexed file is flagged BADPAGE at its second serial number, not
- * decoded.  Out of scope, as above: setups other than the context's (per call the setup header is compared; a context
- * for ANY floor-1 file's setup is made from the file's own headers: vamd_create_decoder, vamd_ogg_read_headers), streams
- * that begin at a nonzero granule, files that start in device memory.  Seeking: "windows", below. */
+ * lap; here the stream is flagged.  BY DEFAULT a chained or multiplexed file is flagged BADPAGE at its second serial
+ * number, a stream that begins at a nonzero granule is cut against a count from 0, and the first page's trim is not
+ * applied: vamd_decode_follow, below, turns all three into what a reader does.  Out of scope, as above: setups other than
+ * the context's (per call the setup header is compared; a context for ANY floor-1 file's setup is made from the file's own
+ * headers: vamd_create_decoder, vamd_ogg_read_headers), files that start in device memory.  Seeking: "windows", below. */
 #define VAMD_STATUS_BADPAGE   32
 #define VAMD_STATUS_BADHEADER 64
 typedef struct vamd_decode_ogg_desc {
@@ -760,6 +792,45 @@ typedef struct vamd_decode_ogg_desc {
 int vamd_decode_ogg_plan(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, int64_t *frames /* host [nstreams] */, int64_t *nblocks /* [2] */);
 int vamd_decode_ogg(vamd_ctx *ctx, const vamd_decode_ogg_desc *desc, const int64_t *offset_out /* host [nstreams] */,
                     float *pcm /* device */, uint8_t *status /* host [nstreams] */);
+
+/* ---- files as a reader takes them: links, foreign pages, page granules (still ABI 9: additions only).  A policy of the
+ * context, off by default, for vamd_decode_ogg_plan and vamd_decode_ogg ALONE: on > 0 turns it on, 0 off, on < 0 changes
+ * nothing (a query).  -> the setting before the call; VAMD_EINVAL for a null context.  The live, index and window entries
+ * keep their behaviour.  With the policy off every entry gives what it gave before.  With it on:
+ *   LINKS.  A file is one or more links (a chained file: an Icecast capture has one per title).  A link opens with its
+ *     begin-of-stream pages -- the file's first page opens the first with or without the flag; its stream is the first of
+ *     those whose first packet is a Vorbis identification header.  A begin-of-stream page behind a page without the flag
+ *     opens the next link; the link in front ends there, with or without an end-of-stream page.
+ *   FOREIGN PAGES.  Pages of any other serial number inside a link (a multiplexed file) are passed over: their headers and
+ *     lacing tables are walked and every length is held against the file (VAMD_STATUS_BADPAGE where one runs past it), but
+ *     they get no page row, so their checksums are not looked at.
+ *   INSIDE A LINK'S STREAM the page sequence numbers are consecutive from its first page's, the continued flag agrees with
+ *     the open packet, and the link does not end inside a packet: else VAMD_STATUS_BADPAGE.  A stream that begins twice in
+ *     its link's begin-of-stream pages is BADPAGE.  A link without a Vorbis stream, or whose three headers do not hold to
+ *     the context as a file's do above -- a link of another setup -- is VAMD_STATUS_BADHEADER.
+ *   FRAMES.  Every audio packet gets the marks of vamd_decode_streams_marked from its page -- the granule position on the
+ *     last packet a page completes (below -1: none), the end-of-stream flag on that packet -- and each link is walked as
+ *     there, from a fresh lap: its first block gives no output.  A file's frames are its links' frames end to end in one
+ *     [ch][frames] row.  A flagged link flags its file, which has no frames; other files are untouched.
+ * Every link's byte range is itself a valid file under the policy.  Out of scope still: resynchronisation behind a damaged
+ * page; skipping packets vorbis_synthesis refuses; links and start granules in the live, index and window entries; bytes
+ * that start in device memory.
+ *
+ * vamd_ogg_links (host only): the links of file[0 .. bytes) as above, the first `cap` of them into out[], their number into
+ * *nlinks whatever cap is.  `serial` is the link's Vorbis stream, or its first page's where it has none.  A C caller lists
+ * links as files through file_offset, and makes a context per setup (vamd_ogg_read_headers_serial on the link's range).
+ * -> VAMD_OK; VAMD_EINVAL where cap is too small or an argument is null; VAMD_EBADHEADER where a page header, lacing table
+ * or body does not hold against the file -- the links begun up to there are listed, the last ending at the break.  No byte
+ * outside the file is read.
+ * vamd_ogg_read_headers_serial (host only): vamd_ogg_read_headers, below, for the first logical stream of the given serial
+ * number instead of the file's first. */
+typedef struct vamd_ogg_link {
+  int64_t begin, end;  /* the link is file[begin .. end) */
+  uint32_t serial;
+} vamd_ogg_link;
+int vamd_decode_follow(vamd_ctx *ctx, int on);
+int vamd_ogg_links(const uint8_t *file, int64_t bytes, vamd_ogg_link *out, int64_t cap, int64_t *nlinks);
+int vamd_ogg_read_headers_serial(const uint8_t *file, int64_t bytes, uint32_t serial, uint8_t *out, int64_t cap, int64_t len[3]);
 
 /* ---- a decoder for a stream the caller did not encode: the context from the stream's own headers (still ABI 9: additions
  * only).  vamd_create_decoder parses the identification and setup header packets (Vorbis I 4.2.2, 4.2.4) as
@@ -833,7 +904,8 @@ int vamd_ogg_read_headers(const uint8_t *file, int64_t bytes, uint8_t *out, int6
  * channel stride below its window's frames.  VAMD_EIMPL as vamd_decode_plan gives it (at create already).  Every index
  * the kernels use is computed and range-checked on the host before the first launch.
  *
- * Out of scope: streams that begin at a nonzero granule; chained files; an index built without a full walk of the files;
+ * Out of scope: streams that begin at a nonzero granule and chained files (vamd_decode_follow is the whole-file entries'
+ * alone: an index flags them as before); an index built without a full walk of the files;
  * bytes in device memory. */
 typedef struct vamd_ogg_index vamd_ogg_index;
 typedef struct vamd_ogg_window_desc {
@@ -910,7 +982,7 @@ int vamd_decode_ogg_window(vamd_ctx *ctx, const vamd_ogg_index *index, const vam
  * further than the buffers reach.
  *
  * Destroy a live Ogg decoder before its context.  Out of scope: resynchronisation behind a damaged page; chained or
- * multiplexed streams; streams that begin at a nonzero granule; bytes that start in device memory; seeking; setups other
+ * multiplexed streams and streams that begin at a nonzero granule (vamd_decode_follow is the whole-file entries' alone); bytes that start in device memory; seeking; setups other
  * than the context's. */
 typedef struct vamd_decode_ogg_live vamd_decode_ogg_live;
 typedef struct vamd_decode_ogg_live_opts {

@@ -60,6 +60,14 @@ class _DecodeDesc(C.Structure):  # vamd_decode_desc
     _fields_ = [("nstreams", C.c_int64), ("npackets", C.c_int64), ("bytes", _vp), ("offset", _vp), ("stream_start", _vp), ("end_granule", _vp)]
 
 
+class _DecodeMarks(C.Structure):  # vamd_decode_marks
+    _fields_ = [("granule", _vp), ("eos", _vp)]
+
+
+class _OggLink(C.Structure):  # vamd_ogg_link
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("serial", C.c_uint32)]
+
+
 class _DecodeLiveDesc(C.Structure):  # vamd_decode_live_desc
     _fields_ = [("nstreams", C.c_int64), ("npackets", C.c_int64), ("slot", _vp), ("bytes", _vp), ("offset", _vp), ("stream_start", _vp),
                 ("close", _vp), ("end_granule", _vp)]
@@ -119,7 +127,7 @@ _pvp, _pint, _plong, _pfloat, _pi32 = C.POINTER(_vp), C.POINTER(C.c_int), C.POIN
 _pDesc, _pIO, _pMIO, _pPlan, _pDecode = C.POINTER(_Desc), C.POINTER(_IO), C.POINTER(_MIO), C.POINTER(_Plan), C.POINTER(_DecodeDesc)
 _pDecodeOgg, _pDecodeLive = C.POINTER(_DecodeOggDesc), C.POINTER(_DecodeLiveDesc)
 _pDecodeOggLive, _pDecodeOggLiveOpts = C.POINTER(_DecodeOggLiveDesc), C.POINTER(_DecodeOggLiveOpts)
-_pOggWindow = C.POINTER(_OggWindowDesc)
+_pOggWindow, _pMarks = C.POINTER(_OggWindowDesc), C.POINTER(_DecodeMarks)
 _vp2 = _vp * 2
 _block = [_vp, _pvp, _int, _int, _int, _int, _float]   # (ctx, pcm[ch], lW, W, nW, blocktype, ampmax_in): how every per-block call begins
 
@@ -162,6 +170,11 @@ PROTOTYPES = {
     "vamd_decode_plan": (_int, [_vp, _pDecode, _vp, _vp]),
     "vamd_decode_streams": (_int, [_vp, _pDecode, _vp, _vp, _vp]),
     "vamd_decode_partial": (_int, [_vp, _int]),
+    "vamd_decode_plan_marked": (_int, [_vp, _pDecode, _pMarks, _vp, _vp]),
+    "vamd_decode_streams_marked": (_int, [_vp, _pDecode, _pMarks, _vp, _vp, _vp]),
+    "vamd_decode_follow": (_int, [_vp, _int]),
+    "vamd_ogg_links": (_int, [_vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "vamd_ogg_read_headers_serial": (_int, [_vp, C.c_int64, C.c_uint32, _vp, C.c_int64, _vp]),
     "vamd_decode_live_create": (_int, [_vp, C.c_int64, _pvp]),
     "vamd_decode_live_destroy": (None, [_vp]),
     "vamd_decode_live_plan": (_int, [_vp, _pDecodeLive, _vp, _vp]),

@@ -7,8 +7,8 @@ import ctypes as C
 import numpy as np
 
 from .abi import (ABI_VERSION, BLOCKTYPE_LONG, LEVEL_FULL, LEVEL_PSY, LEVEL_TRANSFORM, PACKETBLOBS, POSTS_STRIDE, QUANT_LIMIT_INT,
-                  QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_BADHEADER, STATUS_PARTIAL, STATUS_RANGE, VAMD_EDOMAIN, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
-                  _DecodeDesc, _DecodeLiveDesc, _DecodeOggDesc, _DecodeOggLiveDesc, _DecodeOggLiveOpts, _Desc, _OggWindowDesc, _IO, _MIO, _Plan, _vp, load_library)
+                  QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_BADHEADER, STATUS_PARTIAL, STATUS_RANGE, VAMD_EDOMAIN, VAMD_EINVAL, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
+                  _DecodeDesc, _DecodeLiveDesc, _DecodeMarks, _OggLink, _DecodeOggDesc, _DecodeOggLiveDesc, _DecodeOggLiveOpts, _Desc, _OggWindowDesc, _IO, _MIO, _Plan, _vp, load_library)
 from .packets import packet_bytes
 
 
@@ -643,8 +643,9 @@ class Analyzer:
                                              pb, st, _vp(states.data_ptr()), ch_p, fb_p))
         return choice, final
 
-    def decode_prepare(self, streams, granules=None, offset=None, stream_start=None):
-        """The descriptor of decode_streams()'s group (vamd_decode_desc) with the host arrays it points into."""
+    def decode_prepare(self, streams, granules=None, offset=None, stream_start=None, packet_granules=None, eos=None):
+        """The descriptor of decode_streams()'s group (vamd_decode_desc) with the host arrays it points into; with
+        packet_granules, also the marks (vamd_decode_marks)."""
         ns = len(streams)
         for row in streams:
             for p in row:
@@ -666,12 +667,27 @@ class Analyzer:
             self._need(len(granules) == ns, "decode_streams: one granule position per stream")
             gran = np.array([-1 if g is None else int(g) for g in granules], np.int64)
         d = _DecodeDesc(ns, len(flat), _vp(data.ctypes.data), _vp(off.ctypes.data), _vp(start.ctypes.data), _vp(gran.ctypes.data) if gran is not None else None)
-        return dict(desc=d, keep=(data, off, start, gran), nstreams=ns, npackets=len(flat))
+        marks = pg = pe = None
+        self._need(eos is None or packet_granules is not None, "decode_streams: eos goes with packet_granules")
+        if packet_granules is not None:
+            self._need(granules is None, "decode_streams: packet_granules take the place of granules")
+            self._need(len(packet_granules) == ns and all(len(g) == len(row) for g, row in zip(packet_granules, streams)),
+                       "decode_streams: one granule position per packet (-1: none)")
+            pg = np.array([-1 if v is None else int(v) for g in packet_granules for v in g] + [-1], np.int64)
+            if eos is not None:
+                self._need(len(eos) == ns and all(len(e) == len(row) for e, row in zip(eos, streams)), "decode_streams: one eos flag per packet")
+                pe = np.array([1 if v else 0 for e in eos for v in e] + [0], np.uint8)
+            marks = _DecodeMarks(_vp(pg.ctypes.data), _vp(pe.ctypes.data) if pe is not None else None)
+        return dict(desc=d, keep=(data, off, start, gran, pg, pe), nstreams=ns, npackets=len(flat), marks=marks)
 
     def decode_run(self, prep, pcm=None):
         """vamd_decode_plan + vamd_decode_streams over decode_prepare()'s descriptor.  pcm: a float32 tensor on the context's
         device to decode into (at least the planned frames x channels floats), or None: one is made.
         -> (pcm, frames, offset, status): stream s, channel c, frame k at pcm[offset[s] + c * frames[s] + k]"""
+        m = prep.get("marks")
+        if m is not None:  # (vamd_decode_plan_marked + vamd_decode_streams_marked: the marks ride behind the descriptor)
+            return self._decode_run(lambda h, d, *a: self.L.vamd_decode_plan_marked(h, d, C.byref(m), *a),
+                                    lambda h, d, *a: self.L.vamd_decode_streams_marked(h, d, C.byref(m), *a), prep, pcm)
         return self._decode_run(self.L.vamd_decode_plan, self.L.vamd_decode_streams, prep, pcm)
 
     def _decode_run(self, plan, run, prep, pcm):
@@ -707,6 +723,21 @@ class Analyzer:
     def keep_partial(self, keep):
         self._check(min(self.L.vamd_decode_partial(self.h, 1 if keep else 0), 0))
 
+    @property
+    def follow_links(self):
+        """vamd_decode_follow: whether decode_ogg() on this context reads files as a reader does -- chained files link after
+        link (each from a fresh lap, the frames end to end), pages of foreign serial numbers passed over, and every link's
+        frames cut by its pages' granule positions (a start at a nonzero granule, the first page's trim) -- instead of
+        flagging a second serial number STATUS_BADPAGE and cutting against a count from 0, the default.  The live, index
+        and window decoders do not read it."""
+        r = self.L.vamd_decode_follow(self.h, -1)  # (a negative value asks and changes nothing)
+        self._check(min(r, 0))
+        return r > 0
+
+    @follow_links.setter
+    def follow_links(self, on):
+        self._check(min(self.L.vamd_decode_follow(self.h, 1 if on else 0), 0))
+
     def _decoded_tensors(self, n, pcm, frames, out_off, status, with_status):
         out = []
         for s in range(n):
@@ -714,15 +745,20 @@ class Analyzer:
             out.append(pcm[int(out_off[s]):int(out_off[s]) + self.channels * f].view(self.channels, f))
         return (out, status.copy()) if with_status else out
 
-    def decode_streams(self, streams, granules=None, with_status=False, offset=None, stream_start=None):
+    def decode_streams(self, streams, granules=None, with_status=False, offset=None, stream_start=None, packet_granules=None, eos=None):
         """vamd_decode_plan + vamd_decode_streams: audio packets of this context's setup in, PCM out -- k_unpack, k_synth and
         the lap on the GPU.  streams: a list of lists of `bytes`, one list per stream (a Feed's rows plug in as
         [[p for p, _, _, _ in row] for row in rows]); granules: per stream the last packet's granule position (None or -1:
         none), which cuts the last block's frames.  offset / stream_start: test hooks, the descriptor's arrays as given
         instead of as derived.  -> a list of float32 tensors [ch, frames] on the context's device; with_status, also the
         streams' status bytes (numpy uint8): a flagged stream -- STATUS_NOTAUDIO / _BADCODE / _TRUNCATED -- has no frames
-        (STATUS_PARTIAL alone, under keep_partial, is no flag: the stream has its frames)."""
-        return self._decoded_tensors(len(streams), *self.decode_run(self.decode_prepare(streams, granules, offset, stream_start)), with_status)
+        (STATUS_PARTIAL alone, under keep_partial, is no flag: the stream has its frames).
+        packet_granules (in granules' place): per stream a list with, per packet, the granule position of the page on which
+        it completes where it is the last to complete there, else -1 or None; eos: per stream a list of libogg's e_o_s per
+        packet (None: each stream's last packet) -- vamd_decode_streams_marked, the frames a reader of the container keeps:
+        a start at a nonzero granule, the first page's trim."""
+        prep = self.decode_prepare(streams, granules, offset, stream_start, packet_granules, eos)
+        return self._decoded_tensors(len(streams), *self.decode_run(prep), with_status)
 
     def live_decoder(self, max_streams):
         """vamd_decode_live_create: a LiveDecoder for up to max_streams continuing streams on this context.  Closing the
@@ -764,14 +800,20 @@ class Analyzer:
         """vamd_decode_ogg_plan + vamd_decode_ogg over decode_ogg_prepare()'s descriptor; pcm and the result as decode_run's"""
         return self._decode_run(self.L.vamd_decode_ogg_plan, self.L.vamd_decode_ogg, prep, pcm)
 
-    def decode_ogg(self, files, setup_header=None, with_status=False, file_offset=None):
+    def decode_ogg(self, files, setup_header=None, with_status=False, file_offset=None, follow_links=None):
         """vamd_decode_ogg_plan + vamd_decode_ogg: whole Ogg Vorbis files of this context's setup in, PCM out -- the page
         walk on the host, checksums and unpaging (k_ogg_depage), k_unpack, k_synth and the lap on the GPU.  files: a list of
         `bytes`, one file per stream (a Feed's Ogg output plugs in as it is); setup_header: the setup header packet every
         file's third packet must equal, or None: only its type is looked at.  file_offset: a test hook, the descriptor's
         array as given.  -> as decode_streams(); a flagged stream -- STATUS_BADPAGE / _BADHEADER or the packet decoder's
-        bits -- has no frames."""
-        return self._decoded_tensors(len(files), *self.decode_ogg_run(self.decode_ogg_prepare(files, setup_header, file_offset)), with_status)
+        bits -- has no frames.  follow_links: Analyzer.follow_links for this call (None: as the context stands)."""
+        was = self.follow_links
+        if follow_links is not None:
+            self.follow_links = follow_links
+        try:
+            return self._decoded_tensors(len(files), *self.decode_ogg_run(self.decode_ogg_prepare(files, setup_header, file_offset)), with_status)
+        finally:
+            self.follow_links = was
 
     @staticmethod
     def _window_arrays(stream, start, count):
@@ -1206,31 +1248,80 @@ def decode(setup_blob, streams, granules=None, with_status=False, device=None, k
         a.close()
 
 
-def read_ogg_headers(file):
+def ogg_links(file):
+    """vamd_ogg_links: the links of an Ogg file as Analyzer.follow_links reads them -> [(begin, end, serial)], the link
+    file[begin:end] and the serial number of its Vorbis stream (its first page's where it has none).  Raises
+    VamdError(VAMD_EBADHEADER) where a page does not hold against the file."""
+    L = load_library()
+    data = bytes(file)
+    n = C.c_int64(0)
+    r = L.vamd_ogg_links(data, len(data), None, 0, C.byref(n))
+    rows = (_OggLink * max(int(n.value), 1))()
+    if r == VAMD_EINVAL and n.value > 0:
+        r = L.vamd_ogg_links(data, len(data), rows, n.value, C.byref(n))
+    if r != VAMD_OK:
+        raise VamdError(r, "ogg_links: a page of the file does not hold against its length")
+    return [(int(v.begin), int(v.end), int(v.serial)) for v in rows[:n.value]]
+
+
+def read_ogg_headers(file, serial=None):
     """vamd_ogg_read_headers: (identification, comment, setup) -- the three header packets of an Ogg file's first logical
-    stream, as `bytes`.  Raises VamdError(VAMD_EBADHEADER) where the file's pages do not hold three packets."""
+    stream, as `bytes`; with serial, of its first stream of that serial number (vamd_ogg_read_headers_serial).  Raises
+    VamdError(VAMD_EBADHEADER) where the file's pages do not hold three packets."""
     L = load_library()
     data = bytes(file)
     lens = (C.c_int64 * 3)()
     out = C.create_string_buffer(max(len(data), 1))  # (the packets are part of the file: never longer)
-    r = L.vamd_ogg_read_headers(data, len(data), out, len(data), lens)
+    if serial is None:
+        r = L.vamd_ogg_read_headers(data, len(data), out, len(data), lens)
+    else:
+        r = L.vamd_ogg_read_headers_serial(data, len(data), int(serial), out, len(data), lens)
     if r != VAMD_OK:
         raise VamdError(r, "read_ogg_headers: the file's pages do not hold three header packets")
     a, b, c = (int(v) for v in lens)
     return out.raw[:a], out.raw[a:a + b], out.raw[a + b:a + b + c]
 
 
-def decode_ogg_files(files, with_status=False, device=None, keep_partial=False):
-    """Ogg Vorbis files of ANY covered setups in, PCM out: no blob and no settings.  Each file's headers are read
-    (read_ogg_headers); the files are grouped by (identification fields, setup header bytes); one decode-only context is
-    made per distinct setup (Analyzer.from_headers) and decodes its group in one decode_ogg call.  -> a list of float32
-    tensors [ch, frames] in the caller's order; with_status, also the status bytes.  A file whose headers are rejected or
-    refused gets a [0, 0] tensor and STATUS_BADHEADER: it costs only itself.  keep_partial: Analyzer.keep_partial for every context."""
+def _decode_ogg_linked(files, with_status, device, keep_partial, links):
+    """decode_ogg_files(follow_links=True): the files split at their link boundaries (ogg_links; a file whose pages do not
+    hold stays whole and is flagged by the decode), the links decoded as files -- grouped by setup, one context each, the
+    policy on -- and put back together per file."""
+    import torch
+    parts, owner, serials = [], [], []
+    for i, f in enumerate(files):
+        f = bytes(f)
+        try:
+            spans = ogg_links(f) or [(0, len(f), None)]
+        except VamdError:
+            spans = [(0, len(f), None)]
+        for a, b, serial in spans:
+            parts.append(f[a:b]), owner.append(i), serials.append(serial)
+    pcm, st = _decode_ogg_grouped(parts, device, keep_partial, serials)
+    out, status = [], np.zeros(len(files), np.uint8)
+    for i in range(len(files)):
+        mine = [k for k, o in enumerate(owner) if o == i]
+        for k in mine:
+            status[i] |= st[k]
+        flagged = bool(int(status[i]) & ~STATUS_PARTIAL)
+        if links:
+            out.append([pcm[k] for k in mine])
+        elif flagged:
+            out.append(torch.zeros((0, 0), dtype=torch.float32, device=pcm[mine[0]].device))
+        else:
+            if len({int(pcm[k].shape[0]) for k in mine}) != 1:
+                raise ValueError("decode_ogg_files: file %d has links of differing channel counts; links=True gives a tensor per link" % i)
+            out.append(pcm[mine[0]] if len(mine) == 1 else torch.cat([pcm[k] for k in mine], dim=1))
+    return (out, status) if with_status else out
+
+
+def _decode_ogg_grouped(files, device, keep_partial, serials=None):
+    """decode_ogg_files' work: the files (or, with serials -- per file the serial number of its Vorbis stream, None: its
+    first stream's -- the links, read under Analyzer.follow_links) grouped by setup, a context per group -> (tensors, status)"""
     import torch
     groups, out, status = {}, [None] * len(files), np.zeros(len(files), np.uint8)
     for i, f in enumerate(files):
         try:
-            ident, _, setup = read_ogg_headers(f)
+            ident, _, setup = read_ogg_headers(f, serials[i] if serials else None)
             groups.setdefault((ident[7:16] + ident[28:29], setup), (ident, []))[1].append(i)  # version, channels, rate; the block sizes
         except VamdError:
             status[i] = STATUS_BADHEADER
@@ -1242,22 +1333,40 @@ def decode_ogg_files(files, with_status=False, device=None, keep_partial=False):
             continue
         try:
             a.keep_partial = keep_partial
-            pcm, st = a.decode_ogg([files[i] for i in members], with_status=True)
+            pcm, st = a.decode_ogg([files[i] for i in members], with_status=True, follow_links=serials is not None)
             for i, p, v in zip(members, pcm, st):
                 out[i], status[i] = p.clone(), v
         finally:
             a.close()
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
     out = [torch.zeros((0, 0), dtype=torch.float32, device=dev) if p is None else p for p in out]
+    return out, status
+
+
+def decode_ogg_files(files, with_status=False, device=None, keep_partial=False, follow_links=False, links=False):
+    """Ogg Vorbis files of ANY covered setups in, PCM out: no blob and no settings.  Each file's headers are read
+    (read_ogg_headers); the files are grouped by (identification fields, setup header bytes); one decode-only context is
+    made per distinct setup (Analyzer.from_headers) and decodes its group in one decode_ogg call.  -> a list of float32
+    tensors [ch, frames] in the caller's order; with_status, also the status bytes.  A file whose headers are rejected or
+    refused gets a [0, 0] tensor and STATUS_BADHEADER: it costs only itself.  keep_partial: Analyzer.keep_partial for every context.
+    follow_links: files are read as a reader reads them (Analyzer.follow_links): they are split at their link boundaries
+    and the LINKS are grouped by setup, so a chained file may change its setup from link to link; the result per file is
+    its links' signal end to end where they share a channel count (else ValueError: ask for links=True), a flagged link
+    flags its file.  links=True (with follow_links): per file a list of tensors, one per link."""
+    if follow_links:
+        return _decode_ogg_linked(files, with_status, device, keep_partial, links)
+    if links:
+        raise ValueError("decode_ogg_files: links=True goes with follow_links=True")
+    out, status = _decode_ogg_grouped(files, device, keep_partial)
     return (out, status) if with_status else out
 
 
-def decode_ogg(setup_blob, files, setup_header=None, with_status=False, device=None, keep_partial=False):
+def decode_ogg(setup_blob, files, setup_header=None, with_status=False, device=None, keep_partial=False, follow_links=False):
     """Analyzer(setup_blob).decode_ogg(...) for a caller who holds files and no context: the files must come from an
-    encoder of that setup.  keep_partial: Analyzer.keep_partial for the call."""
+    encoder of that setup.  keep_partial / follow_links: Analyzer.keep_partial / Analyzer.follow_links for the call."""
     a = Analyzer(setup_blob, device)
     try:
         a.keep_partial = keep_partial
-        return a.decode_ogg(files, setup_header, with_status)
+        return a.decode_ogg(files, setup_header, with_status, follow_links=follow_links)
     finally:
         a.close()

@@ -478,6 +478,15 @@ VAMD_DEV void lap_window(const LapP &L, long long k0, long long k1, long long a,
   }
 }
 
+// ---- the lap for segments: the runs of frames a reader keeps of a stream (vamd_decode_plan.h, decode_plan_build_marked) ------
+// A stream whose page granules cut frames out of its middle, or whose file is several links, is a few windows laid end to
+// end: each row is one lap_window call, its blocks [k0, k1) of order[] -- rows of one link share them -- its frames
+// [first, first + count) of those blocks' span, at out + `out`, channel c `stride` floats further on.
+struct LapSegment {
+  long long k0, k1, first, count, stride, out;
+};
+VAMD_DEV void lap_segment(const LapP &L, const LapSegment &g, long long q, float *out) { lap_window(L, g.k0, g.k1, g.first, g.count, g.stride, q, out + g.out); }
+
 // ---- the lap across pieces: a continuing stream's last block, carried between calls (vamd_decode_live.h) --------------------
 // lap_sample reads, of the block in front, its second half and its size class.  A live decoder keeps that half per slot
 // in `carry` ([slots][ch][bs1/2]; a short block's half fills the front of its row) and, in the next call, stands it in an

@@ -71,6 +71,7 @@ struct vamd_ctx {
     bool ready = false;
     int lanes = VAMD_UNPACK_LANES;  // packets a wave of k_unpack
     bool partial = false;           // vamd_decode_partial: k_unpack_partial and the bounded k_synth forms in place of k_unpack / k_synth
+    bool follow = false;            // vamd_decode_follow: vamd_decode_ogg* walk links and foreign pages and cut by the page granules
     unsigned char *d_tab = nullptr;
     UnpackP U = {};
     DevBuf bytes, plan, status, files;

@@ -13,6 +13,9 @@
 // with the packet that whole pages leave open carried on the device by two more kernels around k_ogg_depage.
 // The window entries (vamd_decode_window.h) take WINDOWS of streams or of indexed files through the same function too: the
 // plan's "streams" are the windows, only their packets or pages go up, and k_lap_window stands in k_lap's place.
+// The marked entries (vamd_decode_plan_marked, vamd_decode_streams_marked) and, under vamd_decode_follow, the Ogg entry take
+// the plan from per-packet marks instead (decode_plan_build_marked: the reader's granule walk, links from a fresh lap): the
+// same function again, with the plan's runs of kept frames as rows for k_lap_segments in k_lap's place.
 //
 // Workspace per block, in the context, grown on demand and released with it (ch channels, n the block's size, S submaps):
 //   rows     4 ch (post_valid) + ch n/2 (the integer curves) + S * 2048 (res_class) + 2 * vamd_residue_capacity
@@ -142,15 +145,17 @@ struct DecodeWindows {
 // the blocks' and, behind them, the pages' -- folded into their streams.  With `live`, P is live->plan->P: order[] holds
 // carried blocks that have no packet, k_unpack takes the plan's own list, and the carries move between k_synth and k_lap;
 // without, nothing is enqueued or uploaded that was not before.  With `win`, the two lists go up behind the plan and the
-// lap is k_lap_window's; without, likewise nothing changes.
+// lap is k_lap_window's; without, likewise nothing changes.  With `seg` (a plan made from marks: decode_plan_build_marked)
+// the rows of kept frames go up behind those and the lap is k_lap_segments'; without, likewise.
 static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const DecodeInput &in, const int64_t *offset_out, float *pcm, uint8_t *status,
-                      const DecodeCarry *live = nullptr, const DecodeWindows *win = nullptr) {
+                      const DecodeCarry *live = nullptr, const DecodeWindows *win = nullptr, const std::vector<DecodePlan::Segment> *seg = nullptr) {
   int r;
   const std::vector<int32_t> &unpack = live ? live->plan->unpack : P.order;
   const std::vector<int64_t> &unpack_start = live ? live->plan->unpack_start : P.lap_start;
   const size_t nb = unpack.size(), nlap = P.order.size(), npg = in.scan ? in.scan->pages.size() : 0;
   const size_t nin = live ? live->plan->in.size() : 0, nout = live ? live->plan->out.size() : 0;
   const size_t nbin = live && live->bytes_in ? live->bytes_in->size() : 0, nbout = live && live->bytes_out ? live->bytes_out->size() : 0;
+  const size_t nseg = seg ? seg->size() : 0;
   if (!nb && !npg) return VAMD_OK;
   vamd_ctx::Decode &D = c->dec;
   const int ch = c->B.channels;
@@ -182,7 +187,7 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
                o_src1 = a.take(8 * P.src[1].size() + 8), o_bits = a.take(16 * nb), o_frames = a.take(8 * (size_t)ns), o_off = a.take(8 * (size_t)ns),
                o_pages = a.take(sizeof(OggDepage) * npg), o_unpack = live ? a.take(4 * nb) : o_order, o_in = a.take(sizeof(CarryRow) * nin),
                o_out = a.take(sizeof(CarryRow) * nout), o_bin = a.take(sizeof(OggCarryRow) * nbin), o_bout = a.take(sizeof(OggCarryRow) * nbout),
-               o_first = a.take(win ? 8 * (size_t)ns : 0), o_stride = a.take(win ? 8 * (size_t)ns : 0);
+               o_first = a.take(win ? 8 * (size_t)ns : 0), o_stride = a.take(win ? 8 * (size_t)ns : 0), o_seg = a.take(sizeof(LapSegment) * nseg);
   const size_t plan_bytes = a.at, o_status = a.take(nb + npg);
   if ((r = pinned_get(c, D.h_plan, a.at, true))) return r;
   if ((r = dev_need(c, D.plan, plan_bytes))) return r;
@@ -206,6 +211,11 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
   for (int64_t s = 0; s < ns; s++) ((int64_t *)(h + o_off))[s] = P.frames[(size_t)s] > 0 ? offset_out[s] : 0;
   if (npg) memcpy(h + o_pages, in.scan->pages.data(), sizeof(OggDepage) * npg);
   if (win && ns) memcpy(h + o_first, win->first, 8 * (size_t)ns), memcpy(h + o_stride, win->stride, 8 * (size_t)ns);
+  for (size_t g = 0; g < nseg; g++) {  // (a stream's rows fill its [ch][frames] from 0 to frames, in order)
+    const DecodePlan::Segment &e = (*seg)[g];
+    LapSegment row = {e.k0, e.k1, e.first, e.count, P.frames[(size_t)e.stream], offset_out[e.stream] + e.out_at};
+    memcpy(h + o_seg + g * sizeof(LapSegment), &row, sizeof(row));
+  }
   hipStream_t s = c->stream;
   HIP_TRY(c, hipMemcpyAsync(dp, h, plan_bytes, hipMemcpyHostToDevice, s));
   if (npg) {
@@ -254,7 +264,10 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
     L.src0 = (const long long *)(dp + o_src0), L.src1 = (const long long *)(dp + o_src1);
     L.synth0 = (const float *)D.synth[0].p, L.synth1 = (const float *)D.synth[1].p;
     const long per_stream = (long)((P.max_frames + 1023) / 1024);  // (as vamd_synth_streams sizes it)
-    if (win)
+    if (seg)
+      hipLaunchKernelGGL(k_lap_segments, dim3((unsigned)(per_stream < 1024 ? per_stream : 1024), (unsigned)(nseg < 1024 ? nseg : 1024)), dim3(256), 0, s, L, (long)nseg,
+                         (const LapSegment *)(dp + o_seg), pcm);
+    else if (win)
       hipLaunchKernelGGL(k_lap_window, dim3((unsigned)(per_stream < 1024 ? per_stream : 1024), (unsigned)(ns < 1024 ? ns : 1024)), dim3(256), 0, s, L, (long)ns,
                          (const long long *)(dp + o_first), (const long long *)(dp + o_frames), (const long long *)(dp + o_stride),
                          (const long long *)(dp + o_off), pcm);
@@ -314,6 +327,56 @@ int vamd_decode_streams(vamd_ctx *c, const vamd_decode_desc *d, const int64_t *o
   return decode_run(c, P, d->nstreams, in, offset_out, pcm, status);
 }
 
+// ---- packets with marks: vamd_decode_plan_marked, vamd_decode_streams_marked ----
+// The reader's granule walk (vamd_decode_plan.h, decode_plan_build_marked) in the block plan's place; the rest is the
+// packet entry, with the plan's segments for the lap.
+static int decode_plan_marked(vamd_ctx *c, const vamd_decode_desc *d, const vamd_decode_marks *m, DecodePlan *P) {
+  if (!d) return fail(c, VAMD_EINVAL, "decode: null descriptor");
+  if (!m) return fail(c, VAMD_EINVAL, "decode: null marks");
+  int r = decode_ready(c);
+  if (r) return r;
+  std::string err;
+  if (!decode_plan_build_marked(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->nstreams, d->npackets, d->bytes, d->offset, d->stream_start, m->granule,
+                                m->eos, P, &err))
+    return fail(c, VAMD_EINVAL, err.c_str());
+  return VAMD_OK;
+}
+
+int vamd_decode_plan_marked(vamd_ctx *c, const vamd_decode_desc *d, const vamd_decode_marks *m, int64_t *frames, int64_t *nblocks) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  DecodePlan P;
+  int r = decode_plan_marked(c, d, m, &P);
+  if (r) return r;
+  for (int64_t s = 0; frames && s < d->nstreams; s++) frames[s] = P.frames[(size_t)s];
+  if (nblocks) nblocks[0] = P.nblocks[0], nblocks[1] = P.nblocks[1];
+  return VAMD_OK;
+}
+
+int vamd_decode_streams_marked(vamd_ctx *c, const vamd_decode_desc *d, const vamd_decode_marks *m, const int64_t *offset_out, float *pcm, uint8_t *status) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  DecodePlan P;
+  int r = decode_plan_marked(c, d, m, &P);
+  if (r) return r;
+  if ((r = decode_outputs(c, P, d->nstreams, offset_out, pcm, status))) return r;
+  if (P.order.empty()) return VAMD_OK;
+  DecodeInput in;
+  in.offset = d->offset, in.byte0 = d->offset[0], in.nbytes = d->offset[d->npackets] - d->offset[0];
+  in.packets = d->bytes + in.byte0;
+  return decode_run(c, P, d->nstreams, in, offset_out, pcm, status, nullptr, nullptr, &P.segments);
+}
+
+// the policy for files as a reader takes them (include/vorbis_amd.h; vamd_demux.h, "links and foreign pages"): the two
+// whole-file entries below read it, no other entry does
+int vamd_decode_follow(vamd_ctx *c, int on) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  const int was = c->dec.follow ? 1 : 0;
+  if (on >= 0) c->dec.follow = on != 0;  // (a negative value is a query)
+  return was;
+}
+
 // ---- files in: vamd_decode_ogg_plan, vamd_decode_ogg ----
 // The host's walk (vamd_demux.h), then the block plan over its packet table with the first bytes it read in place.
 static int decode_ogg_plan(vamd_ctx *c, const vamd_decode_ogg_desc *d, DemuxScan *X, DecodePlan *P) {
@@ -325,9 +388,13 @@ static int decode_ogg_plan(vamd_ctx *c, const vamd_decode_ogg_desc *d, DemuxScan
   S.setup_header = d->setup_header, S.setup_header_bytes = d->setup_header_bytes;
   demux_own_setup(c, &S);
   std::string err;
-  if (!demux_scan(d->nstreams, d->bytes, d->file_offset, S, X, &err)) return fail(c, VAMD_EINVAL, err.c_str());
+  if (!demux_scan(d->nstreams, d->bytes, d->file_offset, S, X, &err, c->dec.follow)) return fail(c, VAMD_EINVAL, err.c_str());
   if (X->pages.size() > 0x7fffffffu) return fail(c, VAMD_EINVAL, "decode_ogg: more than 2^31 pages");
-  if (!decode_plan_build(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->nstreams, (int64_t)X->first.size(), nullptr, X->offset.data(),
+  if (c->dec.follow) {  // (the marks the walk read off the pages, and its links, in the end granule's place)
+    if (!decode_plan_build_marked(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->nstreams, (int64_t)X->first.size(), nullptr, X->offset.data(),
+                                  X->stream_start.data(), X->granule.data(), X->eos.data(), P, &err, X->first.data(), X->links.data(), (int64_t)X->links.size()))
+      return fail(c, VAMD_EINVAL, err.c_str());
+  } else if (!decode_plan_build(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->nstreams, (int64_t)X->first.size(), nullptr, X->offset.data(),
                          X->stream_start.data(), X->end_granule.data(), P, &err, X->first.data()))
     return fail(c, VAMD_EINVAL, err.c_str());
   for (int64_t s = 0; s < d->nstreams; s++) P->status[(size_t)s] |= X->status[(size_t)s];
@@ -357,15 +424,15 @@ int vamd_decode_ogg(vamd_ctx *c, const vamd_decode_ogg_desc *d, const int64_t *o
   DecodeInput in;
   in.offset = X.offset.data(), in.byte0 = 0, in.nbytes = X.offset.back();
   in.scan = &X, in.files = d->bytes + d->file_offset[0], in.files_bytes = d->file_offset[d->nstreams] - d->file_offset[0];
-  return decode_run(c, P, d->nstreams, in, offset_out, pcm, status);
+  return decode_run(c, P, d->nstreams, in, offset_out, pcm, status, nullptr, nullptr, c->dec.follow ? &P.segments : nullptr);
 }
 
-// ---- a file's three header packets (host only) ----
-int vamd_ogg_read_headers(const uint8_t *file, int64_t bytes, uint8_t *out, int64_t cap, int64_t len[3]) {
+// ---- a file's three header packets, a file's links (host only) ----
+static int ogg_read_headers(const uint8_t *file, int64_t bytes, const uint32_t *serial, uint8_t *out, int64_t cap, int64_t len[3]) {
   if (!file || bytes < 0 || !len || cap < 0 || (cap > 0 && !out)) return VAMD_EINVAL;
   std::vector<uint8_t> header[3];
   len[0] = len[1] = len[2] = 0;
-  if (!demux_read_headers(file, bytes, header)) return VAMD_EBADHEADER;
+  if (!demux_read_headers(file, bytes, header, serial)) return VAMD_EBADHEADER;
   int64_t total = 0;
   for (int k = 0; k < 3; k++) total += len[k] = (int64_t)header[k].size();
   if (total > cap) return VAMD_EINVAL;
@@ -374,4 +441,22 @@ int vamd_ogg_read_headers(const uint8_t *file, int64_t bytes, uint8_t *out, int6
     out += header[k].size();
   }
   return VAMD_OK;
+}
+
+int vamd_ogg_read_headers(const uint8_t *file, int64_t bytes, uint8_t *out, int64_t cap, int64_t len[3]) {
+  return ogg_read_headers(file, bytes, nullptr, out, cap, len);
+}
+
+int vamd_ogg_read_headers_serial(const uint8_t *file, int64_t bytes, uint32_t serial, uint8_t *out, int64_t cap, int64_t len[3]) {
+  return ogg_read_headers(file, bytes, &serial, out, cap, len);
+}
+
+int vamd_ogg_links(const uint8_t *file, int64_t bytes, vamd_ogg_link *out, int64_t cap, int64_t *nlinks) {
+  if (!file || bytes < 0 || !nlinks || cap < 0 || (cap > 0 && !out)) return VAMD_EINVAL;
+  std::vector<DemuxLink> links;
+  const bool whole = demux_links(file, bytes, &links);
+  *nlinks = (int64_t)links.size();
+  for (int64_t k = 0; k < *nlinks && k < cap; k++) out[k].begin = links[(size_t)k].begin, out[k].end = links[(size_t)k].end, out[k].serial = links[(size_t)k].serial;
+  if (!whole) return VAMD_EBADHEADER;
+  return *nlinks > cap ? VAMD_EINVAL : VAMD_OK;
 }

@@ -145,6 +145,12 @@ struct DecodePlan {
   std::vector<int64_t> frames;     // [nstreams]
   std::vector<uint8_t> status;     // [nstreams] what the packets' heads already tell: such a stream has no blocks
   int64_t max_frames = 0;
+  // (a plan made from per-packet marks, decode_plan_build_marked below, also lists the runs of frames its streams keep)
+  struct Segment {
+    int64_t stream, k0, k1;        // blocks [k0, k1) of order[]: the link the run lies in, its first centre at 0
+    int64_t first, count, out_at;  // frames [first, first + count) of the link, at out_at of the stream's frames
+  };
+  std::vector<Segment> segments;
 };
 
 // the size class a packet's first byte names, or -VAMD_STATUS_* (lib/synthesis.c:44-57; the mode number is the size class
@@ -218,6 +224,92 @@ inline bool decode_plan_build(const int bs[2], int modes, int modebits, int64_t 
       P->frames[(size_t)s] = frames;
       P->max_frames = std::max(P->max_frames, frames);
     }
+    P->lap_start[(size_t)s + 1] = (int64_t)P->order.size();
+  }
+  return true;
+}
+
+// The plan from per-packet MARKS, as a reader of the container has them: granule[p] the granule position of the page on
+// which packet p completes where it is the last to complete there, else -1 (a position below -1 is none too, as the page
+// walk reads it: vamd_demux.h); eos[p] libogg's e_o_s (NULL: each stream's last packet).  What a stream keeps of its
+// blocks' frames is what vorbis_synthesis_blockin leaves a caller who drains after every packet (lib/block.c:858-937):
+// with count the frames added so far (0 after the first packet, + add_p = bs[W_{p-1}]/4 + bs[W_p]/4 per later one) and pos
+// the tracked position (-1 at first),
+//   pos == -1, granule[p] != -1   pos = granule[p]; where count > granule[p], min(count - granule[p], add_p) of packet p's
+//                                 own frames go: its last with eos[p], else its first
+//   pos != -1                     pos += add_p; where granule[p] != -1 and differs: with pos > granule[p] and eos[p],
+//                                 min(pos - granule[p], add_p) of its last frames go; pos = granule[p] either way
+// so no cut exceeds what its packet adds, and a first page's trim takes frames of the LAST packet of that page.
+// links (or NULL) / nlinks: packet indices, ascending, at which a stream's packets begin a new LINK (vamd_demux.h): a
+// fresh lap -- its first block gives no output -- and a fresh walk; a stream's frames are its links' end to end.
+// Out come frames[] and segments[], a row per run of kept frames; order[], src[] and packet[] as above, src[] per link.
+inline bool decode_plan_build_marked(const int bs[2], int modes, int modebits, int64_t nstreams, int64_t npackets, const uint8_t *bytes,
+                                     const int64_t *offset, const int64_t *stream_start, const int64_t *granule, const uint8_t *eos, DecodePlan *P,
+                                     std::string *err, const uint8_t *first = nullptr, const int64_t *links = nullptr, int64_t nlinks = 0) {
+  *P = DecodePlan();
+  if (!decode_desc_check(nstreams, npackets, bytes, offset, stream_start, nullptr, first, err)) return false;
+  if (npackets > 0 && !granule) return *err = "decode: null granule marks", false;
+  for (int64_t j = 0; j < nlinks; j++)
+    if (links[j] < 0 || links[j] > npackets || (j && links[j] < links[j - 1])) return *err = "decode: link starts outside the packets", false;
+  P->frames.assign((size_t)nstreams, 0);
+  P->status.assign((size_t)nstreams, 0);
+  P->lap_start.assign((size_t)nstreams + 1, 0);
+  std::vector<int> cls;
+  int64_t link = 0;
+  for (int64_t s = 0; s < nstreams; s++) {
+    const int64_t p0 = stream_start[s], p1 = stream_start[s + 1];
+    cls.clear();
+    uint8_t st = 0;
+    for (int64_t p = p0; p < p1; p++) {
+      const int W = decode_packet_class(first ? first + p : bytes + offset[p], offset[p + 1] - offset[p], modes, modebits);
+      if (W < 0) st |= (uint8_t)-W;
+      cls.push_back(W);
+    }
+    P->status[(size_t)s] = st;
+    while (link < nlinks && links[link] <= p0) link++;
+    int64_t out_at = 0;
+    for (int64_t q0 = p0; !st && q0 < p1;) {
+      int64_t q1 = p1;
+      if (link < nlinks && links[link] < p1) q1 = links[link++];
+      const int64_t k0 = (int64_t)P->order.size();
+      const size_t seg0 = P->segments.size();
+      int64_t count = 0, pos = -1, run_first = 0, run_end = 0;  // the open run of kept frames, in the link's frames
+      auto close_run = [&]() {
+        if (run_end > run_first) P->segments.push_back({s, k0, 0, run_first, run_end - run_first, out_at}), out_at += run_end - run_first;
+      };
+      for (int64_t p = q0; p < q1; p++) {
+        const int W = cls[(size_t)(p - p0)];
+        const int64_t add = p > q0 ? decode_step(bs, cls[(size_t)(p - p0 - 1)], W) : 0;
+        if (P->nblocks[W] >= (1 << 30)) return *err = "decode: more than 2^30 blocks of a size class", false;
+        P->order.push_back((int32_t)(W << 30) | (int32_t)P->nblocks[W]++);
+        P->src[W].push_back(count + add - bs[W] / 2);
+        P->packet.push_back(p);
+        const int64_t lo = count, g = granule[p] < -1 ? -1 : granule[p];
+        const bool e = eos ? eos[p] != 0 : p == p1 - 1;
+        count += add;
+        int64_t front = 0, back = 0;
+        if (pos == -1) {
+          if (g != -1) {
+            pos = g;
+            if (count > g) (e ? back : front) = std::min(count - g, add);
+          }
+        } else {
+          pos = (int64_t)((uint64_t)pos + (uint64_t)add);  // (the reference's sum, wrapping where a position near 2^63 was believed)
+          if (g != -1 && pos != g) {
+            if (pos > g && e) back = std::min(pos - g, add);  // (g >= 0: the difference holds)
+            pos = g;
+          }
+        }
+        if (lo + front != run_end) close_run(), run_first = run_end = lo + front;
+        run_end = count - back;
+        if (back) close_run(), run_first = run_end = count;
+      }
+      close_run();
+      for (size_t i = seg0; i < P->segments.size(); i++) P->segments[i].k1 = (int64_t)P->order.size();
+      q0 = q1;
+    }
+    P->frames[(size_t)s] = out_at;
+    P->max_frames = std::max(P->max_frames, out_at);
     P->lap_start[(size_t)s + 1] = (int64_t)P->order.size();
   }
   return true;

@@ -1719,6 +1719,17 @@ __global__ __launch_bounds__(256) void k_lap_window(LapP L, long nwindows, const
   }
 }
 
+// The kept runs of streams decoded from per-packet marks (k_synth.h, "the lap for segments"): k_lap_window's gather with the
+// block range in the row, so that the rows of one link share its blocks.  A row of the grid per segment, striding beyond
+// 1024; a thread per four consecutive frames.  The host lays the rows out (vamd_decode.h): no two cover the same floats.
+__global__ __launch_bounds__(256) void k_lap_segments(LapP L, long nsegments, const LapSegment *__restrict__ seg, float *__restrict__ out) {
+  for (long g = blockIdx.y; g < nsegments; g += gridDim.y) {
+    const LapSegment S = seg[g];
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; 4 * q < S.count; q += (long long)gridDim.x * blockDim.x)
+      lap_segment(L, S, q, out);
+  }
+}
+
 // The live decoder's carries (k_synth.h, "the lap across pieces"): a workgroup per (row of the table, channel), striding
 // over the pairs; a wave's lanes move 16 bytes each.  k_decode_carry_in before k_lap, k_decode_carry_out behind k_synth,
 // in-before-out on one stream: a slot may be read and written in one call.
