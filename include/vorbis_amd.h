@@ -832,6 +832,46 @@ int vamd_decode_follow(vamd_ctx *ctx, int on);
 int vamd_ogg_links(const uint8_t *file, int64_t bytes, vamd_ogg_link *out, int64_t cap, int64_t *nlinks);
 int vamd_ogg_read_headers_serial(const uint8_t *file, int64_t bytes, uint32_t serial, uint8_t *out, int64_t cap, int64_t len[3]);
 
+/* ---- the decoded signal in the caller's format (still ABI 9: additions only).  Every decode entry above and below --
+ * vamd_decode_streams, _streams_marked, vamd_decode_ogg, vamd_decode_window, vamd_decode_ogg_window, vamd_decode_live_wrote,
+ * vamd_decode_ogg_live_wrote -- writes fp32, planar [ch][frames] per stream.  vamd_decode_output sets, PER CONTEXT, another
+ * element type and/or layout for all of them; the conversion happens in the store of the last kernel (no second pass over
+ * an fp32 buffer, and no fp32 buffer).  Off by default, and with it off (or set back with NULL) every entry gives what it
+ * gave, byte for byte, from the same device code.
+ *   The prototypes stay: `pcm` is read as a pointer to the format's element type, and it must be aligned to that type
+ *     (else VAMD_EINVAL, before anything is enqueued).  offset_out[], and a window call's channel_stride[], count ELEMENTS
+ *     of that type, not floats.  Any offset_out >= 0 works, odd ones included.
+ *   planar       stream (or window) s, channel c, frame k at pcm[offset_out[s] + c * frames[s] + k], as before
+ *   interleaved  ... at pcm[offset_out[s] + k * ch + c].  Crops of one length need no stride: offset_out[w] = w * length * ch,
+ *                the tail behind a window's valid frames is left alone.  A window call that names channel_stride under an
+ *                interleaved format is VAMD_EINVAL.
+ *   No element outside a stream's own ch * frames (a window's ch * count) is written.
+ *   A live decoder reads the context's format at each call: the carry between pieces stays fp32, so the format may change
+ *     between two pieces of one stream.
+ *   vamd_feed_decoded's tensors stay fp32 planar; vamd_pcm_convert, below, converts them.
+ * VAMD_PCM_S16 is ov_read's conversion (lib/vorbisfile.c:2018-2036): val = vorbis_ftoi(x * 32768.f), clipped to
+ *   [-32768, 32767], where vorbis_ftoi rounds to nearest, ties to even (lib/os.h:149-157, as compiled on x86-64).  For
+ *   every float with |x * 32768| < 2^31 the result is bit for bit the reference's.
+ *   DELIBERATE DEVIATION: beyond that (|x| >= 65536, the infinities, NaN) the reference's value is its instruction's
+ *   "indefinite" result, -32768 for either sign and for NaN (its portable branch is undefined there).  Here such a value
+ *   saturates by its sign -- +inf to 32767, -inf to -32768 -- and NaN gives 0.
+ * VAMD_PCM_F16 / _BF16 round to nearest even; F16 overflows to the infinities; a NaN stays a NaN (BF16: 0x7fc0).
+ * vamd_decode_output -> VAMD_OK; VAMD_EINVAL for an unknown dtype (the context's format stays as it was).
+ * vamd_pcm_convert: the same device conversion over an fp32 planar tensor that exists already -- src [ch][frames] floats in
+ *   device memory to dst in the given format (NULL: a copy), frames * ch elements, enqueued on the context's stream.  src
+ *   and dst must not overlap.  -> VAMD_OK; VAMD_EINVAL for an unknown dtype, ch outside 1 .. 8, frames < 0, a null or
+ *   misaligned pointer. */
+#define VAMD_PCM_F32  0   /* what every entry gives by default */
+#define VAMD_PCM_S16  1   /* int16_t, ov_read's conversion (above) */
+#define VAMD_PCM_F16  2   /* IEEE binary16, round to nearest even, overflow to +-inf */
+#define VAMD_PCM_BF16 3   /* bfloat16, round to nearest even, NaN stays NaN */
+typedef struct vamd_pcm_format {
+  int dtype;        /* VAMD_PCM_* */
+  int interleaved;  /* 0: planar [ch][frames]; else [frames][ch] */
+} vamd_pcm_format;
+int vamd_decode_output(vamd_ctx *ctx, const vamd_pcm_format *fmt);
+int vamd_pcm_convert(vamd_ctx *ctx, const float *src, int64_t frames, int ch, const vamd_pcm_format *fmt, void *dst);
+
 /* ---- a decoder for a stream the caller did not encode: the context from the stream's own headers (still ABI 9: additions
  * only).  vamd_create_decoder parses the identification and setup header packets (Vorbis I 4.2.2, 4.2.4) as
  * vorbis_synthesis_headerin does and builds a DECODE-ONLY context: every decode entry above and below works on it as on a

@@ -27,6 +27,7 @@ FEED_S16, FEED_F32 = 0, 1
 FEED_NO_ARENA = 0x100                       # or'ed into fmt: no pinned input arena, device-fed groups only
 FEED_DECODED = 0x200                        # or'ed into fmt: the decoded signal beside the packets (Feed(decoded=True))
 SRC_S16, SRC_F32, SRC_F16, SRC_BF16 = 0, 1, 2, 3   # VAMD_SRC_*: a device-fed group's element type
+PCM_F32, PCM_S16, PCM_F16, PCM_BF16 = 0, 1, 2, 3   # VAMD_PCM_*: the decoded signal's element type (vamd_decode_output)
 
 _vp = C.c_void_p
 
@@ -66,6 +67,10 @@ class _DecodeMarks(C.Structure):  # vamd_decode_marks
 
 class _OggLink(C.Structure):  # vamd_ogg_link
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("serial", C.c_uint32)]
+
+
+class _PcmFormat(C.Structure):  # vamd_pcm_format
+    _fields_ = [("dtype", C.c_int), ("interleaved", C.c_int)]
 
 
 class _DecodeLiveDesc(C.Structure):  # vamd_decode_live_desc
@@ -173,6 +178,8 @@ PROTOTYPES = {
     "vamd_decode_plan_marked": (_int, [_vp, _pDecode, _pMarks, _vp, _vp]),
     "vamd_decode_streams_marked": (_int, [_vp, _pDecode, _pMarks, _vp, _vp, _vp]),
     "vamd_decode_follow": (_int, [_vp, _int]),
+    "vamd_decode_output": (_int, [_vp, C.POINTER(_PcmFormat)]),
+    "vamd_pcm_convert": (_int, [_vp, _vp, C.c_int64, _int, C.POINTER(_PcmFormat), _vp]),
     "vamd_ogg_links": (_int, [_vp, C.c_int64, _vp, C.c_int64, _vp]),
     "vamd_ogg_read_headers_serial": (_int, [_vp, C.c_int64, C.c_uint32, _vp, C.c_int64, _vp]),
     "vamd_decode_live_create": (_int, [_vp, C.c_int64, _pvp]),

@@ -8,6 +8,7 @@ import numpy as np
 
 from .abi import (ABI_VERSION, BLOCKTYPE_LONG, LEVEL_FULL, LEVEL_PSY, LEVEL_TRANSFORM, PACKETBLOBS, POSTS_STRIDE, QUANT_LIMIT_INT,
                   QUANT_LIMIT_SQUARE, RES_CLASS_STRIDE, STATUS_BADHEADER, STATUS_PARTIAL, STATUS_RANGE, VAMD_EDOMAIN, VAMD_EINVAL, VAMD_ENONFINITE, VAMD_OK, EnvelopeState, VamdError,
+                  PCM_BF16, PCM_F16, PCM_F32, PCM_S16, _PcmFormat,
                   _DecodeDesc, _DecodeLiveDesc, _DecodeMarks, _OggLink, _DecodeOggDesc, _DecodeOggLiveDesc, _DecodeOggLiveOpts, _Desc, _OggWindowDesc, _IO, _MIO, _Plan, _vp, load_library)
 from .packets import packet_bytes
 
@@ -74,6 +75,7 @@ class Analyzer:
         self.channels = self.L.vamd_channels(h)
         self.blocksizes = (self.L.vamd_blocksize(h, 0), self.L.vamd_blocksize(h, 1))
         self.posts = (self.L.vamd_posts(h, 0), self.L.vamd_posts(h, 1))
+        self._pcm_dtype, self._pcm_interleaved = torch.float32, False
 
     @classmethod
     def from_headers(cls, id_header, setup_header, device=None):
@@ -681,9 +683,10 @@ class Analyzer:
         return dict(desc=d, keep=(data, off, start, gran, pg, pe), nstreams=ns, npackets=len(flat), marks=marks)
 
     def decode_run(self, prep, pcm=None):
-        """vamd_decode_plan + vamd_decode_streams over decode_prepare()'s descriptor.  pcm: a float32 tensor on the context's
-        device to decode into (at least the planned frames x channels floats), or None: one is made.
-        -> (pcm, frames, offset, status): stream s, channel c, frame k at pcm[offset[s] + c * frames[s] + k]"""
+        """vamd_decode_plan + vamd_decode_streams over decode_prepare()'s descriptor.  pcm: a tensor of pcm_dtype on the
+        context's device to decode into (at least the planned frames x channels elements), or None: one is made.
+        -> (pcm, frames, offset, status): stream s, channel c, frame k at pcm[offset[s] + c * frames[s] + k]; under
+        pcm_interleaved at pcm[offset[s] + k * channels + c]"""
         m = prep.get("marks")
         if m is not None:  # (vamd_decode_plan_marked + vamd_decode_streams_marked: the marks ride behind the descriptor)
             return self._decode_run(lambda h, d, *a: self.L.vamd_decode_plan_marked(h, d, C.byref(m), *a),
@@ -701,9 +704,9 @@ class Analyzer:
             out_off[1:ns] = np.cumsum(frames[:ns - 1] * self.channels)
         total = int((frames[:ns] * self.channels).sum())
         if pcm is None:
-            pcm = t.zeros(total + 4, dtype=t.float32, device=self._dev())
-        self._need_tensor(pcm, t.float32, "pcm")
-        self._need(pcm.numel() >= total, "pcm must hold %d floats" % total)
+            pcm = t.zeros(total + 4, dtype=self._pcm_dtype, device=self._dev())
+        self._need_tensor(pcm, self._pcm_dtype, "pcm")
+        self._need(pcm.numel() >= total, "pcm must hold %d elements" % total)
         status = np.zeros(max(ns, 1), np.uint8)
         self._bind_stream()
         self._check(run(self.h, C.byref(d), _vp(out_off.ctypes.data), _vp(pcm.data_ptr()), _vp(status.ctypes.data)))
@@ -738,14 +741,75 @@ class Analyzer:
     def follow_links(self, on):
         self._check(min(self.L.vamd_decode_follow(self.h, 1 if on else 0), 0))
 
+    _PCM_CODES = {"float32": PCM_F32, "int16": PCM_S16, "float16": PCM_F16, "bfloat16": PCM_BF16}
+
+    def _set_output(self, dtype, interleaved):
+        t = self.torch
+        code = self._PCM_CODES.get(str(dtype).replace("torch.", "")) if isinstance(dtype, t.dtype) else None
+        self._need(code is not None, "pcm_dtype must be torch.float32, int16, float16 or bfloat16 (it is %r)" % (dtype,))
+        fmt = _PcmFormat(code, 1 if interleaved else 0)
+        self._check(self.L.vamd_decode_output(self.h, C.byref(fmt)))
+        self._pcm_dtype, self._pcm_interleaved = dtype, bool(interleaved)
+
+    @property
+    def pcm_dtype(self):
+        """vamd_decode_output: the element type of every decode call's tensors on this context -- torch.float32 (the
+        default), int16 (ov_read's conversion: round to nearest even of x * 32768, clipped), float16 or bfloat16 (round to
+        nearest even) -- converted in the last kernel's store.  A live decoder reads it at each write."""
+        return self._pcm_dtype
+
+    @pcm_dtype.setter
+    def pcm_dtype(self, dtype):
+        self._set_output(dtype, self._pcm_interleaved)
+
+    @property
+    def pcm_interleaved(self):
+        """vamd_decode_output: whether every decode call on this context gives [frames, ch] tensors (crops: [n, length, ch])
+        instead of [ch, frames], the default."""
+        return self._pcm_interleaved
+
+    @pcm_interleaved.setter
+    def pcm_interleaved(self, on):
+        self._set_output(self._pcm_dtype, on)
+
+    def _with_output(self, dtype, interleaved, call):
+        """call() under pcm_dtype / pcm_interleaved for this call alone (None: as the context stands)"""
+        was = (self._pcm_dtype, self._pcm_interleaved)
+        want = (was[0] if dtype is None else dtype, was[1] if interleaved is None else bool(interleaved))
+        if want == was:
+            return call()
+        self._set_output(*want)
+        try:
+            return call()
+        finally:
+            self._set_output(*was)
+
+    def pcm_convert(self, tensor, dtype, interleaved=False):
+        """vamd_pcm_convert: a float32 [ch, frames] tensor on the context's device -> a new tensor of `dtype`, [ch, frames]
+        or, interleaved, [frames, ch]: the conversion of pcm_dtype / pcm_interleaved over a signal that exists already (a
+        Feed's decoded tensors)."""
+        t = self.torch
+        self._need_tensor(tensor, t.float32, "tensor")
+        self._need(tensor.dim() == 2 and 1 <= tensor.shape[0] <= 8, "tensor must be [ch, frames] with 1 .. 8 channels")
+        code = self._PCM_CODES.get(str(dtype).replace("torch.", "")) if isinstance(dtype, t.dtype) else None
+        self._need(code is not None, "dtype must be torch.float32, int16, float16 or bfloat16 (it is %r)" % (dtype,))
+        ch, frames = int(tensor.shape[0]), int(tensor.shape[1])
+        out = t.empty((frames, ch) if interleaved else (ch, frames), dtype=dtype, device=self._dev())
+        fmt = _PcmFormat(code, 1 if interleaved else 0)
+        self._bind_stream()
+        self._check(self.L.vamd_pcm_convert(self.h, _vp(tensor.data_ptr()), frames, ch, C.byref(fmt), _vp(out.data_ptr())))
+        return out
+
     def _decoded_tensors(self, n, pcm, frames, out_off, status, with_status):
         out = []
         for s in range(n):
             f = 0 if int(status[s]) & ~STATUS_PARTIAL else int(frames[s])  # (a packet kept under keep_partial costs its stream nothing)
-            out.append(pcm[int(out_off[s]):int(out_off[s]) + self.channels * f].view(self.channels, f))
+            flat = pcm[int(out_off[s]):int(out_off[s]) + self.channels * f]
+            out.append(flat.view(f, self.channels) if self._pcm_interleaved else flat.view(self.channels, f))
         return (out, status.copy()) if with_status else out
 
-    def decode_streams(self, streams, granules=None, with_status=False, offset=None, stream_start=None, packet_granules=None, eos=None):
+    def decode_streams(self, streams, granules=None, with_status=False, offset=None, stream_start=None, packet_granules=None, eos=None,
+                       dtype=None, interleaved=None):
         """vamd_decode_plan + vamd_decode_streams: audio packets of this context's setup in, PCM out -- k_unpack, k_synth and
         the lap on the GPU.  streams: a list of lists of `bytes`, one list per stream (a Feed's rows plug in as
         [[p for p, _, _, _ in row] for row in rows]); granules: per stream the last packet's granule position (None or -1:
@@ -756,9 +820,11 @@ class Analyzer:
         packet_granules (in granules' place): per stream a list with, per packet, the granule position of the page on which
         it completes where it is the last to complete there, else -1 or None; eos: per stream a list of libogg's e_o_s per
         packet (None: each stream's last packet) -- vamd_decode_streams_marked, the frames a reader of the container keeps:
-        a start at a nonzero granule, the first page's trim."""
+        a start at a nonzero granule, the first page's trim.
+        dtype / interleaved: pcm_dtype / pcm_interleaved for this call (None: as the context stands); interleaved, the
+        tensors are [frames, ch]."""
         prep = self.decode_prepare(streams, granules, offset, stream_start, packet_granules, eos)
-        return self._decoded_tensors(len(streams), *self.decode_run(prep), with_status)
+        return self._with_output(dtype, interleaved, lambda: self._decoded_tensors(len(streams), *self.decode_run(prep), with_status))
 
     def live_decoder(self, max_streams):
         """vamd_decode_live_create: a LiveDecoder for up to max_streams continuing streams on this context.  Closing the
@@ -800,18 +866,20 @@ class Analyzer:
         """vamd_decode_ogg_plan + vamd_decode_ogg over decode_ogg_prepare()'s descriptor; pcm and the result as decode_run's"""
         return self._decode_run(self.L.vamd_decode_ogg_plan, self.L.vamd_decode_ogg, prep, pcm)
 
-    def decode_ogg(self, files, setup_header=None, with_status=False, file_offset=None, follow_links=None):
+    def decode_ogg(self, files, setup_header=None, with_status=False, file_offset=None, follow_links=None, dtype=None, interleaved=None):
         """vamd_decode_ogg_plan + vamd_decode_ogg: whole Ogg Vorbis files of this context's setup in, PCM out -- the page
         walk on the host, checksums and unpaging (k_ogg_depage), k_unpack, k_synth and the lap on the GPU.  files: a list of
         `bytes`, one file per stream (a Feed's Ogg output plugs in as it is); setup_header: the setup header packet every
         file's third packet must equal, or None: only its type is looked at.  file_offset: a test hook, the descriptor's
         array as given.  -> as decode_streams(); a flagged stream -- STATUS_BADPAGE / _BADHEADER or the packet decoder's
-        bits -- has no frames.  follow_links: Analyzer.follow_links for this call (None: as the context stands)."""
+        bits -- has no frames.  follow_links: Analyzer.follow_links for this call (None: as the context stands); dtype /
+        interleaved: pcm_dtype / pcm_interleaved likewise."""
         was = self.follow_links
         if follow_links is not None:
             self.follow_links = follow_links
         try:
-            return self._decoded_tensors(len(files), *self.decode_ogg_run(self.decode_ogg_prepare(files, setup_header, file_offset)), with_status)
+            prep = self.decode_ogg_prepare(files, setup_header, file_offset)
+            return self._with_output(dtype, interleaved, lambda: self._decoded_tensors(len(files), *self.decode_ogg_run(prep), with_status))
         finally:
             self.follow_links = was
 
@@ -833,9 +901,9 @@ class Analyzer:
             out_off[1:nw] = np.cumsum(per[:nw - 1] * self.channels)
         total = int((per[:nw] * self.channels).sum())
         if pcm is None:
-            pcm = t.zeros(total + 4, dtype=t.float32, device=self._dev())
-        self._need_tensor(pcm, t.float32, "pcm")
-        self._need(pcm.numel() >= total, "pcm must hold %d floats" % total)
+            pcm = t.zeros(total + 4, dtype=self._pcm_dtype, device=self._dev())
+        self._need_tensor(pcm, self._pcm_dtype, "pcm")
+        self._need(pcm.numel() >= total, "pcm must hold %d elements" % total)
         status = np.zeros(max(nw, 1), np.uint8)
         self._bind_stream()
         self._check(run(_vp(out_off.ctypes.data), _vp(pcm.data_ptr()), _vp(status.ctypes.data)))
@@ -1182,7 +1250,7 @@ class OggIndex:
         except Exception:
             pass
 
-    def _run(self, stream, start, count, pcm=None, stride=None, files=None, file_offset=None):
+    def _run(self, stream, start, count, pcm=None, stride=None, files=None, file_offset=None, row=None):
         """vamd_decode_ogg_window_plan + vamd_decode_ogg_window -> (pcm, frames, offset, status) per window.  files /
         file_offset: test hooks, other bytes than the index was made of."""
         an = self.an
@@ -1202,23 +1270,36 @@ class OggIndex:
         d = _OggWindowDesc(nw, _vp(ws.ctypes.data), _vp(wa.ctypes.data), _vp(wc.ctypes.data), _vp(data.ctypes.data), _vp(off.ctypes.data),
                            _vp(cs.ctypes.data) if cs is not None else None)
         args = (an.h, self.h, C.byref(d))
-        return an._window_run(lambda *a: an.L.vamd_decode_ogg_window_plan(*args, *a, None), lambda *a: an.L.vamd_decode_ogg_window(*args, *a), nw, pcm, stride)
+        return an._window_run(lambda *a: an.L.vamd_decode_ogg_window_plan(*args, *a, None), lambda *a: an.L.vamd_decode_ogg_window(*args, *a), nw, pcm, stride if row is None else row)
 
-    def decode(self, stream, start, count, with_status=False, files=None, file_offset=None):
+    def decode(self, stream, start, count, with_status=False, files=None, file_offset=None, dtype=None, interleaved=None):
         """Window w = frames [start[w], start[w] + count[w]) of file stream[w], cut to the file's end -> a list of float32
         tensors [ch, frames] on the context's device, one per window; a flagged window has no frames.  with_status, also
-        the windows' status bytes (numpy uint8)."""
-        return self.an._decoded_tensors(len(stream), *self._run(stream, start, count, files=files, file_offset=file_offset), with_status)
+        the windows' status bytes (numpy uint8).  dtype / interleaved: Analyzer.pcm_dtype / pcm_interleaved for this call
+        (None: as the context stands); interleaved, the tensors are [frames, ch]."""
+        an = self.an
+        return an._with_output(dtype, interleaved, lambda: an._decoded_tensors(len(stream), *self._run(stream, start, count, files=files, file_offset=file_offset),
+                                                                              with_status))
 
-    def crops(self, stream, start, length, with_status=False):
+    def crops(self, stream, start, length, with_status=False, dtype=None, interleaved=None):
         """Crops of ONE length: -> (a float32 tensor [n, ch, length] on the context's device, the valid lengths (numpy int64
         [n])).  Row w holds frames [start[w], start[w] + length) of file stream[w]; behind what the file's end (or a flag)
-        cut short the row is zero: the tensor is made zeroed and the kernel writes the valid part alone."""
+        cut short the row is zero: the tensor is made zeroed and the kernel writes the valid part alone.  dtype /
+        interleaved: Analyzer.pcm_dtype / pcm_interleaved for this call (None: as the context stands); the tensor has that
+        dtype and, interleaved, is [n, length, ch]."""
+        an = self.an
+        return an._with_output(dtype, interleaved, lambda: self._crops(stream, start, length, with_status))
+
+    def _crops(self, stream, start, length, with_status):
         an, t = self.an, self.an.torch
         n, length = len(stream), int(length)
         an._need(length >= 0, "crops: a negative length")
-        pcm = t.zeros((n, an.channels, length), dtype=t.float32, device=an._dev())
-        _, frames, _, status = self._run(stream, start, [length] * n, pcm=pcm.view(-1), stride=length)
+        if an.pcm_interleaved:  # (a crop is one row of length * ch elements: no stride, the windows lie length * ch apart)
+            pcm = t.zeros((n, length, an.channels), dtype=an.pcm_dtype, device=an._dev())
+            _, frames, _, status = self._run(stream, start, [length] * n, pcm=pcm.view(-1), row=length)
+        else:
+            pcm = t.zeros((n, an.channels, length), dtype=an.pcm_dtype, device=an._dev())
+            _, frames, _, status = self._run(stream, start, [length] * n, pcm=pcm.view(-1), stride=length)
         flagged = (status & ~np.uint8(STATUS_PARTIAL)) != 0
         valid = np.where(flagged, 0, frames).astype(np.int64)
         for w in np.nonzero(flagged & (frames > 0))[0]:  # (a window the device flagged has no frames: its row goes back to zero)
@@ -1226,10 +1307,12 @@ class OggIndex:
         return (pcm, valid, status.copy()) if with_status else (pcm, valid)
 
 
-def ogg_index(setup_blob, files, setup_header=None, device=None):
-    """Analyzer(setup_blob).ogg_index(...) for a caller who holds files and no context: closing the index closes the context."""
+def ogg_index(setup_blob, files, setup_header=None, device=None, dtype=None, interleaved=None):
+    """Analyzer(setup_blob).ogg_index(...) for a caller who holds files and no context: closing the index closes the context.
+    dtype / interleaved: the context's pcm_dtype / pcm_interleaved, so what the index's decode() and crops() give."""
     a = Analyzer(setup_blob, device)
     try:
+        a._set_output(a.pcm_dtype if dtype is None else dtype, bool(interleaved))
         x = OggIndex(a, files, setup_header, own=True)
     except Exception:
         a.close()
@@ -1237,13 +1320,14 @@ def ogg_index(setup_blob, files, setup_header=None, device=None):
     return x
 
 
-def decode(setup_blob, streams, granules=None, with_status=False, device=None, keep_partial=False):
+def decode(setup_blob, streams, granules=None, with_status=False, device=None, keep_partial=False, dtype=None, interleaved=None):
     """Analyzer(setup_blob).decode_streams(...) for a caller who holds packets and no context: the packets must come from an
-    encoder of that setup.  keep_partial: Analyzer.keep_partial for the call."""
+    encoder of that setup.  keep_partial: Analyzer.keep_partial for the call; dtype / interleaved: Analyzer.pcm_dtype /
+    pcm_interleaved for the call."""
     a = Analyzer(setup_blob, device)
     try:
         a.keep_partial = keep_partial
-        return a.decode_streams(streams, granules, with_status)
+        return a.decode_streams(streams, granules, with_status, dtype=dtype, interleaved=interleaved)
     finally:
         a.close()
 
@@ -1282,7 +1366,18 @@ def read_ogg_headers(file, serial=None):
     return out.raw[:a], out.raw[a:a + b], out.raw[a + b:a + b + c]
 
 
-def _decode_ogg_linked(files, with_status, device, keep_partial, links):
+def pcm_convert(tensor, dtype, interleaved=False):
+    """vamd_pcm_convert for a caller who holds a float32 [ch, frames] tensor on a GPU and no context (a context of the
+    default setup is made for the call: any context converts alike) -> a tensor of `dtype`, [ch, frames] or [frames, ch]."""
+    from .abi import default_setup_blob
+    a = Analyzer(default_setup_blob(), tensor.device.index if hasattr(tensor, "device") and tensor.device.index is not None else None)
+    try:
+        return a.pcm_convert(tensor, dtype, interleaved)
+    finally:
+        a.close()
+
+
+def _decode_ogg_linked(files, with_status, device, keep_partial, links, dtype=None, interleaved=None):
     """decode_ogg_files(follow_links=True): the files split at their link boundaries (ogg_links; a file whose pages do not
     hold stays whole and is flagged by the decode), the links decoded as files -- grouped by setup, one context each, the
     policy on -- and put back together per file."""
@@ -1296,7 +1391,8 @@ def _decode_ogg_linked(files, with_status, device, keep_partial, links):
             spans = [(0, len(f), None)]
         for a, b, serial in spans:
             parts.append(f[a:b]), owner.append(i), serials.append(serial)
-    pcm, st = _decode_ogg_grouped(parts, device, keep_partial, serials)
+    pcm, st = _decode_ogg_grouped(parts, device, keep_partial, serials, dtype, interleaved)
+    cdim = 1 if interleaved else 0  # (the tensors' channel dimension)
     out, status = [], np.zeros(len(files), np.uint8)
     for i in range(len(files)):
         mine = [k for k, o in enumerate(owner) if o == i]
@@ -1306,15 +1402,15 @@ def _decode_ogg_linked(files, with_status, device, keep_partial, links):
         if links:
             out.append([pcm[k] for k in mine])
         elif flagged:
-            out.append(torch.zeros((0, 0), dtype=torch.float32, device=pcm[mine[0]].device))
+            out.append(torch.zeros((0, 0), dtype=dtype or torch.float32, device=pcm[mine[0]].device))
         else:
-            if len({int(pcm[k].shape[0]) for k in mine}) != 1:
+            if len({int(pcm[k].shape[cdim]) for k in mine}) != 1:
                 raise ValueError("decode_ogg_files: file %d has links of differing channel counts; links=True gives a tensor per link" % i)
-            out.append(pcm[mine[0]] if len(mine) == 1 else torch.cat([pcm[k] for k in mine], dim=1))
+            out.append(pcm[mine[0]] if len(mine) == 1 else torch.cat([pcm[k] for k in mine], dim=1 - cdim))
     return (out, status) if with_status else out
 
 
-def _decode_ogg_grouped(files, device, keep_partial, serials=None):
+def _decode_ogg_grouped(files, device, keep_partial, serials=None, dtype=None, interleaved=None):
     """decode_ogg_files' work: the files (or, with serials -- per file the serial number of its Vorbis stream, None: its
     first stream's -- the links, read under Analyzer.follow_links) grouped by setup, a context per group -> (tensors, status)"""
     import torch
@@ -1333,17 +1429,17 @@ def _decode_ogg_grouped(files, device, keep_partial, serials=None):
             continue
         try:
             a.keep_partial = keep_partial
-            pcm, st = a.decode_ogg([files[i] for i in members], with_status=True, follow_links=serials is not None)
+            pcm, st = a.decode_ogg([files[i] for i in members], with_status=True, follow_links=serials is not None, dtype=dtype, interleaved=interleaved)
             for i, p, v in zip(members, pcm, st):
                 out[i], status[i] = p.clone(), v
         finally:
             a.close()
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
-    out = [torch.zeros((0, 0), dtype=torch.float32, device=dev) if p is None else p for p in out]
+    out = [torch.zeros((0, 0), dtype=dtype or torch.float32, device=dev) if p is None else p for p in out]
     return out, status
 
 
-def decode_ogg_files(files, with_status=False, device=None, keep_partial=False, follow_links=False, links=False):
+def decode_ogg_files(files, with_status=False, device=None, keep_partial=False, follow_links=False, links=False, dtype=None, interleaved=None):
     """Ogg Vorbis files of ANY covered setups in, PCM out: no blob and no settings.  Each file's headers are read
     (read_ogg_headers); the files are grouped by (identification fields, setup header bytes); one decode-only context is
     made per distinct setup (Analyzer.from_headers) and decodes its group in one decode_ogg call.  -> a list of float32
@@ -1352,21 +1448,24 @@ def decode_ogg_files(files, with_status=False, device=None, keep_partial=False, 
     follow_links: files are read as a reader reads them (Analyzer.follow_links): they are split at their link boundaries
     and the LINKS are grouped by setup, so a chained file may change its setup from link to link; the result per file is
     its links' signal end to end where they share a channel count (else ValueError: ask for links=True), a flagged link
-    flags its file.  links=True (with follow_links): per file a list of tensors, one per link."""
+    flags its file.  links=True (with follow_links): per file a list of tensors, one per link.
+    dtype / interleaved: Analyzer.pcm_dtype / pcm_interleaved for every context: tensors of that dtype, interleaved [frames, ch]."""
     if follow_links:
-        return _decode_ogg_linked(files, with_status, device, keep_partial, links)
+        return _decode_ogg_linked(files, with_status, device, keep_partial, links, dtype, interleaved)
     if links:
         raise ValueError("decode_ogg_files: links=True goes with follow_links=True")
-    out, status = _decode_ogg_grouped(files, device, keep_partial)
+    out, status = _decode_ogg_grouped(files, device, keep_partial, None, dtype, interleaved)
     return (out, status) if with_status else out
 
 
-def decode_ogg(setup_blob, files, setup_header=None, with_status=False, device=None, keep_partial=False, follow_links=False):
+def decode_ogg(setup_blob, files, setup_header=None, with_status=False, device=None, keep_partial=False, follow_links=False, dtype=None,
+               interleaved=None):
     """Analyzer(setup_blob).decode_ogg(...) for a caller who holds files and no context: the files must come from an
-    encoder of that setup.  keep_partial / follow_links: Analyzer.keep_partial / Analyzer.follow_links for the call."""
+    encoder of that setup.  keep_partial / follow_links / dtype / interleaved: Analyzer.keep_partial / .follow_links /
+    .pcm_dtype / .pcm_interleaved for the call."""
     a = Analyzer(setup_blob, device)
     try:
         a.keep_partial = keep_partial
-        return a.decode_ogg(files, setup_header, with_status, follow_links=follow_links)
+        return a.decode_ogg(files, setup_header, with_status, follow_links=follow_links, dtype=dtype, interleaved=interleaved)
     finally:
         a.close()

@@ -487,6 +487,124 @@ struct LapSegment {
 };
 VAMD_DEV void lap_segment(const LapP &L, const LapSegment &g, long long q, float *out) { lap_window(L, g.k0, g.k1, g.first, g.count, g.stride, q, out + g.out); }
 
+// ---- the lap in the caller's format (include/vorbis_amd.h, vamd_decode_output) -----------------------------------------------
+// D is a VAMD_PCM_* element type, IL the layout.  <VAMD_PCM_F32, planar> is the code above, untouched; the other seven go
+// through lap_row below.  The conversions are what the header states: S16 is ov_read's (lib/vorbisfile.c:2018-2036,
+// vorbis_ftoi as cvtsd2si rounds: to nearest, ties to even -- x * 32768 is exact in a float, so rintf of it is that
+// value), saturating by sign where the reference's instruction gives its "indefinite" result, NaN to 0; F16 and BF16
+// round to nearest even.
+VAMD_DEV uint32_t pcm_bits(float x) {
+  uint32_t u;
+  memcpy(&u, &x, 4);
+  return u;
+}
+VAMD_DEV int16_t pcm_s16(float x) {
+  const float r = rintf(x * 32768.f);  // (v_cvt_i32_f32 truncates: round first)
+  if (!(r == r)) return 0;
+  return (int16_t)(int)(r > 32767.f ? 32767.f : r < -32768.f ? -32768.f : r);
+}
+VAMD_DEV uint16_t pcm_f16(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const _Float16 h = (_Float16)x;  // (v_cvt_f16_f32; the compiler packs pairs)
+  uint16_t o;
+  memcpy(&o, &h, 2);
+  return o;
+#else  // (a host compiler without _Float16: the same rounding by hand; tests/test_decode_formats_cpu.py holds it to torch's)
+  const uint32_t u = pcm_bits(x), sign = (u >> 16) & 0x8000u, m = u & 0x7fffffffu;
+  if (m > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
+  if (m < 0x38800000u) return (uint16_t)(sign | (uint32_t)rintf(fabsf(x) * 16777216.f));  // below 2^-14: a multiple of 2^-24
+  uint32_t r = m - 0x38000000u;
+  r = (r + 0xfffu + ((r >> 13) & 1u)) >> 13;
+  return (uint16_t)(sign | (r < 0x7c00u ? r : 0x7c00u));
+#endif
+}
+VAMD_DEV uint16_t pcm_bf16(float x) {
+  const uint32_t u = pcm_bits(x);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+template <int D> struct PcmElem { typedef float T; };  // VAMD_PCM_F32
+template <> struct PcmElem<1> { typedef int16_t T; };   // VAMD_PCM_S16
+template <> struct PcmElem<2> { typedef uint16_t T; };  // VAMD_PCM_F16, as bits
+template <> struct PcmElem<3> { typedef uint16_t T; };  // VAMD_PCM_BF16, as bits
+template <int D> VAMD_DEV typename PcmElem<D>::T pcm_from(float x) {
+  if constexpr (D == 1) return pcm_s16(x);
+  else if constexpr (D == 2) return pcm_f16(x);
+  else if constexpr (D == 3) return pcm_bf16(x);
+  else return x;
+}
+
+// The output policy: a thread takes `per_thread` consecutive ELEMENTS of a row in `stores` 16-byte stores of `wide`
+// elements.  A planar row is one channel's frames; an interleaved row is all of a stream's (or window's, or segment's)
+// frames x channels.  Eight elements a thread everywhere -- what k_lap's thread gathers of a stereo stream behind one
+// search: DESIGN.md section 5 has what else was tried (more loses: the gather is bound by latency, not by stores).
+template <int D, bool IL> struct PcmOut {
+  typedef typename PcmElem<D>::T T;
+  static constexpr int wide = 16 / (int)sizeof(T);
+  static constexpr int stores = IL && sizeof(T) == 4 ? 2 : 1;
+  static constexpr int per_thread = stores * wide;
+};
+template <class T> struct alignas(16) PcmWide { T v[16 / sizeof(T)]; };
+
+// where a thread stands in order[]: the block pair of frame `frame`, found once and kept while the thread's rows (a planar
+// window's channels) begin at the same frame -- they do wherever the rows are equally aligned
+struct LapAt {
+  long long frame = -1, k = 0, end = 0;
+};
+
+// Elements [0, n) of one row, at `row`: element e is frame a + e of channel c0 (planar), or frame a + e / ch of channel
+// e % ch (interleaved), out of blocks [k0, k1) of order[] as lap_window takes them.  The row may begin at any element:
+// thread 0 takes the elements in front of the first 16-byte boundary one by one, thread q >= 1 the q-th group of
+// per_thread behind it in whole 16-byte stores, and one by one where the row ends inside one.  No element outside
+// [0, n) is touched.  A row needs threads 0 .. n / per_thread + 1.
+template <int D, bool IL>
+VAMD_DEV void lap_row(const LapP &L, long long k0, long long k1, long long a, long long n, int c0, long long q, typename PcmElem<D>::T *row, LapAt &at) {
+  typedef PcmOut<D, IL> O;
+  typedef typename O::T T;
+  long long head = (long long)(((16 - ((uintptr_t)row & 15)) & 15) / sizeof(T));
+  if (head > n) head = n;
+  const long long lo = q ? head + (q - 1) * O::per_thread : 0;
+  long long hi = q ? lo + O::per_thread : head;
+  if (hi > n) hi = n;
+  if (lo >= hi) return;
+  long long t = IL ? lo / L.ch : lo;
+  int c = IL ? (int)(lo - t * L.ch) : c0;
+  if (at.frame != t) at.frame = t, at.k = lap_find(L, k0, k1, a + t), at.end = lap_centre(L, at.k);
+  long long k = at.k, end = at.end;
+#pragma unroll
+  for (int s = 0; s < O::stores; s++) {
+    const long long e = lo + s * O::wide;
+    const bool whole = q && hi - e >= O::wide;
+    PcmWide<T> pack;
+#pragma unroll
+    for (int j = 0; j < O::wide; j++)
+      if (e + j < hi) {
+        while (a + t >= end && k < k1 - 1) end = lap_centre(L, ++k);
+        const T v = pcm_from<D>(lap_sample(L, k, a + t, c));
+        if (whole) pack.v[j] = v;
+        else row[e + j] = v;
+        if (!IL) t++;
+        else if (++c == L.ch) c = 0, t++;
+      }
+    if (whole) *(PcmWide<T> *)(row + e) = pack;
+  }
+}
+
+// lap_window in format <D, IL>: the same window, the same bounds.  Planar, channel c's row is out + c * stride; interleaved,
+// the window is one row of count * ch elements at out and `stride` is not read.
+template <int D, bool IL>
+VAMD_DEV void lap_window_as(const LapP &L, long long k0, long long k1, long long a, long long F, long long stride, long long q, typename PcmElem<D>::T *out) {
+  if (k1 - k0 < 2 || a < lap_centre(L, k0)) return;
+  const long long span = lap_centre(L, k1 - 1) - a, count = F < span ? F : span;
+  LapAt at;
+  if (IL) lap_row<D, true>(L, k0, k1, a, count * L.ch, 0, q, out, at);
+  else
+    for (int c = 0; c < L.ch; c++) lap_row<D, false>(L, k0, k1, a, count, c, q, out + c * stride, at);
+}
+// the threads a window of F frames needs (the grid's sizing and the kernels' loops)
+template <int D, bool IL> VAMD_DEV long long lap_threads_as(long long F, int ch) { return (IL ? F * ch : F) / PcmOut<D, IL>::per_thread + 2; }
+
 // ---- the lap across pieces: a continuing stream's last block, carried between calls (vamd_decode_live.h) --------------------
 // lap_sample reads, of the block in front, its second half and its size class.  A live decoder keeps that half per slot
 // in `carry` ([slots][ch][bs1/2]; a short block's half fills the front of its row) and, in the next call, stands it in an

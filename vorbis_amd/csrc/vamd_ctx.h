@@ -72,6 +72,8 @@ struct vamd_ctx {
     int lanes = VAMD_UNPACK_LANES;  // packets a wave of k_unpack
     bool partial = false;           // vamd_decode_partial: k_unpack_partial and the bounded k_synth forms in place of k_unpack / k_synth
     bool follow = false;            // vamd_decode_follow: vamd_decode_ogg* walk links and foreign pages and cut by the page granules
+    int pcm_dtype = 0;              // vamd_decode_output: the element type (VAMD_PCM_*) and the layout every decode entry writes;
+    bool pcm_interleaved = false;   //   F32 planar takes k_lap / k_lap_window / k_lap_segments, the others their _as forms
     unsigned char *d_tab = nullptr;
     UnpackP U = {};
     DevBuf bytes, plan, status, files;

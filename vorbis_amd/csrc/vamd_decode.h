@@ -140,6 +140,37 @@ struct DecodeWindows {
   const int64_t *first = nullptr, *stride = nullptr;  // [ns]
 };
 
+// The last launch under a format other than F32 planar (vamd_decode_output): the _as form of the gather decode_run would
+// have taken, its grid's x sized by the format's elements per thread (k_synth.h, PcmOut) where the F32 gathers take four
+// frames per thread.
+struct LapLaunch {
+  hipStream_t s;
+  int64_t ns;
+  size_t nseg;
+  int64_t max_frames;
+  const long long *first, *frames, *stride, *offset;
+  const LapSegment *seg;
+  int kind;  // 0 k_lap, 1 k_lap_window, 2 k_lap_segments
+  void *pcm;
+};
+extern "C++" {
+template <int D, bool IL>
+static void launch_lap_as(const LapP &L, const LapLaunch &A) {
+  typedef typename PcmElem<D>::T T;
+  const long long threads = (IL ? A.max_frames * L.ch : A.max_frames) / PcmOut<D, IL>::per_thread + 2, per = (threads + 255) / 256;
+  const unsigned gx = (unsigned)(per < 1024 ? per : 1024);
+  if (A.kind == 2)
+    hipLaunchKernelGGL((k_lap_segments_as<D, IL>), dim3(gx, (unsigned)(A.nseg < 1024 ? A.nseg : 1024)), dim3(256), 0, A.s, L, (long)A.nseg, A.seg, (T *)A.pcm);
+  else if (A.kind == 1)
+    hipLaunchKernelGGL((k_lap_window_as<D, IL>), dim3(gx, (unsigned)(A.ns < 1024 ? A.ns : 1024)), dim3(256), 0, A.s, L, (long)A.ns, A.first, A.frames, A.stride,
+                       A.offset, (T *)A.pcm);
+  else
+    hipLaunchKernelGGL((k_lap_as<D, IL>), dim3(gx, (unsigned)(A.ns < 1024 ? A.ns : 1024)), dim3(256), 0, A.s, L, (long)A.ns, A.frames, A.offset, (T *)A.pcm);
+}
+}  // extern "C++"
+
+static size_t pcm_elem_bytes(int dtype) { return dtype == VAMD_PCM_F32 ? 4 : 2; }
+
 // The tail all entries share, behind a plan that holds and statuses the host has already set: workspace, the plan's
 // upload, the arena (uploaded, or unpaged on the device), k_unpack, k_synth, k_lap, and the statuses back in one copy --
 // the blocks' and, behind them, the pages' -- folded into their streams.  With `live`, P is live->plan->P: order[] holds
@@ -213,7 +244,7 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
   if (win && ns) memcpy(h + o_first, win->first, 8 * (size_t)ns), memcpy(h + o_stride, win->stride, 8 * (size_t)ns);
   for (size_t g = 0; g < nseg; g++) {  // (a stream's rows fill its [ch][frames] from 0 to frames, in order)
     const DecodePlan::Segment &e = (*seg)[g];
-    LapSegment row = {e.k0, e.k1, e.first, e.count, P.frames[(size_t)e.stream], offset_out[e.stream] + e.out_at};
+    LapSegment row = {e.k0, e.k1, e.first, e.count, P.frames[(size_t)e.stream], offset_out[e.stream] + e.out_at * (D.pcm_interleaved ? ch : 1)};
     memcpy(h + o_seg + g * sizeof(LapSegment), &row, sizeof(row));
   }
   hipStream_t s = c->stream;
@@ -264,7 +295,19 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
     L.src0 = (const long long *)(dp + o_src0), L.src1 = (const long long *)(dp + o_src1);
     L.synth0 = (const float *)D.synth[0].p, L.synth1 = (const float *)D.synth[1].p;
     const long per_stream = (long)((P.max_frames + 1023) / 1024);  // (as vamd_synth_streams sizes it)
-    if (seg)
+    if (D.pcm_dtype != VAMD_PCM_F32 || D.pcm_interleaved) {
+      const LapLaunch A = {s, ns, nseg, P.max_frames, (const long long *)(dp + o_first), (const long long *)(dp + o_frames), (const long long *)(dp + o_stride),
+                           (const long long *)(dp + o_off), (const LapSegment *)(dp + o_seg), seg ? 2 : win ? 1 : 0, pcm};
+      switch (D.pcm_dtype * 2 + (D.pcm_interleaved ? 1 : 0)) {
+        case 1: launch_lap_as<VAMD_PCM_F32, true>(L, A); break;
+        case 2: launch_lap_as<VAMD_PCM_S16, false>(L, A); break;
+        case 3: launch_lap_as<VAMD_PCM_S16, true>(L, A); break;
+        case 4: launch_lap_as<VAMD_PCM_F16, false>(L, A); break;
+        case 5: launch_lap_as<VAMD_PCM_F16, true>(L, A); break;
+        case 6: launch_lap_as<VAMD_PCM_BF16, false>(L, A); break;
+        default: launch_lap_as<VAMD_PCM_BF16, true>(L, A); break;
+      }
+    } else if (seg)
       hipLaunchKernelGGL(k_lap_segments, dim3((unsigned)(per_stream < 1024 ? per_stream : 1024), (unsigned)(nseg < 1024 ? nseg : 1024)), dim3(256), 0, s, L, (long)nseg,
                          (const LapSegment *)(dp + o_seg), pcm);
     else if (win)
@@ -288,6 +331,7 @@ static int decode_run(vamd_ctx *c, const DecodePlan &P, int64_t ns, const Decode
 static int decode_outputs(vamd_ctx *c, const DecodePlan &P, int64_t ns, const int64_t *offset_out, const float *pcm, uint8_t *status) {
   if (ns && !status) return fail(c, VAMD_EINVAL, "decode: null status");
   if (P.max_frames > 0 && (!offset_out || !pcm)) return fail(c, VAMD_EINVAL, "decode: null offset_out / pcm");
+  if ((uintptr_t)pcm % pcm_elem_bytes(c->dec.pcm_dtype)) return fail(c, VAMD_EINVAL, "decode: pcm is not aligned to the output format's element type");
   for (int64_t s = 0; s < ns; s++) {
     if (P.frames[(size_t)s] > 0 && offset_out[s] < 0) return fail(c, VAMD_EINVAL, "decode: negative offset_out");
     status[s] = P.status[(size_t)s];
@@ -311,6 +355,57 @@ int vamd_decode_partial(vamd_ctx *c, int keep) {
   }
   c->dec.partial = keep != 0;
   return was;
+}
+
+// the policy for the decoded signal's element type and layout (include/vorbis_amd.h, "the decoded signal in the caller's
+// format"): decode_run picks its last launch by it, so every entry follows, a live decoder at each call
+static int pcm_format_check(vamd_ctx *c, const vamd_pcm_format *fmt) {
+  if (fmt && (fmt->dtype < VAMD_PCM_F32 || fmt->dtype > VAMD_PCM_BF16)) return fail(c, VAMD_EINVAL, "pcm format: an unknown dtype");
+  return VAMD_OK;
+}
+
+int vamd_decode_output(vamd_ctx *c, const vamd_pcm_format *fmt) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  int r = pcm_format_check(c, fmt);
+  if (r) return r;
+  c->dec.pcm_dtype = fmt ? fmt->dtype : VAMD_PCM_F32;
+  c->dec.pcm_interleaved = fmt && fmt->interleaved != 0;
+  return VAMD_OK;
+}
+
+extern "C++" {
+template <int D, bool IL>
+static void launch_pcm_convert(hipStream_t s, const float *src, int64_t frames, int ch, void *dst) {
+  const long long blocks = (frames * ch + 255) / 256;
+  hipLaunchKernelGGL((k_pcm_convert<D, IL>), dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, src, (long long)frames, ch,
+                     (typename PcmElem<D>::T *)dst);
+}
+}  // extern "C++"
+
+int vamd_pcm_convert(vamd_ctx *c, const float *src, int64_t frames, int ch, const vamd_pcm_format *fmt, void *dst) {
+  DeviceGuard dev_guard(c);
+  if (!c) return VAMD_EINVAL;
+  int r = pcm_format_check(c, fmt);
+  if (r) return r;
+  const int dtype = fmt ? fmt->dtype : VAMD_PCM_F32;
+  const bool il = fmt && fmt->interleaved != 0;
+  if (frames < 0 || ch < 1 || ch > VAMD_MAX_CH || frames > ((int64_t)1 << 56)) return fail(c, VAMD_EINVAL, "pcm_convert: frames < 0 or channels outside 1 .. 8");
+  if (!frames) return VAMD_OK;
+  if (!src || !dst) return fail(c, VAMD_EINVAL, "pcm_convert: null src / dst");
+  if ((uintptr_t)src % 4 || (uintptr_t)dst % pcm_elem_bytes(dtype)) return fail(c, VAMD_EINVAL, "pcm_convert: src / dst is not aligned to its element type");
+  switch (dtype * 2 + (il ? 1 : 0)) {
+    case 0: launch_pcm_convert<VAMD_PCM_F32, false>(c->stream, src, frames, ch, dst); break;
+    case 1: launch_pcm_convert<VAMD_PCM_F32, true>(c->stream, src, frames, ch, dst); break;
+    case 2: launch_pcm_convert<VAMD_PCM_S16, false>(c->stream, src, frames, ch, dst); break;
+    case 3: launch_pcm_convert<VAMD_PCM_S16, true>(c->stream, src, frames, ch, dst); break;
+    case 4: launch_pcm_convert<VAMD_PCM_F16, false>(c->stream, src, frames, ch, dst); break;
+    case 5: launch_pcm_convert<VAMD_PCM_F16, true>(c->stream, src, frames, ch, dst); break;
+    case 6: launch_pcm_convert<VAMD_PCM_BF16, false>(c->stream, src, frames, ch, dst); break;
+    default: launch_pcm_convert<VAMD_PCM_BF16, true>(c->stream, src, frames, ch, dst); break;
+  }
+  HIP_TRY(c, hipGetLastError());
+  return VAMD_OK;
 }
 
 int vamd_decode_streams(vamd_ctx *c, const vamd_decode_desc *d, const int64_t *offset_out, float *pcm, uint8_t *status) {

@@ -139,6 +139,8 @@ int vamd_decode_ogg_window(vamd_ctx *c, const vamd_ogg_index *x, const vamd_ogg_
   std::vector<int64_t> stride;
   int r = decode_ogg_window_plan(c, x, d, &WP, &G);
   if (r) return r;
+  if (d->channel_stride && c->dec.pcm_interleaved)  // (an interleaved window is one row: frame k's channels lie side by side)
+    return fail(c, VAMD_EINVAL, "decode_ogg_window: channel_stride has no meaning under an interleaved output format (vamd_decode_output)");
   if ((r = decode_window_strides(c, WP, d->channel_stride, &stride))) return r;
   if ((r = decode_outputs(c, WP.P, d->nwindows, offset_out, pcm, status))) return r;
   if (WP.P.order.empty()) return VAMD_OK;

@@ -1730,6 +1730,50 @@ __global__ __launch_bounds__(256) void k_lap_segments(LapP L, long nsegments, co
   }
 }
 
+// The three gathers in the caller's format (k_synth.h, "the lap in the caller's format"; vamd_decode_output): the same rows
+// of the grid, a thread per PcmOut<D, IL>::per_thread elements of a row instead of per four frames.  offset[], stride[] and
+// LapSegment::out count elements of the format's type.  <VAMD_PCM_F32, planar> is not instantiated: it is the three above.
+template <int D, bool IL>
+__global__ __launch_bounds__(256) void k_lap_as(LapP L, long nstreams, const long long *__restrict__ frames, const long long *__restrict__ offset,
+                                                typename PcmElem<D>::T *__restrict__ out) {
+  for (long s = blockIdx.y; s < nstreams; s += gridDim.y) {
+    const long long k0 = L.stream_start[s], k1 = L.stream_start[s + 1], F = frames[s];
+    if (k1 - k0 < 2) continue;
+    const long long first = lap_centre(L, k0), nq = lap_threads_as<D, IL>(F, L.ch);
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x)
+      lap_window_as<D, IL>(L, k0, k1, first, F, F, q, out + offset[s]);
+  }
+}
+template <int D, bool IL>
+__global__ __launch_bounds__(256) void k_lap_window_as(LapP L, long nwindows, const long long *__restrict__ first, const long long *__restrict__ frames,
+                                                       const long long *__restrict__ stride, const long long *__restrict__ offset,
+                                                       typename PcmElem<D>::T *__restrict__ out) {
+  for (long w = blockIdx.y; w < nwindows; w += gridDim.y) {
+    const long long k0 = L.stream_start[w], k1 = L.stream_start[w + 1], F = frames[w], nq = lap_threads_as<D, IL>(F, L.ch);
+    if (k1 - k0 < 2) continue;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x)
+      lap_window_as<D, IL>(L, k0, k1, first[w], F, stride[w], q, out + offset[w]);
+  }
+}
+template <int D, bool IL>
+__global__ __launch_bounds__(256) void k_lap_segments_as(LapP L, long nsegments, const LapSegment *__restrict__ seg, typename PcmElem<D>::T *__restrict__ out) {
+  for (long g = blockIdx.y; g < nsegments; g += gridDim.y) {
+    const LapSegment S = seg[g];
+    const long long nq = lap_threads_as<D, IL>(S.count, L.ch);
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x)
+      lap_window_as<D, IL>(L, S.k0, S.k1, S.first, S.count, S.stride, q, out + S.out);
+  }
+}
+
+// vamd_pcm_convert: the formats' conversion alone, over an fp32 planar [ch][frames] tensor that exists already; a thread
+// per output element, striding.
+template <int D, bool IL>
+__global__ __launch_bounds__(256) void k_pcm_convert(const float *__restrict__ src, long long frames, int ch, typename PcmElem<D>::T *__restrict__ dst) {
+  const long long n = frames * ch;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
+    dst[e] = pcm_from<D>(src[IL ? (e % ch) * frames + e / ch : e]);
+}
+
 // The live decoder's carries (k_synth.h, "the lap across pieces"): a workgroup per (row of the table, channel), striding
 // over the pairs; a wave's lanes move 16 bytes each.  k_decode_carry_in before k_lap, k_decode_carry_out behind k_synth,
 // in-before-out on one stream: a slot may be read and written in one call.
