@@ -4,6 +4,7 @@
 // vamd_hip.hip, once, after vamd_kernels.h and before the three parts of the host side (vamd_batch.h, vamd_block.h,
 // vamd_plan.h).
 #pragma once
+#include "vamd_arena.h"
 // ---------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------
@@ -201,14 +202,3 @@ static int pinned_get(vamd_ctx *c, HostBuf &b, size_t bytes, bool slack) {
   }
   return VAMD_OK;
 }
-
-// the layout of a host-pointer call's arena (pinned and device side alike): every part begins on a 16-byte boundary --
-// the launch code chooses kernels by pointer alignment, and the mapped pinned arena is read and written in place
-struct Arena {
-  size_t at = 0;  // the arena's size so far
-  size_t take(size_t bytes) {
-    const size_t o = at;
-    at = (at + bytes + 15) & ~(size_t)15;
-    return o;
-  }
-};

@@ -2,7 +2,7 @@
 // Ogg Vorbis streams, in host memory and cut anywhere, to PCM in device memory.  Part of the library's single translation
 // unit, behind vamd_decode_live.h.  It joins the two entries in front of it: the host's page walk with its state per slot
 // (vamd_demux_live.h) in place of vamd_demux.h's walk of a whole file, and the live packet decoder's slots and float carry
-// (vamd_decode_live_plan.h) behind it -- one call of decode_run with both DecodeInput::scan and DecodeCarry.  What the object
+// (vamd_decode_live_plan.h) behind it -- one call of decode_run with both DecodeInput::scan and DecodeAdds::live.  What the object
 // adds to those is a byte carry on the device, [max_streams][max_packet_bytes rounded up to 4]: the audio packet that a
 // slot's whole pages have left open (k_ogg_packet_carry_in / _out, k_demux.h).
 // A call's whole pages are gathered on the host -- the held tail and the piece, stream after stream, into one staging
@@ -11,8 +11,7 @@
 
 struct vamd_decode_ogg_live {
   vamd_ctx *c = nullptr;
-  std::vector<LiveSlot> slots;       // the blocks' side: the lap carried between pieces
-  float *carry = nullptr;
+  LiveLap lap;                       // the blocks' side: the lap carried between pieces
   std::vector<DemuxLiveSlot> demux;  // the container's side
   uint8_t *bytes_carry = nullptr;
   int64_t max_packet_bytes = 0, max_header_bytes = 0, stride = 0;
@@ -25,18 +24,16 @@ int vamd_decode_ogg_live_create(vamd_ctx *c, int64_t max_streams, const vamd_dec
   if (!c) return VAMD_EINVAL;
   if (!out) return fail(c, VAMD_EINVAL, "decode_ogg_live: null out");
   *out = nullptr;
-  if (max_streams < 1 || max_streams > (1 << 20)) return fail(c, VAMD_EINVAL, "decode_ogg_live: max_streams outside 1 .. 2^20");
+  int r = LiveLap::streams(c, "decode_ogg_live", max_streams);
+  if (r) return r;
   if (opts && (opts->setup_header_bytes < 0 || (opts->setup_header_bytes > 0 && !opts->setup_header)))
     return fail(c, VAMD_EINVAL, "decode_ogg_live: setup_header_bytes without a setup header");
   if (opts && (opts->max_packet_bytes < 0 || opts->max_packet_bytes > (1 << 24))) return fail(c, VAMD_EINVAL, "decode_ogg_live: max_packet_bytes outside 0 .. 2^24");
   if (opts && (opts->max_header_bytes < 0 || opts->max_header_bytes > ((int64_t)1 << 30))) return fail(c, VAMD_EINVAL, "decode_ogg_live: max_header_bytes outside 0 .. 2^30");
-  int r = decode_ready(c);
-  if (r) return r;
-  if (c->B.bs[1] < c->B.bs[0]) return fail(c, VAMD_EIMPL, "decode_ogg_live: a long block shorter than the short one");
+  if ((r = LiveLap::ready(c, "decode_ogg_live"))) return r;
   vamd_decode_ogg_live *d = new (std::nothrow) vamd_decode_ogg_live;
   if (!d) return fail(c, VAMD_EFAULT, "decode_ogg_live: out of memory");
   d->c = c;
-  d->slots.assign((size_t)max_streams, LiveSlot());
   d->demux.assign((size_t)max_streams, DemuxLiveSlot());
   d->max_packet_bytes = opts && opts->max_packet_bytes ? opts->max_packet_bytes : std::max(vamd_packet_capacity(c, 0), vamd_packet_capacity(c, 1));
   d->max_header_bytes = opts && opts->max_header_bytes ? opts->max_header_bytes : (int64_t)1 << 20;
@@ -46,15 +43,13 @@ int vamd_decode_ogg_live_create(vamd_ctx *c, int64_t max_streams, const vamd_dec
     delete d;
     return fail(c, VAMD_EINVAL, "decode_ogg_live: more than 2^36 bytes of packet carry");
   }
-  const size_t lap = (size_t)max_streams * c->B.channels * (c->B.bs[1] / 2) * 4, bytes = (size_t)max_streams * (size_t)d->stride + 16;
-  hipError_t e = hipMalloc((void **)&d->carry, lap);
-  if (e == hipSuccess) e = hipMemset(d->carry, 0, lap);
-  if (e == hipSuccess) e = hipMalloc((void **)&d->bytes_carry, bytes);
-  if (e == hipSuccess) e = hipMemset(d->bytes_carry, 0, bytes);
-  if (e != hipSuccess) {
-    if (d->carry) (void)hipFree(d->carry);
-    if (d->bytes_carry) (void)hipFree(d->bytes_carry);
+  if ((r = d->lap.make(c, "decode_ogg_live", max_streams))) {
     delete d;
+    return r;
+  }
+  const hipError_t e = LiveLap::zeros((void **)&d->bytes_carry, (size_t)max_streams * (size_t)d->stride + 16);
+  if (e != hipSuccess) {
+    vamd_decode_ogg_live_destroy(d);
     return fail(c, VAMD_EFAULT, "decode_ogg_live: the carries", e);
   }
   *out = d;
@@ -64,7 +59,7 @@ int vamd_decode_ogg_live_create(vamd_ctx *c, int64_t max_streams, const vamd_dec
 void vamd_decode_ogg_live_destroy(vamd_decode_ogg_live *d) {
   if (!d) return;
   DeviceGuard dev_guard(d->c);
-  if (d->carry) (void)hipFree(d->carry);
+  d->lap.release();
   if (d->bytes_carry) (void)hipFree(d->bytes_carry);
   delete d;
 }
@@ -75,14 +70,11 @@ static int decode_ogg_live_plan(vamd_decode_ogg_live *d, const vamd_decode_ogg_l
   if (!desc) return fail(c, VAMD_EINVAL, "decode_ogg_live: null descriptor");
   int r = decode_ready(c);
   if (r) return r;
-  DemuxSetup S;
-  S.channels = c->B.channels, S.rate = c->B.rate, S.bs[0] = c->B.bs[0], S.bs[1] = c->B.bs[1];
-  S.setup_header = d->has_setup_header ? d->setup_header.data() : nullptr, S.setup_header_bytes = (int64_t)d->setup_header.size();
-  demux_own_setup(c, &S);
+  const DemuxSetup S = demux_setup(c, d->has_setup_header ? d->setup_header.data() : nullptr, (int64_t)d->setup_header.size());
   std::string err;
   if (!demux_live_scan(d->demux, desc->nstreams, desc->slot, desc->bytes, desc->piece_offset, desc->close, S, d->max_packet_bytes, d->max_header_bytes, X, &err))
     return fail(c, VAMD_EINVAL, err.c_str());
-  if (!decode_live_plan_build(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->slots, desc->nstreams, (int64_t)X->X.first.size(), desc->slot, nullptr,
+  if (!decode_live_plan_build(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->lap.slots, desc->nstreams, (int64_t)X->X.first.size(), desc->slot, nullptr,
                               X->X.offset.data(), X->X.stream_start.data(), X->close.data(), X->X.end_granule.data(), L, &err, X->X.first.data()))
     return fail(c, VAMD_EINVAL, err.c_str());
   for (int64_t s = 0; s < desc->nstreams; s++) L->P.status[(size_t)s] |= X->X.status[(size_t)s];
@@ -96,8 +88,7 @@ int vamd_decode_ogg_live_plan(vamd_decode_ogg_live *d, const vamd_decode_ogg_liv
   DecodeLivePlan L;
   int r = decode_ogg_live_plan(d, desc, &X, &L);
   if (r) return r;
-  for (int64_t s = 0; frames && s < desc->nstreams; s++) frames[s] = L.P.frames[(size_t)s];
-  if (nblocks) nblocks[0] = L.P.nblocks[0], nblocks[1] = L.P.nblocks[1];
+  decode_report(L.P, desc->nstreams, frames, nblocks);
   return VAMD_OK;
 }
 
@@ -114,12 +105,12 @@ int vamd_decode_ogg_live_wrote(vamd_decode_ogg_live *d, const vamd_decode_ogg_li
     DecodeInput in;
     in.offset = X.X.offset.data(), in.begin = X.begin.data(), in.byte0 = 0, in.nbytes = X.arena_bytes;
     in.scan = &X.X, in.files = X.upload.data(), in.files_bytes = (int64_t)X.upload.size();
-    DecodeCarry live;
-    live.plan = &L, live.carry = d->carry;
-    live.bytes_in = &X.in, live.bytes_out = &X.out, live.bytes_carry = d->bytes_carry, live.slots = (int64_t)d->demux.size(), live.stride = d->stride;
-    if ((r = decode_run(c, L.P, desc->nstreams, in, offset_out, pcm, status, &live))) return r;
+    DecodeAdds add;
+    add.live = &L, add.carry = d->lap.carry;
+    add.bytes_in = &X.in, add.bytes_out = &X.out, add.bytes_carry = d->bytes_carry, add.slots = (int64_t)d->demux.size(), add.bytes_stride = d->stride;
+    if ((r = decode_run(c, L.P, desc->nstreams, in, offset_out, pcm, status, add))) return r;
   }
-  decode_live_commit(&d->slots, L, desc->nstreams, desc->slot, X.close.data(), status);
+  decode_live_commit(&d->lap.slots, L, desc->nstreams, desc->slot, X.close.data(), status);
   demux_live_commit(&d->demux, &X, desc->nstreams, desc->slot, desc->close, status);
   return VAMD_OK;
 }

@@ -10,16 +10,11 @@
 static int decode_window_plan(vamd_ctx *c, const vamd_decode_desc *d, int64_t nwindows, const int64_t *stream, const int64_t *start,
                               const int64_t *count, WindowPlan *WP) {
   DecodePlan whole;
-  int r = decode_plan(c, d, &whole);
+  int r = decode_plan(c, d, nullptr, &whole);
   if (r) return r;
   std::string err;
   if (!window_plan_build(whole, c->B.bs, nwindows, stream, start, count, WP, &err)) return fail(c, VAMD_EINVAL, err.c_str());
   return VAMD_OK;
-}
-
-static void decode_window_report(const WindowPlan &WP, int64_t nwindows, int64_t *frames, int64_t *nblocks) {
-  for (int64_t w = 0; frames && w < nwindows; w++) frames[w] = WP.P.frames[(size_t)w];
-  if (nblocks) nblocks[0] = WP.P.nblocks[0], nblocks[1] = WP.P.nblocks[1];
 }
 
 int vamd_decode_window_plan(vamd_ctx *c, const vamd_decode_desc *d, int64_t nwindows, const int64_t *stream, const int64_t *start,
@@ -29,7 +24,7 @@ int vamd_decode_window_plan(vamd_ctx *c, const vamd_decode_desc *d, int64_t nwin
   WindowPlan WP;
   int r = decode_window_plan(c, d, nwindows, stream, start, count, &WP);
   if (r) return r;
-  decode_window_report(WP, nwindows, frames, nblocks);
+  decode_report(WP.P, nwindows, frames, nblocks);
   return VAMD_OK;
 }
 
@@ -60,9 +55,9 @@ int vamd_decode_window(vamd_ctx *c, const vamd_decode_desc *d, int64_t nwindows,
   DecodeInput in;
   in.offset = offs.data(), in.byte0 = 0, in.nbytes = offs.back();
   in.packets = (const uint8_t *)c->dec.h_stage.p;
-  DecodeWindows win;
-  win.first = WP.first.data(), win.stride = stride.data();
-  return decode_run(c, WP.P, nwindows, in, offset_out, pcm, status, nullptr, &win);
+  DecodeAdds add;
+  add.first = WP.first.data(), add.stride = stride.data();
+  return decode_run(c, WP.P, nwindows, in, offset_out, pcm, status, add);
 }
 
 // ---- files: the seek index, then windows of the files it was made of ----
@@ -82,10 +77,7 @@ int vamd_ogg_index_create(vamd_ctx *c, const vamd_decode_ogg_desc *d, vamd_ogg_i
   vamd_ogg_index *x = new (std::nothrow) vamd_ogg_index;
   if (!x) return fail(c, VAMD_EFAULT, "ogg_index: out of memory");
   x->c = c;
-  DemuxSetup S;
-  S.channels = c->B.channels, S.rate = c->B.rate, S.bs[0] = c->B.bs[0], S.bs[1] = c->B.bs[1];
-  S.setup_header = d->setup_header, S.setup_header_bytes = d->setup_header_bytes;
-  demux_own_setup(c, &S);
+  const DemuxSetup S = demux_setup(c, d->setup_header, d->setup_header_bytes);
   std::string err;
   if (!ogg_index_build(c->B.bs, c->dec.U.modes, c->dec.U.modebits, d->nstreams, d->bytes, d->file_offset, S, &x->I, &err)) {
     delete x;
@@ -126,7 +118,7 @@ int vamd_decode_ogg_window_plan(vamd_ctx *c, const vamd_ogg_index *x, const vamd
   OggWindowStage G;
   int r = decode_ogg_window_plan(c, x, d, &WP, &G);
   if (r) return r;
-  decode_window_report(WP, d->nwindows, frames, nblocks);
+  decode_report(WP.P, d->nwindows, frames, nblocks);
   if (staged) staged[0] = G.stage_bytes, staged[1] = (int64_t)G.pages.size();
   return VAMD_OK;
 }
@@ -151,7 +143,7 @@ int vamd_decode_ogg_window(vamd_ctx *c, const vamd_ogg_index *x, const vamd_ogg_
   DecodeInput in;
   in.offset = G.offs.data(), in.begin = G.begin.data(), in.byte0 = 0, in.nbytes = G.arena_bytes;
   in.scan = &rows, in.files = (const uint8_t *)c->dec.h_stage.p, in.files_bytes = G.stage_bytes;
-  DecodeWindows win;
-  win.first = WP.first.data(), win.stride = stride.data();
-  return decode_run(c, WP.P, d->nwindows, in, offset_out, pcm, status, nullptr, &win);
+  DecodeAdds add;
+  add.first = WP.first.data(), add.stride = stride.data();
+  return decode_run(c, WP.P, d->nwindows, in, offset_out, pcm, status, add);
 }

@@ -47,6 +47,7 @@
 #define VAMD_OGG_NO_FEED_KERNELS  // (k_ogg.h: k_ogg_plan / _pages / _carry are vamd_feed.hip's)
 #include "vamd_demux.h"
 #include "vamd_demux_live.h"
+#include "vamd_decode_layout.h"  // (namespace vamd, so here and not from vamd_decode.h, which is included inside extern "C")
 #include "vamd_headers.h"
 
 using namespace vamd;
